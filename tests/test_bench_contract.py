@@ -36,8 +36,54 @@ def test_cli_defaults(monkeypatch):
     a = b.parse()
     assert (a.gpus, a.steps, a.warmup, a.config, a.hidden, a.epochs, a.minibatches) == \
         (1, 20, 5, 1, 256, 8, 32)
+    # a plain run is the lean one: --full and --dump-outputs are opt-in
+    assert a.full is False and a.dump_outputs is None
     # the reward-faithful recipe is the default line: 4,096-row minibatches
     assert b.CONFIGS[1] == dict(envs=4096, obs=15, order="sorted", pe="none", d=0, rollout=32)
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs' writer on host tensors: every rollout array as float32, the parameters
+    flat, the metrics float64; over the budget, large arrays become the same seeded sample on
+    every call and small ones stay whole."""
+    import types
+
+    import numpy as np
+    import torch
+
+    b = _bench()
+    T, E, S = 3, 5, 7
+    g = torch.Generator().manual_seed(0)
+    buf = types.SimpleNamespace(
+        states=torch.rand(T + 1, E, S, generator=g), actions=torch.rand(T, E, 2, generator=g),
+        pre_tanh=torch.rand(T, E, 2, generator=g), log_probs=torch.rand(T, E, generator=g),
+        values=torch.rand(T, E, generator=g), rewards=torch.rand(T, E, generator=g),
+        terminated=torch.zeros(T, E, dtype=torch.uint8), ep_return=torch.rand(T, E, generator=g),
+        truncated=torch.ones(T, E, dtype=torch.uint8), dones=torch.ones(T, E, dtype=torch.uint8),
+        ep_length=torch.arange(T * E, dtype=torch.int32).reshape(T, E))
+    net = torch.nn.Linear(4, 3)
+    agent = types.SimpleNamespace(actor_critic=net)
+    metrics = {k: float(i) for i, k in enumerate(b.DUMP_METRICS)}
+    wrote = b.dump_outputs(str(tmp_path / "a"), buf, agent, metrics)
+    st = np.load(tmp_path / "a" / "states.npy")
+    assert st.dtype == np.float32 and np.array_equal(st, buf.states.numpy())
+    ln = np.load(tmp_path / "a" / "ep_length.npy")
+    assert ln.dtype == np.float32 and np.array_equal(ln, buf.ep_length.numpy())
+    pr = np.load(tmp_path / "a" / "params.npy")
+    assert np.array_equal(pr, np.concatenate([net.weight.detach().numpy().ravel(),
+                                              net.bias.detach().numpy().ravel()]))
+    me = np.load(tmp_path / "a" / "metrics.npy")
+    assert me.dtype == np.float64 and me.tolist() == [float(i) for i in range(7)]
+    assert wrote["states"] == [st.size, st.size] and len(wrote) == 13
+    # a budget of 12 arrays x 20 elements: states (140) is sampled, rewards (15) stays whole
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 12 * 20 * 4)
+    w1 = b.dump_outputs(str(tmp_path / "b"), buf, agent, metrics)
+    w2 = b.dump_outputs(str(tmp_path / "c"), buf, agent, metrics)
+    assert w1 == w2 and w1["states"] == [20, 140] and w1["rewards"] == [15, 15]
+    s1, s2 = np.load(tmp_path / "b" / "states.npy"), np.load(tmp_path / "c" / "states.npy")
+    assert s1.shape == (20,) and np.array_equal(s1, s2)
+    assert np.isin(s1, buf.states.numpy()).all()
+    assert sum(np.load(tmp_path / "b" / f).nbytes for f in os.listdir(tmp_path / "b")) <= 64 << 20
 
 
 def test_config_table_matches_baseline_json():

@@ -30,7 +30,8 @@ def test_bench_two_ranks_one_line(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1",
-           "--envs", "256", "--rollout", "8", "--minibatches", "4", "--epochs", "2"]
+           "--envs", "256", "--rollout", "8", "--minibatches", "4", "--epochs", "2",
+           "--full"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=150, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

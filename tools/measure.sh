@@ -22,7 +22,7 @@ tests() {
   step smoke
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || return 1
   step bench default
-  timeout -k 10 400 python -u bench.py > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err" || { tail -20 "$OUT/bench_c1.err"; return 1; }
+  timeout -k 10 400 python -u bench.py --full > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err" || { tail -20 "$OUT/bench_c1.err"; return 1; }
   python3 - "$OUT/bench_c1.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -40,7 +40,7 @@ lines() {
               "4 --pe rank --order shuffled --hidden 384" "4 --pe dist --order sorted"; do
     tag=$(echo "$spec" | tr -d ' -')
     step bench c$tag
-    timeout -k 10 300 python bench.py --config $spec --steps 10 --warmup 3 --no-cpu-baseline \
+    timeout -k 10 300 python bench.py --config $spec --steps 10 --warmup 3 --full --no-cpu-baseline \
       > "$OUT/bench_c$tag.json" 2> "$OUT/bench_c$tag.err" || { tail -20 "$OUT/bench_c$tag.err"; return 1; }
     cut -c1-160 "$OUT/bench_c$tag.json"
   done
@@ -54,7 +54,7 @@ prof() {
     c=$(echo "$spec" | tr -d ' -')
     step rocprof c$c
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_c$c" -o run -- python3 bench.py \
-      --config $spec --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_prof_c$c.log" 2>&1 || { tail -20 "$OUT/bench_prof_c$c.log"; return 1; }
+      --config $spec --steps 10 --warmup 3 --full --no-cpu-baseline > "$OUT/bench_prof_c$c.log" 2>&1 || { tail -20 "$OUT/bench_prof_c$c.log"; return 1; }
     S=$(ls "$OUT"/prof_c$c/run_kernel_stats.csv "$OUT"/prof_c$c/*/run_kernel_stats.csv \
           "$OUT"/prof_c$c/run_results.db "$OUT"/prof_c$c/*/run_results.db 2>/dev/null | head -1)
     python3 tools/summarize_stats.py "$S" 16 > "$OUT/kernel_stats_c$c.txt" && head -8 "$OUT/kernel_stats_c$c.txt"

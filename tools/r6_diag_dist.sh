@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 export HWY_BENCH_DIST_BACKEND=gloo
 timeout -k 10 200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
   --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 2 --warmup 1 \
-  --envs 256 --rollout 8 --minibatches 4 --epochs 2 > "$OUT/dist2.json" 2> "$OUT/dist2.err" || { tail -30 "$OUT/dist2.err"; exit 1; }
+  --envs 256 --rollout 8 --minibatches 4 --epochs 2 --full > "$OUT/dist2.json" 2> "$OUT/dist2.err" || { tail -30 "$OUT/dist2.err"; exit 1; }
 python3 - "$OUT/dist2.json" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
