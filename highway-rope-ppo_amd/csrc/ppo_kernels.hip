@@ -17,6 +17,14 @@
 // General path (other shapes): 11 launches of a 64x64-tile GEMM (gemm64 / gemm64v), the loss
 // head kernel (ppo_head), split-K partial slabs and one deterministic reduction (ppo_reduce).
 // All GEMMs use v_mfma_f32_*_f32: exact fp32 products, fp32 accumulation.
+//
+// This file is compiled twice (Makefile).  ppo_kernels.o holds everything but the mixed-width
+// grouped kernels and their entry points (hwy_ppo_mixed_*); ppo_mixed.o, compiled with
+// -DHWY_PPO_MIXED_TU, holds only those.  They are kept apart because the existing kernels'
+// code generation turned out to depend on what else the unit holds (with the mixed kernels
+// beside them 27 of the 57 row / act kernels changed their VGPR counts, their source untouched):
+// in a unit of their own the mixed kernels leave every other kernel's registers, LDS and
+// occupancy as they were (profiles/r7/mixed/).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -1287,212 +1295,46 @@ __device__ __forceinline__ void rows_body(const RowArgs& r) {
   __shared__ __attribute__((aligned(16))) f32x4 HDOT[NW][RT];
   __shared__ __attribute__((aligned(16))) f32x4 HROW[RT];
   __shared__ float HTAIL[NW][12];
-  float* X = CMP ? P1 : (kOwnX ? XX : AC);
-  PSEC_DECL
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int S = r.S;
-  const int tile = blockIdx.x;
-  const int row0 = tile * RT;
-  const int nrows = min(RT, r.B - row0);
-  const float* P = r.params;
-  constexpr int D = CMP ? kRingDC : ring_depth<TW>();  // CMP: 4 waves per SIMD hide more
-  WRing<TW, D, 7, true, CMP> R;
-  ring_setup(R, P, r.off, S, H, w * (H / NW), r.tiles);
-  // the loss head's inputs and weights, loaded now so that their latency hides behind the
-  // forward: lane l < RPW of wave w holds row RPW*w + l; the head weights of this wave's
-  // output columns nb + 16t + (lane & 15).  The row indices of the head and of
-  // the states gather go out first, then the rows they name, then the weight ring's prime
-  // (vector memory completes in issue order: a gather behind the prime waited for it)
-  const int hl = min(RPW * w + min(lane, RPW - 1), nrows - 1);
-  float hz0, hz1, hold, hadv, hret, hq0, hq1;
-  Gathered<RT, NT> xpre;
-  const long hsrc = (long)r.idx[row0 + hl];
-  gather_issue<RT, NT>(r.states, r.idx, S, nrows, row0, H, xpre);
-  hz0 = r.pre_tanh[hsrc * 2];
-  hz1 = r.pre_tanh[hsrc * 2 + 1];
-  hold = r.old_logp[hsrc];
-  hadv = r.adv[hsrc];
-  hret = r.ret[hsrc];
-  R.prime();
-  const int nb = w * (H / NW);  // this wave's output columns of an H-wide layer
-  f32x4 acc[RB][TW];
-  // the squash correction depends on the stored pre-tanh actions only: computed here, its
-  // latency hides behind the forward instead of lengthening the loss head's dependent chain
-  hq0 = squash_corr(hz0);
-  hq1 = squash_corr(hz1);
-  float wa0[TW], wa1[TW], wc[TW];
-#pragma unroll
-  for (int u = 0; u < TW; ++u) {
-    const int col = w * (H / NW) + 16 * u + (lane & 15);
-    wa0[u] = P[r.off[P_WA2] + col];
-    wa1[u] = P[r.off[P_WA2] + H + col];
-    wc[u] = P[r.off[P_WC2] + col];
-  }
-  const float ba0 = P[r.off[P_BA2]], ba1 = P[r.off[P_BA2] + 1], bcv = P[r.off[P_BC2]];
-  const float ls0 = P[r.off[P_LOGSTD]], ls1 = P[r.off[P_LOGSTD] + 1];
-  // torch Normal: scale = exp(log_std); var = scale**2; log_scale = log(scale) -- parameters
-  // only, so computed here, off the loss head's dependent chain (same bits)
-  const float sc0 = expf(ls0), sc1 = expf(ls1);
-  const float var0 = sc0 * sc0, var1 = sc1 * sc1;
-  const float lsc0 = logf(sc0), lsc1 = logf(sc1);
-  f32x4 av[RB][TW], cv[RB][TW];  // a1, c1 of this wave's columns (C layout)
-  uint32_t mb[2] = {0u, 0u};      // CMP: ReLU decisions of h1, h2 (this lane's C elements)
-  rows_forward<QH, NW, RT, true, D, 7, true, CMP>(R, r.states, r.idx, S, nrows, row0, P, r.off, X,
-                                                  H1, P1, AC, r.xg, r.h1,
-                                                  r.h2, mb, av,
-                                                  cv PSEC_ARGS, &xpre);
-  PSEC(3);
-  const int g4 = lane >> 4, c16 = lane & 15;
+#include "ppo_rows_body.inc"  // the kernel's code, over the images declared above
+}
 
-  // ---- loss head (ppo/agent.py:226-245).  (1) each wave's partial dot products a1 . wa2 and
-  // c1 . wc2 of every row over its columns, from the layer-3 accumulators (16-lane DPP sums);
-  // (2) the per-row scalar part, RPW rows per wave (lane = row), the partials summed in wave
-  // order; (3) dL/d[a1|c1] of this wave's columns into the [a1|c1] image for dh2 and ppo_wgrad,
-  // and the head-parameter gradients of its columns summed over the rows
-#pragma unroll
-  for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float p0 = 0.0f, p1 = 0.0f, pv = 0.0f;
-#pragma unroll
-      for (int u = 0; u < TW; ++u) {
-        p0 += av[rb][u][q] * wa0[u];
-        p1 += av[rb][u][q] * wa1[u];
-        pv += cv[rb][u][q] * wc[u];
-      }
-      p0 = row16_sum(p0), p1 = row16_sum(p1), pv = row16_sum(pv);
-      if (c16 == 0) HDOT[w][16 * rb + 4 * g4 + q] = f32x4{p0, p1, pv, 0.0f};
-    }
-  __syncthreads();
-  PSEC(7);
-  {
-    const float LOG_SQRT_2PI = 0.91893853320467274178f;
-    const float invB = 1.0f / (float)r.B;
-    const float lo = 1.0f - r.eps_clip, hi = 1.0f + r.eps_clip;
-    const int hr = RPW * w + min(lane, RPW - 1);  // this lane's row (lanes >= RPW: a copy)
-    f32x4 dsum = HDOT[0][hr];
-#pragma unroll
-    for (int ww = 1; ww < NW; ++ww) dsum += HDOT[ww][hr];
-    const float mu0 = dsum[0] + ba0, mu1 = dsum[1] + ba1, val = dsum[2] + bcv;
-    const float d0 = hz0 - mu0, d1 = hz1 - mu1;
-    const float lp0 = -(d0 * d0) / (2.0f * var0) - lsc0 - LOG_SQRT_2PI;
-    const float lp1 = -(d1 * d1) / (2.0f * var1) - lsc1 - LOG_SQRT_2PI;
-    const float logp = (lp0 - hq0) + (lp1 - hq1);
-    const float log_ratio = logp - hold;
-    const float ratio = expf(log_ratio);
-    const float cr = fminf(fmaxf(ratio, lo), hi);
-    const float s1 = ratio * hadv, s2 = cr * hadv;
-    const float inr = (ratio >= lo && ratio <= hi) ? 1.0f : 0.0f;
-    // torch.min / clamp backward: ties split the gradient evenly
-    const float wsel = s1 < s2 ? 1.0f : (s1 > s2 ? inr : 0.5f * (1.0f + inr));
-    const float dlogp = -invB * hadv * wsel * ratio;  // d(actor_loss)/d(logp)
-    // rows past nrows (and lanes past RPW) contribute nothing
-    const bool live = lane < RPW && hr < nrows;
-    const float dmu0 = live ? dlogp * d0 / var0 : 0.0f;
-    const float dmu1 = live ? dlogp * d1 / var1 : 0.0f;
-    const float dv = live ? r.value_coef * 2.0f * (val - hret) * invB : 0.0f;
-    if (lane < RPW) HROW[hr] = f32x4{dmu0, dmu1, dv, 0.0f};
-    // this wave's rows' bias / log_std gradient terms and metrics, summed over its lanes in
-    // lane order (the quad / half-row / row DPP tree over RPW <= 16 lanes)
-    float tl[9] = {dmu0, dmu1, dv,
-                   live ? dlogp * ((d0 * d0) / var0 - 1.0f) : 0.0f,
-                   live ? dlogp * ((d1 * d1) / var1 - 1.0f) : 0.0f,
-                   live ? -fminf(s1, s2) : 0.0f,
-                   live ? (val - hret) * (val - hret) : 0.0f,
-                   live ? (fabsf(ratio - 1.0f) > r.eps_clip ? 1.0f : 0.0f) : 0.0f,
-                   live ? (ratio - 1.0f) - log_ratio : 0.0f};
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const float v = row16_sum(lane < 16 ? tl[k] : 0.0f);
-      if (lane == 0) HTAIL[w][k] = v;
-    }
-    if (blockIdx.x == 0 && t == 0) {
-      r.counters[0] += 1;  // Adam step t for this minibatch
-      r.counters[1] += 1;  // metrics row (this step writes row counters[1]-1)
-    }
-  }
-  __syncthreads();
-  PSEC(11);
-  {
-    // dac of this wave's columns (the reference's expression per element), and the head
-    // weight gradients sum_rows dmu * a1 / dv * c1 of its columns: per lane over its rows, then
-    // over the four 16-lane groups
-    float ga0[TW], ga1[TW], gc[TW];
-#pragma unroll
-    for (int u = 0; u < TW; ++u) ga0[u] = ga1[u] = gc[u] = 0.0f;
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int row = 16 * rb + 4 * g4 + q;
-        const f32x4 sc = HROW[row];
-        const float dmu0 = sc[0], dmu1 = sc[1], dv = sc[2];
-        float* arow = AC + row * PA;
-#pragma unroll
-        for (int u = 0; u < TW; ++u) {
-          const int col = nb + 16 * u + c16;
-          const float a = av[rb][u][q], cc = cv[rb][u][q];
-          arow[col] = a > 0.0f ? (dmu0 * wa0[u] + dmu1 * wa1[u]) : 0.0f;
-          arow[H + col] = cc > 0.0f ? dv * wc[u] : 0.0f;
-          ga0[u] += dmu0 * a;
-          ga1[u] += dmu1 * a;
-          gc[u] += dv * cc;
-        }
-      }
-    float* out = r.head_part + (long)tile * r.HP;
-#pragma unroll
-    for (int u = 0; u < TW; ++u) {
-      // lanes c, c+16, c+32, c+48 hold the same column: (g0 + g1) + (g2 + g3)
-      ga0[u] += __shfl_xor(ga0[u], 16);
-      ga1[u] += __shfl_xor(ga1[u], 16);
-      gc[u] += __shfl_xor(gc[u], 16);
-      ga0[u] += __shfl_xor(ga0[u], 32);
-      ga1[u] += __shfl_xor(ga1[u], 32);
-      gc[u] += __shfl_xor(gc[u], 32);
-      if (g4 == 0) {
-        const int col = nb + 16 * u + c16;
-        out[col] = ga0[u];
-        out[H + col] = ga1[u];
-        out[2 * H + col] = gc[u];
-      }
-    }
-    if (w == 0 && lane < 9) {  // the waves' tail sums in wave order
-      float v = HTAIL[0][lane];
-#pragma unroll
-      for (int ww = 1; ww < NW; ++ww) v += HTAIL[ww][lane];
-      out[3 * H + lane] = v;
-    }
-  }
-  __syncthreads();
-  rows_out<NT, RT>(AC, PA, r.dac + (long)row0 * 2 * H, 2 * H, 2 * H, nrows);
-  PSEC(4);
-  // dh2 = (dac [Wa1; Wc1]) * (h2 > 0)   ([Wa1; Wc1] is [2H][H]: k-major); the two halves of
-  // K = 2H (Wa1 rows, Wc1 rows) are summed at the end
-  zero_acc(acc);
-  R.template run<4>(AC, PA, acc);
-  R.template run<5>(AC + H, PA, acc);
-  float* const DH2 = CMP ? H1 : H2;  // CMP: P0
-  float* const DH1 = CMP ? P1 : H1;
-  if constexpr (CMP) {
-    __syncthreads();  // every wave has read dac (P0 | P1)
-    row_epi_maskbits(acc, mb[1], DH2, PH, nb);
-  } else {
-    row_epi_mask(acc, H2, PH, nb);
-  }
-  __syncthreads();
-  if (r.dh2) rows_out<NT, RT>(DH2, PH, r.dh2 + (long)row0 * H, H, H, nrows);
-  PSEC(5);
-  // dh1 = (dh2 W2) * (h1 > 0)
-  zero_acc(acc);
-  R.template run<6>(DH2, PH, acc);
-  if constexpr (CMP)
-    row_epi_maskbits(acc, mb[0], DH1, PH, nb);  // P1: dac is dead, dh2 is in P0
-  else
-    row_epi_mask(acc, H1, PH, nb);  // dh1 over h1 (same thread)
-  __syncthreads();
-  if (r.dh1) rows_out<NT, RT>(DH1, PH, r.dh1 + (long)row0 * H, H, H, nrows);
-  PSEC(6);
-  PSEC_FLUSH;
+// LDS floats of rows_body<QH, NW, RT, false>: its images in declaration order (each a multiple
+// of 4 floats, so every image stays 16-byte aligned inside an arena)
+template <int QH, int NW, int RT>
+constexpr int rows_lds_floats() {
+  constexpr int H = 64 * QH, PH = lds_pitch(H), PA = lds_pitch(2 * H), PXMAX = lds_pitch(kMaxRowS);
+  return (PXMAX > PA ? RT * PXMAX : 0) + 2 * RT * PH + RT * PA + 4 * NW * RT + 4 * RT + 12 * NW;
+}
+
+// rows_body<QH, NW, RT, false> with its LDS images carved from `arena` (the calling kernel's
+// dynamic LDS, rows_lds_floats floats) instead of static arrays: a kernel that holds several
+// instantiations (ppo_rows_mix) then pays for the widest, not for their sum.  The code is
+// rows_body's, the same text compiled over pointers, so the arithmetic and its order are the
+// solo kernel's; rows_body itself keeps its static arrays, and with them its registers and LDS.
+template <int QH, int NW, int RT>
+__device__ __forceinline__ void rows_body_dyn(const RowArgs& r, float* arena) {
+  constexpr bool CMP = false;
+  constexpr int H = 64 * QH;
+  constexpr int TW = H / NW / 16;
+  constexpr int RB = RT / 16;
+  constexpr int RPW = RT / NW;
+  constexpr int NT = 64 * NW;
+  static_assert(TW * 16 * NW == H && RT % 16 == 0 && RPW >= 1 && RPW <= 16, "rows_body's geometry");
+  constexpr int PH = lds_pitch(H), PA = lds_pitch(2 * H), PXMAX = lds_pitch(kMaxRowS);
+  constexpr bool kOwnX = PXMAX > PA;
+  constexpr int oH1 = kOwnX ? RT * PXMAX : 0, oH2 = oH1 + RT * PH, oAC = oH2 + RT * PH;
+  constexpr int oHD = oAC + RT * PA, oHR = oHD + 4 * NW * RT, oHT = oHR + 4 * RT;
+  static_assert(oHT + 12 * NW == rows_lds_floats<QH, NW, RT>(), "arena layout");
+  float* const XX = arena;  // used only when the layout owns a states image (kOwnX)
+  float* const H1 = arena + oH1;
+  float* const H2 = arena + oH2;
+  float* const ACI = arena + oAC;
+  float* const P1 = H2;
+  float* const AC = ACI;
+  f32x4(*const HDOT)[RT] = reinterpret_cast<f32x4(*)[RT]>(arena + oHD);
+  f32x4* const HROW = reinterpret_cast<f32x4*>(arena + oHR);
+  float(*const HTAIL)[12] = reinterpret_cast<float(*)[12]>(arena + oHT);
+#include "ppo_rows_body.inc"
 }
 
 template <int QH, int NW, int RT>
@@ -1544,72 +1386,29 @@ __device__ __forceinline__ void act_body(ActArgs r) {
   __shared__ __attribute__((aligned(16))) float H1[kRowTile * PH];
   __shared__ __attribute__((aligned(16))) float H2[kRowTile * PH];
   __shared__ __attribute__((aligned(16))) float AC[kRowTile * PA];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int row0 = blockIdx.x * kRowTile;
-  const int nrows = min(kRowTile, r.B - row0);
-  const float* P = r.params;
-  constexpr int TW = H_TW(QH, NW);
-  constexpr int D = ring_depth<TW>();
-  WRing<TW, D, 4, TL> R;
-  ring_setup(R, P, r.off, r.S, H, w * (H / NW), r.tiles);
-  R.prime();
-#ifdef HWY_SECTION_PROFILE
-  uint64_t _pt = 0, _pacc[16];
-#endif
-  f32x4 unused_a[kRowTile / 16][TW], unused_c[kRowTile / 16][TW];
-  uint32_t unused_m[2];
-  rows_forward<QH, NW, kRowTile, false>(R, r.states, nullptr, r.S, nrows, row0, P, r.off, X, H1,
-                                        H2, AC, nullptr, nullptr, nullptr, unused_m, unused_a,
-                                        unused_c PSEC_ARGS);
-  float wa0[QH], wa1[QH], wc[QH];
-#pragma unroll
-  for (int q = 0; q < QH; ++q) {
-    const int col = lane + 64 * q;
-    wa0[q] = P[r.off[P_WA2] + col];
-    wa1[q] = P[r.off[P_WA2] + H + col];
-    wc[q] = P[r.off[P_WC2] + col];
-  }
-  const float ba0 = P[r.off[P_BA2]], ba1 = P[r.off[P_BA2] + 1], bcv = P[r.off[P_BC2]];
-  const float ls0 = P[r.off[P_LOGSTD]], ls1 = P[r.off[P_LOGSTD] + 1];
-  const float sc0 = expf(ls0), sc1 = expf(ls1);
-  const float var0 = sc0 * sc0, var1 = sc1 * sc1;
-  const float lsc0 = logf(sc0), lsc1 = logf(sc1);
-  const float LOG_SQRT_2PI = 0.91893853320467274178f;
-  for (int rr = 0; rr < RPW; ++rr) {
-    const int lr = RPW * w + rr;
-    if (lr >= nrows) break;
-    const int b = row0 + lr;
-    const float* arow = AC + lr * PA;
-    float p0 = 0.0f, p1 = 0.0f, pv = 0.0f;
-#pragma unroll
-    for (int q = 0; q < QH; ++q) {
-      const int col = lane + 64 * q;
-      const float a = arow[col], c = arow[H + col];
-      p0 += a * wa0[q];
-      p1 += a * wa1[q];
-      pv += c * wc[q];
-    }
-    const float mu0 = wave_sum_dpp(p0) + ba0, mu1 = wave_sum_dpp(p1) + ba1,
-                val = wave_sum_dpp(pv) + bcv;
-    if (lane == 0) {
-      float z0 = mu0, z1 = mu1, lp = 0.0f;
-      if (r.noise) {
-        z0 = mu0 + sc0 * r.noise[2 * (long)b];
-        z1 = mu1 + sc1 * r.noise[2 * (long)b + 1];
-        const float d0 = z0 - mu0, d1 = z1 - mu1;
-        const float t0 = tanhf(z0), t1 = tanhf(z1);
-        const float lp0 = -(d0 * d0) / (2.0f * var0) - lsc0 - LOG_SQRT_2PI;
-        const float lp1 = -(d1 * d1) / (2.0f * var1) - lsc1 - LOG_SQRT_2PI;
-        lp = (lp0 - log1pf(-(t0 * t0) + 1e-6f)) + (lp1 - log1pf(-(t1 * t1) + 1e-6f));
-      }
-      r.action[2 * (long)b] = tanhf(z0);
-      r.action[2 * (long)b + 1] = tanhf(z1);
-      r.pre_tanh[2 * (long)b] = z0;
-      r.pre_tanh[2 * (long)b + 1] = z1;
-      r.logp[b] = lp;
-      r.value[b] = val;
-    }
-  }
+#include "ppo_act_body.inc"
+}
+
+// LDS floats of act_body<QH, ...> (X | H1 | H2 | AC) and of act_c_body<QH, NW, RT> (P01 | HDOT)
+template <int QH>
+constexpr int act_lds_floats() {
+  return kRowTile * (lds_pitch(kMaxRowS) + 2 * lds_pitch(64 * QH) + lds_pitch(128 * QH));
+}
+template <int QH, int NW, int RT>
+constexpr int act_c_lds_floats() { return 2 * RT * lds_pitch(64 * QH) + 4 * NW * RT; }
+
+// act_body over a dynamic-LDS arena (see rows_body_dyn)
+template <int QH, int NW, bool TL>
+__device__ __forceinline__ void act_body_dyn(ActArgs r, float* arena) {
+  constexpr int H = 64 * QH;
+  constexpr int RPW = kRowTile / NW;
+  constexpr int PH = lds_pitch(H), PA = lds_pitch(2 * H), PXMAX = lds_pitch(kMaxRowS);
+  static_assert(kRowTile * (PXMAX + 2 * PH + PA) == act_lds_floats<QH>(), "arena layout");
+  float* const X = arena;
+  float* const H1 = arena + kRowTile * PXMAX;
+  float* const H2 = arena + kRowTile * (PXMAX + PH);
+  float* const AC = arena + kRowTile * (PXMAX + 2 * PH);
+#include "ppo_act_body.inc"
 }
 
 template <int QH, int NW, bool TL>
@@ -1634,85 +1433,22 @@ __device__ __forceinline__ void act_c_body(ActArgs r) {
   static_assert(TW * 16 * NW == H && PXMAX <= PH && RPW >= 1 && RPW <= 16, "ppo_act_c geometry");
   __shared__ __attribute__((aligned(16))) float P01[2 * RT * PH];
   __shared__ __attribute__((aligned(16))) f32x4 HDOT[NW][RT];
-  float* const H1 = P01;            // P0
-  float* const P1 = P01 + RT * PH;  // the states, then h2
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int row0 = blockIdx.x * RT;
-  const int nrows = min(RT, r.B - row0);
-  const float* P = r.params;
-  constexpr int D = kRingDC;
-  WRing<TW, D, 4, true, true> R;
-  ring_setup(R, P, r.off, r.S, H, w * (H / NW), r.tiles);
-  Gathered<RT, 64 * NW> xpre;  // the states rows, issued before the ring's prime (rows_body)
-  gather_issue<RT, 64 * NW>(r.states, nullptr, r.S, nrows, row0, H, xpre);
-  R.prime();
-#ifdef HWY_SECTION_PROFILE
-  uint64_t _pt = 0, _pacc[16];
-#endif
-  float wa0[TW], wa1[TW], wc[TW];
-#pragma unroll
-  for (int u = 0; u < TW; ++u) {
-    const int col = w * (H / NW) + 16 * u + (lane & 15);
-    wa0[u] = P[r.off[P_WA2] + col];
-    wa1[u] = P[r.off[P_WA2] + H + col];
-    wc[u] = P[r.off[P_WC2] + col];
-  }
-  const float ba0 = P[r.off[P_BA2]], ba1 = P[r.off[P_BA2] + 1], bcv = P[r.off[P_BC2]];
-  const float ls0 = P[r.off[P_LOGSTD]], ls1 = P[r.off[P_LOGSTD] + 1];
-  // this lane's head row (lanes < RPW of wave w: row RPW w + lane) and its noise
-  const int hr = RPW * w + min(lane, RPW - 1);
-  const bool live = lane < RPW && hr < nrows;
-  const long b = row0 + min(hr, nrows - 1);
-  float n0 = 0.0f, n1 = 0.0f;
-  if (r.noise) n0 = r.noise[2 * b], n1 = r.noise[2 * b + 1];
-  f32x4 av[RB][TW], cv[RB][TW];
-  uint32_t mb[2] = {0u, 0u};
-  rows_forward<QH, NW, RT, true, D, 4, true, false>(R, r.states, nullptr, r.S, nrows, row0, P,
-                                                     r.off, P1, H1, P1, nullptr, nullptr,
-                                                     nullptr, nullptr, mb, av, cv PSEC_ARGS,
-                                                     &xpre);
-  const int g4 = lane >> 4, c16 = lane & 15;
-#pragma unroll
-  for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float p0 = 0.0f, p1 = 0.0f, pv = 0.0f;
-#pragma unroll
-      for (int u = 0; u < TW; ++u) {
-        p0 += av[rb][u][q] * wa0[u];
-        p1 += av[rb][u][q] * wa1[u];
-        pv += cv[rb][u][q] * wc[u];
-      }
-      p0 = row16_sum(p0), p1 = row16_sum(p1), pv = row16_sum(pv);
-      if (c16 == 0) HDOT[w][16 * rb + 4 * g4 + q] = f32x4{p0, p1, pv, 0.0f};
-    }
-  __syncthreads();
-  if (!live) return;
-  f32x4 dsum = HDOT[0][hr];
-#pragma unroll
-  for (int ww = 1; ww < NW; ++ww) dsum += HDOT[ww][hr];
-  const float mu0 = dsum[0] + ba0, mu1 = dsum[1] + ba1, val = dsum[2] + bcv;
-  float z0 = mu0, z1 = mu1, lp = 0.0f;
-  if (r.noise) {
-    // torch Normal: scale = exp(log_std); var = scale**2; log_scale = log(scale)
-    const float sc0 = expf(ls0), sc1 = expf(ls1);
-    const float var0 = sc0 * sc0, var1 = sc1 * sc1;
-    const float lsc0 = logf(sc0), lsc1 = logf(sc1);
-    const float LOG_SQRT_2PI = 0.91893853320467274178f;
-    z0 = mu0 + sc0 * n0;
-    z1 = mu1 + sc1 * n1;
-    const float d0 = z0 - mu0, d1 = z1 - mu1;
-    const float t0 = tanhf(z0), t1 = tanhf(z1);
-    const float lp0 = -(d0 * d0) / (2.0f * var0) - lsc0 - LOG_SQRT_2PI;
-    const float lp1 = -(d1 * d1) / (2.0f * var1) - lsc1 - LOG_SQRT_2PI;
-    lp = (lp0 - log1pf(-(t0 * t0) + 1e-6f)) + (lp1 - log1pf(-(t1 * t1) + 1e-6f));
-  }
-  r.action[2 * b] = tanhf(z0);
-  r.action[2 * b + 1] = tanhf(z1);
-  r.pre_tanh[2 * b] = z0;
-  r.pre_tanh[2 * b + 1] = z1;
-  r.logp[b] = lp;
-  r.value[b] = val;
+#include "ppo_act_c_body.inc"
+}
+
+// act_c_body over a dynamic-LDS arena (see rows_body_dyn)
+template <int QH, int NW, int RT>
+__device__ __forceinline__ void act_c_body_dyn(ActArgs r, float* arena) {
+  constexpr int H = 64 * QH;
+  constexpr int TW = H / NW / 16;
+  constexpr int RB = RT / 16;
+  constexpr int RPW = RT / NW;
+  constexpr int PH = lds_pitch(H), PXMAX = lds_pitch(kMaxRowS);
+  static_assert(TW * 16 * NW == H && PXMAX <= PH && RPW >= 1 && RPW <= 16, "ppo_act_c geometry");
+  static_assert(2 * RT * PH + 4 * NW * RT == act_c_lds_floats<QH, NW, RT>(), "arena layout");
+  float* const P01 = arena;
+  f32x4(*const HDOT)[RT] = reinterpret_cast<f32x4(*)[RT]>(arena + 2 * RT * PH);
+#include "ppo_act_c_body.inc"
 }
 
 template <int QH, int NW, int RT>
@@ -2578,6 +2314,102 @@ ppo_act_c_grp(const ActArgs* __restrict__ tab) {
   act_c_body<QH, NW, RT>(tab[blockIdx.y]);
 }
 
+#ifdef HWY_PPO_MIXED_TU
+// ----------------------------------------------------------------------------- mixed widths
+// Grouped learners whose hidden widths differ (hwy_ppo_mixed_*).  ppo_wgrad_grp, ppo_wsum_grp and
+// ppo_adam_tiles_grp read H from each learner's arguments already; the row and act kernels are
+// templated on the width, so these kernels read learner y's width class qh[y] = H / 64 and run,
+// uniformly for the whole workgroup, the solo instantiation's body for it: the same code as the
+// solo launch, so the same bits.  One kernel covers one wave-count class (NW = 8: H 128, 256,
+// 384, 512; NW = 4: H 64, 192, 320, 448), because the solo kernels' workgroup size differs
+// between them; a workgroup of a learner of the other class, or past its learner's row grid,
+// returns whole before any barrier.  The bodies take their LDS images from the kernel's dynamic
+// LDS (the *_dyn bodies), which the launch sizes to the widest learner of its class
+// (mix_*_lds_bytes): static images of several instantiations would add up (33 + 66 + 99 + 132 KB)
+// past the compute unit's 160 KB.
+extern __shared__ __attribute__((aligned(16))) float mix_lds[];
+
+template <int NW>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_rows_mix(const RowArgs* __restrict__ tab,
+                                                           const GroupLim* __restrict__ lim,
+                                                           const int* __restrict__ qh) {
+  const int q = qh[blockIdx.y];
+  if ((q & 1) != (NW == 4 ? 1 : 0) || (int)blockIdx.x >= lim[blockIdx.y].rows) return;
+  const RowArgs& r = tab[blockIdx.y];
+  if constexpr (NW == 8) {
+    switch (q) {
+      case 2: rows_body_dyn<2, 8, kRowTile>(r, mix_lds); break;
+      case 4: rows_body_dyn<4, 8, kRowTile>(r, mix_lds); break;
+      case 6: rows_body_dyn<6, 8, kRowTile>(r, mix_lds); break;
+      case 8: rows_body_dyn<8, 8, kRowTile>(r, mix_lds); break;
+      default: break;
+    }
+  } else {
+    switch (q) {
+      case 1: rows_body_dyn<1, 4, kRowTile>(r, mix_lds); break;
+      case 3: rows_body_dyn<3, 4, kRowTile>(r, mix_lds); break;
+      case 5: rows_body_dyn<5, 4, kRowTile>(r, mix_lds); break;
+      case 7: rows_body_dyn<7, 4, kRowTile>(r, mix_lds); break;
+      default: break;
+    }
+  }
+}
+
+// TL: the learners carry tile images; H = 256 then runs the compact body, as hwy_ppo_act does
+template <int NW, bool TL>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_act_mix(const ActArgs* __restrict__ tab,
+                                                          const int* __restrict__ qh) {
+  const int q = qh[blockIdx.y];
+  if ((q & 1) != (NW == 4 ? 1 : 0)) return;
+  const ActArgs& r = tab[blockIdx.y];
+  if constexpr (NW == 8) {
+    switch (q) {
+      case 2: act_body_dyn<2, 8, TL>(r, mix_lds); break;
+      case 4:
+        if constexpr (TL)
+          act_c_body_dyn<4, 8, kRowTile>(r, mix_lds);
+        else
+          act_body_dyn<4, 8, TL>(r, mix_lds);
+        break;
+      case 6: act_body_dyn<6, 8, TL>(r, mix_lds); break;
+      case 8: act_body_dyn<8, 8, TL>(r, mix_lds); break;
+      default: break;
+    }
+  } else {
+    switch (q) {
+      case 1: act_body_dyn<1, 4, TL>(r, mix_lds); break;
+      case 3: act_body_dyn<3, 4, TL>(r, mix_lds); break;
+      case 5: act_body_dyn<5, 4, TL>(r, mix_lds); break;
+      case 7: act_body_dyn<7, 4, TL>(r, mix_lds); break;
+      default: break;
+    }
+  }
+}
+
+// dynamic LDS bytes of the mixed kernels for one learner's width class
+inline int mix_rows_lds_bytes(int qh) {
+  constexpr int T = kRowTile;
+  const int f[9] = {0,
+                    rows_lds_floats<1, 4, T>(), rows_lds_floats<2, 8, T>(),
+                    rows_lds_floats<3, 4, T>(), rows_lds_floats<4, 8, T>(),
+                    rows_lds_floats<5, 4, T>(), rows_lds_floats<6, 8, T>(),
+                    rows_lds_floats<7, 4, T>(), rows_lds_floats<8, 8, T>()};
+  return 4 * f[qh];
+}
+inline int mix_act_lds_bytes(int qh, bool tiles) {
+  if (tiles && qh == 4) return 4 * act_c_lds_floats<4, 8, kRowTile>();
+  const int f[9] = {0, act_lds_floats<1>(), act_lds_floats<2>(), act_lds_floats<3>(),
+                    act_lds_floats<4>(), act_lds_floats<5>(), act_lds_floats<6>(),
+                    act_lds_floats<7>(), act_lds_floats<8>()};
+  return 4 * f[qh];
+}
+constexpr int kMixLdsMax = 160 * 1024;  // LDS of a gfx950 compute unit
+static_assert(4 * rows_lds_floats<8, 8, kRowTile>() <= kMixLdsMax &&
+                  4 * rows_lds_floats<7, 4, kRowTile>() <= kMixLdsMax &&
+                  4 * act_lds_floats<8>() <= kMixLdsMax,
+              "the widest learner's images fit a compute unit's LDS");
+
+#endif
 template <int AM, int BM, int EPI>
 int launch_gemm(const GemmArgs& g, int splits, hipStream_t s) {
   dim3 grid((g.M + kTile - 1) / kTile, (g.N + kTile - 1) / kTile, splits);
@@ -2602,29 +2434,6 @@ GemmArgs gemm_args() {
 }  // namespace
 
 extern "C" {
-
-int hwy_ppo_param_layout(const hwy_ppo_dims* d, int64_t* offsets, int64_t* numel) {
-  if (!d || d->A != 2 || d->H < 64 || d->H % 64 || d->S < 1 || d->B < 1) return -1;
-  Layout L = make_layout(*d);
-  if (offsets)
-    for (int i = 0; i < 13; ++i) offsets[i] = L.off[i];
-  if (numel) *numel = L.numel;
-  return 0;
-}
-
-int64_t hwy_ppo_workspace_bytes(const hwy_ppo_dims* d) {
-  if (!d || d->A != 2 || d->H < 64 || d->H % 64 || d->H > 512 || d->S < 1 || d->B < 1) return -1;
-  int64_t bytes = 0;
-  carve(*d, nullptr, &bytes);
-  return bytes;
-}
-
-int64_t hwy_ppo_tile_image_offset(const hwy_ppo_dims* d) {
-  if (hwy_ppo_workspace_bytes(d) < 0 || !fused_ok(*d)) return -1;
-  char* base = reinterpret_cast<char*>(uintptr_t(1) << 20);  // carve only adds offsets to it
-  const Work w = carve(*d, base, nullptr);
-  return (int64_t)(reinterpret_cast<char*>(w.wtile) - base);
-}
 
 // The fused path's per-kernel arguments for one learner's minibatch step (shared by the solo
 // launches and the grouped table of hwy_ppo_group_prepare).
@@ -2707,6 +2516,65 @@ static bool adam_tiles_ok(const hwy_ppo_args& a, const OptArgs& o, const Work& w
 static int adam_tiles_grid(const OptArgs& o) {
   const int nsmall = (int)((o.run_pre[4] + 1023) / 1024);
   return o.nwg1 + 3 * o.nwgh + nsmall;
+}
+
+// ---- grouped learners (include/hwy_ppo.h): the device table of one minibatch step is
+// [G RowArgs | G WgArgs | G OptArgs | G GroupLim], each section 256-byte aligned.  The learners
+// share B and H (so every learner takes the 16-row tiles and the same row-kernel grid); their
+// state dims may differ, which changes the weight-gradient tile count and Adam's W1 blocks, so
+// each launch covers the largest learner's grid and a learner's surplus workgroups exit.
+static int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
+static int64_t grp_row_off(int) { return 0; }
+static int64_t grp_wg_off(int G) { return align256((int64_t)G * sizeof(RowArgs)); }
+static int64_t grp_opt_off(int G) { return grp_wg_off(G) + align256((int64_t)G * sizeof(WgArgs)); }
+static int64_t grp_lim_off(int G) { return grp_opt_off(G) + align256((int64_t)G * sizeof(OptArgs)); }
+
+static bool group_dims_ok(const hwy_ppo_dims& d) {
+  if (hwy_ppo_workspace_bytes(&d) < 0 || !fused_ok(d) || d.A != 2 || d.B < 1) return false;
+  char* base = reinterpret_cast<char*>(uintptr_t(1) << 20);  // carve only adds offsets to it
+  const Work w = carve(d, base, nullptr);
+  // 16-row tiles (minibatches below the 32-row threshold) and one workgroup per (tile, slice):
+  // the balanced weight-gradient partition reads gridDim.x, which the grouped launch widens
+  return w.fused && w.rt == kRowTile && !w.bal;
+}
+
+// one learner's grids (the solo launches'): rows, ppo_wgrad, ppo_wsum, ppo_adam_tiles
+static GroupLim group_lim(const hwy_ppo_dims& d) {
+  char* base = reinterpret_cast<char*>(uintptr_t(1) << 20);
+  const Work w = carve(d, base, nullptr);
+  hwy_ppo_args geom = {};
+  geom.dims = d;
+  const OptArgs og = opt_args(geom, make_layout(d), w);
+  GroupLim l;
+  l.rows = w.n1, l.wgrad = w.grid2, l.wsum = (w.tac + w.t2 + w.t1) * (kWgTM * kWgTN / 1024);
+  l.adam = adam_tiles_grid(og);
+  return l;
+}
+
+// Everything but the mixed-width entry points (this file's head: the two translation units)
+#ifndef HWY_PPO_MIXED_TU
+
+int hwy_ppo_param_layout(const hwy_ppo_dims* d, int64_t* offsets, int64_t* numel) {
+  if (!d || d->A != 2 || d->H < 64 || d->H % 64 || d->S < 1 || d->B < 1) return -1;
+  Layout L = make_layout(*d);
+  if (offsets)
+    for (int i = 0; i < 13; ++i) offsets[i] = L.off[i];
+  if (numel) *numel = L.numel;
+  return 0;
+}
+
+int64_t hwy_ppo_workspace_bytes(const hwy_ppo_dims* d) {
+  if (!d || d->A != 2 || d->H < 64 || d->H % 64 || d->H > 512 || d->S < 1 || d->B < 1) return -1;
+  int64_t bytes = 0;
+  carve(*d, nullptr, &bytes);
+  return bytes;
+}
+
+int64_t hwy_ppo_tile_image_offset(const hwy_ppo_dims* d) {
+  if (hwy_ppo_workspace_bytes(d) < 0 || !fused_ok(*d)) return -1;
+  char* base = reinterpret_cast<char*>(uintptr_t(1) << 20);  // carve only adds offsets to it
+  const Work w = carve(*d, base, nullptr);
+  return (int64_t)(reinterpret_cast<char*>(w.wtile) - base);
 }
 
 // mask (fused path; hwy_ppo_time_kernels launches them one at a time): bit 0 ppo_rows, bit 1
@@ -3027,39 +2895,6 @@ int hwy_ppo_act(const hwy_ppo_act_args* a, void* stream) {
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// ---- grouped learners (include/hwy_ppo.h): the device table of one minibatch step is
-// [G RowArgs | G WgArgs | G OptArgs | G GroupLim], each section 256-byte aligned.  The learners
-// share B and H (so every learner takes the 16-row tiles and the same row-kernel grid); their
-// state dims may differ, which changes the weight-gradient tile count and Adam's W1 blocks, so
-// each launch covers the largest learner's grid and a learner's surplus workgroups exit.
-static int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
-static int64_t grp_row_off(int) { return 0; }
-static int64_t grp_wg_off(int G) { return align256((int64_t)G * sizeof(RowArgs)); }
-static int64_t grp_opt_off(int G) { return grp_wg_off(G) + align256((int64_t)G * sizeof(WgArgs)); }
-static int64_t grp_lim_off(int G) { return grp_opt_off(G) + align256((int64_t)G * sizeof(OptArgs)); }
-
-static bool group_dims_ok(const hwy_ppo_dims& d) {
-  if (hwy_ppo_workspace_bytes(&d) < 0 || !fused_ok(d) || d.A != 2 || d.B < 1) return false;
-  char* base = reinterpret_cast<char*>(uintptr_t(1) << 20);  // carve only adds offsets to it
-  const Work w = carve(d, base, nullptr);
-  // 16-row tiles (minibatches below the 32-row threshold) and one workgroup per (tile, slice):
-  // the balanced weight-gradient partition reads gridDim.x, which the grouped launch widens
-  return w.fused && w.rt == kRowTile && !w.bal;
-}
-
-// one learner's grids (the solo launches'): rows, ppo_wgrad, ppo_wsum, ppo_adam_tiles
-static GroupLim group_lim(const hwy_ppo_dims& d) {
-  char* base = reinterpret_cast<char*>(uintptr_t(1) << 20);
-  const Work w = carve(d, base, nullptr);
-  hwy_ppo_args geom = {};
-  geom.dims = d;
-  const OptArgs og = opt_args(geom, make_layout(d), w);
-  GroupLim l;
-  l.rows = w.n1, l.wgrad = w.grid2, l.wsum = (w.tac + w.t2 + w.t1) * (kWgTM * kWgTN / 1024);
-  l.adam = adam_tiles_grid(og);
-  return l;
-}
-
 int64_t hwy_ppo_group_table_bytes(const hwy_ppo_dims* d, int G) {
   if (!d || G < 1 || !group_dims_ok(*d)) return -1;
   return grp_lim_off(G) + align256((int64_t)G * sizeof(GroupLim));
@@ -3235,5 +3070,200 @@ int hwy_ppo_debug_sections(unsigned long long* out, int reset) {
   return 0;
 }
 #endif
+
+#else  // HWY_PPO_MIXED_TU
+
+// ---- grouped learners of different hidden widths (include/hwy_ppo.h): the step table is the
+// grouped one plus each learner's width class, [G RowArgs | G WgArgs | G OptArgs | G GroupLim |
+// G int32 H/64]; the act table is [G ActArgs | G int32 H/64].
+static int64_t mix_qh_off(int G) { return grp_lim_off(G) + align256((int64_t)G * sizeof(GroupLim)); }
+static int64_t mix_act_qh_off(int G) { return align256((int64_t)G * sizeof(ActArgs)); }
+
+// The mixed kernels' dynamic LDS passes the 64-KB default limit: raised here, to the widest
+// learner the kernel can hold, from the prepare calls (never inside a capture).
+static bool mix_raise_lds(const void* kernel, int bytes) {
+  return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) ==
+         hipSuccess;
+}
+
+int64_t hwy_ppo_mixed_table_bytes(const hwy_ppo_dims* d, int G) {
+  if (!d || G < 1) return -1;
+  for (int g = 0; g < G; ++g)
+    if (d[g].B != d[0].B || d[g].A != d[0].A || !group_dims_ok(d[g])) return -1;
+  return mix_qh_off(G) + align256((int64_t)G * sizeof(int32_t));
+}
+
+int hwy_ppo_mixed_prepare(const hwy_ppo_args* a, int G, void* table, hwy_ppo_mixed_plan* plan,
+                          void* stream) {
+  if (!a || G < 1 || !table || !plan) return -1;
+  const hwy_ppo_dims& d0 = a[0].dims;
+  hwy_ppo_mixed_plan p = {};
+  p.G = G, p.B = d0.B;
+  for (int g = 0; g < G; ++g) {
+    const hwy_ppo_args& ag = a[g];
+    if (ag.dims.B != d0.B || ag.dims.A != d0.A || !group_dims_ok(ag.dims) || ag.grads_modified ||
+        !ag.workspace || !ag.counters || !ag.params || !ag.grads || !ag.adam_m || !ag.adam_v)
+      return -1;
+  }
+  const int64_t bytes = mix_qh_off(G) + align256((int64_t)G * sizeof(int32_t));
+  char* host = static_cast<char*>(calloc((size_t)bytes, 1));
+  if (!host) return -2;
+  int rc = 0;
+  for (int g = 0; g < G && rc == 0; ++g) {
+    const hwy_ppo_args& ag = a[g];
+    const hwy_ppo_dims& d = ag.dims;
+    const Layout L = make_layout(d);
+    const Work w = carve(d, ag.workspace, nullptr);
+    const OptArgs o = opt_args(ag, L, w);
+    if (!adam_tiles_ok(ag, o, w)) {
+      rc = -1;
+      break;
+    }
+    reinterpret_cast<RowArgs*>(host + grp_row_off(G))[g] = row_args(ag, L, w);
+    reinterpret_cast<WgArgs*>(host + grp_wg_off(G))[g] = wg_args(ag, L, w);
+    reinterpret_cast<OptArgs*>(host + grp_opt_off(G))[g] = o;
+    const GroupLim l = group_lim(d);
+    reinterpret_cast<GroupLim*>(host + grp_lim_off(G))[g] = l;
+    const int qh = d.H / 64, cls = qh & 1;
+    reinterpret_cast<int32_t*>(host + mix_qh_off(G))[g] = qh;
+    p.present[cls] += 1;
+    p.grid_rows[cls] = std::max(p.grid_rows[cls], l.rows);
+    p.lds_bytes[cls] = std::max(p.lds_bytes[cls], mix_rows_lds_bytes(qh));
+    p.grid_wgrad = std::max(p.grid_wgrad, l.wgrad);
+    p.grid_wsum = std::max(p.grid_wsum, l.wsum), p.grid_adam = std::max(p.grid_adam, l.adam);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (rc == 0 && p.present[0] &&
+      !mix_raise_lds((const void*)ppo_rows_mix<8>, 4 * rows_lds_floats<8, 8, kRowTile>()))
+    rc = -2;
+  if (rc == 0 && p.present[1] &&
+      !mix_raise_lds((const void*)ppo_rows_mix<4>, 4 * rows_lds_floats<7, 4, kRowTile>()))
+    rc = -2;
+  if (rc == 0 && (hipMemcpyAsync(table, host, (size_t)bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+                  hipStreamSynchronize(s) != hipSuccess))
+    rc = -2;
+  free(host);
+  if (rc == 0) *plan = p;
+  return rc;
+}
+
+int hwy_ppo_mixed_step(const hwy_ppo_mixed_plan* plan, const void* table, void* stream) {
+  if (!plan || !table || plan->G < 1 || plan->grid_wgrad < 1 || plan->grid_wsum < 1 ||
+      plan->grid_adam < 1 || (!plan->present[0] && !plan->present[1]))
+    return -1;
+  for (int c = 0; c < 2; ++c)
+    if (plan->present[c] && (plan->grid_rows[c] < 1 || plan->lds_bytes[c] < 1 ||
+                             plan->lds_bytes[c] > kMixLdsMax))
+      return -1;
+  const int G = plan->G;
+  const char* t = static_cast<const char*>(table);
+  const RowArgs* tr = reinterpret_cast<const RowArgs*>(t + grp_row_off(G));
+  const WgArgs* tw = reinterpret_cast<const WgArgs*>(t + grp_wg_off(G));
+  const OptArgs* to = reinterpret_cast<const OptArgs*>(t + grp_opt_off(G));
+  const GroupLim* tl = reinterpret_cast<const GroupLim*>(t + grp_lim_off(G));
+  const int* tq = reinterpret_cast<const int*>(t + mix_qh_off(G));
+  hipStream_t s = (hipStream_t)stream;
+  int rc = 0;
+  if (plan->present[0]) {
+    hipLaunchKernelGGL((ppo_rows_mix<8>), dim3(plan->grid_rows[0], G), dim3(512),
+                       plan->lds_bytes[0], s, tr, tl, tq);
+    rc |= hipGetLastError() == hipSuccess ? 0 : -1;
+  }
+  if (plan->present[1]) {
+    hipLaunchKernelGGL((ppo_rows_mix<4>), dim3(plan->grid_rows[1], G), dim3(256),
+                       plan->lds_bytes[1], s, tr, tl, tq);
+    rc |= hipGetLastError() == hipSuccess ? 0 : -1;
+  }
+  hipLaunchKernelGGL(ppo_wgrad_grp, dim3(plan->grid_wgrad, G), dim3(64 * kWgWaves), 0, s, tw, tl);
+  rc |= hipGetLastError() == hipSuccess ? 0 : -1;
+  hipLaunchKernelGGL(ppo_wsum_grp, dim3(plan->grid_wsum, G), dim3(256), 0, s, tw, tl);
+  rc |= hipGetLastError() == hipSuccess ? 0 : -1;
+  hipLaunchKernelGGL(ppo_adam_tiles_grp, dim3(plan->grid_adam, G), dim3(256), 0, s, to, tl);
+  rc |= hipGetLastError() == hipSuccess ? 0 : -1;
+  return rc;
+}
+
+int64_t hwy_ppo_mixed_act_table_bytes(int G) {
+  return G < 1 ? -1 : mix_act_qh_off(G) + align256((int64_t)G * sizeof(int32_t));
+}
+
+int hwy_ppo_mixed_act_prepare(const hwy_ppo_act_args* a, int G, void* table,
+                              hwy_ppo_mixed_act_plan* plan, void* stream) {
+  if (!a || G < 1 || !table || !plan) return -1;
+  const hwy_ppo_dims& d = a[0].dims;
+  // the 16-row kernels only: at 64 x CUs rows the solo H = 256 call moves to 32-row tiles
+  if (d.B < 1 || d.B >= 64 * chip_geom().cus) return -1;
+  hwy_ppo_mixed_act_plan p = {};
+  p.G = G, p.B = d.B, p.tiles = a[0].tiles ? 1 : 0;
+  const int64_t bytes = hwy_ppo_mixed_act_table_bytes(G);
+  char* host = static_cast<char*>(calloc((size_t)bytes, 1));
+  if (!host) return -2;
+  int rc = 0;
+  for (int g = 0; g < G; ++g) {
+    const hwy_ppo_act_args& ag = a[g];
+    if (ag.dims.B != d.B || ag.dims.A != 2 || !fused_ok(ag.dims) ||
+        !ag.states || !ag.params || !ag.action || !ag.pre_tanh || !ag.logp || !ag.value ||
+        (!ag.tiles) != (!a[0].tiles) || (!ag.noise) != (!a[0].noise)) {
+      rc = -1;
+      break;
+    }
+    const Layout Lg = make_layout(ag.dims);
+    ActArgs r = {};
+    r.B = d.B, r.S = ag.dims.S, r.states = ag.states, r.params = ag.params, r.noise = ag.noise;
+    for (int i = 0; i < 13; ++i) r.off[i] = Lg.off[i];
+    r.action = ag.action, r.pre_tanh = ag.pre_tanh, r.logp = ag.logp, r.value = ag.value;
+    r.tiles = ag.tiles;
+    reinterpret_cast<ActArgs*>(host)[g] = r;
+    const int qh = ag.dims.H / 64, cls = qh & 1;
+    reinterpret_cast<int32_t*>(host + mix_act_qh_off(G))[g] = qh;
+    p.present[cls] += 1;
+    p.lds_bytes[cls] = std::max(p.lds_bytes[cls], mix_act_lds_bytes(qh, p.tiles != 0));
+  }
+  const int m8 = 4 * act_lds_floats<8>(), m4 = 4 * act_lds_floats<7>();
+  if (rc == 0 && p.present[0] &&
+      !(p.tiles ? mix_raise_lds((const void*)ppo_act_mix<8, true>, m8) : mix_raise_lds((const void*)ppo_act_mix<8, false>, m8)))
+    rc = -2;
+  if (rc == 0 && p.present[1] &&
+      !(p.tiles ? mix_raise_lds((const void*)ppo_act_mix<4, true>, m4) : mix_raise_lds((const void*)ppo_act_mix<4, false>, m4)))
+    rc = -2;
+  hipStream_t s = (hipStream_t)stream;
+  if (rc == 0 && (hipMemcpyAsync(table, host, (size_t)bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+                  hipStreamSynchronize(s) != hipSuccess))
+    rc = -2;
+  free(host);
+  if (rc == 0) *plan = p;
+  return rc;
+}
+
+int hwy_ppo_mixed_act(const hwy_ppo_mixed_act_plan* plan, const void* table, void* stream) {
+  if (!plan || !table || plan->G < 1 || plan->B < 1 || (!plan->present[0] && !plan->present[1]))
+    return -1;
+  for (int c = 0; c < 2; ++c)
+    if (plan->present[c] && (plan->lds_bytes[c] < 1 || plan->lds_bytes[c] > kMixLdsMax)) return -1;
+  const int G = plan->G;
+  const char* t = static_cast<const char*>(table);
+  const ActArgs* ta = reinterpret_cast<const ActArgs*>(t);
+  const int* tq = reinterpret_cast<const int*>(t + mix_act_qh_off(G));
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g((plan->B + kRowTile - 1) / kRowTile, G);
+  int rc = 0;
+  if (plan->present[0]) {
+    if (plan->tiles)
+      hipLaunchKernelGGL((ppo_act_mix<8, true>), g, dim3(512), plan->lds_bytes[0], s, ta, tq);
+    else
+      hipLaunchKernelGGL((ppo_act_mix<8, false>), g, dim3(512), plan->lds_bytes[0], s, ta, tq);
+    rc |= hipGetLastError() == hipSuccess ? 0 : -1;
+  }
+  if (plan->present[1]) {
+    if (plan->tiles)
+      hipLaunchKernelGGL((ppo_act_mix<4, true>), g, dim3(256), plan->lds_bytes[1], s, ta, tq);
+    else
+      hipLaunchKernelGGL((ppo_act_mix<4, false>), g, dim3(256), plan->lds_bytes[1], s, ta, tq);
+    rc |= hipGetLastError() == hipSuccess ? 0 : -1;
+  }
+  return rc;
+}
+
+#endif  // HWY_PPO_MIXED_TU
 
 }  // extern "C"

@@ -176,20 +176,12 @@ class ExperimentRunner:
         in order."""
         return self.launch_batch([exps])[0]
 
-    def launch_batch(self, cells) -> list:
-        """launch_group for several cells at once: each cell (experiments that differ only in
-        seed) becomes an ExperimentGroup, and the cells, which must share envs per experiment,
-        rollout length and hidden width (e.g. a sweep's four h256 conditions, whose state dims
-        differ), are stepped together by one GroupBatch: one acting launch, one env launch and
-        one grouped minibatch step for all their learners.  Every experiment stays bit-identical
-        to its solo launch().  Returns one list of status dicts per cell."""
-        import math
-
-        from ppo.group import GroupBatch, build_group
-        from training.routine import train_batch
-
-        cells = [list(c) for c in cells]
-        t0 = time.time()
+    @staticmethod
+    def check_batch(cells) -> None:
+        """launch_batch's argument checks (no device needed): within a cell the experiments
+        differ only in seed and name and use the vectorised loop; across cells they share what
+        one GroupBatch's launches share -- envs per experiment, rollout length, minibatch rows
+        and epochs -- and the training schedule.  The hidden width may differ between cells."""
         for exps in cells:
             key = {(e.condition, repr(e.hp), repr(sorted(e.extra.items())),
                     repr(e.env_config_overrides), e.max_episodes, e.target_reward) for e in exps}
@@ -198,12 +190,32 @@ class ExperimentRunner:
             if int(exps[0].extra.get("num_envs", 1)) <= 1:
                 raise ValueError("launch_group needs extra['num_envs'] > 1 (the vectorised loop)")
         first = [c[0] for c in cells]
-        shared = {(int(e.extra.get("num_envs", 1)), e.hp.steps_per_update, e.hp.hidden_dim,
-                   e.max_episodes, e.target_reward, e.extra.get("eval_interval", 50))
+        shared = {(int(e.extra.get("num_envs", 1)), e.hp.steps_per_update, e.hp.batch_size,
+                   e.hp.epochs, e.extra.get("num_minibatches"), e.max_episodes, e.target_reward,
+                   e.extra.get("eval_interval", 50))
                   for e in first}
         if len(shared) != 1:
             raise ValueError("launch_batch: the cells must share num_envs, steps_per_update, "
-                             "hidden_dim, max_episodes, target_reward and eval_interval")
+                             "batch_size, epochs, num_minibatches, max_episodes, target_reward "
+                             "and eval_interval (hidden_dim and the condition may differ)")
+
+    def launch_batch(self, cells) -> list:
+        """launch_group for several cells at once: each cell (experiments that differ only in
+        seed) becomes an ExperimentGroup, and the cells, which must share envs per experiment,
+        rollout length, minibatch rows and epochs (e.g. a sweep's conditions, whose state dims
+        differ, across its hidden widths), are stepped together by one GroupBatch: one set of
+        acting launches, one env launch and one grouped minibatch step for all their learners.
+        Every experiment stays bit-identical to its solo launch().  Returns one list of status
+        dicts per cell."""
+        import math
+
+        from ppo.group import GroupBatch, build_group
+        from training.routine import train_batch
+
+        cells = [list(c) for c in cells]
+        t0 = time.time()
+        self.check_batch(cells)
+        first = [c[0] for c in cells]
         results = [[{"experiment_name": e.name, "status": "FAILED"} for e in exps]
                    for exps in cells]
         loggers = []

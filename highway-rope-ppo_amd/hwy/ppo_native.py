@@ -609,6 +609,28 @@ class PpoGroupPlan(ctypes.Structure):
                 ("grid_wsum", ctypes.c_int32), ("grid_adam", ctypes.c_int32)]
 
 
+class PpoMixedPlan(ctypes.Structure):
+    _fields_ = [("G", ctypes.c_int32), ("B", ctypes.c_int32),
+                ("present", ctypes.c_int32 * 2), ("grid_rows", ctypes.c_int32 * 2),
+                ("lds_bytes", ctypes.c_int32 * 2), ("grid_wgrad", ctypes.c_int32),
+                ("grid_wsum", ctypes.c_int32), ("grid_adam", ctypes.c_int32)]
+
+    @property
+    def launches(self) -> int:
+        """Launches of one hwy_ppo_mixed_step: a row launch per wave-count class present, then
+        the weight-gradient, slice-sum and Adam launches."""
+        return sum(1 for c in self.present if c) + 3
+
+
+class PpoMixedActPlan(ctypes.Structure):
+    _fields_ = [("G", ctypes.c_int32), ("B", ctypes.c_int32), ("tiles", ctypes.c_int32),
+                ("present", ctypes.c_int32 * 2), ("lds_bytes", ctypes.c_int32 * 2)]
+
+    @property
+    def launches(self) -> int:
+        return sum(1 for c in self.present if c)
+
+
 def _bind_group(L):
     if getattr(L, "_grp_bound", False):
         return L
@@ -618,55 +640,101 @@ def _bind_group(L):
     L.hwy_ppo_group_step.argtypes = [ctypes.POINTER(PpoGroupPlan), ctypes.c_void_p,
                                      ctypes.c_void_p]
     L.hwy_ppo_group_step.restype = ctypes.c_int
+    # learners of different hidden widths (include/hwy_ppo.h); a development build of the
+    # library without them (make prof / waves) still serves groups of one width, and a mixed
+    # group on it fails in _need_mixed with a message instead of an AttributeError here
+    if hasattr(L, "hwy_ppo_mixed_step"):
+        L.hwy_ppo_mixed_table_bytes.argtypes = [ctypes.POINTER(PpoDims), ctypes.c_int]
+        L.hwy_ppo_mixed_table_bytes.restype = ctypes.c_int64
+        L.hwy_ppo_mixed_prepare.argtypes = [ctypes.POINTER(PpoArgs), ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.POINTER(PpoMixedPlan), ctypes.c_void_p]
+        L.hwy_ppo_mixed_prepare.restype = ctypes.c_int
+        L.hwy_ppo_mixed_step.argtypes = [ctypes.POINTER(PpoMixedPlan), ctypes.c_void_p,
+                                         ctypes.c_void_p]
+        L.hwy_ppo_mixed_step.restype = ctypes.c_int
+        L.hwy_ppo_mixed_act_table_bytes.argtypes = [ctypes.c_int]
+        L.hwy_ppo_mixed_act_table_bytes.restype = ctypes.c_int64
+        L.hwy_ppo_mixed_act_prepare.argtypes = [ctypes.POINTER(PpoActArgs), ctypes.c_int,
+                                                ctypes.c_void_p, ctypes.POINTER(PpoMixedActPlan),
+                                                ctypes.c_void_p]
+        L.hwy_ppo_mixed_act_prepare.restype = ctypes.c_int
+        L.hwy_ppo_mixed_act.argtypes = [ctypes.POINTER(PpoMixedActPlan), ctypes.c_void_p,
+                                        ctypes.c_void_p]
+        L.hwy_ppo_mixed_act.restype = ctypes.c_int
     L._grp_bound = True
     return L
 
 
+def _need_mixed(L):
+    if not hasattr(L, "hwy_ppo_mixed_step"):
+        raise RuntimeError("this libhwy build has no hwy_ppo_mixed_* entry points (learners of "
+                           "different hidden widths need the product library)")
+
+
 class GroupAct:
-    """ActorCritic.act for G agents (same hidden width and rows per agent; state dims may
-    differ) in ONE launch (hwy_ppo_group_act): agent g acts on its own B rows and writes its own
-    output rows, each bit for bit what fused_act(agent g, its rows) writes.  The kernel arguments
-    live in a device table prepared once per (buffers, weights) key, so the launch is
-    graph-capturable."""
+    """ActorCritic.act for G agents (the same rows per agent; state dims and hidden widths may
+    differ) in ONE set of launches: agent g acts on its own B rows and writes its own output
+    rows, each bit for bit what fused_act(agent g, its rows) writes.  Agents of one hidden width
+    take hwy_ppo_group_act (one launch); agents of different widths take hwy_ppo_mixed_act (one
+    launch per wave-count class present, ``launches_per_act``).  The kernel arguments live in a
+    device table prepared once per (buffers, weights) key, so the launch is graph-capturable."""
 
     def __init__(self, agents, B: int):
         self.agents = list(agents)
         self.G, self.B = len(self.agents), int(B)
-        self.L = _bind(lib())
+        self.L = _bind_group(_bind(lib()))
         self.S = [ag.actor_critic.shared[0].weight.shape[1] for ag in self.agents]
-        self.H = self.agents[0].actor_critic.shared[0].weight.shape[0]
-        if any(ag.actor_critic.shared[0].weight.shape[0] != self.H for ag in self.agents):
-            raise ValueError("grouped acting needs one hidden width")
+        self.Hs = [ag.actor_critic.shared[0].weight.shape[0] for ag in self.agents]
+        self.H = self.Hs[0]
+        self.mixed = len(set(self.Hs)) > 1
+        if self.mixed:
+            _need_mixed(self.L)
         self.dims = PpoDims(self.B, self.S[0], self.H, 2)
-        nb = self.L.hwy_ppo_group_act_table_bytes(self.G)
+        nb = (self.L.hwy_ppo_mixed_act_table_bytes(self.G) if self.mixed
+              else self.L.hwy_ppo_group_act_table_bytes(self.G))
         self.dev = self.agents[0].device
         self._tables = {}
         self._nb = int(nb)
+        # launches one launch() issues: 1 for one width; the wave-count classes present otherwise
+        self.launches_per_act = len({(H // 64) & 1 for H in self.Hs}) if self.mixed else 1
+        self.launch_calls = 0
 
     def tiles(self):
         out = []
-        for ag, S in zip(self.agents, self.S):
+        for ag, S, H in zip(self.agents, self.S, self.Hs):
             flat = flat_params(ag)[0]
-            out.append(act_tiles(ag, flat, S, self.H))
+            out.append(act_tiles(ag, flat, S, H))
+        if self.mixed and any(t is None for t in out) and any(t is not None for t in out):
+            # one launch streams tile images for every learner or for none: the learners that
+            # have no image in step yet (only H = 256 keeps an acting-only one) get one
+            out = [_act_tiles(ag, flat_params(ag)[0], S, H) if t is None else t
+                   for ag, S, H, t in zip(self.agents, self.S, self.Hs, out)]
         return out
 
-    def table(self, rows, tiles) -> torch.Tensor:
+    def table(self, rows, tiles):
         """The device argument table for these row addresses (cached by them): rows[g] =
-        (states, noise or None, action, pre_tanh, logp, value) device addresses of agent g."""
+        (states, noise or None, action, pre_tanh, logp, value) device addresses of agent g.
+        Returns the table, or (table, plan) for agents of different widths."""
         key = (tuple(rows), tuple(tiles), tuple(flat_params(ag)[0].data_ptr() for ag in self.agents))
         t = self._tables.get(key)
         if t is not None:
             return t
         arr = (PpoActArgs * self.G)()
-        for g, (ag, tl, r, S) in enumerate(zip(self.agents, tiles, rows, self.S)):
+        for g, (ag, tl, r, S, H) in enumerate(zip(self.agents, tiles, rows, self.S, self.Hs)):
             a = arr[g]
-            a.dims = PpoDims(self.B, S, self.H, 2)
+            a.dims = PpoDims(self.B, S, H, 2)
             a.states, a.noise, a.action, a.pre_tanh, a.logp, a.value = r
             a.params = flat_params(ag)[0].data_ptr()
             a.tiles = tl
         t = torch.empty(self._nb, dtype=torch.uint8, device=self.dev)
-        check(self.L.hwy_ppo_group_act_prepare(arr, self.G, t.data_ptr(), stream_ptr()),
-              "hwy_ppo_group_act_prepare")
+        if self.mixed:
+            plan = PpoMixedActPlan()
+            check(self.L.hwy_ppo_mixed_act_prepare(arr, self.G, t.data_ptr(), ctypes.byref(plan),
+                                                   stream_ptr()), "hwy_ppo_mixed_act_prepare")
+            t = (t, plan)
+        else:
+            check(self.L.hwy_ppo_group_act_prepare(arr, self.G, t.data_ptr(), stream_ptr()),
+                  "hwy_ppo_group_act_prepare")
         self._tables[key] = t
         return t
 
@@ -688,6 +756,11 @@ class GroupAct:
     def launch(self, rows, tiles=None):
         tiles = self.tiles() if tiles is None else tiles
         t = self.table(rows, tiles)
+        self.launch_calls += 1
+        if self.mixed:
+            check(self.L.hwy_ppo_mixed_act(ctypes.byref(t[1]), t[0].data_ptr(), stream_ptr()),
+                  "hwy_ppo_mixed_act")
+            return
         check(self.L.hwy_ppo_group_act(ctypes.byref(self.dims), self.G,
                                        int(tiles[0] is not None), t.data_ptr(), stream_ptr()),
               "hwy_ppo_group_act")
@@ -698,25 +771,37 @@ class GroupAct:
 
 
 class GroupStep:
-    """One minibatch step of G FusedPPO learners (same rows and hidden width; state dims may
-    differ) in four launches (hwy_ppo_group_step): learner g's arguments are its own
-    FusedPPO._args, so each learner steps bit for bit as its solo run() would.  One device table
-    (and plan) per minibatch index."""
+    """One minibatch step of G FusedPPO learners (same minibatch rows; state dims and hidden
+    widths may differ): learner g's arguments are its own FusedPPO._args, so each learner steps
+    bit for bit as its solo run() would.  Learners of one hidden width take hwy_ppo_group_step
+    (four launches); learners of different widths take hwy_ppo_mixed_step (a row launch per
+    wave-count class present, then three: ``launches_per_step``).  One device table (and plan)
+    per minibatch index."""
 
     def __init__(self, fused):
         self.fused = list(fused)
         self.G = len(self.fused)
         F0 = self.fused[0]
         self.L = _bind_group(F0.L)
-        if any(F.mb != F0.mb or F.H != F0.H for F in self.fused):
-            raise ValueError("grouped PPO step: the learners share minibatch rows and hidden width")
-        nb = self.L.hwy_ppo_group_table_bytes(ctypes.byref(F0.dims), self.G)
+        if any(F.mb != F0.mb for F in self.fused):
+            raise ValueError("grouped PPO step: the learners share minibatch rows")
+        self.mixed = any(F.H != F0.H for F in self.fused)
+        if self.mixed:
+            _need_mixed(self.L)
+            dims = (PpoDims * self.G)(*[F.dims for F in self.fused])
+            nb = self.L.hwy_ppo_mixed_table_bytes(dims, self.G)
+        else:
+            nb = self.L.hwy_ppo_group_table_bytes(ctypes.byref(F0.dims), self.G)
         if nb < 0:
-            raise ValueError(f"grouped PPO step: unsupported dims B={F0.mb} S={F0.S} H={F0.H} "
+            raise ValueError(f"grouped PPO step: unsupported dims B={F0.mb} "
+                             f"S={sorted({F.S for F in self.fused})} "
+                             f"H={sorted({F.H for F in self.fused})} "
                              "(16-row tiles: minibatches below 8,192 rows)")
         self._nb = int(nb)
         self.tables: List[torch.Tensor] = []
-        self.plans: List[PpoGroupPlan] = []
+        self.plans: list = []
+        self.launches_per_step = (len({(F.H // 64) & 1 for F in self.fused}) + 3
+                                  if self.mixed else 4)
 
     def prepare(self, per_learner_args) -> None:
         """per_learner_args[g][i]: learner g's PpoArgs of minibatch i."""
@@ -728,12 +813,22 @@ class GroupStep:
                 ctypes.memmove(ctypes.byref(arr[g]), ctypes.byref(per_learner_args[g][i]),
                                ctypes.sizeof(PpoArgs))
             t = torch.empty(self._nb, dtype=torch.uint8, device=self.fused[0].flat.device)
-            plan = PpoGroupPlan()
-            check(self.L.hwy_ppo_group_prepare(arr, self.G, t.data_ptr(), ctypes.byref(plan),
-                                               stream_ptr()), "hwy_ppo_group_prepare")
+            if self.mixed:
+                plan = PpoMixedPlan()
+                check(self.L.hwy_ppo_mixed_prepare(arr, self.G, t.data_ptr(), ctypes.byref(plan),
+                                                   stream_ptr()), "hwy_ppo_mixed_prepare")
+                self.launches_per_step = plan.launches
+            else:
+                plan = PpoGroupPlan()
+                check(self.L.hwy_ppo_group_prepare(arr, self.G, t.data_ptr(), ctypes.byref(plan),
+                                                   stream_ptr()), "hwy_ppo_group_prepare")
             self.tables.append(t)
             self.plans.append(plan)
 
     def step(self, i: int) -> None:
+        if self.mixed:
+            check(self.L.hwy_ppo_mixed_step(ctypes.byref(self.plans[i]), self.tables[i].data_ptr(),
+                                            stream_ptr()), "hwy_ppo_mixed_step")
+            return
         check(self.L.hwy_ppo_group_step(ctypes.byref(self.plans[i]), self.tables[i].data_ptr(),
                                         stream_ptr()), "hwy_ppo_group_step")

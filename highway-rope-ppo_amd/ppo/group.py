@@ -121,7 +121,7 @@ class ExperimentGroup:
         captured as one HIP graph once its launch arguments repeat."""
         self._draw_noise()
         tiles = self.act.tiles()  # also syncs acting-only tile images, outside any capture
-        key = (self.env._handle.value, self.env.launch_version, tuple(tiles))
+        key = (self.env._handle.value, self.env.launch_version, tuple(tiles), _flat_ptrs(self.agents))
         self._roll_graph, self._roll_key, self._roll_seen = _graph_run(
             self, self.use_graphs, key, lambda: self._steps(tiles), self._roll_graph,
             self._roll_key, self._roll_seen, "rollout")
@@ -236,6 +236,15 @@ class ExperimentGroup:
         return r[d != 0]
 
 
+def _flat_ptrs(agents) -> tuple:
+    """The agents' flat-parameter addresses: part of a rollout graph's key, as of
+    LockstepRollout._launch_key -- the acting table keys on them, so a graph captured before
+    flat_params rebuilt an agent's buffer would replay a table that points at the old weights."""
+    from hwy.ppo_native import flat_params
+
+    return tuple(flat_params(ag)[0].data_ptr() for ag in agents)
+
+
 def _graph_run(owner, use_graphs, key, steps, graph, gkey, seen, what):
     """LockstepRollout's issue policy for a launch sequence `steps`: replay the captured graph
     when its key repeats, run eagerly the first time a key is seen (allocations, argument
@@ -305,13 +314,17 @@ def _run_group_steps(owner, ctxs, runner):
 
 
 class GroupBatch:
-    """Several ExperimentGroups of one hidden width and the same rows per learner (a sweep's
-    cells that differ only in observation layout, e.g. the four h256 cells: no PE, RoPE, DistPE,
-    RankPE, whose state dims are 60 or 120) stepped as ONE set of launches: per rollout step one
+    """Several ExperimentGroups with the same rows per learner -- a sweep's cells, which may
+    differ in observation layout (state dims 60 or 120: no PE, RoPE, DistPE, RankPE) and in
+    hidden width (h128, h256, h384, ...) -- stepped as ONE set of launches: per rollout step the
     acting launch for every learner of every group and one env launch for every group's handle
-    (hwy_step_group); per minibatch step one grouped fused step over all their learners (hwy_ppo_group_step takes learners of
-    different state dims).  Each experiment stays bit-identical to its solo run: the same
-    kernel bodies per learner, each group's own generator order, GAE and normalisation."""
+    (hwy_step_group); per minibatch step one grouped fused step over all their learners.  Groups
+    of one hidden width take hwy_ppo_group_act / hwy_ppo_group_step (one acting launch, four per
+    step); groups of different widths take hwy_ppo_mixed_act / hwy_ppo_mixed_step, which add one
+    acting and one row launch when the widths span both wave-count classes (include/hwy_ppo.h).
+    The groups still share minibatch rows and count, epochs, envs per experiment and rollout
+    length.  Each experiment stays bit-identical to its solo run: the same kernel bodies per
+    learner, each group's own generator order, GAE and normalisation."""
 
     def __init__(self, groups, use_graphs: bool = True):
         from hwy.ppo_native import GroupAct
@@ -335,6 +348,12 @@ class GroupBatch:
         self.stats = {"rollout_replay": 0, "rollout_eager": 0, "rollout_capture": 0,
                       "update_prepare": 0, "update_capture": 0}
 
+    @property
+    def launches_per_step(self):
+        """Launches of one minibatch step over all the learners (GroupStep.launches_per_step);
+        None before the first update."""
+        return None if self._runner is None else self._runner[1].launches_per_step
+
     def _rows(self, t, deterministic=False):
         return [r for g in self.groups for r in g.act_rows(t, deterministic)]
 
@@ -353,7 +372,7 @@ class GroupBatch:
             g._draw_noise()
         tiles = self.act.tiles()
         key = (tuple((g.env._handle.value, g.env.launch_version) for g in self.groups),
-               tuple(tiles))
+               tuple(tiles), _flat_ptrs(self.agents))
         self._roll = _graph_run(self, self.use_graphs, key, lambda: self._steps(tiles), *self._roll,
                                 "rollout")
 

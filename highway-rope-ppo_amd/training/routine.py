@@ -128,10 +128,14 @@ def _run_eval_vector(env, agent, num_episodes, exp_seed):
 def evaluate_many(items, num_episodes=5):
     """evaluate(env, agent, num_episodes, exp_seed) for every (env, agent, exp_seed) of `items`,
     each result exactly what evaluate returns for it alone: the evaluations that are not memoised
-    run together, one grouped acting launch (hwy_ppo_group_act) and one grouped env launch
-    (hwy_step_group) per step over all their evaluation envs, the same kernels and the same
-    per-episode float64 sums as the solo loop.  Falls back to one evaluate per item where the
-    items cannot share launches (torch acting, mixed hidden widths, single items)."""
+    run together, one set of grouped acting launches (hwy_ppo_group_act, or hwy_ppo_mixed_act
+    when their hidden widths differ) and one grouped env launch (hwy_step_group) per step over all
+    their evaluation envs, the same kernels and the same per-episode float64 sums as the solo
+    loop.  Falls back to one evaluate per item where the items cannot share launches: torch
+    acting, a single item, or (_run_eval_group, agents of one width) weight tile images that only
+    some agents have -- agents of different widths never take that fallback, because
+    GroupAct.tiles() gives those without an image an acting-only one (hwy_ppo_act's two weight
+    paths give the same bits: tests/test_mixed_group_gpu.py)."""
     out = [None] * len(items)
     todo = []
     for i, (env, agent, seed) in enumerate(items):
@@ -141,21 +145,20 @@ def evaluate_many(items, num_episodes=5):
             out[i] = memo[1]
         else:
             todo.append(i)
-    groups = {}
+    grouped, solo = [], []
     for i in todo:
         env, agent, _ = items[i]
         ok = (_is_vector(env) and getattr(agent, "backend", "torch") != "torch"
               and agent.device.type == "cuda")
-        H = agent.actor_critic.shared[0].weight.shape[0] if ok else None
-        groups.setdefault(H, []).append(i)
-    for H, idx in groups.items():
-        if H is None or len(idx) < 2:
-            for i in idx:
-                out[i] = evaluate(items[i][0], items[i][1], num_episodes=num_episodes,
-                                  exp_seed=items[i][2])
-            continue
-        res = _run_eval_group([items[i] for i in idx], num_episodes)
-        for i, r in zip(idx, res):
+        (grouped if ok else solo).append(i)
+    if len(grouped) < 2:
+        solo, grouped = sorted(solo + grouped), []
+    for i in solo:
+        out[i] = evaluate(items[i][0], items[i][1], num_episodes=num_episodes,
+                          exp_seed=items[i][2])
+    if grouped:
+        res = _run_eval_group([items[i] for i in grouped], num_episodes)
+        for i, r in zip(grouped, res):
             env, agent, seed = items[i]
             env.unwrapped._eval_memo = (_eval_key(agent, num_episodes, seed), r)
             out[i] = r

@@ -139,6 +139,46 @@ int64_t hwy_ppo_group_act_table_bytes(int G);
 int hwy_ppo_group_act_prepare(const hwy_ppo_act_args* a /*[G]*/, int G, void* table, void* stream);
 int hwy_ppo_group_act(const hwy_ppo_dims* d, int G, int tiles, const void* table, void* stream);
 
+/* ---- Grouped learners of different hidden widths: the grouped calls above for learners that
+ * share B and A while H and S vary per learner (a sweep across hidden_dim in one set of
+ * launches).  The weight-gradient, slice-sum and Adam launches read each learner's H from the
+ * table; the row and act kernels read learner y's width class and run the solo kernel's body for
+ * it, so each learner stays bit for bit its solo run.  The solo kernels run 8 waves for
+ * H = 128, 256, 384, 512 (class 0) and 4 waves for H = 64, 192, 320, 448 (class 1); a launch covers
+ * one class, so a table holding both issues two row (or act) launches, each skipping the other
+ * class's learners.  The kernels take their LDS as dynamic LDS sized to the widest learner of the
+ * class (lds_bytes; prepare raises the kernels' dynamic-LDS limit, never a launch).
+ *
+ * Every learner must satisfy what hwy_ppo_group_prepare asks of one (fused path, 16-row tiles,
+ * grads_modified == 0, 16-byte aligned flat buffers).  Prepare is synchronous (it waits for
+ * `stream`) and not capturable; hwy_ppo_mixed_step / hwy_ppo_mixed_act are asynchronous, allocate
+ * nothing and are hipGraph-capturable.  -1 bad arguments / unsupported dims, -2 HIP error. */
+typedef struct hwy_ppo_mixed_plan {
+  int32_t G, B;              /* learners; shared minibatch rows */
+  int32_t present[2];        /* learners of wave-count class 0 (8 waves) / 1 (4 waves): 0 = none */
+  int32_t grid_rows[2];      /* each class's row grid */
+  int32_t lds_bytes[2];      /* each class's dynamic LDS: its widest learner's images */
+  int32_t grid_wgrad, grid_wsum, grid_adam; /* the largest learner's */
+} hwy_ppo_mixed_plan;
+int64_t hwy_ppo_mixed_table_bytes(const hwy_ppo_dims* d /*[G]*/, int G);
+int hwy_ppo_mixed_prepare(const hwy_ppo_args* a /*[G]*/, int G, void* table,
+                          hwy_ppo_mixed_plan* plan, void* stream);
+/* hwy_ppo_forward_backward + hwy_ppo_optimizer for every learner: one row launch per class
+ * present, then one launch each of the weight-gradient, slice-sum and Adam kernels. */
+int hwy_ppo_mixed_step(const hwy_ppo_mixed_plan* plan, const void* table, void* stream);
+/* hwy_ppo_act for G learners of different H (and S); all carry tile images or none do, all carry
+ * noise or none do; B below the 32-row-tile threshold (64 x CUs).  Each learner runs the kernel
+ * body its solo hwy_ppo_act call runs (with tile images H = 256 takes the compact one). */
+typedef struct hwy_ppo_mixed_act_plan {
+  int32_t G, B, tiles;       /* learners; rows per learner; tile images carried */
+  int32_t present[2];        /* as hwy_ppo_mixed_plan */
+  int32_t lds_bytes[2];
+} hwy_ppo_mixed_act_plan;
+int64_t hwy_ppo_mixed_act_table_bytes(int G);
+int hwy_ppo_mixed_act_prepare(const hwy_ppo_act_args* a /*[G]*/, int G, void* table,
+                              hwy_ppo_mixed_act_plan* plan, void* stream);
+int hwy_ppo_mixed_act(const hwy_ppo_mixed_act_plan* plan, const void* table, void* stream);
+
 /* Build flags of this library: bit 0 = development knobs compiled in (HWY_DEV_KNOBS: the
  * HWY_WG_BAL / HWY_ROWS_RT / HWY_WG_FILL environment variables are read), bit 1 = section clocks
  * (HWY_SECTION_PROFILE).  A product build returns 0 and reads no environment variable. */

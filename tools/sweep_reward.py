@@ -17,7 +17,7 @@ reproduce them exactly.  Also writes OUT/sweep.json (wall time, per-cell agreeme
 one line per cell.
 
     python tools/sweep_reward.py --out gpurun_out/sweep_reward [--cells sorted_h256 ...]
-        [--seeds 42 1042 ...] [--work /tmp/sweep_work] [--batch]
+        [--seeds 42 1042 ...] [--work /tmp/sweep_work] [--batch [--mixed]]
 """
 
 from __future__ import annotations
@@ -109,6 +109,9 @@ def main():
     p.add_argument("--batch", action="store_true",
                    help="run the cells of one hidden width as one ExperimentRunner.launch_batch "
                         "(one GroupBatch: shared acting, env and minibatch-step launches)")
+    p.add_argument("--mixed", action="store_true",
+                   help="with --batch: run ALL the cells, whatever their hidden widths, as one "
+                        "launch_batch (the mixed-width grouped launches, hwy_ppo_mixed_*)")
     args = p.parse_args()
     out = os.path.abspath(args.out)
     os.makedirs(out, exist_ok=True)
@@ -146,8 +149,11 @@ def main():
                                    max_episodes=args.episodes, target_reward=130.0, extra=extra,
                                    env_config_overrides={}))
         cell_exps[cell] = exps
-    # execution units: one launch_group per cell, or (--batch) one launch_batch per hidden width
-    if args.batch:
+    # execution units: one launch_group per cell, or (--batch) one launch_batch per hidden width,
+    # or (--batch --mixed) one launch_batch for every cell
+    if args.batch and args.mixed:
+        units = [list(args.cells)]
+    elif args.batch:
         by_h = {}
         for cell in args.cells:
             by_h.setdefault(CELLS[cell][1], []).append(cell)
@@ -155,7 +161,8 @@ def main():
     else:
         units = [[cell] for cell in args.cells]
     for unit in units:
-        tag = unit[0] if len(unit) == 1 else "batch_h%d" % CELLS[unit[0]][1]
+        tag = (unit[0] if len(unit) == 1 else
+               "batch_mixed" if args.mixed else "batch_h%d" % CELLS[unit[0]][1])
         work_dir = os.path.join(os.path.abspath(args.work) if args.work else out, tag)
         os.makedirs(work_dir, exist_ok=True)
         cwd = os.getcwd()
