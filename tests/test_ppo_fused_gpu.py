@@ -8,167 +8,11 @@ import pytest
 import torch
 
 from hwy.ppo_native import FusedPPO
+from ppo_ref_util import (_agents, _check_grads, _data, _fused_relu_masks, _gamma,  # noqa: F401
+                          _grad64, _MaskMul, _torch_grad)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
-
-
-def _agents(S, H, backend_b="hip", seed=0, **kw):
-    from ppo.agent import PPOAgent
-
-    torch.manual_seed(seed)
-    a = PPOAgent(S, 2, lr=3e-4, epochs=kw.get("epochs", 2), hidden_dim=H, device=DEV,
-                 use_graphs=False, backend="torch")
-    b = PPOAgent(S, 2, lr=3e-4, epochs=kw.get("epochs", 2), hidden_dim=H, device=DEV,
-                 use_graphs=kw.get("graphs", False), backend=backend_b)
-    b.actor_critic.load_state_dict(a.actor_critic.state_dict())
-    with torch.no_grad():
-        a.actor_critic.log_std.copy_(torch.tensor([-0.4, 0.3]))
-        b.actor_critic.log_std.copy_(torch.tensor([-0.4, 0.3]))
-    return a, b
-
-
-def _data(n, S, agent, seed=1):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    s = torch.randn(n, S, device=DEV, generator=g)
-    with torch.no_grad():
-        _, z, lp, v = agent.actor_critic.act(s, generator=g)
-    lp = lp + 0.05 * torch.randn(n, device=DEV, generator=g)  # ratios != 1, some clipped
-    adv = torch.randn(n, device=DEV, generator=g)
-    ret = v + torch.randn(n, device=DEV, generator=g)
-    perm = torch.randperm(n, device=DEV, generator=g)
-    return s, z.contiguous(), lp.contiguous(), adv, ret, perm
-
-
-class _MaskMul(torch.nn.Module):
-    """ReLU with its decisions given: z * mask."""
-
-    def __init__(self, mask):
-        super().__init__()
-        self.mask = mask
-
-    def forward(self, z):
-        return z * self.mask
-
-
-U32 = 2.0 ** -24  # binary32 unit roundoff
-
-
-def _gamma(k):
-    """Higham's gamma_k = k u / (1 - k u): the relative bound of any k-term fp32 sum/product
-    evaluation order (MFMA accumulation included; fp32 products of fp32 inputs are exact)."""
-    return k * U32 / (1.0 - k * U32)
-
-
-def _fused_relu_masks(F, agent, s, idx, mb, H):
-    """The fused step's own ReLU decisions for the four hidden layers, from its workspace rows
-    (h1, h2 post-ReLU; dac, which is zero wherever [a1 | c1]'s ReLU is off), each checked
-    against float64: a decision may differ from float64's only where the float64
-    pre-activation z lies within the per-element fp32 error bound of that element,
-    e = gamma_(K+1) (|W| |x| + |b|) + |W| e_x   (float64; K the fan-in, e_x the bound of the
-    layer's input, propagated through the 1-Lipschitz ReLU; e_x = 0 for the states).
-    Any fp32 evaluation order can land on either side of zero inside that bound and none can
-    outside it.  Returns the masks and the number of such rounding-level flips."""
-    import copy
-
-    ws = F.workspace.view(torch.float32)  # carve order: h1, h2, ac, dac (256-B aligned)
-    al = lambda k: (k + 63) // 64 * 64  # noqa: E731
-    n = mb * H
-    h1 = ws[0:n].view(mb, H).double()
-    h2 = ws[al(n):al(n) + n].view(mb, H).double()
-    o = 2 * al(n) + al(2 * n)
-    dac = ws[o:o + 2 * n].view(mb, 2 * H).double()
-    m = copy.deepcopy(agent.actor_critic).double()
-    x = s.double()[idx]
-    with torch.no_grad():
-        W1, b1 = m.shared[0].weight, m.shared[0].bias
-        W2, b2 = m.shared[2].weight, m.shared[2].bias
-        Wa, ba = m.actor_mean[0].weight, m.actor_mean[0].bias
-        Wc, bc = m.critic[0].weight, m.critic[0].bias
-        z1 = x @ W1.T + b1
-        e1 = _gamma(W1.shape[1] + 1) * (x.abs() @ W1.abs().T + b1.abs())
-        a1 = z1.clamp_min(0)
-        z2 = a1 @ W2.T + b2
-        e2 = _gamma(H + 1) * (a1.abs() @ W2.abs().T + b2.abs()) + e1 @ W2.abs().T
-        a2 = z2.clamp_min(0)
-        za = a2 @ Wa.T + ba
-        ea = _gamma(H + 1) * (a2.abs() @ Wa.abs().T + ba.abs()) + e2 @ Wa.abs().T
-        zc = a2 @ Wc.T + bc
-        ec = _gamma(H + 1) * (a2.abs() @ Wc.abs().T + bc.abs()) + e2 @ Wc.abs().T
-    pre = {"z1": (z1, e1), "z2": (z2, e2), "za": (za, ea), "zc": (zc, ec)}
-    ma = torch.where(dac[:, :H] != 0, 1.0, (za > 0).double())
-    mc = torch.where(dac[:, H:] != 0, 1.0, (zc > 0).double())
-    # rows whose actor / critic upstream gradient is nonzero: there dac == 0 means "ReLU off"
-    live_a = (dac[:, :H] != 0).any(1, keepdim=True)
-    live_c = (dac[:, H:] != 0).any(1, keepdim=True)
-    ma = torch.where(live_a & (dac[:, :H] == 0), 0.0, ma)
-    mc = torch.where(live_c & (dac[:, H:] == 0), 0.0, mc)
-    masks = {"z1": (h1 > 0).double(), "z2": (h2 > 0).double(), "za": ma, "zc": mc}
-    flips = 0
-    for k, mk in masks.items():
-        z, e = pre[k]
-        diff = mk != (z > 0).double()
-        flips += int(diff.sum())
-        if diff.any():
-            excess = (z[diff].abs() - e[diff]).max().item()
-            assert excess <= 0.0, (k, int(diff.sum()), excess)
-    return masks, flips
-
-
-def _grad64(agent, s, z, lp, adv, ret, idx, masks=None):
-    """The same minibatch loss and gradient (ppo/agent.py:216-248) in float64 autograd;
-    `masks` (from _fused_relu_masks) replaces the four ReLUs by those decisions."""
-    import copy
-
-    import torch.nn.functional as Fn
-    from torch.distributions import Normal
-
-    ag = agent
-    m = copy.deepcopy(ag.actor_critic).double()
-    if masks is not None:
-        m.shared[1], m.shared[3] = _MaskMul(masks["z1"]), _MaskMul(masks["z2"])
-        m.actor_mean[1], m.critic[1] = _MaskMul(masks["za"]), _MaskMul(masks["zc"])
-    s, z, lp, adv, ret = (t.double()[idx] for t in (s, z, lp, adv, ret))
-    mean, std, v = m(s)
-    dist = Normal(mean, std, validate_args=False)
-    nlp = (dist.log_prob(z) - torch.log1p(-torch.tanh(z).pow(2) + 1e-6)).sum(-1)
-    r = torch.exp(nlp - lp)
-    loss = (-torch.min(r * adv, torch.clamp(r, 1 - ag.eps_clip, 1 + ag.eps_clip) * adv).mean()
-            + ag.value_coef * Fn.mse_loss(v.squeeze(-1), ret)
-            - ag.entropy_coef * dist.entropy().sum(-1).mean())
-    loss.backward()
-    return {n: p.grad for n, p in m.named_parameters()}
-
-
-def _torch_grad(agent, s, z, lp, adv, ret, idx):
-    from ppo.agent import _Learner
-
-    L = _Learner(agent, s.shape[0], idx.numel(), 1, False)
-    L.bind(s, z, lp, adv, ret)
-    L.idx.copy_(idx)
-    L._fwd_bwd()
-    return L.flat_grad.clone(), L.metrics[0].clone()
-
-
-def _check_grads(ga, gb, g64, msg=""):
-    """Fused gradients (gb) against float64 autograd (g64) and torch fp32 (ga): elementwise
-    agreement with float64 or with torch fp32 (whichever the fp32 rounding of the shape
-    allows), and never further from float64 than torch fp32 is, up to rounding.  Returns the
-    largest fused error relative to each parameter's gradient scale."""
-    worst = 0.0
-    for name, pa in ga.items():
-        ref = g64[name]
-        t32 = pa.grad.double()
-        scale = max(ref.abs().max().item(), 1e-3)
-        got = gb[name].grad.double()
-        ok64 = torch.allclose(got, ref, rtol=1e-3, atol=2e-5 * scale)
-        ok32 = torch.allclose(got, t32, rtol=1e-3, atol=2e-5 * scale)
-        e_fused = (got - ref).abs().max().item()
-        e_torch = (t32 - ref).abs().max().item()
-        assert ok64 or ok32, (msg, name, e_fused, e_torch)
-        assert e_fused <= 2 * e_torch + 2e-5 * scale, (msg, name, e_fused, e_torch)
-        worst = max(worst, e_fused / scale)
-    return worst
 
 
 @pytest.mark.parametrize("S,H,mb", [(60, 256, 4096), (60, 64, 256), (120, 512, 256), (136, 128, 128),
