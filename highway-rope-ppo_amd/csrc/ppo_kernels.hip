@@ -19,8 +19,8 @@
 // All GEMMs use v_mfma_f32_*_f32: exact fp32 products, fp32 accumulation.
 //
 // This file is compiled twice (Makefile).  ppo_kernels.o holds everything but the mixed-width
-// grouped kernels and their entry points (hwy_ppo_mixed_*); ppo_mixed.o, compiled with
-// -DHWY_PPO_MIXED_TU, holds only those.  They are kept apart because the existing kernels'
+// and scheduled grouped kernels and their entry points (hwy_ppo_mixed_*, hwy_ppo_sched_*);
+// ppo_mixed.o, compiled with -DHWY_PPO_MIXED_TU, holds only those.  They are kept apart because the existing kernels'
 // code generation turned out to depend on what else the unit holds (with the mixed kernels
 // beside them 27 of the 57 row / act kernels changed their VGPR counts, their source untouched):
 // in a unit of their own the mixed kernels leave every other kernel's registers, LDS and
@@ -2329,13 +2329,10 @@ ppo_act_c_grp(const ActArgs* __restrict__ tab) {
 // past the compute unit's 160 KB.
 extern __shared__ __attribute__((aligned(16))) float mix_lds[];
 
+// the solo row body of width class q (a learner of this kernel's wave-count class), uniformly for
+// the whole workgroup; shared by ppo_rows_mix and ppo_rows_sched
 template <int NW>
-__global__ void __launch_bounds__(64 * NW, 1) ppo_rows_mix(const RowArgs* __restrict__ tab,
-                                                           const GroupLim* __restrict__ lim,
-                                                           const int* __restrict__ qh) {
-  const int q = qh[blockIdx.y];
-  if ((q & 1) != (NW == 4 ? 1 : 0) || (int)blockIdx.x >= lim[blockIdx.y].rows) return;
-  const RowArgs& r = tab[blockIdx.y];
+__device__ __forceinline__ void rows_of_width(const RowArgs& r, int q) {
   if constexpr (NW == 8) {
     switch (q) {
       case 2: rows_body_dyn<2, 8, kRowTile>(r, mix_lds); break;
@@ -2353,6 +2350,91 @@ __global__ void __launch_bounds__(64 * NW, 1) ppo_rows_mix(const RowArgs* __rest
       default: break;
     }
   }
+}
+
+template <int NW>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_rows_mix(const RowArgs* __restrict__ tab,
+                                                           const GroupLim* __restrict__ lim,
+                                                           const int* __restrict__ qh) {
+  const int q = qh[blockIdx.y];
+  if ((q & 1) != (NW == 4 ? 1 : 0) || (int)blockIdx.x >= lim[blockIdx.y].rows) return;
+  rows_of_width<NW>(tab[blockIdx.y], q);
+}
+
+// ----------------------------------------------------------------------------- scheduled
+// Grouped learners whose minibatch rows, minibatch counts and epochs differ (hwy_ppo_sched_*):
+// the schedule of one whole update lives in the device table.  Slot s of an update is its s-th
+// grouped step; learner y takes part in it iff s < steps[y] = epochs[y] * nmb[y], and then runs
+// its solo step for minibatch s % nmb[y] (epoch-major, minibatch-minor: FusedPPO.run's order).
+// Its row arguments of minibatch i are entry row0[y] + i of a ragged array (the entries of one
+// learner differ only in idx); the weight-gradient, slice-sum and Adam arguments do not depend
+// on the minibatch.  A workgroup of a learner that sits the slot out returns whole before any
+// barrier and touches nothing of it; the bodies are the solo kernels', so a learner's bits are
+// its solo run's.
+//
+// Ordering: s = *base + slot, `slot` a launch argument (its place in a captured graph of P
+// slots) and `base` one word of the table that the step kernels only read.  It is written by
+// hwy_ppo_sched_begin (a memset node) and by ppo_sched_advance (one thread, an ordinary store),
+// both stream-ordered between whole slots, so no kernel reads it while another writes it.  The
+// slot is NOT derived from counters[1]: the row kernel's workgroup 0 increments the counters in
+// mid-kernel (ppo_rows_body.inc) while later workgroups of the same launch are still starting.
+struct SchedRec {
+  int row0, nmb, steps;
+};
+
+// learner y's minibatch index in slot base + slot, or -1 when it sits the slot out
+__device__ __forceinline__ int sched_minibatch(const SchedRec& c, const int* __restrict__ base,
+                                               int slot) {
+  const int s = *base + slot;
+  return (unsigned)s < (unsigned)c.steps ? s % c.nmb : -1;
+}
+
+template <int NW>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_rows_sched(const RowArgs* __restrict__ tab,
+                                                             const GroupLim* __restrict__ lim,
+                                                             const int* __restrict__ qh,
+                                                             const SchedRec* __restrict__ rec,
+                                                             const int* __restrict__ base,
+                                                             int slot) {
+  const int q = qh[blockIdx.y];
+  if ((q & 1) != (NW == 4 ? 1 : 0) || (int)blockIdx.x >= lim[blockIdx.y].rows) return;
+  const SchedRec c = rec[blockIdx.y];
+  const int i = sched_minibatch(c, base, slot);
+  if (i < 0) return;  // whole workgroup
+  rows_of_width<NW>(tab[c.row0 + i], q);
+}
+
+__global__ void __launch_bounds__(512) ppo_wgrad_sched(const WgArgs* __restrict__ tab,
+                                                       const GroupLim* __restrict__ lim,
+                                                       const SchedRec* __restrict__ rec,
+                                                       const int* __restrict__ base, int slot) {
+  if ((int)blockIdx.x >= lim[blockIdx.y].wgrad || sched_minibatch(rec[blockIdx.y], base, slot) < 0)
+    return;
+  ppo_wgrad_body(tab[blockIdx.y]);
+}
+
+__global__ void __launch_bounds__(256) ppo_wsum_sched(const WgArgs* __restrict__ tab,
+                                                      const GroupLim* __restrict__ lim,
+                                                      const SchedRec* __restrict__ rec,
+                                                      const int* __restrict__ base, int slot) {
+  if ((int)blockIdx.x >= lim[blockIdx.y].wsum || sched_minibatch(rec[blockIdx.y], base, slot) < 0)
+    return;
+  wsum_body(tab[blockIdx.y]);
+}
+
+__global__ void __launch_bounds__(256) ppo_adam_tiles_sched(const OptArgs* __restrict__ tab,
+                                                            const GroupLim* __restrict__ lim,
+                                                            const SchedRec* __restrict__ rec,
+                                                            const int* __restrict__ base,
+                                                            int slot) {
+  if ((int)blockIdx.x >= lim[blockIdx.y].adam || sched_minibatch(rec[blockIdx.y], base, slot) < 0)
+    return;
+  adam_tiles_body(tab[blockIdx.y]);
+}
+
+// base += slots, between two whole slots (one thread)
+__global__ void __launch_bounds__(64) ppo_sched_advance(int* base, int slots) {
+  if (threadIdx.x == 0) *base += slots;
 }
 
 // TL: the learners carry tile images; H = 256 then runs the compact body, as hwy_ppo_act does
@@ -3262,6 +3344,170 @@ int hwy_ppo_mixed_act(const hwy_ppo_mixed_act_plan* plan, const void* table, voi
     rc |= hipGetLastError() == hipSuccess ? 0 : -1;
   }
   return rc;
+}
+
+// ---- grouped learners with schedules of their own (include/hwy_ppo.h: hwy_ppo_sched_*).  The
+// table is [G WgArgs | G OptArgs | G GroupLim | G int32 H/64 | G SchedRec | slot base word |
+// sum(nmb) RowArgs], each section 256-byte aligned: the per-learner sections come first, so the
+// launch calls find every section from G alone, and the ragged row arguments (learner g owns
+// entries row0[g] .. row0[g] + nmb[g]) close it.
+static int64_t sch_wg_off(int) { return 0; }
+static int64_t sch_opt_off(int G) { return align256((int64_t)G * sizeof(WgArgs)); }
+static int64_t sch_lim_off(int G) { return sch_opt_off(G) + align256((int64_t)G * sizeof(OptArgs)); }
+static int64_t sch_qh_off(int G) { return sch_lim_off(G) + align256((int64_t)G * sizeof(GroupLim)); }
+static int64_t sch_rec_off(int G) { return sch_qh_off(G) + align256((int64_t)G * sizeof(int32_t)); }
+static int64_t sch_base_off(int G) { return sch_rec_off(G) + align256((int64_t)G * sizeof(SchedRec)); }
+static int64_t sch_row_off(int G) { return sch_base_off(G) + 256; }
+
+static int sched_gcd(int a, int b) {
+  while (b) {
+    const int t = a % b;
+    a = b, b = t;
+  }
+  return a;
+}
+
+static bool sched_plan_ok(const hwy_ppo_sched_plan* plan) {
+  if (!plan || plan->G < 1 || plan->grid_wgrad < 1 || plan->grid_wsum < 1 || plan->grid_adam < 1 ||
+      plan->max_steps < 1 || plan->period < 1 || (!plan->present[0] && !plan->present[1]))
+    return false;
+  for (int c = 0; c < 2; ++c)
+    if (plan->present[c] && (plan->grid_rows[c] < 1 || plan->lds_bytes[c] < 1 ||
+                             plan->lds_bytes[c] > kMixLdsMax))
+      return false;
+  return true;
+}
+
+int64_t hwy_ppo_sched_table_bytes(const hwy_ppo_dims* d, const int32_t* nmb, int G) {
+  if (!d || !nmb || G < 1) return -1;
+  int64_t rows = 0;
+  for (int g = 0; g < G; ++g) {
+    if (d[g].A != d[0].A || nmb[g] < 1 || !group_dims_ok(d[g])) return -1;
+    rows += nmb[g];
+  }
+  return sch_row_off(G) + align256(rows * (int64_t)sizeof(RowArgs));
+}
+
+int hwy_ppo_sched_prepare(const hwy_ppo_args* a, const int32_t* nmb, const int32_t* epochs, int G,
+                          void* table, hwy_ppo_sched_plan* plan, void* stream) {
+  if (!a || !nmb || !epochs || G < 1 || !table || !plan) return -1;
+  hwy_ppo_sched_plan p = {};
+  p.G = G;
+  int64_t rows = 0;
+  for (int g = 0; g < G; ++g) {
+    const hwy_ppo_args& ag = a[g];
+    if (ag.dims.A != a[0].dims.A || !group_dims_ok(ag.dims) || ag.grads_modified ||
+        nmb[g] < 1 || epochs[g] < 1 || (int64_t)nmb[g] * epochs[g] > (int64_t)1 << 30 ||
+        !ag.idx || !ag.workspace || !ag.counters || !ag.params || !ag.grads || !ag.adam_m ||
+        !ag.adam_v)
+      return -1;
+    rows += nmb[g];
+  }
+  if (rows > (int64_t)1 << 30) return -1;
+  const int64_t bytes = sch_row_off(G) + align256(rows * (int64_t)sizeof(RowArgs));
+  char* host = static_cast<char*>(calloc((size_t)bytes, 1));
+  if (!host) return -2;
+  int rc = 0;
+  int row0 = 0;
+  for (int g = 0; g < G && rc == 0; ++g) {
+    const hwy_ppo_args& ag = a[g];
+    const hwy_ppo_dims& d = ag.dims;
+    const Layout L = make_layout(d);
+    const Work w = carve(d, ag.workspace, nullptr);
+    const OptArgs o = opt_args(ag, L, w);
+    if (!adam_tiles_ok(ag, o, w)) {
+      rc = -1;
+      break;
+    }
+    // minibatch i reads rows idx + i * B of the learner's permutation; nothing else changes
+    RowArgs r = row_args(ag, L, w);
+    for (int i = 0; i < nmb[g]; ++i) {
+      r.idx = ag.idx + (int64_t)i * d.B;
+      reinterpret_cast<RowArgs*>(host + sch_row_off(G))[row0 + i] = r;
+    }
+    reinterpret_cast<WgArgs*>(host + sch_wg_off(G))[g] = wg_args(ag, L, w);
+    reinterpret_cast<OptArgs*>(host + sch_opt_off(G))[g] = o;
+    const GroupLim l = group_lim(d);
+    reinterpret_cast<GroupLim*>(host + sch_lim_off(G))[g] = l;
+    const int qh = d.H / 64, cls = qh & 1;
+    reinterpret_cast<int32_t*>(host + sch_qh_off(G))[g] = qh;
+    SchedRec c;
+    c.row0 = row0, c.nmb = nmb[g], c.steps = nmb[g] * epochs[g];
+    reinterpret_cast<SchedRec*>(host + sch_rec_off(G))[g] = c;
+    row0 += nmb[g];
+    p.present[cls] += 1;
+    p.grid_rows[cls] = std::max(p.grid_rows[cls], l.rows);
+    p.lds_bytes[cls] = std::max(p.lds_bytes[cls], mix_rows_lds_bytes(qh));
+    p.grid_wgrad = std::max(p.grid_wgrad, l.wgrad);
+    p.grid_wsum = std::max(p.grid_wsum, l.wsum), p.grid_adam = std::max(p.grid_adam, l.adam);
+    p.max_steps = std::max(p.max_steps, c.steps);
+    p.period = sched_gcd(p.period, c.steps);  // gcd(0, x) = x
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (rc == 0 && p.present[0] &&
+      !mix_raise_lds((const void*)ppo_rows_sched<8>, 4 * rows_lds_floats<8, 8, kRowTile>()))
+    rc = -2;
+  if (rc == 0 && p.present[1] &&
+      !mix_raise_lds((const void*)ppo_rows_sched<4>, 4 * rows_lds_floats<7, 4, kRowTile>()))
+    rc = -2;
+  // the slot base word is part of the copy: 0, as after hwy_ppo_sched_begin
+  if (rc == 0 && (hipMemcpyAsync(table, host, (size_t)bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+                  hipStreamSynchronize(s) != hipSuccess))
+    rc = -2;
+  free(host);
+  if (rc == 0) *plan = p;
+  return rc;
+}
+
+int hwy_ppo_sched_begin(const hwy_ppo_sched_plan* plan, void* table, void* stream) {
+  if (!sched_plan_ok(plan) || !table) return -1;
+  char* t = static_cast<char*>(table);
+  return hipMemsetAsync(t + sch_base_off(plan->G), 0, sizeof(int32_t), (hipStream_t)stream) ==
+                 hipSuccess
+             ? 0
+             : -2;
+}
+
+int hwy_ppo_sched_step(const hwy_ppo_sched_plan* plan, const void* table, int slot, void* stream) {
+  if (!sched_plan_ok(plan) || !table || slot < 0) return -1;
+  const int G = plan->G;
+  const char* t = static_cast<const char*>(table);
+  const RowArgs* tr = reinterpret_cast<const RowArgs*>(t + sch_row_off(G));
+  const WgArgs* tw = reinterpret_cast<const WgArgs*>(t + sch_wg_off(G));
+  const OptArgs* to = reinterpret_cast<const OptArgs*>(t + sch_opt_off(G));
+  const GroupLim* tl = reinterpret_cast<const GroupLim*>(t + sch_lim_off(G));
+  const int* tq = reinterpret_cast<const int*>(t + sch_qh_off(G));
+  const SchedRec* tc = reinterpret_cast<const SchedRec*>(t + sch_rec_off(G));
+  const int* tb = reinterpret_cast<const int*>(t + sch_base_off(G));
+  hipStream_t s = (hipStream_t)stream;
+  int rc = 0;
+  if (plan->present[0]) {
+    hipLaunchKernelGGL((ppo_rows_sched<8>), dim3(plan->grid_rows[0], G), dim3(512),
+                       plan->lds_bytes[0], s, tr, tl, tq, tc, tb, slot);
+    rc |= hipGetLastError() == hipSuccess ? 0 : -2;
+  }
+  if (plan->present[1]) {
+    hipLaunchKernelGGL((ppo_rows_sched<4>), dim3(plan->grid_rows[1], G), dim3(256),
+                       plan->lds_bytes[1], s, tr, tl, tq, tc, tb, slot);
+    rc |= hipGetLastError() == hipSuccess ? 0 : -2;
+  }
+  hipLaunchKernelGGL(ppo_wgrad_sched, dim3(plan->grid_wgrad, G), dim3(64 * kWgWaves), 0, s, tw, tl,
+                     tc, tb, slot);
+  rc |= hipGetLastError() == hipSuccess ? 0 : -2;
+  hipLaunchKernelGGL(ppo_wsum_sched, dim3(plan->grid_wsum, G), dim3(256), 0, s, tw, tl, tc, tb, slot);
+  rc |= hipGetLastError() == hipSuccess ? 0 : -2;
+  hipLaunchKernelGGL(ppo_adam_tiles_sched, dim3(plan->grid_adam, G), dim3(256), 0, s, to, tl, tc,
+                     tb, slot);
+  rc |= hipGetLastError() == hipSuccess ? 0 : -2;
+  return rc;
+}
+
+int hwy_ppo_sched_advance(const hwy_ppo_sched_plan* plan, void* table, int slots, void* stream) {
+  if (!sched_plan_ok(plan) || !table || slots < 0) return -1;
+  char* t = static_cast<char*>(table);
+  hipLaunchKernelGGL(ppo_sched_advance, dim3(1), dim3(1), 0, (hipStream_t)stream,
+                     reinterpret_cast<int*>(t + sch_base_off(plan->G)), slots);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 #endif  // HWY_PPO_MIXED_TU

@@ -34,6 +34,11 @@ from .config import Experiment
 from .wrappers import make_env
 
 
+# the grouped PPO step runs the 16-row-tile kernels: minibatches below 32 rows per compute unit,
+# taken here, without a device, at an MI355X's 256 compute units (GroupStep refuses the rest)
+GROUPED_MINIBATCH_ROWS = 32 * 256
+
+
 class DevicePool:
     """One HIP device per process (torch.distributed rank or LOCAL_RANK), not oversubscribed."""
 
@@ -177,11 +182,19 @@ class ExperimentRunner:
         return self.launch_batch([exps])[0]
 
     @staticmethod
-    def check_batch(cells) -> None:
+    def check_batch(cells, own_schedules: bool = False) -> None:
         """launch_batch's argument checks (no device needed): within a cell the experiments
         differ only in seed and name and use the vectorised loop; across cells they share what
-        one GroupBatch's launches share -- envs per experiment, rollout length, minibatch rows
-        and epochs -- and the training schedule.  The hidden width may differ between cells."""
+        one GroupBatch's launches share -- envs per experiment and rollout length -- and the
+        training schedule.  The condition and the hidden width may differ between cells.  The
+        update's own schedule (batch_size, num_minibatches, epochs) must be shared too, unless
+        ``own_schedules`` (what launch_batch passes): then it may differ between cells
+        (hwy_ppo_sched_*), and each cell's minibatches must all be of one size, below the grouped
+        step's 16-row-tile bound."""
+        import math
+
+        from ppo.agent import PPOAgent
+
         for exps in cells:
             key = {(e.condition, repr(e.hp), repr(sorted(e.extra.items())),
                     repr(e.env_config_overrides), e.max_episodes, e.target_reward) for e in exps}
@@ -190,23 +203,51 @@ class ExperimentRunner:
             if int(exps[0].extra.get("num_envs", 1)) <= 1:
                 raise ValueError("launch_group needs extra['num_envs'] > 1 (the vectorised loop)")
         first = [c[0] for c in cells]
-        shared = {(int(e.extra.get("num_envs", 1)), e.hp.steps_per_update, e.hp.batch_size,
-                   e.hp.epochs, e.extra.get("num_minibatches"), e.max_episodes, e.target_reward,
-                   e.extra.get("eval_interval", 50))
-                  for e in first}
-        if len(shared) != 1:
+
+        def shared(e):
+            return (int(e.extra.get("num_envs", 1)), e.hp.steps_per_update, e.max_episodes,
+                    e.target_reward, e.extra.get("eval_interval", 50))
+
+        def schedule(e):
+            return (e.hp.batch_size, e.hp.epochs, e.extra.get("num_minibatches"))
+
+        if not own_schedules and any((shared(e), schedule(e)) != (shared(first[0]),
+                                                                   schedule(first[0]))
+                                     for e in first):
             raise ValueError("launch_batch: the cells must share num_envs, steps_per_update, "
                              "batch_size, epochs, num_minibatches, max_episodes, target_reward "
                              "and eval_interval (hidden_dim and the condition may differ)")
+        for e in first:
+            if shared(e) != shared(first[0]):
+                raise ValueError(f"launch_batch: the cells must share num_envs, steps_per_update, "
+                                 f"max_episodes, target_reward and eval_interval (the condition, "
+                                 f"hidden_dim, batch_size, num_minibatches and epochs may differ): "
+                                 f"cell {e.name} has {shared(e)}, cell {first[0].name} "
+                                 f"{shared(first[0])}")
+            E = int(e.extra.get("num_envs", 1))
+            n = max(1, math.ceil(e.hp.steps_per_update / E)) * E
+            # PPOAgent.minibatch_sizes, which reads only these two attributes
+            sizes = PPOAgent.minibatch_sizes(
+                type("_Partition", (), {"num_minibatches": e.extra.get("num_minibatches"),
+                                        "batch_size": e.hp.batch_size})(), n)
+            if len(set(sizes)) != 1:
+                raise ValueError(f"launch_batch: cell {e.name} splits its {n} samples into "
+                                 f"minibatches of {sorted(set(sizes))} rows; a grouped update "
+                                 f"needs equal minibatches")
+            if sizes[0] >= GROUPED_MINIBATCH_ROWS:
+                raise ValueError(f"launch_batch: cell {e.name} has minibatches of {sizes[0]} rows; "
+                                 f"the grouped step takes the 16-row tiles, minibatches below "
+                                 f"{GROUPED_MINIBATCH_ROWS} rows")
 
     def launch_batch(self, cells) -> list:
         """launch_group for several cells at once: each cell (experiments that differ only in
-        seed) becomes an ExperimentGroup, and the cells, which must share envs per experiment,
-        rollout length, minibatch rows and epochs (e.g. a sweep's conditions, whose state dims
-        differ, across its hidden widths), are stepped together by one GroupBatch: one set of
-        acting launches, one env launch and one grouped minibatch step for all their learners.
-        Every experiment stays bit-identical to its solo launch().  Returns one list of status
-        dicts per cell."""
+        seed) becomes an ExperimentGroup, and the cells, which must share envs per experiment and
+        rollout length (e.g. a sweep's conditions, whose state dims differ, across its hidden
+        widths, batch sizes and epochs), are stepped together by one GroupBatch: one set of
+        acting launches, one env launch and one grouped minibatch step for all their learners;
+        cells whose batch_size, num_minibatches or epochs differ each keep their own minibatch
+        schedule inside those steps (hwy_ppo_sched_*).  Every experiment stays bit-identical to
+        its solo launch().  Returns one list of status dicts per cell."""
         import math
 
         from ppo.group import GroupBatch, build_group
@@ -214,7 +255,7 @@ class ExperimentRunner:
 
         cells = [list(c) for c in cells]
         t0 = time.time()
-        self.check_batch(cells)
+        self.check_batch(cells, own_schedules=True)
         first = [c[0] for c in cells]
         results = [[{"experiment_name": e.name, "status": "FAILED"} for e in exps]
                    for exps in cells]

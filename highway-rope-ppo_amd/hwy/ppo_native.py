@@ -631,6 +631,19 @@ class PpoMixedActPlan(ctypes.Structure):
         return sum(1 for c in self.present if c)
 
 
+class PpoSchedPlan(ctypes.Structure):
+    _fields_ = [("G", ctypes.c_int32),
+                ("present", ctypes.c_int32 * 2), ("grid_rows", ctypes.c_int32 * 2),
+                ("lds_bytes", ctypes.c_int32 * 2), ("grid_wgrad", ctypes.c_int32),
+                ("grid_wsum", ctypes.c_int32), ("grid_adam", ctypes.c_int32),
+                ("max_steps", ctypes.c_int32), ("period", ctypes.c_int32)]
+
+    @property
+    def launches(self) -> int:
+        """Launches of one hwy_ppo_sched_step (as PpoMixedPlan.launches)."""
+        return sum(1 for c in self.present if c) + 3
+
+
 def _bind_group(L):
     if getattr(L, "_grp_bound", False):
         return L
@@ -661,6 +674,22 @@ def _bind_group(L):
         L.hwy_ppo_mixed_act.argtypes = [ctypes.POINTER(PpoMixedActPlan), ctypes.c_void_p,
                                         ctypes.c_void_p]
         L.hwy_ppo_mixed_act.restype = ctypes.c_int
+    # learners with schedules of their own (hwy_ppo_sched_*), likewise only where the library
+    # has them
+    if hasattr(L, "hwy_ppo_sched_step"):
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        planp = ctypes.POINTER(PpoSchedPlan)
+        L.hwy_ppo_sched_table_bytes.argtypes = [ctypes.POINTER(PpoDims), i32p, ctypes.c_int]
+        L.hwy_ppo_sched_table_bytes.restype = ctypes.c_int64
+        L.hwy_ppo_sched_prepare.argtypes = [ctypes.POINTER(PpoArgs), i32p, i32p, ctypes.c_int,
+                                            ctypes.c_void_p, planp, ctypes.c_void_p]
+        L.hwy_ppo_sched_prepare.restype = ctypes.c_int
+        L.hwy_ppo_sched_begin.argtypes = [planp, ctypes.c_void_p, ctypes.c_void_p]
+        L.hwy_ppo_sched_begin.restype = ctypes.c_int
+        L.hwy_ppo_sched_step.argtypes = [planp, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.hwy_ppo_sched_step.restype = ctypes.c_int
+        L.hwy_ppo_sched_advance.argtypes = [planp, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.hwy_ppo_sched_advance.restype = ctypes.c_int
     L._grp_bound = True
     return L
 
@@ -669,6 +698,12 @@ def _need_mixed(L):
     if not hasattr(L, "hwy_ppo_mixed_step"):
         raise RuntimeError("this libhwy build has no hwy_ppo_mixed_* entry points (learners of "
                            "different hidden widths need the product library)")
+
+
+def _need_sched(L):
+    if not hasattr(L, "hwy_ppo_sched_step"):
+        raise RuntimeError("this libhwy build has no hwy_ppo_sched_* entry points (learners of "
+                           "different batch_size or epochs need the product library)")
 
 
 class GroupAct:
@@ -771,48 +806,77 @@ class GroupAct:
 
 
 class GroupStep:
-    """One minibatch step of G FusedPPO learners (same minibatch rows; state dims and hidden
-    widths may differ): learner g's arguments are its own FusedPPO._args, so each learner steps
-    bit for bit as its solo run() would.  Learners of one hidden width take hwy_ppo_group_step
-    (four launches); learners of different widths take hwy_ppo_mixed_step (a row launch per
-    wave-count class present, then three: ``launches_per_step``).  One device table (and plan)
-    per minibatch index."""
+    """One minibatch step of G FusedPPO learners: learner g's arguments are its own
+    FusedPPO._args, so each learner steps bit for bit as its solo run() would.
+
+    Learners that share minibatch rows, minibatch count and epochs (state dims and hidden widths
+    may differ) keep one device table (and plan) per minibatch index; ``step(i)`` steps all of
+    them through minibatch i.  Learners of one hidden width take hwy_ppo_group_step (four
+    launches); learners of different widths take hwy_ppo_mixed_step (a row launch per wave-count
+    class present, then three: ``launches_per_step``).
+
+    Learners whose (minibatch rows, minibatch count, epochs) differ run scheduled
+    (``self.sched``, hwy_ppo_sched_*): ONE table holds the whole update's schedule.  After
+    ``begin()``, ``step(s)`` issues slot s -- every learner still active runs its own minibatch
+    s % nmb -- for s < ``max_steps``; in a captured graph of P slots ``step(0..P-1)`` then
+    ``advance(P)`` moves the table's slot base, so the same graph replays for every P slots."""
 
     def __init__(self, fused):
         self.fused = list(fused)
         self.G = len(self.fused)
         F0 = self.fused[0]
         self.L = _bind_group(F0.L)
-        if any(F.mb != F0.mb for F in self.fused):
-            raise ValueError("grouped PPO step: the learners share minibatch rows")
+        self.sched = len({(F.mb, F.nmb, F.agent.epochs) for F in self.fused}) > 1
         self.mixed = any(F.H != F0.H for F in self.fused)
-        if self.mixed:
+        self.tables: List[torch.Tensor] = []
+        self.plans: list = []
+        self.max_steps = self.period = None
+        dims = (PpoDims * self.G)(*[F.dims for F in self.fused])
+        if self.sched:
+            _need_sched(self.L)
+            self._nmb = (ctypes.c_int32 * self.G)(*[F.nmb for F in self.fused])
+            self._epochs = (ctypes.c_int32 * self.G)(*[F.agent.epochs for F in self.fused])
+            nb = self.L.hwy_ppo_sched_table_bytes(dims, self._nmb, self.G)
+        elif self.mixed:
             _need_mixed(self.L)
-            dims = (PpoDims * self.G)(*[F.dims for F in self.fused])
             nb = self.L.hwy_ppo_mixed_table_bytes(dims, self.G)
         else:
             nb = self.L.hwy_ppo_group_table_bytes(ctypes.byref(F0.dims), self.G)
         if nb < 0:
-            raise ValueError(f"grouped PPO step: unsupported dims B={F0.mb} "
+            raise ValueError(f"grouped PPO step: unsupported dims B={sorted({F.mb for F in self.fused})} "
                              f"S={sorted({F.S for F in self.fused})} "
                              f"H={sorted({F.H for F in self.fused})} "
                              "(16-row tiles: minibatches below 8,192 rows)")
         self._nb = int(nb)
-        self.tables: List[torch.Tensor] = []
-        self.plans: list = []
         self.launches_per_step = (len({(F.H // 64) & 1 for F in self.fused}) + 3
-                                  if self.mixed else 4)
+                                  if self.mixed or self.sched else 4)
 
     def prepare(self, per_learner_args) -> None:
-        """per_learner_args[g][i]: learner g's PpoArgs of minibatch i."""
-        nmb = len(per_learner_args[0])
+        """per_learner_args[g][i]: learner g's PpoArgs of minibatch i (scheduled: only i = 0 is
+        read -- its idx is the start of the learner's whole permutation)."""
+        dev = self.fused[0].flat.device
         self.tables, self.plans = [], []
+        if self.sched:
+            arr = (PpoArgs * self.G)()
+            for g in range(self.G):
+                ctypes.memmove(ctypes.byref(arr[g]), ctypes.byref(per_learner_args[g][0]),
+                               ctypes.sizeof(PpoArgs))
+            t = torch.empty(self._nb, dtype=torch.uint8, device=dev)
+            plan = PpoSchedPlan()
+            check(self.L.hwy_ppo_sched_prepare(arr, self._nmb, self._epochs, self.G, t.data_ptr(),
+                                               ctypes.byref(plan), stream_ptr()),
+                  "hwy_ppo_sched_prepare")
+            self.tables, self.plans = [t], [plan]
+            self.launches_per_step = plan.launches
+            self.max_steps, self.period = int(plan.max_steps), int(plan.period)
+            return
+        nmb = len(per_learner_args[0])
         for i in range(nmb):
             arr = (PpoArgs * self.G)()
             for g in range(self.G):
                 ctypes.memmove(ctypes.byref(arr[g]), ctypes.byref(per_learner_args[g][i]),
                                ctypes.sizeof(PpoArgs))
-            t = torch.empty(self._nb, dtype=torch.uint8, device=self.fused[0].flat.device)
+            t = torch.empty(self._nb, dtype=torch.uint8, device=dev)
             if self.mixed:
                 plan = PpoMixedPlan()
                 check(self.L.hwy_ppo_mixed_prepare(arr, self.G, t.data_ptr(), ctypes.byref(plan),
@@ -825,7 +889,22 @@ class GroupStep:
             self.tables.append(t)
             self.plans.append(plan)
 
+    def begin(self) -> None:
+        """Scheduled mode: the start of an update (slot base 0)."""
+        check(self.L.hwy_ppo_sched_begin(ctypes.byref(self.plans[0]), self.tables[0].data_ptr(),
+                                         stream_ptr()), "hwy_ppo_sched_begin")
+
+    def advance(self, slots: int) -> None:
+        """Scheduled mode: slot base += slots (the last node of a captured graph of `slots`)."""
+        check(self.L.hwy_ppo_sched_advance(ctypes.byref(self.plans[0]), self.tables[0].data_ptr(),
+                                           int(slots), stream_ptr()), "hwy_ppo_sched_advance")
+
     def step(self, i: int) -> None:
+        """Minibatch i of every learner; scheduled: slot (slot base + i) of the update."""
+        if self.sched:
+            check(self.L.hwy_ppo_sched_step(ctypes.byref(self.plans[0]), self.tables[0].data_ptr(),
+                                            int(i), stream_ptr()), "hwy_ppo_sched_step")
+            return
         if self.mixed:
             check(self.L.hwy_ppo_mixed_step(ctypes.byref(self.plans[i]), self.tables[i].data_ptr(),
                                             stream_ptr()), "hwy_ppo_mixed_step")

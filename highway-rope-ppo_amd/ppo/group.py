@@ -139,7 +139,8 @@ class ExperimentGroup:
         rollout, the learners' FusedPPO (its Adam state handed over) with its per-update
         refresh (counters, tile image).  Returns the context post_update and the step runner
         use; ctx["args"][g][i] is learner g's PpoArgs of minibatch i, rebuilt only when the
-        buffers or hyper-parameters change (ctx["key"])."""
+        buffers or hyper-parameters change (ctx["key"]); ctx["mb"], ctx["nmb"] and ctx["epochs"]
+        are the cell's schedule (minibatch rows, minibatches per epoch, epochs)."""
         from hwy import ops
 
         buf, G, E, T = self.buf, self.G, self.E, self.T
@@ -189,7 +190,8 @@ class ExperimentGroup:
             F._last_args, F._last_inputs = a, (states, pre, old_lp, adv_grp, ret_flat, idx_all)
             F.counters[1].zero_()
             F.sync_params(a[0])  # FusedPPO.run's tile-image refresh
-        return {"fused": fused, "args": args, "key": key, "sizes": sizes, "nmb": nmb, "ret": ret}
+        return {"fused": fused, "args": args, "key": key, "sizes": sizes, "mb": mb, "nmb": nmb,
+                "epochs": self.agents[0].epochs, "ret": ret}
 
     def post_update(self, ctx: dict, return_metrics=True):
         buf, E, T = self.buf, self.E, self.T
@@ -272,41 +274,96 @@ def _graph_run(owner, use_graphs, key, steps, graph, gkey, seen, what):
     return g, key, seen
 
 
+def update_schedule(nmbs: Sequence[int], epochs: Sequence[int]):
+    """(max_steps, period) of one update of learners stepped together, learner y running
+    steps[y] = epochs[y] * nmbs[y] grouped steps: the update takes max(steps) slots, and every
+    learner ends on a multiple of period = gcd(steps) (hwy_ppo_sched_plan)."""
+    import math
+
+    steps = [int(e) * int(n) for n, e in zip(nmbs, epochs)]
+    if not steps or min(steps) < 1:
+        raise ValueError("a schedule needs nmb >= 1 and epochs >= 1 for every learner")
+    return max(steps), math.gcd(*steps)
+
+
+def slot_minibatch(slot: int, nmb: int, epochs: int) -> Optional[int]:
+    """The minibatch a learner of `nmb` minibatches and `epochs` epochs runs in slot `slot` of
+    an update (epoch-major, minibatch-minor: FusedPPO.run's order), or None once it is done."""
+    return slot % nmb if 0 <= slot < nmb * epochs else None
+
+
+def graph_slots(period: int, cap: int = 256) -> int:
+    """Slots of the captured update graph: the schedule's period, or, past `cap` slots, its
+    largest divisor below the cap (any length works -- the kernels add the table's slot base --
+    and a divisor keeps every learner's end on a replay boundary)."""
+    return max(d for d in range(1, min(period, cap) + 1) if period % d == 0)
+
+
+def _capture_steps(owner, steps):
+    """`steps()` captured as one graph on a stream of its own (FusedPPO._capture)."""
+    owner.stats["update_capture"] += 1
+    graph = torch.cuda.CUDAGraph()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        with graph_capture(graph, stream=s):
+            steps()
+    torch.cuda.current_stream().wait_stream(s)
+    return graph
+
+
 def _run_group_steps(owner, ctxs, runner):
     """Every epoch's minibatch steps of the learners of `ctxs` (pre_update contexts) as grouped
     launches: one GroupStep over all of them, its tables prepared when any member's arguments
-    changed, one epoch captured as a graph and replayed `epochs` times (FusedPPO.run's
-    schedule).  runner = (key, GroupStep, graph) kept by the owner between updates."""
+    changed.  Cells that share minibatch rows, minibatch count and epochs: one epoch captured as
+    a graph and replayed `epochs` times (FusedPPO.run's schedule).  Cells whose schedules differ
+    (GroupStep.sched): one table holding every learner's schedule, graph_slots(period) slots
+    plus the slot-base advance captured as one graph and replayed until the longest learner is
+    done; a learner that is done sits the remaining slots out.  runner = (key, GroupStep, graph)
+    kept by the owner between updates."""
     from hwy.ppo_native import GroupStep
 
     fused = [F for c in ctxs for F in c["fused"]]
     args = [a for c in ctxs for a in c["args"]]
-    key = (tuple(id(F) for F in fused),) + tuple(c["key"] for c in ctxs)
-    nmb = ctxs[0]["nmb"]
-    if any(c["nmb"] != nmb for c in ctxs):
-        raise ValueError("grouped learners need the same minibatch count")
+    sched = tuple((c["mb"], c["nmb"], c["epochs"]) for c in ctxs)
+    key = (tuple(id(F) for F in fused), sched) + tuple(c["key"] for c in ctxs)
     if runner is None or runner[0] != key:
         owner.stats["update_prepare"] += 1
         step = GroupStep(fused)
         step.prepare(args)
         runner = (key, step, None)
     _, step, graph = runner
-    epochs = fused[0].agent.epochs
+    if step.sched:
+        want = update_schedule([c["nmb"] for c in ctxs], [c["epochs"] for c in ctxs])
+        if (step.max_steps, step.period) != want:
+            raise RuntimeError(f"scheduled step: the table's schedule {step.max_steps, step.period} "
+                               f"is not the cells' {want}")
+        if not owner.use_graphs:
+            step.begin()
+            for s in range(step.max_steps):
+                step.step(s)
+            return runner
+        P = graph_slots(step.period)
+        if graph is None:
+            def slots():
+                for s in range(P):
+                    step.step(s)
+                step.advance(P)
+
+            graph = _capture_steps(owner, slots)
+            runner = (key, step, graph)
+        step.begin()
+        for _ in range(-(-step.max_steps // P)):
+            graph.replay()
+        return runner
+    nmb, epochs = ctxs[0]["nmb"], ctxs[0]["epochs"]
     if not owner.use_graphs:
         for _ in range(epochs):
             for i in range(nmb):
                 step.step(i)
         return runner
     if graph is None:  # one epoch's minibatch steps as one graph (FusedPPO._capture)
-        owner.stats["update_capture"] += 1
-        graph = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            with graph_capture(graph, stream=s):
-                for i in range(nmb):
-                    step.step(i)
-        torch.cuda.current_stream().wait_stream(s)
+        graph = _capture_steps(owner, lambda: [step.step(i) for i in range(nmb)])
         runner = (key, step, graph)
     for _ in range(epochs):
         graph.replay()
@@ -314,16 +371,18 @@ def _run_group_steps(owner, ctxs, runner):
 
 
 class GroupBatch:
-    """Several ExperimentGroups with the same rows per learner -- a sweep's cells, which may
-    differ in observation layout (state dims 60 or 120: no PE, RoPE, DistPE, RankPE) and in
-    hidden width (h128, h256, h384, ...) -- stepped as ONE set of launches: per rollout step the
+    """Several ExperimentGroups -- a sweep's cells, which may differ in observation layout
+    (state dims 60 or 120: no PE, RoPE, DistPE, RankPE), in hidden width (h128, h256, h384, ...)
+    and in batch_size / num_minibatches / epochs -- stepped as ONE set of launches: per rollout step the
     acting launch for every learner of every group and one env launch for every group's handle
     (hwy_step_group); per minibatch step one grouped fused step over all their learners.  Groups
     of one hidden width take hwy_ppo_group_act / hwy_ppo_group_step (one acting launch, four per
     step); groups of different widths take hwy_ppo_mixed_act / hwy_ppo_mixed_step, which add one
     acting and one row launch when the widths span both wave-count classes (include/hwy_ppo.h).
-    The groups still share minibatch rows and count, epochs, envs per experiment and rollout
-    length.  Each experiment stays bit-identical to its solo run: the same kernel bodies per
+    Groups whose minibatch rows, minibatch count or epochs differ take hwy_ppo_sched_step: the
+    update runs max(epochs x minibatches) grouped steps, each learner on its own minibatch index
+    and sitting the rest out once its epochs are done (_run_group_steps).  The groups still share
+    envs per experiment and rollout length.  Each experiment stays bit-identical to its solo run: the same kernel bodies per
     learner, each group's own generator order, GAE and normalisation."""
 
     def __init__(self, groups, use_graphs: bool = True):

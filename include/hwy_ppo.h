@@ -179,6 +179,48 @@ int hwy_ppo_mixed_act_prepare(const hwy_ppo_act_args* a /*[G]*/, int G, void* ta
                               hwy_ppo_mixed_act_plan* plan, void* stream);
 int hwy_ppo_mixed_act(const hwy_ppo_mixed_act_plan* plan, const void* table, void* stream);
 
+/* ---- Grouped learners with schedules of their own: G learners stepped through one WHOLE update
+ * when, besides H and S, their minibatch rows B, minibatches per epoch nmb and epochs differ (a
+ * sweep across batch_size and epochs in one set of launches).  Slot s of an update is its s-th
+ * grouped step.  Learner y is active in slot s iff s < steps[y] = epochs[y] * nmb[y], and then
+ * runs its solo step (hwy_ppo_forward_backward + hwy_ppo_optimizer) for minibatch s % nmb[y]:
+ * epoch-major, minibatch-minor, the order of a solo update.  A learner that sits a slot out is not
+ * touched at all (parameters, gradients, moments, tile image, counters, metrics rows), so its
+ * counters[1] ends the update at steps[y]; each active learner is bit for bit its solo run.
+ *
+ * a[g].idx points at learner g's WHOLE permutation, nmb[g] * B_g indices; minibatch i reads
+ * idx + i * B_g.  Every learner must satisfy what hwy_ppo_mixed_prepare asks of one (fused path,
+ * 16-row tiles, grads_modified == 0, 16-byte aligned flat buffers, the same A); B may differ.
+ *
+ * The schedule lives in the device table: the step kernels take the slot as slot base + `slot`,
+ * the slot base a word of the table that hwy_ppo_sched_begin zeroes and hwy_ppo_sched_advance
+ * adds to, `slot` a launch argument.  One captured graph of P slots -- hwy_ppo_sched_step(slot =
+ * 0..P-1), then hwy_ppo_sched_advance(P) -- replayed ceil(max_steps / P) times after one
+ * hwy_ppo_sched_begin therefore runs the update for any P; with P = plan.period (or a divisor)
+ * no learner ends inside a replay, and slots past max_steps do nothing.  The step kernels only
+ * read the slot base; begin (a memset) and advance (one thread's ordinary store) write it,
+ * stream-ordered between whole slots.
+ *
+ * hwy_ppo_sched_prepare is synchronous (it waits for `stream`), leaves the slot base at 0 and is
+ * not capturable; begin, step (slot >= 0) and advance (slots >= 0) are asynchronous, allocate
+ * nothing and are hipGraph-capturable.  A step issues a row launch per wave-count class present,
+ * then the weight-gradient, slice-sum and Adam launches.  -1 bad arguments / unsupported dims,
+ * -2 HIP error. */
+typedef struct hwy_ppo_sched_plan {
+  int32_t G;
+  int32_t present[2], grid_rows[2], lds_bytes[2]; /* as hwy_ppo_mixed_plan */
+  int32_t grid_wgrad, grid_wsum, grid_adam;
+  int32_t max_steps; /* max over learners of epochs * nmb */
+  int32_t period;    /* gcd of the learners' steps: every learner ends on a multiple of it */
+} hwy_ppo_sched_plan;
+int64_t hwy_ppo_sched_table_bytes(const hwy_ppo_dims* d /*[G]*/, const int32_t* nmb /*[G]*/, int G);
+int hwy_ppo_sched_prepare(const hwy_ppo_args* a /*[G]*/, const int32_t* nmb /*[G]*/,
+                          const int32_t* epochs /*[G]*/, int G, void* table,
+                          hwy_ppo_sched_plan* plan, void* stream);
+int hwy_ppo_sched_begin(const hwy_ppo_sched_plan* plan, void* table, void* stream);
+int hwy_ppo_sched_step(const hwy_ppo_sched_plan* plan, const void* table, int slot, void* stream);
+int hwy_ppo_sched_advance(const hwy_ppo_sched_plan* plan, void* table, int slots, void* stream);
+
 /* Build flags of this library: bit 0 = development knobs compiled in (HWY_DEV_KNOBS: the
  * HWY_WG_BAL / HWY_ROWS_RT / HWY_WG_FILL environment variables are read), bit 1 = section clocks
  * (HWY_SECTION_PROFILE).  A product build returns 0 and reads no environment variable. */
