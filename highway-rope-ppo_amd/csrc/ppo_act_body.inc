@@ -12,9 +12,9 @@
 #endif
   f32x4 unused_a[kRowTile / 16][TW], unused_c[kRowTile / 16][TW];
   uint32_t unused_m[2];
-  rows_forward<QH, NW, kRowTile, false>(R, r.states, nullptr, r.S, nrows, row0, P, r.off, X, H1,
-                                        H2, AC, nullptr, nullptr, nullptr, unused_m, unused_a,
-                                        unused_c PSEC_ARGS);
+  rows_forward<QH, NW, kRowTile, false, D, 4, TL, false, false, WIDE>(
+      R, r.states, nullptr, r.S, nrows, row0, P, r.off, X, H1, H2, AC, nullptr, nullptr, nullptr,
+      unused_m, unused_a, unused_c PSEC_ARGS);
   float wa0[QH], wa1[QH], wc[QH];
 #pragma unroll
   for (int q = 0; q < QH; ++q) {

@@ -8,7 +8,7 @@
   WRing<TW, D, 4, true, true> R;
   ring_setup(R, P, r.off, r.S, H, w * (H / NW), r.tiles);
   Gathered<RT, 64 * NW> xpre;  // the states rows, issued before the ring's prime (rows_body)
-  gather_issue<RT, 64 * NW>(r.states, nullptr, r.S, nrows, row0, H, xpre);
+  gather_first<RT, 64 * NW, WIDE>(r.states, nullptr, r.S, nrows, row0, H, xpre);
   R.prime();
 #ifdef HWY_SECTION_PROFILE
   uint64_t _pt = 0, _pacc[16];
@@ -31,10 +31,9 @@
   if (r.noise) n0 = r.noise[2 * b], n1 = r.noise[2 * b + 1];
   f32x4 av[RB][TW], cv[RB][TW];
   uint32_t mb[2] = {0u, 0u};
-  rows_forward<QH, NW, RT, true, D, 4, true, false>(R, r.states, nullptr, r.S, nrows, row0, P,
-                                                     r.off, P1, H1, P1, nullptr, nullptr,
-                                                     nullptr, nullptr, mb, av, cv PSEC_ARGS,
-                                                     &xpre);
+  rows_forward<QH, NW, RT, true, D, 4, true, false, true, WIDE>(
+      R, r.states, nullptr, r.S, nrows, row0, P, r.off, P1, H1, P1, nullptr, nullptr, nullptr,
+      nullptr, mb, av, cv PSEC_ARGS, &xpre);
   const int g4 = lane >> 4, c16 = lane & 15;
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)

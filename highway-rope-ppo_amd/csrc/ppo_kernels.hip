@@ -2,8 +2,9 @@
 //
 // One minibatch step of the reference's PPOAgent.update (ppo/agent.py:216-252).
 //
-// Fused path (S % 4 == 0, S <= 256, H a multiple of 64 up to 512): four launches, captured per
-// epoch in one HIP graph:
+// Fused path (S % 4 == 0, S <= 1,024, H a multiple of 64 up to 512): four launches, captured per
+// epoch in one HIP graph (past S = 256 the row and act kernels run their first layer
+// over chunks of 256 state columns, at 16-row tiles):
 //   ppo_rows   16 or 32 minibatch rows per workgroup (rows_tile): forward (h1, h2, [a1|c1]),
 //              the loss head (ratio, clipped surrogate, MSE, entropy, their gradients,
 //              head-parameter partials), backward data gradients (dh2, dh1); weights streamed
@@ -18,13 +19,17 @@
 // head kernel (ppo_head), split-K partial slabs and one deterministic reduction (ppo_reduce).
 // All GEMMs use v_mfma_f32_*_f32: exact fp32 products, fp32 accumulation.
 //
-// This file is compiled twice (Makefile).  ppo_kernels.o holds everything but the mixed-width
+// This file is compiled three times (Makefile).  ppo_kernels.o holds everything but the mixed-width
 // and scheduled grouped kernels and their entry points (hwy_ppo_mixed_*, hwy_ppo_sched_*);
-// ppo_mixed.o, compiled with -DHWY_PPO_MIXED_TU, holds only those.  They are kept apart because the existing kernels'
+// ppo_mixed.o, compiled with -DHWY_PPO_MIXED_TU, holds only those; ppo_wide.o, compiled with
+// -DHWY_PPO_WIDE_TU, holds only the row / act kernels for S > 256 (solo, grouped, mixed and
+// scheduled) and the launchers the other two units call them through (hwy_ppo_wide_*; no entry
+// point of its own).  They are kept apart because the existing kernels'
 // code generation turned out to depend on what else the unit holds (with the mixed kernels
 // beside them 27 of the 57 row / act kernels changed their VGPR counts, their source untouched):
 // in a unit of their own the mixed kernels leave every other kernel's registers, LDS and
-// occupancy as they were (profiles/r7/mixed/).
+// occupancy as they were (profiles/r7/mixed/), and so do the wide ones
+// (profiles/r9/wide/).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -111,7 +116,8 @@ constexpr int kTile = 64;
 constexpr int kKStep = 32;
 constexpr int kHeadRows = 16;  // minibatch rows per head workgroup (4 per wave)
 constexpr int kRowTile = 16;   // minibatch rows per ppo_rows workgroup
-constexpr int kMaxRowS = 256;  // states dim bound of the fused path (LDS)
+constexpr int kMaxRowS = 256;  // state columns the row kernels' LDS image holds at once
+constexpr int kMaxFusedS = 1024;  // states dim bound of the fused path (chunks of kMaxRowS)
 // Product constants, each measured against its alternatives (the rejected
 // alternatives are in git history, round 4 and earlier):
 //  - ppo_rows at H = 256, 16-row tiles: 8 waves (2 per SIMD, two 16-column tiles each);
@@ -522,9 +528,10 @@ inline bool wg_balance_on() { return dev_knob_int("HWY_WG_BAL", 1) != 0; }
 
 // minibatch rows per ppo_rows workgroup: 32 (two 16-row blocks sharing every weight register
 // block: half the weight stream per row) when the grid still covers the chip and the LDS images
-// fit (H <= 256), else 16.
-inline int rows_tile(int B, int H) {
-  if (H > 256) return kRowTile;
+// fit (H <= 256), else 16.  Wide states (S > kMaxRowS) take the 16-row tile at every B: the chunked
+// first layer exists for that tile only.
+inline int rows_tile(int B, int H, int S) {
+  if (H > 256 || S > kMaxRowS) return kRowTile;
   // 64-row tiles (ppo_rows_c64, one workgroup per CU) once every CU gets one: each weight
   // fragment then feeds 4 row blocks, half the weight loads per MFMA of the 32-row tiles
   const int force = dev_knob_int("HWY_ROWS_RT", 0);  // development builds only
@@ -533,10 +540,13 @@ inline int rows_tile(int B, int H) {
   return B >= 32 * chip_geom().cus ? 2 * kRowTile : kRowTile;
 }
 
-// the fused row path covers the reference's shapes: float4 state rows, H a multiple of 64
+// the fused row path covers the reference's shapes and wider states: float4 state rows up to
+// kMaxFusedS floats, H a multiple of 64
 inline bool fused_ok(const hwy_ppo_dims& d) {
-  return d.S % 4 == 0 && d.S <= kMaxRowS && d.H % 64 == 0 && d.H >= 64 && d.H <= 512;
+  return d.S % 4 == 0 && d.S <= kMaxFusedS && d.H % 64 == 0 && d.H >= 64 && d.H <= 512;
 }
+// states wider than one LDS image: the chunked kernels of the wide unit (this file's head)
+[[maybe_unused]] inline bool wide_s(int S) { return S > kMaxRowS; }
 
 inline int head_stride(int H) { return 3 * H + 16; }
 
@@ -562,7 +572,7 @@ inline Work carve(const hwy_ppo_dims& d, void* ws, int64_t* bytes_out) {
   const Layout L = make_layout(d);
   w.nred = (int)((L.numel + kRedThreads - 1) / kRedThreads);
   w.fused = fused_ok(d);
-  w.rt = rows_tile(B, H);
+  w.rt = rows_tile(B, H, S);
   w.n1 = (B + w.rt - 1) / w.rt;
   const int tmh = (H + kWgTM - 1) / kWgTM, tnh = (H + kWgTN - 1) / kWgTN;
   w.tac = ((2 * H + kWgTM - 1) / kWgTM) * tnh;
@@ -950,6 +960,47 @@ struct WRing {
       }
     }
   }
+  // run() over blocks bs .. bs + nb - 1 of segment SEG only (bs, nb multiples of D): `act` holds
+  // the activation columns of just these blocks, from column 0.  A layer whose activations are
+  // staged in sub-ranges (the chunked first layer of wide states, rows_forward) calls it once per
+  // sub-range with ascending bs: the weight stream and the accumulation order are those of one
+  // run() over the whole segment.
+  template <int SEG, int RB>
+  __device__ __forceinline__ void run_part(const float* act, int pa, f32x4 (&acc)[RB][TW], int bs,
+                                           int nb) {
+    const float* arow = act + c * pa + 4 * g;
+    f32x4 a_nxt[RB];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+      a_nxt[rb] = *reinterpret_cast<const f32x4*>(arow + 16 * rb * pa);
+    for (int b0 = 0; b0 < nb; b0 += D) {
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        const int kb = 16 * (b0 + d);  // column of the block inside `act`
+        f32x4 a[RB];
+        const int kn = min(kb + 16, 16 * (nb - 1));
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) {
+          a[rb] = a_nxt[rb];
+          a_nxt[rb] = *reinterpret_cast<const f32x4*>(arow + 16 * rb * pa + kn);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const bool kin = 16 * bs + kb + 4 * g < sg[SEG].K;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int t = 0; t < TW; ++t) {
+            const float bw = kin ? buf[d][t][j] : 0.0f;
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb)
+              acc[rb][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rb][j], bw, acc[rb][t], 0, 0, 0);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+        load_ahead<SEG>(bs + b0 + d + D, buf[d]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
 };
 
 template <int RB, int TW>
@@ -1153,6 +1204,61 @@ __device__ __forceinline__ void gather_issue(const float* states, const int64_t*
   }
 }
 
+// Wide states (kMaxRowS < S <= kMaxFusedS): the first layer runs over chunks of kMaxRowS state
+// columns, each staged in the same X image (rows_forward).  gather_chunk: gather_issue for the
+// columns k0 .. k0 + 4 q4 - 1 of the tile's rows (q4 float4s per image row, zero past S and past
+// nrows); store_chunk: those registers into the image (pitch px) and, live ones, into xg.
+template <int RT, int NT>
+__device__ __forceinline__ void gather_chunk(const float* states, const int64_t* idx, int S,
+                                             int nrows, int row0, int k0, int q4,
+                                             Gathered<RT, NT>& x) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < Gathered<RT, NT>::N; ++i) {
+    const int e = t + i * NT;
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (e < RT * q4) {
+      const int row = e / q4, k = k0 + 4 * (e - row * q4);
+      if (row < nrows && k < S) {
+        const long src = idx ? (long)idx[row0 + row] : (long)(row0 + row);
+        v = *reinterpret_cast<const f32x4*>(states + src * S + k);
+      }
+    }
+    x.v[i] = v;
+  }
+}
+template <int RT, int NT>
+__device__ __forceinline__ void store_chunk(const Gathered<RT, NT>& x, float* X, int px, float* xg,
+                                            int S, int nrows, int row0, int k0, int q4) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < Gathered<RT, NT>::N; ++i) {
+    const int e = t + i * NT;
+    if (e < RT * q4) {
+      const int row = e / q4, kl = 4 * (e - row * q4);
+      const f32x4 v = x.v[i];
+      if (xg && row < nrows && k0 + kl < S)
+        *reinterpret_cast<f32x4*>(xg + (long)(row0 + row) * S + k0 + kl) = v;
+      *reinterpret_cast<f32x4*>(&X[row * px + kl]) = v;
+    }
+  }
+}
+constexpr int kChunkBlk = kMaxRowS / 16;  // 16-deep k blocks per chunk
+
+// the gather a row / act body issues before the ring's prime: the whole (narrow) states rows, or
+// (WIDE) their first chunk
+template <int RT, int NT, bool WIDE>
+__device__ __forceinline__ void gather_first(const float* states, const int64_t* idx, int S,
+                                             int nrows, int row0, int H, Gathered<RT, NT>& x) {
+  if constexpr (WIDE) {
+    int sbk, hbk;
+    rows_blocks(S, H, &sbk, &hbk);
+    gather_chunk<RT, NT>(states, idx, S, nrows, row0, 0, 4 * min(sbk, kChunkBlk), x);
+  } else {
+    gather_issue<RT, NT>(states, idx, S, nrows, row0, H, x);
+  }
+}
+
 // Forward of the RT rows starting at row0 (rows idx[row0 + i], or row0 + i without idx) into
 // the LDS images X, H1, H2, AC = [a1 | c1]; optionally also to HBM (xg, h1, h2; null = no).
 // X may alias AC (it is dead once h1 is computed).  Ends with a workgroup barrier.
@@ -1160,8 +1266,14 @@ __device__ __forceinline__ void gather_issue(const float* states, const int64_t*
 // instead of going to AC, and the function ends without the barrier.
 // MSK: the ReLU decisions of h1 and h2 (this lane's C elements) also go to mb[0], mb[1] as bits
 // (row_epi_bias_relu_bits), so the backward needs neither image for its masks.
+// WIDE: the first layer as a loop over chunks of at most kMaxRowS state columns (S up to
+// kMaxFusedS): chunk c's columns of the tile's rows are staged in X, its k blocks accumulate into
+// the same layer-1 accumulators (WRing::run_part: ascending k, the order of one long image), and
+// the next chunk -- gathered into registers while this one's MFMAs run -- is staged after a
+// barrier.  The chunk count is a runtime value; at S <= kMaxRowS it is 1 and the arithmetic is the
+// narrow path's.
 template <int QH, int NW, int RT, bool KEEP, int D, int NSEG, bool TL, bool MSK = false,
-          bool UNI = false>
+          bool UNI = false, bool WIDE = false>
 __device__ __forceinline__ void rows_forward(WRing<H_TW(QH, NW), D, NSEG, TL, UNI>& R,
                                              const float* states,
                                              const int64_t* idx, int S, int nrows, int row0,
@@ -1190,39 +1302,61 @@ __device__ __forceinline__ void rows_forward(WRing<H_TW(QH, NW), D, NSEG, TL, UN
   // zero-padded to whole ring groups of 16-deep blocks (the ring's layer-1 segment, rows_blocks)
   int sbk, hbk;
   rows_blocks(S, H, &sbk, &hbk);
-  const int Sp = 16 * sbk, px = row_pitch(Sp);
-  // states rows, zero-padded to Sp columns and RT rows (pre: gathered by gather_issue)
-  if (pre) {
+  const int nb = R.n_base;  // this wave's output columns of an H-wide layer
+  f32x4 acc[RB][TW];
+  if constexpr (WIDE) {
+    const int px = row_pitch(16 * min(sbk, kChunkBlk));
+    const int nchunk = (sbk + kChunkBlk - 1) / kChunkBlk;
+    Gathered<RT, NT> cur;
+    if (pre)
+      cur = *pre;
+    else
+      gather_chunk<RT, NT>(states, idx, S, nrows, row0, 0, 4 * min(sbk, kChunkBlk), cur);
+    zero_acc(acc);
+    for (int c = 0; c < nchunk; ++c) {
+      const int cb = min(kChunkBlk, sbk - kChunkBlk * c);  // this chunk's blocks
+      store_chunk<RT, NT>(cur, X, px, xg, S, nrows, row0, kMaxRowS * c, 4 * cb);
+      __syncthreads();
+      if (c + 1 < nchunk)  // in flight during this chunk's MFMAs
+        gather_chunk<RT, NT>(states, idx, S, nrows, row0, kMaxRowS * (c + 1),
+                             4 * min(kChunkBlk, sbk - kChunkBlk * (c + 1)), cur);
+      R.template run_part<0>(X, px, acc, kChunkBlk * c, cb);
+      if (c + 1 < nchunk) __syncthreads();  // every wave has read this chunk's image
+    }
+    PSEC(0);
+  } else {
+    const int Sp = 16 * sbk, px = row_pitch(Sp);
+    // states rows, zero-padded to Sp columns and RT rows (pre: gathered by gather_issue)
+    if (pre) {
 #pragma unroll
-    for (int i = 0; i < Gathered<RT, NT>::N; ++i) {
-      const int e = t + i * NT;
-      if (e < RT * (Sp / 4)) {
-        const int row = e / (Sp / 4), k = 4 * (e - row * (Sp / 4));
-        const f32x4 v = pre->v[i];
-        if (xg && row < nrows && k < S)
-          *reinterpret_cast<f32x4*>(xg + (long)(row0 + row) * S + k) = v;
+      for (int i = 0; i < Gathered<RT, NT>::N; ++i) {
+        const int e = t + i * NT;
+        if (e < RT * (Sp / 4)) {
+          const int row = e / (Sp / 4), k = 4 * (e - row * (Sp / 4));
+          const f32x4 v = pre->v[i];
+          if (xg && row < nrows && k < S)
+            *reinterpret_cast<f32x4*>(xg + (long)(row0 + row) * S + k) = v;
+          *reinterpret_cast<f32x4*>(&X[row * px + k]) = v;
+        }
+      }
+    } else {
+      for (int e = t; e < RT * (Sp / 4); e += NT) {
+        const int row = e / (Sp / 4), k = 4 * (e % (Sp / 4));
+        f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (row < nrows && k < S) {
+          const long src = idx ? (long)idx[row0 + row] : (long)(row0 + row);
+          v = *reinterpret_cast<const f32x4*>(states + src * S + k);
+          if (xg) *reinterpret_cast<f32x4*>(xg + (long)(row0 + row) * S + k) = v;
+        }
         *reinterpret_cast<f32x4*>(&X[row * px + k]) = v;
       }
     }
-  } else {
-    for (int e = t; e < RT * (Sp / 4); e += NT) {
-      const int row = e / (Sp / 4), k = 4 * (e % (Sp / 4));
-      f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (row < nrows && k < S) {
-        const long src = idx ? (long)idx[row0 + row] : (long)(row0 + row);
-        v = *reinterpret_cast<const f32x4*>(states + src * S + k);
-        if (xg) *reinterpret_cast<f32x4*>(xg + (long)(row0 + row) * S + k) = v;
-      }
-      *reinterpret_cast<f32x4*>(&X[row * px + k]) = v;
-    }
+    __syncthreads();
+    PSEC(0);
+    // h1 = relu(x W1^T + b1)
+    zero_acc(acc);
+    R.template run<0>(X, px, acc);
   }
-  __syncthreads();
-  PSEC(0);
-  const int nb = R.n_base;  // this wave's output columns of an H-wide layer
-  f32x4 acc[RB][TW];
-  // h1 = relu(x W1^T + b1)
-  zero_acc(acc);
-  R.template run<0>(X, px, acc);
   if constexpr (MSK)
     mb[0] = row_epi_bias_relu_bits(acc, bias[0], H1, PH, nb);
   else
@@ -1271,7 +1405,7 @@ __device__ __forceinline__ float squash_corr(float z) {
 // workgroups share a CU (4 waves per SIMD, <= 128 VGPRs) and one's phase boundaries, gather and
 // loss head overlap the other's MFMAs.  One extra barrier: dh2 overwrites dac's image only after
 // every wave has finished reading it.
-template <int QH, int NW, int RT, bool CMP>
+template <int QH, int NW, int RT, bool CMP, bool WIDE = false>
 __device__ __forceinline__ void rows_body(const RowArgs& r) {
   constexpr int H = 64 * QH;
   constexpr int TW = H / NW / 16;        // 16-column output tiles per wave
@@ -1311,7 +1445,7 @@ constexpr int rows_lds_floats() {
 // instantiations (ppo_rows_mix) then pays for the widest, not for their sum.  The code is
 // rows_body's, the same text compiled over pointers, so the arithmetic and its order are the
 // solo kernel's; rows_body itself keeps its static arrays, and with them its registers and LDS.
-template <int QH, int NW, int RT>
+template <int QH, int NW, int RT, bool WIDE = false>
 __device__ __forceinline__ void rows_body_dyn(const RowArgs& r, float* arena) {
   constexpr bool CMP = false;
   constexpr int H = 64 * QH;
@@ -1377,7 +1511,7 @@ struct ActArgs {
   const float* tiles;  // weight tile image in step with params (TL), else null
 };
 
-template <int QH, int NW, bool TL>
+template <int QH, int NW, bool TL, bool WIDE = false>
 __device__ __forceinline__ void act_body(ActArgs r) {
   constexpr int H = 64 * QH;
   constexpr int RPW = kRowTile / NW;
@@ -1398,7 +1532,7 @@ template <int QH, int NW, int RT>
 constexpr int act_c_lds_floats() { return 2 * RT * lds_pitch(64 * QH) + 4 * NW * RT; }
 
 // act_body over a dynamic-LDS arena (see rows_body_dyn)
-template <int QH, int NW, bool TL>
+template <int QH, int NW, bool TL, bool WIDE = false>
 __device__ __forceinline__ void act_body_dyn(ActArgs r, float* arena) {
   constexpr int H = 64 * QH;
   constexpr int RPW = kRowTile / NW;
@@ -1423,7 +1557,7 @@ __global__ void __launch_bounds__(64 * NW, 1) ppo_act(ActArgs r) {
 // summed in wave order, so mean / value are the bits the minibatch step recomputes.
 // (A 4-deep ring with the one-workgroup-per-CU register budget at 4,096 rows measured 22.4 against
 // 21.9 us, round 5.)
-template <int QH, int NW, int RT>
+template <int QH, int NW, int RT, bool WIDE = false>
 __device__ __forceinline__ void act_c_body(ActArgs r) {
   constexpr int H = 64 * QH;
   constexpr int TW = H / NW / 16;
@@ -1437,7 +1571,7 @@ __device__ __forceinline__ void act_c_body(ActArgs r) {
 }
 
 // act_c_body over a dynamic-LDS arena (see rows_body_dyn)
-template <int QH, int NW, int RT>
+template <int QH, int NW, int RT, bool WIDE = false>
 __device__ __forceinline__ void act_c_body_dyn(ActArgs r, float* arena) {
   constexpr int H = 64 * QH;
   constexpr int TW = H / NW / 16;
@@ -2314,7 +2448,7 @@ ppo_act_c_grp(const ActArgs* __restrict__ tab) {
   act_c_body<QH, NW, RT>(tab[blockIdx.y]);
 }
 
-#ifdef HWY_PPO_MIXED_TU
+#if defined(HWY_PPO_MIXED_TU) || defined(HWY_PPO_WIDE_TU)
 // ----------------------------------------------------------------------------- mixed widths
 // Grouped learners whose hidden widths differ (hwy_ppo_mixed_*).  ppo_wgrad_grp, ppo_wsum_grp and
 // ppo_adam_tiles_grp read H from each learner's arguments already; the row and act kernels are
@@ -2330,28 +2464,30 @@ ppo_act_c_grp(const ActArgs* __restrict__ tab) {
 extern __shared__ __attribute__((aligned(16))) float mix_lds[];
 
 // the solo row body of width class q (a learner of this kernel's wave-count class), uniformly for
-// the whole workgroup; shared by ppo_rows_mix and ppo_rows_sched
-template <int NW>
+// the whole workgroup; shared by ppo_rows_mix and ppo_rows_sched (WIDE: by their chunked twins)
+template <int NW, bool WIDE = false>
 __device__ __forceinline__ void rows_of_width(const RowArgs& r, int q) {
   if constexpr (NW == 8) {
     switch (q) {
-      case 2: rows_body_dyn<2, 8, kRowTile>(r, mix_lds); break;
-      case 4: rows_body_dyn<4, 8, kRowTile>(r, mix_lds); break;
-      case 6: rows_body_dyn<6, 8, kRowTile>(r, mix_lds); break;
-      case 8: rows_body_dyn<8, 8, kRowTile>(r, mix_lds); break;
+      case 2: rows_body_dyn<2, 8, kRowTile, WIDE>(r, mix_lds); break;
+      case 4: rows_body_dyn<4, 8, kRowTile, WIDE>(r, mix_lds); break;
+      case 6: rows_body_dyn<6, 8, kRowTile, WIDE>(r, mix_lds); break;
+      case 8: rows_body_dyn<8, 8, kRowTile, WIDE>(r, mix_lds); break;
       default: break;
     }
   } else {
     switch (q) {
-      case 1: rows_body_dyn<1, 4, kRowTile>(r, mix_lds); break;
-      case 3: rows_body_dyn<3, 4, kRowTile>(r, mix_lds); break;
-      case 5: rows_body_dyn<5, 4, kRowTile>(r, mix_lds); break;
-      case 7: rows_body_dyn<7, 4, kRowTile>(r, mix_lds); break;
+      case 1: rows_body_dyn<1, 4, kRowTile, WIDE>(r, mix_lds); break;
+      case 3: rows_body_dyn<3, 4, kRowTile, WIDE>(r, mix_lds); break;
+      case 5: rows_body_dyn<5, 4, kRowTile, WIDE>(r, mix_lds); break;
+      case 7: rows_body_dyn<7, 4, kRowTile, WIDE>(r, mix_lds); break;
       default: break;
     }
   }
 }
+#endif
 
+#ifdef HWY_PPO_MIXED_TU
 template <int NW>
 __global__ void __launch_bounds__(64 * NW, 1) ppo_rows_mix(const RowArgs* __restrict__ tab,
                                                            const GroupLim* __restrict__ lim,
@@ -2378,6 +2514,8 @@ __global__ void __launch_bounds__(64 * NW, 1) ppo_rows_mix(const RowArgs* __rest
 // both stream-ordered between whole slots, so no kernel reads it while another writes it.  The
 // slot is NOT derived from counters[1]: the row kernel's workgroup 0 increments the counters in
 // mid-kernel (ppo_rows_body.inc) while later workgroups of the same launch are still starting.
+#endif
+#if defined(HWY_PPO_MIXED_TU) || defined(HWY_PPO_WIDE_TU)
 struct SchedRec {
   int row0, nmb, steps;
 };
@@ -2388,6 +2526,8 @@ __device__ __forceinline__ int sched_minibatch(const SchedRec& c, const int* __r
   const int s = *base + slot;
   return (unsigned)s < (unsigned)c.steps ? s % c.nmb : -1;
 }
+#endif
+#ifdef HWY_PPO_MIXED_TU
 
 template <int NW>
 __global__ void __launch_bounds__(64 * NW, 1) ppo_rows_sched(const RowArgs* __restrict__ tab,
@@ -2492,6 +2632,105 @@ static_assert(4 * rows_lds_floats<8, 8, kRowTile>() <= kMixLdsMax &&
               "the widest learner's images fit a compute unit's LDS");
 
 #endif
+#ifdef HWY_PPO_WIDE_TU
+// ----------------------------------------------------------------------------- wide states
+// The row and act kernels for kMaxRowS < S <= kMaxFusedS: the solo, grouped, mixed and scheduled
+// kernels above with the chunked first layer (the bodies' WIDE flag; rows_forward), 16-row tiles.
+// Same images, so the same LDS per (H, tile) as the narrow kernels.  A grouped table that holds
+// a wide learner runs these for every learner of the launch: at S <= kMaxRowS the loop runs one
+// chunk and the arithmetic, and with it every bit, is the narrow kernel's.
+template <int QH, int NW>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_rows_w(RowArgs r) {
+  rows_body<QH, NW, kRowTile, false, true>(r);
+}
+
+template <int QH, int NW, bool TL>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_act_w(ActArgs r) {
+  act_body<QH, NW, TL, true>(r);
+}
+
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8)))
+ppo_act_c_w(ActArgs r) {
+  act_c_body<4, 8, kRowTile, true>(r);
+}
+
+template <int QH, int NW>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_rows_grp_w(const RowArgs* __restrict__ tab,
+                                                             const GroupLim* __restrict__ lim) {
+  if ((int)blockIdx.x >= lim[blockIdx.y].rows) return;  // whole workgroup
+  rows_body<QH, NW, kRowTile, false, true>(tab[blockIdx.y]);
+}
+
+template <int QH, int NW, bool TL>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_act_grp_w(const ActArgs* __restrict__ tab) {
+  act_body<QH, NW, TL, true>(tab[blockIdx.y]);
+}
+
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8)))
+ppo_act_c_grp_w(const ActArgs* __restrict__ tab) {
+  act_c_body<4, 8, kRowTile, true>(tab[blockIdx.y]);
+}
+
+template <int NW>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_rows_mix_w(const RowArgs* __restrict__ tab,
+                                                             const GroupLim* __restrict__ lim,
+                                                             const int* __restrict__ qh) {
+  const int q = qh[blockIdx.y];
+  if ((q & 1) != (NW == 4 ? 1 : 0) || (int)blockIdx.x >= lim[blockIdx.y].rows) return;
+  rows_of_width<NW, true>(tab[blockIdx.y], q);
+}
+
+template <int NW>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_rows_sched_w(const RowArgs* __restrict__ tab,
+                                                               const GroupLim* __restrict__ lim,
+                                                               const int* __restrict__ qh,
+                                                               const SchedRec* __restrict__ rec,
+                                                               const int* __restrict__ base,
+                                                               int slot) {
+  const int q = qh[blockIdx.y];
+  if ((q & 1) != (NW == 4 ? 1 : 0) || (int)blockIdx.x >= lim[blockIdx.y].rows) return;
+  const SchedRec c = rec[blockIdx.y];
+  const int i = sched_minibatch(c, base, slot);
+  if (i < 0) return;  // whole workgroup
+  rows_of_width<NW, true>(tab[c.row0 + i], q);
+}
+
+template <int NW, bool TL>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_act_mix_w(const ActArgs* __restrict__ tab,
+                                                            const int* __restrict__ qh) {
+  const int q = qh[blockIdx.y];
+  if ((q & 1) != (NW == 4 ? 1 : 0)) return;
+  const ActArgs& r = tab[blockIdx.y];
+  if constexpr (NW == 8) {
+    switch (q) {
+      case 2: act_body_dyn<2, 8, TL, true>(r, mix_lds); break;
+      case 4:
+        if constexpr (TL)
+          act_c_body_dyn<4, 8, kRowTile, true>(r, mix_lds);
+        else
+          act_body_dyn<4, 8, TL, true>(r, mix_lds);
+        break;
+      case 6: act_body_dyn<6, 8, TL, true>(r, mix_lds); break;
+      case 8: act_body_dyn<8, 8, TL, true>(r, mix_lds); break;
+      default: break;
+    }
+  } else {
+    switch (q) {
+      case 1: act_body_dyn<1, 4, TL, true>(r, mix_lds); break;
+      case 3: act_body_dyn<3, 4, TL, true>(r, mix_lds); break;
+      case 5: act_body_dyn<5, 4, TL, true>(r, mix_lds); break;
+      case 7: act_body_dyn<7, 4, TL, true>(r, mix_lds); break;
+      default: break;
+    }
+  }
+}
+#endif  // HWY_PPO_WIDE_TU
+
+// Set in a plan's grid_rows (hwy_ppo_mixed_act_plan: lds_bytes) by the prepare calls when the
+// table holds a learner with wide states: the launch calls then run the wide unit's kernels
+// (include/hwy_ppo.h: HWY_PPO_PLAN_WIDE)
+[[maybe_unused]] constexpr int kPlanWide = HWY_PPO_PLAN_WIDE;
+
 template <int AM, int BM, int EPI>
 int launch_gemm(const GemmArgs& g, int splits, hipStream_t s) {
   dim3 grid((g.M + kTile - 1) / kTile, (g.N + kTile - 1) / kTile, splits);
@@ -2514,6 +2753,180 @@ GemmArgs gemm_args() {
 }
 
 }  // namespace
+
+// ---- the wide unit's launchers (ppo_wide.o), called by the entry points of the other two units
+// where a learner's S passes kMaxRowS.  The argument structs and tables travel as untyped
+// pointers: every unit compiles the same definitions.  0, or -1 when the launch failed.
+#define HWY_LOCAL __attribute__((visibility("hidden")))
+HWY_LOCAL int hwy_ppo_wide_rows(const void* row_args, int H, int grid, hipStream_t s);
+HWY_LOCAL int hwy_ppo_wide_act(const void* act_args, int H, int B, hipStream_t s);
+HWY_LOCAL int hwy_ppo_wide_rows_grp(int H, int grid, int G, const void* tr, const void* tl,
+                                    hipStream_t s);
+HWY_LOCAL int hwy_ppo_wide_act_grp(int H, int B, int G, int tiles, const void* ta, hipStream_t s);
+HWY_LOCAL int hwy_ppo_wide_rows_mix(int cls, int grid, int G, int lds, const void* tr,
+                                    const void* tl, const void* tq, hipStream_t s);
+HWY_LOCAL int hwy_ppo_wide_rows_sched(int cls, int grid, int G, int lds, const void* tr,
+                                      const void* tl, const void* tq, const void* tc,
+                                      const void* tb, int slot, hipStream_t s);
+HWY_LOCAL int hwy_ppo_wide_act_mix(int cls, int tiles, int B, int G, int lds, const void* ta,
+                                   const void* tq, hipStream_t s);
+// raises the dynamic-LDS limit of a mixed kernel's wide twin (kind 0 ppo_rows_mix_w, 1
+// ppo_rows_sched_w, 2 ppo_act_mix_w) for wave-count class cls, as the prepare calls do for the
+// narrow kernels; false on a HIP error
+HWY_LOCAL bool hwy_ppo_wide_raise_lds(int kind, int cls, int tiles);
+
+#ifdef HWY_PPO_WIDE_TU
+static int wide_rc() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+
+int hwy_ppo_wide_rows(const void* row_args, int H, int grid, hipStream_t s) {
+  const RowArgs& r = *static_cast<const RowArgs*>(row_args);
+  const dim3 g1(grid), b4(256), b8(512);
+  switch (H / 64) {
+    case 1: hipLaunchKernelGGL((ppo_rows_w<1, 4>), g1, b4, 0, s, r); break;
+    case 2: hipLaunchKernelGGL((ppo_rows_w<2, 8>), g1, b8, 0, s, r); break;
+    case 3: hipLaunchKernelGGL((ppo_rows_w<3, 4>), g1, b4, 0, s, r); break;
+    case 4: hipLaunchKernelGGL((ppo_rows_w<4, 8>), g1, b8, 0, s, r); break;
+    case 5: hipLaunchKernelGGL((ppo_rows_w<5, 4>), g1, b4, 0, s, r); break;
+    case 6: hipLaunchKernelGGL((ppo_rows_w<6, 8>), g1, b8, 0, s, r); break;
+    case 7: hipLaunchKernelGGL((ppo_rows_w<7, 4>), g1, b4, 0, s, r); break;
+    default: hipLaunchKernelGGL((ppo_rows_w<8, 8>), g1, b8, 0, s, r); break;
+  }
+  return wide_rc();
+}
+
+// hwy_ppo_act's choice at 16-row tiles: H = 256 from a tile image runs the compact body
+int hwy_ppo_wide_act(const void* act_args, int H, int B, hipStream_t s) {
+  const ActArgs& r = *static_cast<const ActArgs*>(act_args);
+  const dim3 g((B + kRowTile - 1) / kRowTile), b4(256), b8(512);
+  auto launch = [&](auto tl) {
+    constexpr bool TL = decltype(tl)::value;
+    switch (H / 64) {
+      case 1: hipLaunchKernelGGL((ppo_act_w<1, 4, TL>), g, b4, 0, s, r); break;
+      case 2: hipLaunchKernelGGL((ppo_act_w<2, 8, TL>), g, b8, 0, s, r); break;
+      case 3: hipLaunchKernelGGL((ppo_act_w<3, 4, TL>), g, b4, 0, s, r); break;
+      case 4: hipLaunchKernelGGL((ppo_act_w<4, 8, TL>), g, b8, 0, s, r); break;
+      case 5: hipLaunchKernelGGL((ppo_act_w<5, 4, TL>), g, b4, 0, s, r); break;
+      case 6: hipLaunchKernelGGL((ppo_act_w<6, 8, TL>), g, b8, 0, s, r); break;
+      case 7: hipLaunchKernelGGL((ppo_act_w<7, 4, TL>), g, b4, 0, s, r); break;
+      default: hipLaunchKernelGGL((ppo_act_w<8, 8, TL>), g, b8, 0, s, r); break;
+    }
+  };
+  if (r.tiles && H == 256)
+    hipLaunchKernelGGL(ppo_act_c_w, g, b8, 0, s, r);
+  else if (r.tiles)
+    launch(std::integral_constant<bool, true>());
+  else
+    launch(std::integral_constant<bool, false>());
+  return wide_rc();
+}
+
+int hwy_ppo_wide_rows_grp(int H, int grid, int G, const void* tr_, const void* tl_,
+                          hipStream_t s) {
+  const RowArgs* tr = static_cast<const RowArgs*>(tr_);
+  const GroupLim* tl = static_cast<const GroupLim*>(tl_);
+  const dim3 g1(grid, G), b4(256), b8(512);
+  switch (H / 64) {
+    case 1: hipLaunchKernelGGL((ppo_rows_grp_w<1, 4>), g1, b4, 0, s, tr, tl); break;
+    case 2: hipLaunchKernelGGL((ppo_rows_grp_w<2, 8>), g1, b8, 0, s, tr, tl); break;
+    case 3: hipLaunchKernelGGL((ppo_rows_grp_w<3, 4>), g1, b4, 0, s, tr, tl); break;
+    case 4: hipLaunchKernelGGL((ppo_rows_grp_w<4, 8>), g1, b8, 0, s, tr, tl); break;
+    case 5: hipLaunchKernelGGL((ppo_rows_grp_w<5, 4>), g1, b4, 0, s, tr, tl); break;
+    case 6: hipLaunchKernelGGL((ppo_rows_grp_w<6, 8>), g1, b8, 0, s, tr, tl); break;
+    case 7: hipLaunchKernelGGL((ppo_rows_grp_w<7, 4>), g1, b4, 0, s, tr, tl); break;
+    default: hipLaunchKernelGGL((ppo_rows_grp_w<8, 8>), g1, b8, 0, s, tr, tl); break;
+  }
+  return wide_rc();
+}
+
+int hwy_ppo_wide_act_grp(int H, int B, int G, int tiles, const void* ta_, hipStream_t s) {
+  const ActArgs* ta = static_cast<const ActArgs*>(ta_);
+  const dim3 g((B + kRowTile - 1) / kRowTile, G), b4(256), b8(512);
+  auto launch = [&](auto tl) {
+    constexpr bool TL = decltype(tl)::value;
+    switch (H / 64) {
+      case 1: hipLaunchKernelGGL((ppo_act_grp_w<1, 4, TL>), g, b4, 0, s, ta); break;
+      case 2: hipLaunchKernelGGL((ppo_act_grp_w<2, 8, TL>), g, b8, 0, s, ta); break;
+      case 3: hipLaunchKernelGGL((ppo_act_grp_w<3, 4, TL>), g, b4, 0, s, ta); break;
+      case 4: hipLaunchKernelGGL((ppo_act_grp_w<4, 8, TL>), g, b8, 0, s, ta); break;
+      case 5: hipLaunchKernelGGL((ppo_act_grp_w<5, 4, TL>), g, b4, 0, s, ta); break;
+      case 6: hipLaunchKernelGGL((ppo_act_grp_w<6, 8, TL>), g, b8, 0, s, ta); break;
+      case 7: hipLaunchKernelGGL((ppo_act_grp_w<7, 4, TL>), g, b4, 0, s, ta); break;
+      default: hipLaunchKernelGGL((ppo_act_grp_w<8, 8, TL>), g, b8, 0, s, ta); break;
+    }
+  };
+  if (tiles && H == 256)
+    hipLaunchKernelGGL(ppo_act_c_grp_w, g, b8, 0, s, ta);
+  else if (tiles)
+    launch(std::integral_constant<bool, true>());
+  else
+    launch(std::integral_constant<bool, false>());
+  return wide_rc();
+}
+
+int hwy_ppo_wide_rows_mix(int cls, int grid, int G, int lds, const void* tr, const void* tl,
+                          const void* tq, hipStream_t s) {
+  const RowArgs* r = static_cast<const RowArgs*>(tr);
+  const GroupLim* l = static_cast<const GroupLim*>(tl);
+  const int* q = static_cast<const int*>(tq);
+  if (cls == 0)
+    hipLaunchKernelGGL((ppo_rows_mix_w<8>), dim3(grid, G), dim3(512), lds, s, r, l, q);
+  else
+    hipLaunchKernelGGL((ppo_rows_mix_w<4>), dim3(grid, G), dim3(256), lds, s, r, l, q);
+  return wide_rc();
+}
+
+int hwy_ppo_wide_rows_sched(int cls, int grid, int G, int lds, const void* tr, const void* tl,
+                            const void* tq, const void* tc, const void* tb, int slot,
+                            hipStream_t s) {
+  const RowArgs* r = static_cast<const RowArgs*>(tr);
+  const GroupLim* l = static_cast<const GroupLim*>(tl);
+  const int* q = static_cast<const int*>(tq);
+  const SchedRec* c = static_cast<const SchedRec*>(tc);
+  const int* b = static_cast<const int*>(tb);
+  if (cls == 0)
+    hipLaunchKernelGGL((ppo_rows_sched_w<8>), dim3(grid, G), dim3(512), lds, s, r, l, q, c, b, slot);
+  else
+    hipLaunchKernelGGL((ppo_rows_sched_w<4>), dim3(grid, G), dim3(256), lds, s, r, l, q, c, b, slot);
+  return wide_rc();
+}
+
+int hwy_ppo_wide_act_mix(int cls, int tiles, int B, int G, int lds, const void* ta_,
+                         const void* tq_, hipStream_t s) {
+  const ActArgs* ta = static_cast<const ActArgs*>(ta_);
+  const int* tq = static_cast<const int*>(tq_);
+  const dim3 g((B + kRowTile - 1) / kRowTile, G);
+  if (cls == 0) {
+    if (tiles)
+      hipLaunchKernelGGL((ppo_act_mix_w<8, true>), g, dim3(512), lds, s, ta, tq);
+    else
+      hipLaunchKernelGGL((ppo_act_mix_w<8, false>), g, dim3(512), lds, s, ta, tq);
+  } else {
+    if (tiles)
+      hipLaunchKernelGGL((ppo_act_mix_w<4, true>), g, dim3(256), lds, s, ta, tq);
+    else
+      hipLaunchKernelGGL((ppo_act_mix_w<4, false>), g, dim3(256), lds, s, ta, tq);
+  }
+  return wide_rc();
+}
+
+bool hwy_ppo_wide_raise_lds(int kind, int cls, int tiles) {
+  const int rows = 4 * (cls == 0 ? rows_lds_floats<8, 8, kRowTile>()
+                                 : rows_lds_floats<7, 4, kRowTile>());
+  const int act = 4 * (cls == 0 ? act_lds_floats<8>() : act_lds_floats<7>());
+  const void* k;
+  if (kind == 0)
+    k = cls == 0 ? (const void*)ppo_rows_mix_w<8> : (const void*)ppo_rows_mix_w<4>;
+  else if (kind == 1)
+    k = cls == 0 ? (const void*)ppo_rows_sched_w<8> : (const void*)ppo_rows_sched_w<4>;
+  else if (cls == 0)
+    k = tiles ? (const void*)ppo_act_mix_w<8, true> : (const void*)ppo_act_mix_w<8, false>;
+  else
+    k = tiles ? (const void*)ppo_act_mix_w<4, true> : (const void*)ppo_act_mix_w<4, false>;
+  return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             kind == 2 ? act : rows) == hipSuccess;
+}
+
+#else  // HWY_PPO_WIDE_TU
 
 extern "C" {
 
@@ -2676,6 +3089,8 @@ static int forward_backward_k(const hwy_ppo_args* a, void* stream, int mask) {
     // 8 waves (2 per SIMD) when the columns split into 16-wide tiles, else 4
     const dim3 g1(w.n1), b4(256), b8(512), blk(256);
     if (!(mask & 1)) {
+    } else if (wide_s(S)) {  // the chunked first layer: the wide unit's ppo_rows_w
+      rc |= hwy_ppo_wide_rows(&r, H, w.n1, s);
     } else if (w.rt == 4 * kRowTile) {
       hipLaunchKernelGGL((ppo_rows_c64<4, 8>), g1, b8, 0, s, r);
     } else if (w.rt == 2 * kRowTile) {
@@ -2949,6 +3364,7 @@ int hwy_ppo_act(const hwy_ppo_act_args* a, void* stream) {
   for (int i = 0; i < 13; ++i) r.off[i] = L.off[i];
   r.action = a->action, r.pre_tanh = a->pre_tanh, r.logp = a->logp, r.value = a->value;
   r.tiles = a->tiles;
+  if (wide_s(d.S)) return hwy_ppo_wide_act(&r, d.H, d.B, s);  // chunked first layer, 16-row tiles
   const dim3 g((d.B + kRowTile - 1) / kRowTile), b4(256), b8(512);
   auto launch = [&](auto tl) {
     constexpr bool TL = decltype(tl)::value;
@@ -2993,9 +3409,11 @@ int hwy_ppo_group_prepare(const hwy_ppo_args* a, int G, void* table, hwy_ppo_gro
   hwy_ppo_group_plan p = {};
   p.G = G, p.B = d0.B, p.H = d0.H;
   int rc = 0;
+  bool wide = false;
   for (int g = 0; g < G && rc == 0; ++g) {
     const hwy_ppo_args& ag = a[g];
     const hwy_ppo_dims& d = ag.dims;
+    wide = wide || wide_s(d.S);
     if (d.B != d0.B || d.H != d0.H || d.A != d0.A || !group_dims_ok(d) || ag.grads_modified ||
         !ag.workspace || !ag.counters || !ag.params || !ag.grads || !ag.adam_m || !ag.adam_v) {
       rc = -1;
@@ -3016,6 +3434,7 @@ int hwy_ppo_group_prepare(const hwy_ppo_args* a, int G, void* table, hwy_ppo_gro
     p.grid_rows = std::max(p.grid_rows, l.rows), p.grid_wgrad = std::max(p.grid_wgrad, l.wgrad);
     p.grid_wsum = std::max(p.grid_wsum, l.wsum), p.grid_adam = std::max(p.grid_adam, l.adam);
   }
+  if (wide) p.grid_rows |= kPlanWide;
   hipStream_t s = (hipStream_t)stream;
   if (rc == 0 && (hipMemcpyAsync(table, host, (size_t)bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
                   hipStreamSynchronize(s) != hipSuccess))
@@ -3036,16 +3455,21 @@ int hwy_ppo_group_step(const hwy_ppo_group_plan* plan, const void* table, void* 
   const OptArgs* to = reinterpret_cast<const OptArgs*>(t + grp_opt_off(G));
   const GroupLim* tl = reinterpret_cast<const GroupLim*>(t + grp_lim_off(G));
   hipStream_t s = (hipStream_t)stream;
-  const dim3 g1(plan->grid_rows, G), b4(256), b8(512);
-  switch (plan->H / 64) {
-    case 1: hipLaunchKernelGGL((ppo_rows_grp<1, 4, 16>), g1, b4, 0, s, tr, tl); break;
-    case 2: hipLaunchKernelGGL((ppo_rows_grp<2, 8, 16>), g1, b8, 0, s, tr, tl); break;
-    case 3: hipLaunchKernelGGL((ppo_rows_grp<3, 4, 16>), g1, b4, 0, s, tr, tl); break;
-    case 4: hipLaunchKernelGGL((ppo_rows_grp<4, 8, 16>), g1, b8, 0, s, tr, tl); break;
-    case 5: hipLaunchKernelGGL((ppo_rows_grp<5, 4, 16>), g1, b4, 0, s, tr, tl); break;
-    case 6: hipLaunchKernelGGL((ppo_rows_grp<6, 8, 16>), g1, b8, 0, s, tr, tl); break;
-    case 7: hipLaunchKernelGGL((ppo_rows_grp<7, 4, 16>), g1, b4, 0, s, tr, tl); break;
-    default: hipLaunchKernelGGL((ppo_rows_grp<8, 8, 16>), g1, b8, 0, s, tr, tl); break;
+  const int grid_rows = plan->grid_rows & ~kPlanWide;
+  const dim3 g1(grid_rows, G), b4(256), b8(512);
+  if (plan->grid_rows & kPlanWide) {
+    if (hwy_ppo_wide_rows_grp(plan->H, grid_rows, G, tr, tl, s) != 0) return -1;
+  } else {
+    switch (plan->H / 64) {
+      case 1: hipLaunchKernelGGL((ppo_rows_grp<1, 4, 16>), g1, b4, 0, s, tr, tl); break;
+      case 2: hipLaunchKernelGGL((ppo_rows_grp<2, 8, 16>), g1, b8, 0, s, tr, tl); break;
+      case 3: hipLaunchKernelGGL((ppo_rows_grp<3, 4, 16>), g1, b4, 0, s, tr, tl); break;
+      case 4: hipLaunchKernelGGL((ppo_rows_grp<4, 8, 16>), g1, b8, 0, s, tr, tl); break;
+      case 5: hipLaunchKernelGGL((ppo_rows_grp<5, 4, 16>), g1, b4, 0, s, tr, tl); break;
+      case 6: hipLaunchKernelGGL((ppo_rows_grp<6, 8, 16>), g1, b8, 0, s, tr, tl); break;
+      case 7: hipLaunchKernelGGL((ppo_rows_grp<7, 4, 16>), g1, b4, 0, s, tr, tl); break;
+      default: hipLaunchKernelGGL((ppo_rows_grp<8, 8, 16>), g1, b8, 0, s, tr, tl); break;
+    }
   }
   int rc = hipGetLastError() == hipSuccess ? 0 : -1;
   hipLaunchKernelGGL(ppo_wgrad_grp, dim3(plan->grid_wgrad, G), dim3(64 * kWgWaves), 0, s, tw, tl);
@@ -3098,6 +3522,8 @@ int hwy_ppo_group_act(const hwy_ppo_dims* d, int G, int tiles, const void* table
   if (!d || G < 1 || !table || !fused_ok(*d) || d->A != 2 || d->B < 1) return -1;
   const ActArgs* ta = static_cast<const ActArgs*>(table);
   hipStream_t s = (hipStream_t)stream;
+  // d->S is the widest learner's: past kMaxRowS every learner runs the chunked kernel
+  if (wide_s(d->S)) return hwy_ppo_wide_act_grp(d->H, d->B, G, tiles, ta, s);
   const dim3 g((d->B + kRowTile - 1) / kRowTile, G), b4(256), b8(512);
   auto launch = [&](auto tl) {
     constexpr bool TL = decltype(tl)::value;
@@ -3191,6 +3617,7 @@ int hwy_ppo_mixed_prepare(const hwy_ppo_args* a, int G, void* table, hwy_ppo_mix
   char* host = static_cast<char*>(calloc((size_t)bytes, 1));
   if (!host) return -2;
   int rc = 0;
+  bool wide[2] = {false, false};
   for (int g = 0; g < G && rc == 0; ++g) {
     const hwy_ppo_args& ag = a[g];
     const hwy_ppo_dims& d = ag.dims;
@@ -3208,6 +3635,7 @@ int hwy_ppo_mixed_prepare(const hwy_ppo_args* a, int G, void* table, hwy_ppo_mix
     reinterpret_cast<GroupLim*>(host + grp_lim_off(G))[g] = l;
     const int qh = d.H / 64, cls = qh & 1;
     reinterpret_cast<int32_t*>(host + mix_qh_off(G))[g] = qh;
+    wide[cls] = wide[cls] || wide_s(d.S);
     p.present[cls] += 1;
     p.grid_rows[cls] = std::max(p.grid_rows[cls], l.rows);
     p.lds_bytes[cls] = std::max(p.lds_bytes[cls], mix_rows_lds_bytes(qh));
@@ -3215,11 +3643,15 @@ int hwy_ppo_mixed_prepare(const hwy_ppo_args* a, int G, void* table, hwy_ppo_mix
     p.grid_wsum = std::max(p.grid_wsum, l.wsum), p.grid_adam = std::max(p.grid_adam, l.adam);
   }
   hipStream_t s = (hipStream_t)stream;
+  for (int c = 0; c < 2; ++c)
+    if (wide[c]) p.grid_rows[c] |= kPlanWide;
   if (rc == 0 && p.present[0] &&
-      !mix_raise_lds((const void*)ppo_rows_mix<8>, 4 * rows_lds_floats<8, 8, kRowTile>()))
+      !(wide[0] ? hwy_ppo_wide_raise_lds(0, 0, 0)
+                : mix_raise_lds((const void*)ppo_rows_mix<8>, 4 * rows_lds_floats<8, 8, kRowTile>())))
     rc = -2;
   if (rc == 0 && p.present[1] &&
-      !mix_raise_lds((const void*)ppo_rows_mix<4>, 4 * rows_lds_floats<7, 4, kRowTile>()))
+      !(wide[1] ? hwy_ppo_wide_raise_lds(0, 1, 0)
+                : mix_raise_lds((const void*)ppo_rows_mix<4>, 4 * rows_lds_floats<7, 4, kRowTile>())))
     rc = -2;
   if (rc == 0 && (hipMemcpyAsync(table, host, (size_t)bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
                   hipStreamSynchronize(s) != hipSuccess))
@@ -3246,12 +3678,16 @@ int hwy_ppo_mixed_step(const hwy_ppo_mixed_plan* plan, const void* table, void* 
   const int* tq = reinterpret_cast<const int*>(t + mix_qh_off(G));
   hipStream_t s = (hipStream_t)stream;
   int rc = 0;
-  if (plan->present[0]) {
+  for (int c = 0; c < 2; ++c)  // a class with a wide learner: the wide unit's kernel for all of it
+    if (plan->present[c] && (plan->grid_rows[c] & kPlanWide))
+      rc |= hwy_ppo_wide_rows_mix(c, plan->grid_rows[c] & ~kPlanWide, G, plan->lds_bytes[c], tr, tl,
+                                  tq, s);
+  if (plan->present[0] && !(plan->grid_rows[0] & kPlanWide)) {
     hipLaunchKernelGGL((ppo_rows_mix<8>), dim3(plan->grid_rows[0], G), dim3(512),
                        plan->lds_bytes[0], s, tr, tl, tq);
     rc |= hipGetLastError() == hipSuccess ? 0 : -1;
   }
-  if (plan->present[1]) {
+  if (plan->present[1] && !(plan->grid_rows[1] & kPlanWide)) {
     hipLaunchKernelGGL((ppo_rows_mix<4>), dim3(plan->grid_rows[1], G), dim3(256),
                        plan->lds_bytes[1], s, tr, tl, tq);
     rc |= hipGetLastError() == hipSuccess ? 0 : -1;
@@ -3281,6 +3717,7 @@ int hwy_ppo_mixed_act_prepare(const hwy_ppo_act_args* a, int G, void* table,
   char* host = static_cast<char*>(calloc((size_t)bytes, 1));
   if (!host) return -2;
   int rc = 0;
+  bool wide[2] = {false, false};
   for (int g = 0; g < G; ++g) {
     const hwy_ppo_act_args& ag = a[g];
     if (ag.dims.B != d.B || ag.dims.A != 2 || !fused_ok(ag.dims) ||
@@ -3298,16 +3735,23 @@ int hwy_ppo_mixed_act_prepare(const hwy_ppo_act_args* a, int G, void* table,
     reinterpret_cast<ActArgs*>(host)[g] = r;
     const int qh = ag.dims.H / 64, cls = qh & 1;
     reinterpret_cast<int32_t*>(host + mix_act_qh_off(G))[g] = qh;
+    wide[cls] = wide[cls] || wide_s(ag.dims.S);
     p.present[cls] += 1;
     p.lds_bytes[cls] = std::max(p.lds_bytes[cls], mix_act_lds_bytes(qh, p.tiles != 0));
   }
   const int m8 = 4 * act_lds_floats<8>(), m4 = 4 * act_lds_floats<7>();
   if (rc == 0 && p.present[0] &&
-      !(p.tiles ? mix_raise_lds((const void*)ppo_act_mix<8, true>, m8) : mix_raise_lds((const void*)ppo_act_mix<8, false>, m8)))
+      !(wide[0]   ? hwy_ppo_wide_raise_lds(2, 0, p.tiles)
+        : p.tiles ? mix_raise_lds((const void*)ppo_act_mix<8, true>, m8)
+                  : mix_raise_lds((const void*)ppo_act_mix<8, false>, m8)))
     rc = -2;
   if (rc == 0 && p.present[1] &&
-      !(p.tiles ? mix_raise_lds((const void*)ppo_act_mix<4, true>, m4) : mix_raise_lds((const void*)ppo_act_mix<4, false>, m4)))
+      !(wide[1]   ? hwy_ppo_wide_raise_lds(2, 1, p.tiles)
+        : p.tiles ? mix_raise_lds((const void*)ppo_act_mix<4, true>, m4)
+                  : mix_raise_lds((const void*)ppo_act_mix<4, false>, m4)))
     rc = -2;
+  for (int c = 0; c < 2 && rc == 0; ++c)
+    if (wide[c]) p.lds_bytes[c] |= kPlanWide;
   hipStream_t s = (hipStream_t)stream;
   if (rc == 0 && (hipMemcpyAsync(table, host, (size_t)bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
                   hipStreamSynchronize(s) != hipSuccess))
@@ -3321,7 +3765,9 @@ int hwy_ppo_mixed_act(const hwy_ppo_mixed_act_plan* plan, const void* table, voi
   if (!plan || !table || plan->G < 1 || plan->B < 1 || (!plan->present[0] && !plan->present[1]))
     return -1;
   for (int c = 0; c < 2; ++c)
-    if (plan->present[c] && (plan->lds_bytes[c] < 1 || plan->lds_bytes[c] > kMixLdsMax)) return -1;
+    if (plan->present[c] && (plan->lds_bytes[c] < 1 ||
+                             (plan->lds_bytes[c] & ~kPlanWide) > kMixLdsMax))
+      return -1;
   const int G = plan->G;
   const char* t = static_cast<const char*>(table);
   const ActArgs* ta = reinterpret_cast<const ActArgs*>(t);
@@ -3329,14 +3775,18 @@ int hwy_ppo_mixed_act(const hwy_ppo_mixed_act_plan* plan, const void* table, voi
   hipStream_t s = (hipStream_t)stream;
   const dim3 g((plan->B + kRowTile - 1) / kRowTile, G);
   int rc = 0;
-  if (plan->present[0]) {
+  for (int c = 0; c < 2; ++c)  // a class with a wide learner: the wide unit's kernel for all of it
+    if (plan->present[c] && (plan->lds_bytes[c] & kPlanWide))
+      rc |= hwy_ppo_wide_act_mix(c, plan->tiles, plan->B, G, plan->lds_bytes[c] & ~kPlanWide, ta, tq,
+                                 s);
+  if (plan->present[0] && !(plan->lds_bytes[0] & kPlanWide)) {
     if (plan->tiles)
       hipLaunchKernelGGL((ppo_act_mix<8, true>), g, dim3(512), plan->lds_bytes[0], s, ta, tq);
     else
       hipLaunchKernelGGL((ppo_act_mix<8, false>), g, dim3(512), plan->lds_bytes[0], s, ta, tq);
     rc |= hipGetLastError() == hipSuccess ? 0 : -1;
   }
-  if (plan->present[1]) {
+  if (plan->present[1] && !(plan->lds_bytes[1] & kPlanWide)) {
     if (plan->tiles)
       hipLaunchKernelGGL((ppo_act_mix<4, true>), g, dim3(256), plan->lds_bytes[1], s, ta, tq);
     else
@@ -3409,6 +3859,7 @@ int hwy_ppo_sched_prepare(const hwy_ppo_args* a, const int32_t* nmb, const int32
   if (!host) return -2;
   int rc = 0;
   int row0 = 0;
+  bool wide[2] = {false, false};
   for (int g = 0; g < G && rc == 0; ++g) {
     const hwy_ppo_args& ag = a[g];
     const hwy_ppo_dims& d = ag.dims;
@@ -3431,6 +3882,7 @@ int hwy_ppo_sched_prepare(const hwy_ppo_args* a, const int32_t* nmb, const int32
     reinterpret_cast<GroupLim*>(host + sch_lim_off(G))[g] = l;
     const int qh = d.H / 64, cls = qh & 1;
     reinterpret_cast<int32_t*>(host + sch_qh_off(G))[g] = qh;
+    wide[cls] = wide[cls] || wide_s(d.S);
     SchedRec c;
     c.row0 = row0, c.nmb = nmb[g], c.steps = nmb[g] * epochs[g];
     reinterpret_cast<SchedRec*>(host + sch_rec_off(G))[g] = c;
@@ -3444,11 +3896,15 @@ int hwy_ppo_sched_prepare(const hwy_ppo_args* a, const int32_t* nmb, const int32
     p.period = sched_gcd(p.period, c.steps);  // gcd(0, x) = x
   }
   hipStream_t s = (hipStream_t)stream;
+  for (int c = 0; c < 2; ++c)
+    if (wide[c]) p.grid_rows[c] |= kPlanWide;
   if (rc == 0 && p.present[0] &&
-      !mix_raise_lds((const void*)ppo_rows_sched<8>, 4 * rows_lds_floats<8, 8, kRowTile>()))
+      !(wide[0] ? hwy_ppo_wide_raise_lds(1, 0, 0)
+                : mix_raise_lds((const void*)ppo_rows_sched<8>, 4 * rows_lds_floats<8, 8, kRowTile>())))
     rc = -2;
   if (rc == 0 && p.present[1] &&
-      !mix_raise_lds((const void*)ppo_rows_sched<4>, 4 * rows_lds_floats<7, 4, kRowTile>()))
+      !(wide[1] ? hwy_ppo_wide_raise_lds(1, 1, 0)
+                : mix_raise_lds((const void*)ppo_rows_sched<4>, 4 * rows_lds_floats<7, 4, kRowTile>())))
     rc = -2;
   // the slot base word is part of the copy: 0, as after hwy_ppo_sched_begin
   if (rc == 0 && (hipMemcpyAsync(table, host, (size_t)bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -3481,12 +3937,16 @@ int hwy_ppo_sched_step(const hwy_ppo_sched_plan* plan, const void* table, int sl
   const int* tb = reinterpret_cast<const int*>(t + sch_base_off(G));
   hipStream_t s = (hipStream_t)stream;
   int rc = 0;
-  if (plan->present[0]) {
+  for (int c = 0; c < 2; ++c)  // a class with a wide learner: the wide unit's kernel for all of it
+    if (plan->present[c] && (plan->grid_rows[c] & kPlanWide))
+      rc |= hwy_ppo_wide_rows_sched(c, plan->grid_rows[c] & ~kPlanWide, G, plan->lds_bytes[c], tr,
+                                    tl, tq, tc, tb, slot, s) ? -2 : 0;
+  if (plan->present[0] && !(plan->grid_rows[0] & kPlanWide)) {
     hipLaunchKernelGGL((ppo_rows_sched<8>), dim3(plan->grid_rows[0], G), dim3(512),
                        plan->lds_bytes[0], s, tr, tl, tq, tc, tb, slot);
     rc |= hipGetLastError() == hipSuccess ? 0 : -2;
   }
-  if (plan->present[1]) {
+  if (plan->present[1] && !(plan->grid_rows[1] & kPlanWide)) {
     hipLaunchKernelGGL((ppo_rows_sched<4>), dim3(plan->grid_rows[1], G), dim3(256),
                        plan->lds_bytes[1], s, tr, tl, tq, tc, tb, slot);
     rc |= hipGetLastError() == hipSuccess ? 0 : -2;
@@ -3513,3 +3973,5 @@ int hwy_ppo_sched_advance(const hwy_ppo_sched_plan* plan, void* table, int slots
 #endif  // HWY_PPO_MIXED_TU
 
 }  // extern "C"
+
+#endif  // HWY_PPO_WIDE_TU

@@ -18,7 +18,7 @@
   float hz0, hz1, hold, hadv, hret, hq0, hq1;
   Gathered<RT, NT> xpre;
   const long hsrc = (long)r.idx[row0 + hl];
-  gather_issue<RT, NT>(r.states, r.idx, S, nrows, row0, H, xpre);
+  gather_first<RT, NT, WIDE>(r.states, r.idx, S, nrows, row0, H, xpre);
   hz0 = r.pre_tanh[hsrc * 2];
   hz1 = r.pre_tanh[hsrc * 2 + 1];
   hold = r.old_logp[hsrc];
@@ -48,10 +48,9 @@
   const float lsc0 = logf(sc0), lsc1 = logf(sc1);
   f32x4 av[RB][TW], cv[RB][TW];  // a1, c1 of this wave's columns (C layout)
   uint32_t mb[2] = {0u, 0u};      // CMP: ReLU decisions of h1, h2 (this lane's C elements)
-  rows_forward<QH, NW, RT, true, D, 7, true, CMP>(R, r.states, r.idx, S, nrows, row0, P, r.off, X,
-                                                  H1, P1, AC, r.xg, r.h1,
-                                                  r.h2, mb, av,
-                                                  cv PSEC_ARGS, &xpre);
+  rows_forward<QH, NW, RT, true, D, 7, true, CMP, CMP, WIDE>(R, r.states, r.idx, S, nrows, row0, P,
+                                                             r.off, X, H1, P1, AC, r.xg, r.h1,
+                                                             r.h2, mb, av, cv PSEC_ARGS, &xpre);
   PSEC(3);
   const int g4 = lane >> 4, c16 = lane & 15;
 

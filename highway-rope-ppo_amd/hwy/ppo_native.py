@@ -232,8 +232,14 @@ def _act_tiles(agent, flat: torch.Tensor, S: int, H: int) -> Optional[int]:
     return T.current()
 
 
+# widest state row of the fused step and of hwy_ppo_act (include/hwy_ppo.h; past 256 floats the
+# kernels run their first layer in chunks of 256 columns)
+MAX_FUSED_STATE_DIM = 1024
+
+
 def act_supported(S: int, H: int, A: int) -> bool:
-    return A == 2 and S % 4 == 0 and S <= 256 and H % 64 == 0 and 64 <= H <= 512
+    return (A == 2 and S % 4 == 0 and 0 < S <= MAX_FUSED_STATE_DIM and H % 64 == 0
+            and 64 <= H <= 512)
 
 
 def act_tiles(agent, flat: torch.Tensor, S: int, H: int) -> Optional[int]:
@@ -724,7 +730,8 @@ class GroupAct:
         self.mixed = len(set(self.Hs)) > 1
         if self.mixed:
             _need_mixed(self.L)
-        self.dims = PpoDims(self.B, self.S[0], self.H, 2)
+        # hwy_ppo_group_act takes the shared B and H and the widest learner's S
+        self.dims = PpoDims(self.B, max(self.S), self.H, 2)
         nb = (self.L.hwy_ppo_mixed_act_table_bytes(self.G) if self.mixed
               else self.L.hwy_ppo_group_act_table_bytes(self.G))
         self.dev = self.agents[0].device

@@ -455,7 +455,7 @@ class PPOAgent:
         ok = act_supported(state.shape[1], H, self.actor_critic.log_std.numel())
         if not ok and self.backend == "hip":
             raise ValueError("backend='hip' acting needs action_dim 2, state_dim % 4 == 0 "
-                             "(<= 256) and hidden_dim in {64,128,...,512}")
+                             "(<= 1024) and hidden_dim in {64,128,...,512}")
         return ok
 
     # ------------------------------------------------------------------ metrics

@@ -17,8 +17,10 @@
  * products, fp32 accumulate).
  * Calls are asynchronous, allocate nothing and are hipGraph-capturable.
  *
- * Weight tile image: on the fused path (S % 4 == 0, S <= 256, H <= 512) the row kernel streams
- * the weights from a tiled copy kept in the workspace.  hwy_ppo_optimizer rewrites it with every
+ * Weight tile image: on the fused path (S % 4 == 0, S <= 1024, H <= 512) the row kernel streams
+ * the weights from a tiled copy kept in the workspace.  (Past S = 256 the row and act kernels run
+ * their first layer over chunks of 256 state columns, always at 16-row tiles; every other shape
+ * outside the fused range takes the general path.)  hwy_ppo_optimizer rewrites it with every
  * Adam step; call hwy_ppo_sync_params once before the first hwy_ppo_forward_backward on a
  * workspace, and again whenever params were written by anything other than hwy_ppo_optimizer
  * (a checkpoint load, a torch optimizer step, a broadcast).
@@ -91,7 +93,7 @@ int64_t hwy_ppo_tile_image_offset(const hwy_ppo_dims* d);
 /* ActorCritic.act on a batch (replaces ppo/agent.py:86-95's forward + Normal sample + tanh +
  * squashed log-prob on the batched rollout path): dims.B rows of states [B][S] (contiguous);
  * noise [B][2] standard-normal draws (the caller's generator, as act() draws them) or NULL for
- * act(deterministic=True) (z = mean, log_prob = 0).  Needs S % 4 == 0, S <= 256,
+ * act(deterministic=True) (z = mean, log_prob = 0).  Needs S % 4 == 0, S <= 1024,
  * H in {64, 128, ..., 512}.  tiles: NULL, or the tile image of a hwy_ppo workspace with the same
  * S and H that is in step with params (workspace + hwy_ppo_tile_image_offset; current after
  * hwy_ppo_optimizer / hwy_ppo_sync_params until params are written by anything else): the
@@ -124,7 +126,14 @@ int hwy_ppo_act(const hwy_ppo_act_args* a, void* stream);
  * h256 cells of a sweep: no PE S = N*F, RankPE / DistPE S = N*(F+d)): each launch covers the
  * largest learner's grid (the plan prepare writes) and a learner's surplus workgroups exit.
  * hwy_ppo_group_table_bytes depends on B, H and G only.  -1 bad arguments / unsupported dims,
- * -2 HIP error. */
+ * -2 HIP error.
+ *
+ * Wide states: when a learner of the table has S > 256, the row (or act) launch runs the chunked
+ * kernels for every learner it covers -- at S <= 256 they run one chunk and produce the narrow
+ * kernels' bits -- and prepare marks that in the plan by setting HWY_PPO_PLAN_WIDE in grid_rows
+ * (hwy_ppo_mixed_plan / hwy_ppo_sched_plan: in grid_rows[c] of the class; hwy_ppo_mixed_act_plan:
+ * in lds_bytes[c]); the value itself is the field without that bit. */
+#define HWY_PPO_PLAN_WIDE (1 << 30)
 typedef struct hwy_ppo_group_plan {
   int32_t G, B, H;                                    /* learners; shared minibatch rows, hidden */
   int32_t grid_rows, grid_wgrad, grid_wsum, grid_adam; /* each launch's grid: the largest learner's */
@@ -134,7 +143,8 @@ int hwy_ppo_group_prepare(const hwy_ppo_args* a /*[G]*/, int G, void* table,
                           hwy_ppo_group_plan* plan, void* stream);
 int hwy_ppo_group_step(const hwy_ppo_group_plan* plan, const void* table, void* stream);
 /* hwy_ppo_act for G learners (same B and H; S may differ); `tiles` = whether the learners' args
- * carry tile images (all or none), which picks the solo call's kernel. */
+ * carry tile images (all or none), which picks the solo call's kernel.  hwy_ppo_group_act's d
+ * carries the shared B and H and the LARGEST S of the learners (S > 256: the chunked kernels). */
 int64_t hwy_ppo_group_act_table_bytes(int G);
 int hwy_ppo_group_act_prepare(const hwy_ppo_act_args* a /*[G]*/, int G, void* table, void* stream);
 int hwy_ppo_group_act(const hwy_ppo_dims* d, int G, int tiles, const void* table, void* stream);
