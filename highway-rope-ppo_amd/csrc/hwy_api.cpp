@@ -254,6 +254,19 @@ int hwy_step(hwy_handle* h, const float* actions, float* obs, float* reward, uin
   return HWY_OK;
 }
 
+int hwy_cut_episodes(hwy_handle* h, float* obs, float* ep_return, int32_t* ep_length,
+                     uint8_t* cut, void* stream) {
+  if (!h) return fail(HWY_EINVAL, "handle is NULL");
+  if (!obs) return fail(HWY_EINVAL, "hwy_cut_episodes: obs must be non-NULL");
+  StepParams p = params_of(h);
+  p.obs = obs;
+  p.ep_ret = ep_return;
+  p.ep_len = ep_length;
+  if (hwy_launch_cut(&p, cut, (hipStream_t)stream))
+    return hip_fail(hipGetLastError(), "hwy_cut_kernel");
+  return HWY_OK;
+}
+
 int64_t hwy_step_group_table_bytes(int n) {
   return n < 1 ? -1 : (int64_t)n * (int64_t)sizeof(StepParams);
 }

@@ -35,6 +35,8 @@ int hwy_launch_step_group(const StepParams* dtab, int n, int blocks, int big, hi
 int hwy_step_blocks(int num_envs);
 int hwy_step_big(int64_t total_envs);
 int hwy_launch_reset(const StepParams* p, hipStream_t s);
+// hwy_cut_episodes: p->obs / ep_ret / ep_len as for a step, cut [E] u8 (nullable)
+int hwy_launch_cut(const StepParams* p, uint8_t* cut, hipStream_t s);
 int hwy_launch_obs_pe(const float* in, float* out, int E, int N, int F, int kind, int d, int ego,
                       float max_dist, const float* table, const float* dov, hipStream_t s);
 int hwy_launch_gae(const float* rew, const uint8_t* done, const float* val, const float* last_val,

@@ -1370,6 +1370,53 @@ __device__ __forceinline__ void step_body(const StepParams& P) {
   SEC_FLUSH(sp, lane, e);
 }
 
+// hwy_cut_kernel is compiled as a translation unit of its own from this source (-DHWY_CUT_TU ->
+// hwy_cut.o, as ppo_mixed.o / ppo_wide.o are from ppo_kernels.hip): that unit holds the cut
+// kernel and its launcher and none of the other kernels, the main unit everything but them, so
+// the main unit's code object is the one it was before the cut kernel existed.
+#ifdef HWY_CUT_TU
+// hwy_cut_episodes: end every running episode (step >= 1) and start the next one of the
+// schedule, exactly as step_body's autoreset branch does at a truncation; an env at step 0 is
+// left alone (no state or obs store).  One wave per env, as hwy_reset_kernel.
+__global__ void __launch_bounds__(256) hwy_cut_kernel(StepParams P, uint8_t* __restrict__ cut) {
+  __shared__ int lds_vor[ENVS_PER_BLOCK][WAVE];
+  __shared__ int lds_inv[ENVS_PER_BLOCK][WAVE];
+  __shared__ unsigned long long lds_key[ENVS_PER_BLOCK][WAVE];
+  const hwy_config& C = P.cfg;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int w = threadIdx.x / WAVE;
+  const int e = blockIdx.x * ENVS_PER_BLOCK + w;
+  if (e >= C.num_envs) return;  // whole wave
+  const int V = C.vehicles_count + 1;
+  const size_t fstride = (size_t)C.num_envs * WAVE;
+  const uint32_t idx = (uint32_t)e * WAVE + lane;  // < 2^32: hwy_create bounds num_envs
+  const uint32_t ew = (P.state + HWY_F_ENV * fstride)[idx];
+  const int step = rdli((int)ew, HWY_E_STEP);
+  const int episode = rdli((int)ew, HWY_E_EPISODE) + 1;
+  const float ep_return = hm_bits2f((uint32_t)rdli((int)ew, HWY_E_RETURN));
+  const bool running = step >= 1;  // wave-uniform
+  if (lane == 0) {
+    if (cut) cut[e] = running ? 1 : 0;
+    if (P.ep_ret) P.ep_ret[e] = running ? ep_return : 0.0f;
+    if (P.ep_len) P.ep_len[e] = running ? step : 0;
+  }
+  if (!running) return;
+  const uint64_t seed = episode_seed(P, e, episode);
+  Veh v;
+  reset_wave(C, lane, seed, v);
+  observe_wave(C, lane, v, 1.0f, 0.0f, 0, seed, group_pe_table(P, e),
+               P.obs + (size_t)e * C.obs_vehicles * P.fout, P.fout, lds_vor[w], lds_inv[w],
+               lds_key[w]);
+  store_veh(P.state, fstride, idx, lane, V, v, reset_order_pos(lane, V));
+  store_env_words(P.state, fstride, idx, lane, 0, episode, seed, 0.0f, 0.0f, 0.0f);
+}
+
+extern "C" int hwy_launch_cut(const StepParams* p, uint8_t* cut, hipStream_t s) {
+  const int blocks = (p->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  hipLaunchKernelGGL(hwy_cut_kernel, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p, cut);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+#else  // the main unit, to the end of the file
 template <int W>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
 hwy_step_kernel(StepParams P) {
@@ -1612,3 +1659,4 @@ extern "C" int hwy_debug_sections(unsigned long long* out, int reset) {
   return 0;
 }
 #endif
+#endif  // HWY_CUT_TU

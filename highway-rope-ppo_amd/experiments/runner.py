@@ -3,7 +3,10 @@
 Same launch sequence and status dict: acquire device -> seed -> logger -> make_env ->
 ``env.to(device)`` when the wrapper has it -> state/action dims -> PPOAgent ->
 train_with_experiment_name -> {"status": "COMPLETED"|"FAILED", ...}.  Experiment.extra may carry
-``num_envs`` (lockstep envs, > 1 selects the vectorised loop) and ``num_minibatches``.
+``num_envs`` (lockstep envs, > 1 selects the vectorised loop), ``num_minibatches`` and
+``episode_schedule`` ("lockstep", the default, or "reference": episodes cut at the update
+boundary and evaluations ahead of the update, training/routine.py; with it ``num_envs`` 1 runs
+the vectorised loop on a one-env HighwayVecEnv, which is the reference's own episode stream).
 
 Launched under torchrun (WORLD_SIZE > 1) one experiment spans the ranks, one GPU each: the
 runner joins the process group (RCCL, or ``HWY_DIST_BACKEND``), gives rank r the envs
@@ -122,6 +125,9 @@ class ExperimentRunner:
                         overrides.setdefault("num_envs", exp.extra["num_envs"])
                     if device.type == "cuda":
                         overrides.setdefault("device", device)
+                    schedule = exp.extra.get("episode_schedule", "lockstep")
+                    if schedule == "reference":
+                        overrides.setdefault("vector_env", True)
                     if group is not None:
                         e = int(overrides.get("num_envs", 1))
                         if e <= 1:
@@ -148,7 +154,8 @@ class ExperimentRunner:
                         log_interval=exp.extra.get("log_interval", 20),
                         eval_interval=exp.extra.get("eval_interval", 50),
                         steps_per_update=exp.hp.steps_per_update, experiment_name=exp.name,
-                        exp_seed=exp.seed, logger=logger)
+                        exp_seed=exp.seed, logger=logger,
+                        **({} if schedule == "lockstep" else {"episode_schedule": schedule}))
                     results.update(status="COMPLETED", rewards=rewards, avg_rewards=avg_rewards,
                                    metrics_history=metrics)
                 except Exception as e:
@@ -177,15 +184,16 @@ class ExperimentRunner:
         the env, acting and minibatch-step launches; each bit-identical to its solo launch()).
         The reference runs such a cell as len(exps) separate processes oversubscribing the GPUs
         (main.py:188-242, utils/device_pool.py:44-72).  Needs the vectorised loop
-        (extra["num_envs"] > 1) and the fused HIP learner; returns one status dict per experiment,
-        in order."""
+        (extra["num_envs"] > 1, or 1 with extra["episode_schedule"] = "reference") and the fused
+        HIP learner; returns one status dict per experiment, in order."""
         return self.launch_batch([exps])[0]
 
     @staticmethod
     def check_batch(cells, own_schedules: bool = False) -> None:
         """launch_batch's argument checks (no device needed): within a cell the experiments
-        differ only in seed and name and use the vectorised loop; across cells they share what
-        one GroupBatch's launches share -- envs per experiment and rollout length -- and the
+        differ only in seed and name and use the vectorised loop (num_envs > 1, or num_envs 1 on
+        the reference episode schedule); across cells they share what one GroupBatch's launches
+        share -- envs per experiment, rollout length and the episode schedule -- and the
         training schedule.  The condition and the hidden width may differ between cells.  The
         update's own schedule (batch_size, num_minibatches, epochs) must be shared too, unless
         ``own_schedules`` (what launch_batch passes): then it may differ between cells
@@ -194,15 +202,22 @@ class ExperimentRunner:
         import math
 
         from ppo.agent import PPOAgent
+        from ppo.rollout import check_episode_schedule
+
+        def episode_schedule(e):
+            return check_episode_schedule(e.extra.get("episode_schedule", "lockstep"))
 
         for exps in cells:
             key = {(e.condition, repr(e.hp), repr(sorted(e.extra.items())),
                     repr(e.env_config_overrides), e.max_episodes, e.target_reward) for e in exps}
             if len(key) != 1:
                 raise ValueError("launch_group: the experiments must differ only in seed and name")
-            if int(exps[0].extra.get("num_envs", 1)) <= 1:
+            if (int(exps[0].extra.get("num_envs", 1)) <= 1
+                    and episode_schedule(exps[0]) != "reference"):
                 raise ValueError("launch_group needs extra['num_envs'] > 1 (the vectorised loop)")
         first = [c[0] for c in cells]
+        if len({episode_schedule(e) for e in first}) != 1:
+            raise ValueError("launch_batch: the cells must share extra['episode_schedule']")
 
         def shared(e):
             return (int(e.extra.get("num_envs", 1)), e.hp.steps_per_update, e.max_episodes,
@@ -257,6 +272,9 @@ class ExperimentRunner:
         t0 = time.time()
         self.check_batch(cells, own_schedules=True)
         first = [c[0] for c in cells]
+        schedule = first[0].extra.get("episode_schedule", "lockstep")
+        # the default schedule passes no keyword: that path is the one without the feature
+        sched_kw = {} if schedule == "lockstep" else {"episode_schedule": schedule}
         results = [[{"experiment_name": e.name, "status": "FAILED"} for e in exps]
                    for exps in cells]
         loggers = []
@@ -283,7 +301,8 @@ class ExperimentRunner:
                     groups.append(build_group(e0.condition, self.base_config,
                                               [e.seed for e in exps], E, T, device, make_agent,
                                               d_embed=e0.hp.d_embed,
-                                              env_overrides=e0.env_config_overrides))
+                                              env_overrides=e0.env_config_overrides,
+                                              **sched_kw))
                 stepper = groups[0] if len(groups) == 1 else GroupBatch(groups)
                 e0 = first[0]
                 outs = train_batch(stepper, groups, [e.name for c in cells for e in c],
@@ -291,7 +310,7 @@ class ExperimentRunner:
                                    max_episodes=e0.max_episodes, target_reward=e0.target_reward,
                                    log_interval=e0.extra.get("log_interval", 20),
                                    eval_interval=e0.extra.get("eval_interval", 50),
-                                   loggers=loggers)
+                                   loggers=loggers, **sched_kw)
                 flat = [res for cell in results for res in cell]
                 for res, (rewards, avg_rewards, metrics) in zip(flat, outs):
                     res.update(status="COMPLETED", rewards=rewards, avg_rewards=avg_rewards,

@@ -13,6 +13,8 @@ Same signature, config resolution and errors as the reference's experiments/wrap
 Extra (native-only) keys read from the merged config, all optional:
   ``num_envs``        lockstep envs on this GPU; > 1 returns a HighwayVecEnv (torch tensors),
                       1 (default) the numpy single-env facade the reference's routine expects
+  ``vector_env``      True returns a HighwayVecEnv even for ``num_envs`` 1 (the reference episode
+                      schedule's one-env stream on the vectorised loop; training/routine.py)
   ``device``          HIP device (default: current)
   ``autoreset``       vector env only, default True
   ``env_offset``, ``global_envs``   episode-seed schedule for env-sharded multi-GPU runs
@@ -32,7 +34,7 @@ from .dist_embed import DistanceEmbedWrapper
 from .rank_embed import RankEmbedWrapper
 from .rope_embed import RotaryEmbedWrapper
 
-_NATIVE_KEYS = ("num_envs", "device", "autoreset", "env_offset", "global_envs")
+_NATIVE_KEYS = ("num_envs", "device", "autoreset", "env_offset", "global_envs", "vector_env")
 
 _SHUFFLED_FAMILY = (
     Condition.SHUFFLED,
@@ -81,7 +83,7 @@ def make_env(exp_condition: Condition, base_cfg: Dict[str, Any], d_embed: Option
              env_overrides: Dict[str, Any] = {}):  # noqa: B006 - reference signature
     cfg, native = resolve_config(exp_condition, base_cfg, d_embed, env_overrides)
     num_envs = int(native.get("num_envs", 1))
-    if num_envs > 1:
+    if num_envs > 1 or bool(native.get("vector_env", False)):
         env = HighwayVecEnv(cfg, num_envs=num_envs, device=native.get("device"),
                             autoreset=bool(native.get("autoreset", True)),
                             env_offset=int(native.get("env_offset", 0)),

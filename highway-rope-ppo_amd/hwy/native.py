@@ -73,6 +73,7 @@ def lib():
     L.hwy_set_seed_schedule.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64]
     L.hwy_reset.argtypes = [vp, vp, vp, vp, vp]
     L.hwy_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.hwy_cut_episodes.argtypes = [vp, vp, vp, vp, vp, vp]
     L.hwy_export_state.argtypes = [vp, vp, vp]
     L.hwy_import_state.argtypes = [vp, vp, vp]
     L.hwy_obs_pe.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp]
@@ -84,7 +85,8 @@ def lib():
     L.hwy_step_group_prepare.argtypes = [vp, vp, i32, vp, ctypes.POINTER(HwyStepGroupPlan), vp]
     L.hwy_step_group.argtypes = [ctypes.POINTER(HwyStepGroupPlan), vp, vp]
     for name in ("hwy_create", "hwy_obs_features", "hwy_set_pe_table", "hwy_set_seed_schedule",
-                 "hwy_set_seed_groups", "hwy_reset", "hwy_step", "hwy_step_group_prepare",
+                 "hwy_set_seed_groups", "hwy_reset", "hwy_step", "hwy_cut_episodes",
+                 "hwy_step_group_prepare",
                  "hwy_step_group",
                  "hwy_export_state", "hwy_import_state", "hwy_obs_pe", "hwy_gae",
                  "hwy_math_selftest"):

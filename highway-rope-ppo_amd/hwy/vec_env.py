@@ -188,6 +188,16 @@ class HighwayVecEnv:
                              ptr(truncated), ptr(ep_return), ptr(ep_length), stream_ptr()),
               "hwy_step")
 
+    def cut_episodes(self, obs: torch.Tensor, ep_return: Optional[torch.Tensor] = None,
+                     ep_length: Optional[torch.Tensor] = None,
+                     cut: Optional[torch.Tensor] = None) -> None:
+        """End every running episode and start the schedule's next one (hwy_cut_episodes: the
+        reference's cut at the update boundary, training/routine.py:125-132,153-156), writing
+        into caller-owned device tensors (graph-safe).  Envs at step 0 are left alone: their obs
+        rows are not written and their ``cut`` byte is 0."""
+        check(lib().hwy_cut_episodes(self._handle, ptr(obs), ptr(ep_return), ptr(ep_length),
+                                     ptr(cut), stream_ptr()), "hwy_cut_episodes")
+
     def set_seed_schedule(self, seed_base: int, env_offset: Optional[int] = None,
                           seed_stride: Optional[int] = None) -> None:
         """seed(env e, episode k) = seed_base + env_offset + e + 1 + seed_stride * k."""

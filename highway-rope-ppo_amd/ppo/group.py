@@ -18,6 +18,11 @@ Every experiment keeps its own weights, Adam state, torch generator (sampling no
 minibatch permutation) and advantage normalisation, drawn in its solo run's order, and the
 kernels run the solo calls' bodies per learner, so each experiment is bit for bit its solo run
 (training/routine.py's _train_vector with the same seed): tests/test_group_gpu.py.
+
+``episode_schedule="reference"`` cuts every experiment's running episodes at the update boundary
+as ppo/rollout.py does for a solo run (hwy_cut_episodes on the group's handle, seed groups
+included); with it one env per experiment (E = 1, T = steps_per_update) is the reference's own
+stream.
 """
 
 from __future__ import annotations
@@ -27,14 +32,20 @@ from typing import Callable, Optional, Sequence
 import torch
 
 from utils.graphs import capture as graph_capture
+from utils.graphs import run_or_replay as _graph_run
+from utils.graphs import run_or_replay_chunks as _graph_run_chunks
 
 from .agent import RolloutBuffer
+from .rollout import alloc_cut_buffers, check_episode_schedule, rollout_chunks
 
 
 class ExperimentGroup:
     def __init__(self, agents: Sequence, env, seeds: Sequence[int], envs_per_experiment: int,
-                 rollout_len: int, use_graphs: bool = True, rank_tables=None):
+                 rollout_len: int, use_graphs: bool = True, rank_tables=None,
+                 episode_schedule: str = "lockstep"):
         from hwy.ppo_native import GroupAct
+
+        self.episode_schedule = check_episode_schedule(episode_schedule)
 
         self.agents = list(agents)
         self.G, self.E, self.T = len(self.agents), int(envs_per_experiment), int(rollout_len)
@@ -71,6 +82,9 @@ class ExperimentGroup:
         self._roll_graph = None
         self._roll_key = None
         self._roll_seen = None
+        self._roll_chunks = None  # reference schedule, long rollout: (graph, key, seen) per chunk
+        if self.episode_schedule == "reference":
+            alloc_cut_buffers(self, GE, self.sd, self.dev)
         self._upd = None  # the update's static inputs and argument structs (pre_update)
         self.iterations = 0
         # how the rollouts / updates were issued (graph replays vs eager runs vs captures, and
@@ -110,18 +124,39 @@ class ExperimentGroup:
     def env_step(self, t: int) -> None:
         self.env.step_into(*self.env_io(t))
 
-    def _steps(self, tiles) -> None:
-        for t in range(self.T):
+    def cut_episodes(self) -> None:
+        """The reference schedule's cut after the rollout's last step (LockstepRollout._steps)."""
+        obs_shape = self.env.obs_buf.shape[1:]
+        self.next0.copy_(self.buf.states[self.T])
+        self.env.cut_episodes(self.next0.view(self.G * self.E, *obs_shape), self.cut_return,
+                              self.cut_length, self.cut)
+
+    def finish_rollout(self) -> None:
+        self.buf.finish_dones()
+        if self.episode_schedule == "reference":
+            self.cut_episodes()
+
+    def _steps(self, tiles, t0: int = 0, t1: Optional[int] = None) -> None:
+        t1 = self.T if t1 is None else t1
+        for t in range(t0, t1):
             self.act.launch(self.act_rows(t), tiles)
             self.env_step(t)
-        self.buf.finish_dones()
+        if t1 == self.T:
+            self.finish_rollout()
 
     def rollout(self) -> None:
         """T steps of every experiment (LockstepRollout's order: act, then env step, per t);
-        captured as one HIP graph once its launch arguments repeat."""
+        captured as one HIP graph once its launch arguments repeat (a long reference-schedule
+        rollout: one graph per chunk of steps, ppo/rollout.py rollout_chunks)."""
         self._draw_noise()
         tiles = self.act.tiles()  # also syncs acting-only tile images, outside any capture
         key = (self.env._handle.value, self.env.launch_version, tuple(tiles), _flat_ptrs(self.agents))
+        chunks = rollout_chunks(self.T, self.episode_schedule)
+        if len(chunks) > 1:
+            self._roll_chunks = _graph_run_chunks(self, self.use_graphs, key, chunks,
+                                                  lambda t0, t1: self._steps(tiles, t0, t1),
+                                                  self._roll_chunks)
+            return
         self._roll_graph, self._roll_key, self._roll_seen = _graph_run(
             self, self.use_graphs, key, lambda: self._steps(tiles), self._roll_graph,
             self._roll_key, self._roll_seen, "rollout")
@@ -169,7 +204,9 @@ class ExperimentGroup:
         _, adv_grp, ret_flat, idx_all, perms, bound, args = self._upd
         adv3 = adv_grp.view(T, G, E)
         for g, ag in enumerate(self.agents):
-            a = ag.normalize_advantages(adv[:, g * E:(g + 1) * E].reshape(n))
+            # contiguous, as the solo run's [T, E] advantages are: with E = 1 the slice's
+            # reshape is a strided view, whose mean / std torch reduces in another order
+            a = ag.normalize_advantages(adv[:, g * E:(g + 1) * E].contiguous().reshape(n))
             adv3[:, g].copy_(a.view(T, E))
             torch.randperm(n, device=self.dev, generator=ag.generator, out=perms[g])
         # sample (t, l) of experiment g sits at t*G*E + g*E + l of the grouped rollout
@@ -201,12 +238,12 @@ class ExperimentGroup:
             F._tiles_version = F._param_versions()
             ag.updates += 1
             if return_metrics:
-                vals = buf.values[:, g * E:(g + 1) * E].reshape(n)
-                rets = ctx["ret"][:, g * E:(g + 1) * E].reshape(n)
+                vals = buf.values[:, g * E:(g + 1) * E].contiguous().reshape(n)
+                rets = ctx["ret"][:, g * E:(g + 1) * E].contiguous().reshape(n)
                 out.append(ag._finish_metrics(F.metrics, ctx["sizes"], vals, rets,
                                               deferred=return_metrics == "deferred"))
         self.iterations += 1
-        buf.states[0].copy_(buf.states[T])
+        buf.states[0].copy_(self.next0 if self.episode_schedule == "reference" else buf.states[T])
         return out if return_metrics else None
 
     def update(self, return_metrics: bool = True):
@@ -237,6 +274,12 @@ class ExperimentGroup:
         r = self.buf.ep_return[:, g * E:(g + 1) * E]
         return r[d != 0]
 
+    def cut_episode_returns(self, g: int):
+        """(cut, partial return) of experiment g's envs after the last reference-schedule
+        rollout, in env order."""
+        E = self.E
+        return self.cut[g * E:(g + 1) * E], self.cut_return[g * E:(g + 1) * E]
+
 
 def _flat_ptrs(agents) -> tuple:
     """The agents' flat-parameter addresses: part of a rollout graph's key, as of
@@ -245,33 +288,6 @@ def _flat_ptrs(agents) -> tuple:
     from hwy.ppo_native import flat_params
 
     return tuple(flat_params(ag)[0].data_ptr() for ag in agents)
-
-
-def _graph_run(owner, use_graphs, key, steps, graph, gkey, seen, what):
-    """LockstepRollout's issue policy for a launch sequence `steps`: replay the captured graph
-    when its key repeats, run eagerly the first time a key is seen (allocations, argument
-    tables), capture it the second time.  Returns the new (graph, graph key, seen key)."""
-    if not use_graphs:
-        steps()
-        return graph, gkey, seen
-    if graph is not None and key == gkey:
-        owner.stats[f"{what}_replay"] += 1
-        graph.replay()
-        return graph, gkey, seen
-    if key != seen:
-        owner.stats[f"{what}_eager"] += 1
-        steps()
-        return graph, gkey, key
-    owner.stats[f"{what}_capture"] += 1
-    g = torch.cuda.CUDAGraph()
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        with graph_capture(g, stream=s):
-            steps()
-    torch.cuda.current_stream().wait_stream(s)
-    g.replay()
-    return g, key, seen
 
 
 def update_schedule(nmbs: Sequence[int], epochs: Sequence[int]):
@@ -392,6 +408,9 @@ class GroupBatch:
         g0 = self.groups[0]
         if any(g.E != g0.E or g.T != g0.T for g in self.groups):
             raise ValueError("a batch's groups share envs per experiment and rollout length")
+        if any(g.episode_schedule != g0.episode_schedule for g in self.groups):
+            raise ValueError("a batch's groups share the episode schedule")
+        self.episode_schedule = g0.episode_schedule
         self.agents = [a for g in self.groups for a in g.agents]
         self.act = GroupAct(self.agents, g0.E)
         # the groups' env steps as one launch (hwy_step_group): each group's handle alone holds
@@ -403,6 +422,7 @@ class GroupBatch:
         self.use_graphs = bool(use_graphs)
         self.T = g0.T
         self._roll = (None, None, None)
+        self._roll_chunks = None
         self._runner = None
         self.stats = {"rollout_replay": 0, "rollout_eager": 0, "rollout_capture": 0,
                       "update_prepare": 0, "update_capture": 0}
@@ -416,15 +436,17 @@ class GroupBatch:
     def _rows(self, t, deterministic=False):
         return [r for g in self.groups for r in g.act_rows(t, deterministic)]
 
-    def _steps(self, tiles):
-        for t in range(self.T):
+    def _steps(self, tiles, t0=0, t1=None):
+        t1 = self.T if t1 is None else t1
+        for t in range(t0, t1):
             self.act.launch(self._rows(t), tiles)
             if self.envstep is not None:
                 self.envstep.launch([g.env_io(t) for g in self.groups])
             else:
                 self.groups[0].env_step(t)
-        for g in self.groups:
-            g.buf.finish_dones()
+        if t1 == self.T:
+            for g in self.groups:
+                g.finish_rollout()  # the reference schedule's cut: once per handle
 
     def rollout(self) -> None:
         for g in self.groups:
@@ -432,6 +454,12 @@ class GroupBatch:
         tiles = self.act.tiles()
         key = (tuple((g.env._handle.value, g.env.launch_version) for g in self.groups),
                tuple(tiles), _flat_ptrs(self.agents))
+        chunks = rollout_chunks(self.T, self.episode_schedule)
+        if len(chunks) > 1:
+            self._roll_chunks = _graph_run_chunks(self, self.use_graphs, key, chunks,
+                                                  lambda t0, t1: self._steps(tiles, t0, t1),
+                                                  self._roll_chunks)
+            return
         self._roll = _graph_run(self, self.use_graphs, key, lambda: self._steps(tiles), *self._roll,
                                 "rollout")
 
@@ -449,7 +477,8 @@ class GroupBatch:
 
 def build_group(condition, base_config, seeds: Sequence[int], envs_per_experiment: int,
                 rollout_len: int, device: torch.device, make_agent: Callable, d_embed=None,
-                env_overrides: Optional[dict] = None, use_graphs: bool = True):
+                env_overrides: Optional[dict] = None, use_graphs: bool = True,
+                episode_schedule: str = "lockstep"):
     """A group of len(seeds) experiments of one condition, each constructed as
     experiments/runner.py constructs its solo run: set_random_seeds(seed), make_env (whose RankPE
     table draws from the global torch RNG), env.to(device), then ``make_agent(state_dim)`` (the
@@ -464,6 +493,8 @@ def build_group(condition, base_config, seeds: Sequence[int], envs_per_experimen
 
     E = int(envs_per_experiment)
     ov = copy.deepcopy(env_overrides or {})
+    if episode_schedule == "reference":
+        ov.setdefault("vector_env", True)  # E = 1 too: the reference's one-env stream
     agents, tables, solos = [], [], []
     for s in seeds:
         set_random_seeds(int(s))
@@ -484,7 +515,9 @@ def build_group(condition, base_config, seeds: Sequence[int], envs_per_experimen
         env = env.to(device)
     rank = env.unwrapped.hwy_config.pe_kind == PE_RANK and tables[0] is not None
     grp = ExperimentGroup(agents, env, seeds, E, rollout_len, use_graphs=use_graphs,
-                          rank_tables=tables if rank else None)
+                          rank_tables=tables if rank else None,
+                          **({} if episode_schedule == "lockstep"
+                             else {"episode_schedule": episode_schedule}))
     grp.solo_envs = solos
     grp.group_env = env
     return grp

@@ -9,6 +9,15 @@ once and replayed as a single graph: no host work per step and ~1 us instead of 
 dependent launches.  The graph is re-captured whenever something it baked in changes: the env
 handle or its launch configuration (seed schedule, fused PE table), the acting weights (the
 update's tile image or the flat parameters), or the buffers.
+
+``episode_schedule="reference"`` adds the reference's cut at the update boundary
+(training/routine.py:125-132,153-156): after the T steps every running episode is ended and the
+schedule's next one started (hwy_cut_episodes), the new first observations going to ``next0``
+-- a buffer of its own, since states[0..T] are the update's inputs -- with the cut episodes'
+partial returns in ``cut_return``.  The cut step's ``dones`` stays 0, so GAE bootstraps it with
+V(states[T]).  The next rollout starts from ``next0`` (``start_next``).  A reference rollout of
+T > REFERENCE_GRAPH_CHUNK steps is issued as fixed chunk graphs of that many steps (the buffers
+are static, so each chunk replays) instead of one graph of 2T launches.
 """
 
 from __future__ import annotations
@@ -17,11 +26,39 @@ from typing import Optional
 
 import torch
 
-from utils.graphs import capture as graph_capture
+from utils.graphs import run_or_replay, run_or_replay_chunks
+
+EPISODE_SCHEDULES = ("lockstep", "reference")
+# steps per captured graph of a reference-schedule rollout (2 launches per step)
+REFERENCE_GRAPH_CHUNK = 256
+
+
+def check_episode_schedule(episode_schedule: str) -> str:
+    if episode_schedule not in EPISODE_SCHEDULES:
+        raise ValueError(f"episode_schedule must be one of {EPISODE_SCHEDULES}, "
+                         f"got {episode_schedule!r}")
+    return episode_schedule
+
+
+def rollout_chunks(T: int, episode_schedule: str):
+    """The (t0, t1) step ranges a rollout of T steps is issued (and captured) in: the whole
+    rollout, or, for a long reference-schedule rollout, chunks of REFERENCE_GRAPH_CHUNK steps."""
+    if episode_schedule != "reference" or T <= REFERENCE_GRAPH_CHUNK:
+        return [(0, T)]
+    return [(t0, min(T, t0 + REFERENCE_GRAPH_CHUNK)) for t0 in range(0, T, REFERENCE_GRAPH_CHUNK)]
+
+
+def alloc_cut_buffers(owner, E: int, sd: int, device) -> None:
+    """The fixed buffers of the reference schedule's cut on `owner` (a rollout or a group)."""
+    owner.next0 = torch.zeros(E, sd, dtype=torch.float32, device=device)
+    owner.cut_return = torch.zeros(E, dtype=torch.float32, device=device)
+    owner.cut_length = torch.zeros(E, dtype=torch.int32, device=device)
+    owner.cut = torch.zeros(E, dtype=torch.uint8, device=device)
 
 
 class LockstepRollout:
-    def __init__(self, agent, env, buf, use_graph: bool = True):
+    def __init__(self, agent, env, buf, use_graph: bool = True,
+                 episode_schedule: str = "lockstep"):
         self.agent = agent
         self.env = env.unwrapped if hasattr(env, "unwrapped") else env
         self.buf = buf
@@ -36,6 +73,12 @@ class LockstepRollout:
         from hwy.vec_env import GroupEnvStep
 
         self._envstep = GroupEnvStep([self.env]) if hasattr(self.env, "_handle") else None
+        self.episode_schedule = check_episode_schedule(episode_schedule)
+        self._chunks = None  # reference schedule, long rollout: (graph, key, seen) per chunk
+        # how the rollouts were issued (utils/graphs.py run_or_replay)
+        self.stats = {"rollout_replay": 0, "rollout_eager": 0, "rollout_capture": 0}
+        if self.episode_schedule == "reference":
+            alloc_cut_buffers(self, buf.E, buf.states.shape[-1], buf.states.device)
 
     def _launch_key(self):
         from hwy.ppo_native import flat_params
@@ -48,11 +91,12 @@ class LockstepRollout:
         return (env._handle.value, getattr(env, "launch_version", 0), tiles, params,
                 buf.states.data_ptr(), buf.noise.data_ptr(), buf.T, buf.E)
 
-    def _steps(self) -> None:
+    def _steps(self, t0: int = 0, t1: Optional[int] = None) -> None:
         ag, env, buf = self.agent, self.env, self.buf
         E = buf.E
         obs_shape = env.obs_buf.shape[1:]
-        for t in range(buf.T):
+        t1 = buf.T if t1 is None else t1
+        for t in range(t0, t1):
             ag.select_action(buf.states[t], out=(buf.actions[t], buf.pre_tanh[t],
                                                  buf.log_probs[t], buf.values[t]),
                              noise=buf.noise[t])
@@ -62,7 +106,20 @@ class LockstepRollout:
                 self._envstep.launch([io])
             else:
                 env.step_into(*io)
+        if t1 < buf.T:
+            return
         buf.finish_dones()
+        if self.episode_schedule == "reference":
+            self.next0.copy_(buf.states[buf.T])
+            env.cut_episodes(self.next0.view(E, *obs_shape), self.cut_return, self.cut_length,
+                             self.cut)
+
+    def start_next(self) -> None:
+        """states[0] of the next rollout: the last observation, or, on the reference schedule,
+        the first observations after the cut."""
+        buf = self.buf
+        buf.states[0].copy_(self.next0 if self.episode_schedule == "reference"
+                            else buf.states[buf.T])
 
     def run(self) -> None:
         """One rollout into buf (rows 0..T-1, states[1..T]); buf.states[0] holds the first obs."""
@@ -71,19 +128,9 @@ class LockstepRollout:
             self._steps()
             return
         key = self._launch_key()
-        if self._graph is not None and key == self._key:
-            self._graph.replay()
+        chunks = rollout_chunks(self.buf.T, self.episode_schedule)
+        if len(chunks) > 1:  # a long reference rollout: one graph per chunk
+            self._chunks = run_or_replay_chunks(self, True, key, chunks, self._steps, self._chunks)
             return
-        if key != self._seen:  # first rollout at these arguments: eager (allocations, set-up)
-            self._seen = key
-            self._steps()
-            return
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            with graph_capture(g, stream=s):
-                self._steps()
-        torch.cuda.current_stream().wait_stream(s)
-        self._graph, self._key = g, key
-        g.replay()
+        self._graph, self._key, self._seen = run_or_replay(
+            self, True, key, self._steps, self._graph, self._key, self._seen, "rollout")

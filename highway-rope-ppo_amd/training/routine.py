@@ -18,6 +18,13 @@ Two loops behind it:
     ``agent.update_rollout``.  Episode bookkeeping (logging / eval every ``eval_interval``
     completed episodes, best / solved checkpoints, moving average over the last 10 evals) follows
     the reference, with completed episodes counted in env order within each step.
+``episode_schedule="reference"`` (vectorised loop, train_group, train_batch) runs the reference's
+own schedule (:121-243): after each rollout every running episode is cut (hwy_cut_episodes,
+ppo/rollout.py), booked with its partial return after the rollout's finished episodes and
+bootstrapped with V of its last state; the next rollout starts the schedule's next episodes; and
+the evaluation points that stream crosses are evaluated before the update, on the weights that
+collected it (:173-175).  With one env and T = ``steps_per_update`` that is the reference's
+episode stream, seeds exp_seed + episode_num.  The default, "lockstep", is the loop above.
 ``evaluate`` runs ``num_episodes`` deterministic episodes seeded exp_seed + 1000 + k (:14-29),
 as one batched env for the vectorised path.
 """
@@ -313,7 +320,16 @@ class _EvalTracker:
 # ---------------------------------------------------------------------------------- training
 def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, log_interval=20,
                                eval_interval=50, steps_per_update=2048, experiment_name="",
-                               exp_seed: int = 0, logger=None):
+                               exp_seed: int = 0, logger=None, episode_schedule="lockstep"):
+    from ppo.rollout import check_episode_schedule
+
+    if check_episode_schedule(episode_schedule) == "reference":
+        if getattr(agent, "_dist", None) is not None:
+            raise ValueError("episode_schedule='reference' does not run over a process group")
+        if not _is_vector(env):
+            raise ValueError("episode_schedule='reference' needs a HighwayVecEnv (make_env's "
+                             "vector_env key for one env); the one-env facade already runs the "
+                             "reference loop")
     if logger is None:
         logger = setup_experiment_logger(experiment_name)
     exp_prefix = f"[{experiment_name}]" if experiment_name else ""
@@ -341,9 +357,10 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
     if not _is_vector(env) and getattr(agent, "_dist", None) is not None:
         raise ValueError("a process group needs the vectorised env (num_envs > 1)")
     loop = _train_vector if _is_vector(env) else _train_single
+    sched_kw = {} if episode_schedule == "lockstep" else {"episode_schedule": episode_schedule}
     episode_rewards, training_episodes, total_steps = loop(
         env, agent, max_episodes, log_interval, eval_interval, steps_per_update, exp_seed, logger,
-        exp_prefix, metrics_history, tracker, start_time)
+        exp_prefix, metrics_history, tracker, start_time, **sched_kw)
     if rank != 0:
         return tracker.rewards, tracker.avg_rewards, metrics_history
     _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_history,
@@ -404,8 +421,12 @@ def _train_single(env, agent, max_episodes, log_interval, eval_interval, steps_p
 
 
 def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_per_update,
-                  exp_seed, logger, prefix, mh, tracker, start_time):
+                  exp_seed, logger, prefix, mh, tracker, start_time, episode_schedule="lockstep"):
     """E lockstep envs, device rollout of T steps, batched PPO update.
+
+    episode_schedule "reference": the rollout ends with the cut; its episode stream (finished,
+    then cut episodes) is booked and its evaluations run before the update; the next rollout
+    starts from the cut's first observations.
 
     With a process group on the agent (one rank per GPU, envs env_offset = rank*E of world*E),
     every rank steps its own E envs and joins the update's collectives; the episode stream is
@@ -424,16 +445,23 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
     base.set_seed_schedule(exp_seed)
     obs, _ = env.reset()
     buf.states[0].copy_(obs.reshape(E, sd))
-    roll = LockstepRollout(agent, base, buf, use_graph=getattr(agent, "use_graphs", True))
+    reference = episode_schedule == "reference"
+    roll = LockstepRollout(agent, base, buf, use_graph=getattr(agent, "use_graphs", True),
+                           **({"episode_schedule": episode_schedule} if reference else {}))
     episode_rewards, training_episodes = [], []
     total_steps = episode_num = 0
     while episode_num < max_episodes:
         t_update = time.time()
         roll.run()
         total_steps += T * E * world
-        upd = agent.update_rollout(buf, agent.value(buf.states[T]))
-        # episode bookkeeping, in (step, global env) order -- identical on every rank
-        for r in _episode_ends(buf.dones, buf.ep_return, group):
+        if reference:  # the stream's evaluations run below, ahead of the update (:173-175)
+            stream = _episode_stream(buf.dones, buf.ep_return, roll.cut, roll.cut_return)
+            upd = None
+        else:
+            upd = agent.update_rollout(buf, agent.value(buf.states[T]))
+            # episode bookkeeping, in (step, global env) order -- identical on every rank
+            stream = _episode_ends(buf.dones, buf.ep_return, group)
+        for r in stream:
             if episode_num >= max_episodes:
                 break
             episode_num += 1
@@ -446,14 +474,16 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
                          total_steps, start_time)
             if episode_num % eval_interval == 0 and rank == 0:
                 tracker.on_episode(episode_num)
+        if reference:
+            upd = agent.update_rollout(buf, agent.value(buf.states[T]))
         mh["policy_updates"].append({"episode": episode_num, "steps": T * E * world,
                                      "time": time.time() - t_update, **upd})
-        buf.states[0].copy_(buf.states[T])
+        roll.start_next()
     return episode_rewards, training_episodes, total_steps
 
 
 def train_group(group, experiment_names, exp_seeds, max_episodes=500, target_reward=0.0,
-                log_interval=20, eval_interval=50, loggers=None):
+                log_interval=20, eval_interval=50, loggers=None, episode_schedule="lockstep"):
     """train_with_experiment_name for every experiment of an ExperimentGroup (ppo/group.py) at
     once: one grouped rollout + update per iteration, then each experiment's bookkeeping exactly
     as _train_vector does it on its own [T, E] slice (episode stream in (step, env) order,
@@ -465,16 +495,28 @@ def train_group(group, experiment_names, exp_seeds, max_episodes=500, target_rew
     (tests/test_group_gpu.py) and evaluation draws no random numbers."""
     return train_batch(group, [group], experiment_names, exp_seeds, max_episodes=max_episodes,
                        target_reward=target_reward, log_interval=log_interval,
-                       eval_interval=eval_interval, loggers=loggers)
+                       eval_interval=eval_interval, loggers=loggers,
+                       episode_schedule=episode_schedule)
 
 
 def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, target_reward=0.0,
-                log_interval=20, eval_interval=50, loggers=None):
+                log_interval=20, eval_interval=50, loggers=None, episode_schedule="lockstep"):
     """train_group over the experiments of several ExperimentGroups stepped together: `stepper`
     is the ExperimentGroup itself (groups = [it]) or a GroupBatch over `groups` (ppo/group.py:
     the cells of one hidden width in one set of launches).  experiment_names / exp_seeds /
     loggers list every group's experiments in group order; each experiment's bookkeeping is its
-    solo run's, on its own [T, E] slice of its group's rollout."""
+    solo run's, on its own [T, E] slice of its group's rollout.  episode_schedule "reference"
+    (the groups must have been built with it): each experiment's stream is its finished then
+    its cut episodes, and the due evaluations run, still as one evaluate_many, ahead of the
+    update."""
+    from ppo.rollout import check_episode_schedule
+
+    reference = check_episode_schedule(episode_schedule) == "reference"
+    if any(getattr(g, "episode_schedule", "lockstep") != episode_schedule for g in groups):
+        raise ValueError(f"train_batch: every group must be built with episode_schedule="
+                         f"{episode_schedule!r}")
+    if reference and any(getattr(a, "_dist", None) is not None for g in groups for a in g.agents):
+        raise ValueError("episode_schedule='reference' does not run over a process group")
     members = [(g, j) for g in groups for j in range(g.G)]
     if len(experiment_names) != len(members) or len(exp_seeds) != len(members):
         raise ValueError(f"train_batch: {len(members)} experiments, "
@@ -509,17 +551,21 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
     while not all(r["done"] for r in runs):
         t_update = time.time()
         stepper.rollout()
-        upds = stepper.update(return_metrics=True)
-        if len(groups) > 1 or stepper is not groups[0]:  # a GroupBatch: one list per group
-            upds = [m for per_group in upds for m in per_group]
-        for r, upd in zip(runs, upds):
+        if not reference:
+            upds = _flat_updates(stepper, groups)
+        for k, r in enumerate(runs):
             if r["done"]:
                 continue
             grp, j = r["group"], r["j"]
             E, T = grp.E, grp.T
             r["total_steps"] += T * E
             sl = slice(j * E, (j + 1) * E)
-            for ret in _episode_ends(grp.buf.dones[:, sl], grp.buf.ep_return[:, sl]):
+            if reference:
+                stream = _episode_stream(grp.buf.dones[:, sl], grp.buf.ep_return[:, sl],
+                                         grp.cut[sl], grp.cut_return[sl])
+            else:
+                stream = _episode_ends(grp.buf.dones[:, sl], grp.buf.ep_return[:, sl])
+            for ret in stream:
                 if r["episode_num"] >= max_episodes:
                     break
                 r["episode_num"] += 1
@@ -532,13 +578,17 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
                              log_interval, r["total_steps"], start_time)
                 if r["episode_num"] % eval_interval == 0:
                     r["pending"].append(r["episode_num"])
+            if reference:
+                r["booked"] = True
+                continue
             r["mh"]["policy_updates"].append({"episode": r["episode_num"], "steps": T * E,
-                                              "time": time.time() - t_update, **upd})
+                                              "time": time.time() - t_update, **upds[k]})
             if r["episode_num"] >= max_episodes:
                 r["done"] = True
-        # this iteration's evaluations (weights unchanged since its update): one per experiment
-        # that crossed an evaluation point, all together; a second point in the same iteration
-        # evaluates the same weights and gets the same (memoised) value
+        # this iteration's evaluations (weights unchanged since its update -- on the reference
+        # schedule since the previous one: they run ahead of this iteration's): one per
+        # experiment that crossed an evaluation point, all together; a second point in the same
+        # iteration evaluates the same weights and gets the same (memoised) value
         due = [r for r in runs if r["pending"]]
         if due:
             vals = evaluate_many([(r["tracker"].env, r["tracker"].agent, r["tracker"].exp_seed)
@@ -547,6 +597,16 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
                 for ep in r["pending"]:
                     r["tracker"].on_episode(ep, v)
                 r["pending"] = []
+        if reference:
+            upds = _flat_updates(stepper, groups)
+            for r, upd in zip(runs, upds):
+                if not r.pop("booked", False):
+                    continue
+                r["mh"]["policy_updates"].append({"episode": r["episode_num"],
+                                                  "steps": r["group"].T * r["group"].E,
+                                                  "time": time.time() - t_update, **upd})
+                if r["episode_num"] >= max_episodes:
+                    r["done"] = True
     out = []
     for r in runs:
         tr = r["tracker"]
@@ -555,6 +615,14 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
                         target_reward, r["total_steps"], r["logger"], r["prefix"])
         out.append((tr.rewards, tr.avg_rewards, r["mh"]))
     return out
+
+
+def _flat_updates(stepper, groups):
+    """stepper.update's metrics, one per experiment in group order."""
+    upds = stepper.update(return_metrics=True)
+    if len(groups) > 1 or stepper is not groups[0]:  # a GroupBatch: one list per group
+        upds = [m for per_group in upds for m in per_group]
+    return upds
 
 
 def _rank_world(group):
@@ -578,3 +646,13 @@ def _episode_ends(dones, rets, group=None):
         pack = torch.cat(parts, dim=2)
     pack = pack.cpu().numpy()
     return pack[1][pack[0] != 0]
+
+
+def _episode_stream(dones, rets, cut, cut_rets):
+    """The reference schedule's episode stream of one rollout: the returns of the episodes that
+    finished in the [T, E] rollout, in (step, env) order (_episode_ends), then those of the
+    episodes cut at its end (cut [E] nonzero), in env order, each with its partial return
+    (reference training/routine.py:153-156 books the unfinished episode like any other)."""
+    ends = _episode_ends(dones, rets)
+    pack = torch.stack([cut.to(torch.float64), cut_rets.to(torch.float64)]).cpu().numpy()
+    return np.concatenate([ends, pack[1][pack[0] != 0]])

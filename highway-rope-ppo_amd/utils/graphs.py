@@ -33,3 +33,42 @@ def capture(graph: torch.cuda.CUDAGraph, stream=None, collect: bool = True, **kw
     finally:
         if was:
             gc.enable()
+
+
+def run_or_replay(owner, use_graphs, key, steps, graph, gkey, seen, what):
+    """The issue policy for a launch sequence `steps` (a rollout, ppo/rollout.py and
+    ppo/group.py): replay the captured graph when its key repeats, run eagerly the first time a
+    key is seen (allocations, argument tables), capture it the second time.  Counts what it did
+    in owner.stats[f"{what}_replay" | "_eager" | "_capture"].  Returns the new (graph, graph
+    key, seen key)."""
+    if not use_graphs:
+        steps()
+        return graph, gkey, seen
+    if graph is not None and key == gkey:
+        owner.stats[f"{what}_replay"] += 1
+        graph.replay()
+        return graph, gkey, seen
+    if key != seen:
+        owner.stats[f"{what}_eager"] += 1
+        steps()
+        return graph, gkey, key
+    owner.stats[f"{what}_capture"] += 1
+    g = torch.cuda.CUDAGraph()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        with capture(g, stream=s):
+            steps()
+    torch.cuda.current_stream().wait_stream(s)
+    g.replay()
+    return g, key, seen
+
+
+def run_or_replay_chunks(owner, use_graphs, key, chunks, steps, state):
+    """run_or_replay per (t0, t1) chunk of a rollout, `steps(t0, t1)` issuing one chunk; state =
+    one (graph, graph key, seen key) per chunk, or None."""
+    if state is None or len(state) != len(chunks):
+        state = [(None, None, None)] * len(chunks)
+    return [run_or_replay(owner, use_graphs, key, lambda t0=t0, t1=t1: steps(t0, t1), *st,
+                          "rollout")
+            for (t0, t1), st in zip(chunks, state)]

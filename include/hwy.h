@@ -14,7 +14,9 @@
  *                                (AbstractEnv.step/_simulate, HighwayEnv._reward/_is_terminated/
  *                                 _is_truncated, KinematicObservation.observe [highway-env 1.10.1])
  *                                + the PE wrapper's .observation() fused in (pe_kind != 0)
- *   hwy_set_pe_table          <- RankEmbedWrapper.__init__ table         experiments/rank_embed.py:21-22
+ *   hwy_cut_episodes          <- the collection loop's cut at steps_per_update
+ *                                                                        training/routine.py:125-132,153-156
+ *   hwy_set_pe_table          <- RankEmbedWrapper.__init__ table        experiments/rank_embed.py:21-22
  *                                DistanceEmbedWrapper freqs               experiments/dist_embed.py:48-52
  *                                RotaryEmbedWrapper inv_freq              experiments/rope_embed.py:36-39
  *   hwy_obs_pe                <- RotaryEmbedWrapper.observation          experiments/rope_embed.py:64-74
@@ -198,6 +200,22 @@ int hwy_reset(hwy_handle* h, const uint64_t* seeds, const uint8_t* mask, float* 
  *   holds the first observation of the next episode. */
 int hwy_step(hwy_handle* h, const float* actions, float* obs, float* reward, uint8_t* terminated,
              uint8_t* truncated, float* ep_return, int32_t* ep_length, void* stream);
+
+/* End every running episode and start the next one of the schedule (the reference's collection
+ * loop, training/routine.py:125-132, 153-156).  For each env whose episode has taken >= 1 policy
+ * step: cut[e] = 1, ep_return[e] / ep_length[e] = its running return / steps so far, then exactly
+ * what hwy_step's autoreset does at a truncation: episode k -> k + 1, seed = the schedule's seed
+ * for (e, k + 1) (seed groups included), reset, first observation written to obs row e.
+ * An env at step 0 (it finished on its last step and was autoreset, or was just reset) is not
+ * touched: cut[e] = 0, ep_return[e] = 0, ep_length[e] = 0, its obs row is NOT written, its
+ * state words stay.  obs [E,N,F_out]; ep_return / ep_length / cut nullable.  Asynchronous,
+ * allocates nothing, hipGraph-capturable.  Meant for cfg.autoreset handles, where a finished env
+ * is back at step 0.  With autoreset off the launch works the same way, but an env that hwy_step
+ * has just reported terminated / truncated still holds its step count: the cut would book that
+ * episode a second time (cut = 1 and the return hwy_step already gave) before restarting it, so
+ * such a caller masks those envs out of what it reads back. */
+int hwy_cut_episodes(hwy_handle* h, float* obs, float* ep_return, int32_t* ep_length,
+                     uint8_t* cut, void* stream);
 
 /* ---- Grouped step: n handles (the cells of a sweep batch, each one experiment group's handle;
  * ppo/group.py GroupBatch) stepped in ONE launch instead of n.  Workgroup (x, y) runs hwy_step's

@@ -18,6 +18,12 @@ one line per cell.
 
     python tools/sweep_reward.py --out gpurun_out/sweep_reward [--cells sorted_h256 ...]
         [--seeds 42 1042 ...] [--work /tmp/sweep_work] [--batch [--mixed]]
+
+--reference-schedule runs the same cells and seeds on the reference's own training schedule
+(extra["episode_schedule"] = "reference": one env, 2,048 consecutive steps per update, episodes
+cut at the update boundary, seeds exp_seed + episode_num, evaluations ahead of the update), all
+cells as one launch_batch; there are no solo runs of that recipe to compare with.  sweep.json then
+also holds the mean time of a policy update's iteration (rollout + update) per cell.
 """
 
 from __future__ import annotations
@@ -74,6 +80,9 @@ def _write_cell(out, cell, exps, results, wall, unit_cells, E, T, M, args, refer
                            updates=len(ups),
                            # the group's (or batch's) wall clock, shared by its experiments
                            wall_s=round(wall, 1), train_s=round(wall, 1))
+                if args.reference_schedule:  # mean time of one iteration (rollout + update)
+                    row["iteration_s"] = round(sum(u.get("time", 0.0) for u in ups)
+                                               / max(1, len(ups)), 4)
                 if e.seed in ref:
                     row.update(reference_final_reward=ref[e.seed],
                                delta=round(row["final_reward"] - ref[e.seed], 4))
@@ -85,7 +94,9 @@ def _write_cell(out, cell, exps, results, wall, unit_cells, E, T, M, args, refer
             rows.append(row)
             f.write(json.dumps(row) + "\n")
     done = [r["final_reward"] for r in rows if "final_reward" in r]
+    its = [r["iteration_s"] for r in rows if "iteration_s" in r]
     return {"wall_s": round(wall, 1), "n": len(done),
+            **({"iteration_s": round(sum(its) / len(its), 4)} if its else {}),
             "mean_final_reward": round(sum(done) / len(done), 4) if done else None,
             "equal_to_solo_r4": f"{sum(same)}/{len(same)}" if same else None,
             "env_steps": int(sum(r.get("env_steps", 0) for r in rows)),
@@ -112,7 +123,14 @@ def main():
     p.add_argument("--mixed", action="store_true",
                    help="with --batch: run ALL the cells, whatever their hidden widths, as one "
                         "launch_batch (the mixed-width grouped launches, hwy_ppo_mixed_*)")
+    p.add_argument("--reference-schedule", action="store_true",
+                   help="the reference's schedule: --num-envs 1 --rollout 2048, episodes cut at "
+                        "the update boundary, evaluation before the update; implies --batch "
+                        "--mixed")
     args = p.parse_args()
+    if args.reference_schedule:
+        args.num_envs, args.rollout = 1, 2048
+        args.batch = args.mixed = True
     out = os.path.abspath(args.out)
     os.makedirs(out, exist_ok=True)
 
@@ -126,7 +144,9 @@ def main():
              "shuffled_rankpe": Condition.SHUFFLED_RANKPE}
     E, T, M = args.num_envs, args.rollout, args.minibatches
     report = {"recipe": {"num_envs": E, "rollout": T, "minibatches": M, "episodes": args.episodes,
-                         "eval_interval": args.eval_interval, "seeds": args.seeds},
+                         "eval_interval": args.eval_interval, "seeds": args.seeds,
+                         "episode_schedule": ("reference" if args.reference_schedule
+                                              else "lockstep")},
               "cells": {}}
     t_all = time.time()
     cell_exps = {}
@@ -145,6 +165,8 @@ def main():
             hp.steps_per_update = E * T
             extra = {"log_interval": max(50, args.episodes // 200),
                      "eval_interval": args.eval_interval, "num_envs": E, "num_minibatches": M}
+            if args.reference_schedule:
+                extra["episode_schedule"] = "reference"
             exps.append(Experiment(name=name, condition=conds[cname], hp=hp, seed=seed,
                                    max_episodes=args.episodes, target_reward=130.0, extra=extra,
                                    env_config_overrides={}))
