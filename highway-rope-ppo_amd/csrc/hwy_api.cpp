@@ -254,6 +254,36 @@ int hwy_step(hwy_handle* h, const float* actions, float* obs, float* reward, uin
   return HWY_OK;
 }
 
+int hwy_step_info_size(void) { return (int)sizeof(hwy_step_info); }
+
+static int check_info(const hwy_step_info* info, const char* who) {
+  if (!info) return fail(HWY_EINVAL, "%s: info is NULL", who);
+  if (info->ep_stats && !info->acc)
+    return fail(HWY_EINVAL, "%s: ep_stats needs acc (the episode's running sums)", who);
+  return HWY_OK;
+}
+
+int hwy_step_with_info(hwy_handle* h, const float* actions, float* obs, float* reward,
+                       uint8_t* terminated, uint8_t* truncated, float* ep_return,
+                       int32_t* ep_length, const hwy_step_info* info, void* stream) {
+  if (!h) return fail(HWY_EINVAL, "handle is NULL");
+  if (!actions || !obs || !reward || !terminated || !truncated)
+    return fail(HWY_EINVAL,
+                "hwy_step_with_info: actions/obs/reward/terminated/truncated must be non-NULL");
+  if (int rc = check_info(info, "hwy_step_with_info")) return rc;
+  StepParams p = params_of(h);
+  p.actions = actions;
+  p.obs = obs;
+  p.reward = reward;
+  p.term = terminated;
+  p.trunc = truncated;
+  p.ep_ret = ep_return;
+  p.ep_len = ep_length;
+  if (hwy_launch_step_info(&p, info, (hipStream_t)stream))
+    return hip_fail(hipGetLastError(), "hwy_step_info_kernel");
+  return HWY_OK;
+}
+
 int hwy_cut_episodes(hwy_handle* h, float* obs, float* ep_return, int32_t* ep_length,
                      uint8_t* cut, void* stream) {
   if (!h) return fail(HWY_EINVAL, "handle is NULL");
@@ -324,6 +354,36 @@ int hwy_step_group(const hwy_step_group_plan* plan, const void* table, void* str
   if (hwy_launch_step_group((const StepParams*)table, plan->n, plan->blocks, plan->big,
                             (hipStream_t)stream))
     return hip_fail(hipGetLastError(), "hwy_step_grp_kernel");
+  return HWY_OK;
+}
+
+int64_t hwy_step_group_info_table_bytes(int n) {
+  return n < 1 ? -1 : (int64_t)n * (int64_t)sizeof(InfoParams);
+}
+
+int hwy_step_group_info_prepare(hwy_handle* const* handles, const hwy_step_io* io,
+                                const hwy_step_info* info, int n, void* table, void* info_table,
+                                hwy_step_group_plan* plan, void* stream) {
+  if (!info || !info_table || n < 1)
+    return fail(HWY_EINVAL, "hwy_step_group_info_prepare: info/info_table NULL or n < 1");
+  for (int i = 0; i < n; ++i)
+    if (int rc = check_info(info + i, "hwy_step_group_info_prepare")) return rc;
+  if (int rc = hwy_step_group_prepare(handles, io, n, table, plan, stream)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e =
+      hipMemcpyAsync(info_table, info, (size_t)n * sizeof(InfoParams), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return hip_fail(e, "hwy_step_group_info_prepare");
+  return HWY_OK;
+}
+
+int hwy_step_group_info(const hwy_step_group_plan* plan, const void* table, const void* info_table,
+                        void* stream) {
+  if (!plan || !table || !info_table || plan->n < 1 || plan->blocks < 1)
+    return fail(HWY_EINVAL, "hwy_step_group_info: empty plan or NULL table");
+  if (hwy_launch_step_group_info((const StepParams*)table, (const InfoParams*)info_table, plan->n,
+                                 plan->blocks, plan->big, (hipStream_t)stream))
+    return hip_fail(hipGetLastError(), "hwy_step_grp_info_kernel");
   return HWY_OK;
 }
 

@@ -27,11 +27,18 @@ struct StepParams {
   int pe_group_stride;
 };
 
+// the info kernels' second argument (solo) / second table's record (grouped): the ABI's struct
+typedef hwy_step_info InfoParams;
+
 extern "C" {
 int hwy_launch_step(const StepParams* p, hipStream_t s);
 // n handles' steps in one launch: dtab = n StepParams in device memory, blocks = the largest
 // handle's hwy_step_blocks, big = hwy_step_big(total envs) (the register budget of the launch)
 int hwy_launch_step_group(const StepParams* dtab, int n, int blocks, int big, hipStream_t s);
+// the info variants (their own unit): info / itab as above, the rest as the plain launches
+int hwy_launch_step_info(const StepParams* p, const InfoParams* info, hipStream_t s);
+int hwy_launch_step_group_info(const StepParams* dtab, const InfoParams* itab, int n, int blocks,
+                               int big, hipStream_t s);
 int hwy_step_blocks(int num_envs);
 int hwy_step_big(int64_t total_envs);
 int hwy_launch_reset(const StepParams* p, hipStream_t s);

@@ -1237,8 +1237,10 @@ __device__ void frame_wave(const hwy_config& C, int lane, Veh& v, float dt, floa
 // The step of one handle's envs; the kernels below run it for one handle (hwy_step) or for
 // handle blockIdx.y of a table (hwy_step_group: a sweep's cells in one launch).  It reads no
 // gridDim and no blockIdx.y, so a grouped launch computes every env exactly as its handle's own.
-template <int W>
-__device__ __forceinline__ void step_body(const StepParams& P) {
+// INFO (the info unit's kernels only, below): the ego's per-step info and the running episode
+// sums go to *I; everything inside `if constexpr (INFO)` is absent from the plain kernels.
+template <int W, bool INFO>
+__device__ __forceinline__ void step_body(const StepParams& P, const InfoParams* I) {
   __shared__ int lds_vor[ENVS_PER_BLOCK][WAVE];
   __shared__ int lds_inv[ENVS_PER_BLOCK][WAVE];
   __shared__ CollLds lds_coll[ENVS_PER_BLOCK];
@@ -1259,6 +1261,7 @@ __device__ __forceinline__ void step_body(const StepParams& P) {
   Veh v;
   int order_pos;
   load_veh(st, fstride, idx, lane, V, v, order_pos);
+  [[maybe_unused]] const int ln_start = v.ln;  // INFO: the lane word as loaded
   const uint32_t ew = (st + HWY_F_ENV * fstride)[idx];
   int step = rdli((int)ew, HWY_E_STEP);
   int episode = rdli((int)ew, HWY_E_EPISODE);
@@ -1311,6 +1314,7 @@ __device__ __forceinline__ void step_body(const StepParams& P) {
   // HighwayEnv._reward / _is_terminated / _is_truncated on the ego (lane 0)
   float rew = 0.0f;
   int terminated = 0;
+  [[maybe_unused]] float terms[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // INFO: what enters rew
   if (lane == 0) {
     const float forward_speed = v.spd * cos_h;  // hm_cosf(v.h), carried from the last frame
     const float scaled_speed = hm_lmap(forward_speed, C.reward_speed_range[0],
@@ -1330,6 +1334,12 @@ __device__ __forceinline__ void step_body(const StepParams& P) {
       rew = hm_lmap(rew, C.collision_reward, C.high_speed_reward + C.right_lane_reward, 0.0f, 1.0f);
     rew = rew * on_road_f;
     terminated = v.crashed || (C.offroad_terminal && !on_road);
+    if constexpr (INFO) {
+      terms[0] = collision;
+      terms[1] = right_lane;
+      terms[2] = high_speed;
+      terms[3] = on_road_f;
+    }
   }
   rew = rdlf(rew, 0);
   terminated = rdli(terminated, 0);
@@ -1342,6 +1352,41 @@ __device__ __forceinline__ void step_body(const StepParams& P) {
     P.trunc[e] = (uint8_t)truncated;
     if (P.ep_ret) P.ep_ret[e] = done ? ep_return : 0.0f;
     if (P.ep_len) P.ep_len[e] = done ? step : 0;
+  }
+  if constexpr (INFO) {
+    // AbstractEnv._info / HighwayEnv._rewards of the ego, and the episode's running sums (the
+    // form of ep_return: acc = acc + value in float32, so a host can mirror them exactly)
+    if (lane == 0) {
+      if (I->speed) I->speed[e] = v.spd;
+      if (I->crashed) I->crashed[e] = v.crashed ? 1 : 0;
+      if (I->lane) I->lane[e] = v.ln;
+      if (I->rewards) {
+        float* r = I->rewards + 4 * (size_t)e;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = terms[k];
+      }
+      if (I->acc) {
+        float* a = I->acc + HWY_INFO_NACC * (size_t)e;
+        const bool fresh = step == 1;  // step 0 on entry: a new episode's sums start from zero
+        const float val[6] = {v.spd, terms[0], terms[1], terms[2], terms[3],
+                              v.ln != ln_start ? 1.0f : 0.0f};
+        float sum[HWY_INFO_NACC];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          const float prev = a[k];
+          sum[k] = (fresh ? 0.0f : prev) + val[k];
+        }
+        sum[6] = sum[7] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < HWY_INFO_NACC; ++k) a[k] = sum[k];
+        if (I->ep_stats) {
+          float* es = I->ep_stats + HWY_INFO_NACC * (size_t)e;
+          sum[6] = v.crashed ? 1.0f : 0.0f;
+#pragma unroll
+          for (int k = 0; k < HWY_INFO_NACC; ++k) es[k] = done ? sum[k] : 0.0f;
+        }
+      }
+    }
   }
   SEC(sp, 11);
   if (done && C.autoreset) {
@@ -1369,6 +1414,11 @@ __device__ __forceinline__ void step_body(const StepParams& P) {
   WAVE_T(e, lane, 2, (unsigned long long)done | WAVE_HWID());
   SEC_FLUSH(sp, lane, e);
 }
+
+// waves per SIMD the step kernel's registers are sized for at large E (5 and 8 measured slower)
+#ifndef HWY_STEP_BIG_W
+#define HWY_STEP_BIG_W 6
+#endif
 
 // hwy_cut_kernel is compiled as a translation unit of its own from this source (-DHWY_CUT_TU ->
 // hwy_cut.o, as ppo_mixed.o / ppo_wide.o are from ppo_kernels.hip): that unit holds the cut
@@ -1416,11 +1466,48 @@ extern "C" int hwy_launch_cut(const StepParams* p, uint8_t* cut, hipStream_t s) 
   hipLaunchKernelGGL(hwy_cut_kernel, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p, cut);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#elif defined(HWY_INFO_TU)
+// The info variants of the step kernels, likewise a unit of their own (-DHWY_INFO_TU ->
+// hwy_info.o): step_body with INFO on, the info pointers a second, separate argument (solo) or a
+// second device table (grouped), so StepParams -- the plain kernels' kernarg and table layout --
+// is untouched.  Launch geometry and register budgets are the plain kernels'.
+template <int W>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
+hwy_step_info_kernel(StepParams P, InfoParams I) {
+  step_body<W, true>(P, &I);
+}
+
+template <int W>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
+hwy_step_grp_info_kernel(const StepParams* __restrict__ tab, const InfoParams* __restrict__ itab) {
+  step_body<W, true>(tab[blockIdx.y], itab + blockIdx.y);
+}
+
+extern "C" int hwy_launch_step_info(const StepParams* p, const InfoParams* info, hipStream_t s) {
+  const int blocks = (p->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  if (hwy_step_big(p->cfg.num_envs))
+    hipLaunchKernelGGL(hwy_step_info_kernel<HWY_STEP_BIG_W>, dim3(blocks),
+                       dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p, *info);
+  else
+    hipLaunchKernelGGL(hwy_step_info_kernel<4>, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s,
+                       *p, *info);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int hwy_launch_step_group_info(const StepParams* dtab, const InfoParams* itab, int n,
+                                          int blocks, int big, hipStream_t s) {
+  if (big)
+    hipLaunchKernelGGL(hwy_step_grp_info_kernel<HWY_STEP_BIG_W>, dim3(blocks, n),
+                       dim3(ENVS_PER_BLOCK * WAVE), 0, s, dtab, itab);
+  else
+    hipLaunchKernelGGL(hwy_step_grp_info_kernel<4>, dim3(blocks, n), dim3(ENVS_PER_BLOCK * WAVE),
+                       0, s, dtab, itab);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 #else  // the main unit, to the end of the file
 template <int W>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
 hwy_step_kernel(StepParams P) {
-  step_body<W>(P);
+  step_body<W, false>(P, nullptr);
 }
 
 // handle blockIdx.y of tab; blocks past a handle's envs exit in step_body (whole waves).  The
@@ -1428,7 +1515,7 @@ hwy_step_kernel(StepParams P) {
 template <int W>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
 hwy_step_grp_kernel(const StepParams* __restrict__ tab) {
-  step_body<W>(tab[blockIdx.y]);
+  step_body<W, false>(tab[blockIdx.y], nullptr);
 }
 
 __global__ void __launch_bounds__(256) hwy_reset_kernel(StepParams P) {
@@ -1548,10 +1635,6 @@ __global__ void hwy_math_kernel(int op, const float* in, const float* in2, float
 // ------------------------------------------------------------------------- launch helpers
 extern "C" {
 // compute units of the current device (cached per device; 256 without one)
-// waves per SIMD the step kernel's registers are sized for at large E (5 and 8 measured slower)
-#ifndef HWY_STEP_BIG_W
-#define HWY_STEP_BIG_W 6
-#endif
 // envs per CU above which the big build runs: at 8,192 envs (32 per CU) the 4-wave build is
 // 6-7 % faster than the 6-wave one (0.205 vs 0.219-0.245 ms per step), at 16,384 the 6-wave build
 // wins (0.295 vs 0.324) and at 32,768 ties the 5-wave one (profiles/r6/micro/ab_bigw.log)
@@ -1659,4 +1742,4 @@ extern "C" int hwy_debug_sections(unsigned long long* out, int reset) {
   return 0;
 }
 #endif
-#endif  // HWY_CUT_TU
+#endif  // HWY_CUT_TU / HWY_INFO_TU

@@ -6,7 +6,9 @@ train_with_experiment_name -> {"status": "COMPLETED"|"FAILED", ...}.  Experiment
 ``num_envs`` (lockstep envs, > 1 selects the vectorised loop), ``num_minibatches`` and
 ``episode_schedule`` ("lockstep", the default, or "reference": episodes cut at the update
 boundary and evaluations ahead of the update, training/routine.py; with it ``num_envs`` 1 runs
-the vectorised loop on a one-env HighwayVecEnv, which is the reference's own episode stream).
+the vectorised loop on a one-env HighwayVecEnv, which is the reference's own episode stream)
+and ``episode_stats`` (True: per-episode lengths, crashes, mean speeds and lane changes in the
+metrics and a crash rate in the summary, training/routine.py; vectorised loop only).
 
 Launched under torchrun (WORLD_SIZE > 1) one experiment spans the ranks, one GPU each: the
 runner joins the process group (RCCL, or ``HWY_DIST_BACKEND``), gives rank r the envs
@@ -128,6 +130,8 @@ class ExperimentRunner:
                     schedule = exp.extra.get("episode_schedule", "lockstep")
                     if schedule == "reference":
                         overrides.setdefault("vector_env", True)
+                    stats_kw = ({"episode_stats": True} if exp.extra.get("episode_stats")
+                                else {})
                     if group is not None:
                         e = int(overrides.get("num_envs", 1))
                         if e <= 1:
@@ -155,7 +159,8 @@ class ExperimentRunner:
                         eval_interval=exp.extra.get("eval_interval", 50),
                         steps_per_update=exp.hp.steps_per_update, experiment_name=exp.name,
                         exp_seed=exp.seed, logger=logger,
-                        **({} if schedule == "lockstep" else {"episode_schedule": schedule}))
+                        **({} if schedule == "lockstep" else {"episode_schedule": schedule}),
+                        **stats_kw)
                     results.update(status="COMPLETED", rewards=rewards, avg_rewards=avg_rewards,
                                    metrics_history=metrics)
                 except Exception as e:
@@ -194,7 +199,8 @@ class ExperimentRunner:
         differ only in seed and name and use the vectorised loop (num_envs > 1, or num_envs 1 on
         the reference episode schedule); across cells they share what one GroupBatch's launches
         share -- envs per experiment, rollout length and the episode schedule -- and the
-        training schedule.  The condition and the hidden width may differ between cells.  The
+        training schedule -- and extra["episode_stats"], which selects the env launch they
+        share.  The condition and the hidden width may differ between cells.  The
         update's own schedule (batch_size, num_minibatches, epochs) must be shared too, unless
         ``own_schedules`` (what launch_batch passes): then it may differ between cells
         (hwy_ppo_sched_*), and each cell's minibatches must all be of one size, below the grouped
@@ -218,6 +224,8 @@ class ExperimentRunner:
         first = [c[0] for c in cells]
         if len({episode_schedule(e) for e in first}) != 1:
             raise ValueError("launch_batch: the cells must share extra['episode_schedule']")
+        if len({bool(e.extra.get("episode_stats", False)) for e in first}) != 1:
+            raise ValueError("launch_batch: the cells must share extra['episode_stats']")
 
         def shared(e):
             return (int(e.extra.get("num_envs", 1)), e.hp.steps_per_update, e.max_episodes,
@@ -275,6 +283,8 @@ class ExperimentRunner:
         schedule = first[0].extra.get("episode_schedule", "lockstep")
         # the default schedule passes no keyword: that path is the one without the feature
         sched_kw = {} if schedule == "lockstep" else {"episode_schedule": schedule}
+        if first[0].extra.get("episode_stats"):
+            sched_kw["episode_stats"] = True
         results = [[{"experiment_name": e.name, "status": "FAILED"} for e in exps]
                    for exps in cells]
         loggers = []

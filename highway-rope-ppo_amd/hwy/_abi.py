@@ -49,6 +49,20 @@ FLOAT_FIELDS = (F_X, F_Y, F_HEADING, F_SPEED, F_TSPEED, F_DELTA, F_TIMER, F_IMPX
 DEFAULT_STEPS_PER_DURATION = 5
 
 
+# hwy_step_with_info (include/hwy.h): floats per env of the episode sums, their slots, and the
+# keys of upstream's info["rewards"] (HighwayEnv._rewards) in the order of the rewards output
+HWY_INFO_NACC = 8
+(ACC_SPEED, ACC_COLLISION, ACC_RIGHT_LANE, ACC_HIGH_SPEED, ACC_ON_ROAD, ACC_LANE_CHANGES,
+ ACC_CRASHED) = range(7)
+REWARD_KEYS = ("collision_reward", "right_lane_reward", "high_speed_reward", "on_road_reward")
+
+
+class HwyStepInfo(ctypes.Structure):
+    """hwy_step_info: the info outputs of one handle's step (device pointers, all nullable)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("speed", "crashed", "lane", "rewards", "acc",
+                                               "ep_stats")]
+
+
 class HwyConfig(ctypes.Structure):
     _fields_ = [
         ("num_envs", ctypes.c_int32),

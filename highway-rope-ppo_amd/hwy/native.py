@@ -13,7 +13,7 @@ import os
 import subprocess
 from typing import Optional
 
-from ._abi import HWY_ABI_VERSION, HwyConfig
+from ._abi import HWY_ABI_VERSION, HwyConfig, HwyStepInfo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhwy.so")
@@ -74,6 +74,13 @@ def lib():
     L.hwy_reset.argtypes = [vp, vp, vp, vp, vp]
     L.hwy_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.hwy_cut_episodes.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.hwy_step_info_size.restype = i32
+    L.hwy_step_with_info.argtypes = [vp] * 8 + [ctypes.POINTER(HwyStepInfo), vp]
+    L.hwy_step_group_info_table_bytes.argtypes = [i32]
+    L.hwy_step_group_info_table_bytes.restype = ctypes.c_int64
+    L.hwy_step_group_info_prepare.argtypes = [vp, vp, vp, i32, vp, vp,
+                                              ctypes.POINTER(HwyStepGroupPlan), vp]
+    L.hwy_step_group_info.argtypes = [ctypes.POINTER(HwyStepGroupPlan), vp, vp, vp]
     L.hwy_export_state.argtypes = [vp, vp, vp]
     L.hwy_import_state.argtypes = [vp, vp, vp]
     L.hwy_obs_pe.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp]
@@ -87,10 +94,13 @@ def lib():
     for name in ("hwy_create", "hwy_obs_features", "hwy_set_pe_table", "hwy_set_seed_schedule",
                  "hwy_set_seed_groups", "hwy_reset", "hwy_step", "hwy_cut_episodes",
                  "hwy_step_group_prepare",
-                 "hwy_step_group",
+                 "hwy_step_group", "hwy_step_with_info", "hwy_step_group_info_prepare",
+                 "hwy_step_group_info",
                  "hwy_export_state", "hwy_import_state", "hwy_obs_pe", "hwy_gae",
                  "hwy_math_selftest"):
         getattr(L, name).restype = i32
+    if L.hwy_step_info_size() != ctypes.sizeof(HwyStepInfo):
+        raise HwyNativeError("libhwy.so's hwy_step_info differs from the python mirror; rebuild")
     if L.hwy_abi_version() != HWY_ABI_VERSION:
         raise HwyNativeError(
             f"libhwy.so ABI {L.hwy_abi_version()} != python ABI {HWY_ABI_VERSION}; rebuild"

@@ -14,6 +14,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
+from ._abi import REWARD_KEYS
 from .gym import Env, spaces
 from .vec_env import HighwayVecEnv
 
@@ -23,8 +24,10 @@ class HighwayEnv(Env):
 
     metadata = {"render_modes": []}
 
-    def __init__(self, config: Dict[str, Any], device: Optional[torch.device] = None):
-        self._vec = HighwayVecEnv(config, num_envs=1, device=device, autoreset=False)
+    def __init__(self, config: Dict[str, Any], device: Optional[torch.device] = None,
+                 info: bool = False):
+        self._vec = HighwayVecEnv(config, num_envs=1, device=device, autoreset=False, info=info)
+        self._info = bool(info)
         self.config = self._vec.config
         self.action_space = spaces.Box(-1.0, 1.0, shape=(2,), dtype=np.float32)
         self.observation_space = self._vec.single_observation_space
@@ -68,8 +71,17 @@ class HighwayEnv(Env):
         a = torch.as_tensor(np.asarray(action, dtype=np.float32).reshape(1, 2))
         self._act.copy_(a, non_blocking=False)
         obs, rew, term, trunc, _ = self._vec.step(self._act)
-        host = torch.cat([rew.view(1), term.view(1).float(), trunc.view(1).float()]).cpu().numpy()
-        return (obs[0].cpu().numpy(), float(host[0]), bool(host[1] > 0), bool(host[2] > 0), {})
+        parts = [rew.view(1), term.view(1).float(), trunc.view(1).float()]
+        if self._info:  # upstream's AbstractEnv._info, in the same single transfer
+            b = self._vec.info_buf
+            parts += [b["speed"].view(1), b["crashed"].view(1).float(), b["rewards"].view(4)]
+        host = torch.cat(parts).cpu().numpy()
+        info = {}
+        if self._info:
+            info = {"speed": float(host[3]), "crashed": bool(host[4] > 0),
+                    "action": np.asarray(action, dtype=np.float32).reshape(2).copy(),
+                    "rewards": {k: float(host[5 + i]) for i, k in enumerate(REWARD_KEYS)}}
+        return (obs[0].cpu().numpy(), float(host[0]), bool(host[1] > 0), bool(host[2] > 0), info)
 
     def close(self):
         self._vec.close()

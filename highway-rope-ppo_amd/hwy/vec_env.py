@@ -11,6 +11,13 @@ tensors instead of numpy:
 With ``autoreset=True`` finished envs restart inside the step kernel with the next seed of the
 episode schedule (include/hwy.h) and ``info["episode_return"/"episode_length"]`` report the
 finished episode (0 elsewhere).  Every call is asynchronous on the current HIP stream.
+
+``info=True`` opts into upstream's per-step info (AbstractEnv._info / HighwayEnv._rewards) for
+the ego of every env -- ``info["speed"]``, ``["crashed"]``, ``["lane"]``, ``["rewards"]`` (a dict
+of the four unweighted terms) -- and ``info["episode_stats"]`` ([E, 8]: where an episode finished,
+its sums of speed and of the four terms, its lane-change count and its crashed flag; the slots
+are _abi.ACC_*).  The step then runs the info variant of the kernel (hwy_step_with_info), which
+computes the same step and stores these besides.
 """
 
 from __future__ import annotations
@@ -23,10 +30,32 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._abi import HWY_MAX_VEHICLES, NFIELDS, PE_NONE, config_from_dict
+from ._abi import (HWY_INFO_NACC, HWY_MAX_VEHICLES, NFIELDS, PE_NONE, REWARD_KEYS, HwyStepInfo,
+                   config_from_dict)
 from .gym import spaces
 from .native import (HwyNativeError, HwyStepGroupPlan, HwyStepIO, check, lib, ptr,
                      stream_ptr)
+
+INFO_FIELDS = tuple(n for n, _ in HwyStepInfo._fields_)
+
+
+def alloc_step_info(num_envs: int, device) -> Dict[str, torch.Tensor]:
+    """Device tensors for every output of hwy_step_with_info, keyed by hwy_step_info's fields."""
+    E, kw = int(num_envs), dict(device=device)
+    return {"speed": torch.zeros(E, dtype=torch.float32, **kw),
+            "crashed": torch.zeros(E, dtype=torch.uint8, **kw),
+            "lane": torch.zeros(E, dtype=torch.int32, **kw),
+            "rewards": torch.zeros(E, 4, dtype=torch.float32, **kw),
+            "acc": torch.zeros(E, HWY_INFO_NACC, dtype=torch.float32, **kw),
+            "ep_stats": torch.zeros(E, HWY_INFO_NACC, dtype=torch.float32, **kw)}
+
+
+def _info_ptrs(info: Dict[str, Any]) -> tuple:
+    """hwy_step_info's pointers from a dict of caller-owned tensors (missing / None = NULL)."""
+    unknown = set(info) - set(INFO_FIELDS)
+    if unknown:
+        raise ValueError(f"unknown step info outputs {sorted(unknown)}; known: {INFO_FIELDS}")
+    return tuple(ptr(info.get(n)) for n in INFO_FIELDS)
 
 
 class HighwayVecEnv:
@@ -38,7 +67,7 @@ class HighwayVecEnv:
                  device: Optional[torch.device] = None, autoreset: bool = True,
                  seed_base: int = 0, env_offset: int = 0, global_envs: Optional[int] = None,
                  pe_kind: int = PE_NONE, d_embed: int = 0, pe_table: Optional[np.ndarray] = None,
-                 ego_idx: int = 0, pe_max_dist: float = 100.0):
+                 ego_idx: int = 0, pe_max_dist: float = 100.0, info: bool = False):
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         device = torch.device(device)
@@ -59,6 +88,8 @@ class HighwayVecEnv:
         self._pe_table = None if pe_table is None else np.ascontiguousarray(pe_table, np.float32)
         self._create()
         self._alloc_buffers()
+        # the opt-in step info: buffers owned by the env (None: step() is the plain hwy_step)
+        self.info_buf = alloc_step_info(self.num_envs, self.device) if info else None
         self.action_space = spaces.Box(-1.0, 1.0, shape=(2,), dtype=np.float32)
         self._set_obs_space()
 
@@ -172,6 +203,8 @@ class HighwayVecEnv:
             a = torch.as_tensor(a, device=self.device, dtype=torch.float32).contiguous()
         if a.numel() != 2 * self.num_envs:
             raise ValueError(f"actions must have {self.num_envs}x2 elements, got {tuple(a.shape)}")
+        if self.info_buf is not None:
+            return self._step_info(a)
         check(lib().hwy_step(self._handle, ptr(a), ptr(self.obs_buf), ptr(self.reward_buf),
                              ptr(self.term_buf), ptr(self.trunc_buf), ptr(self.ep_ret_buf),
                              ptr(self.ep_len_buf), stream_ptr()), "hwy_step")
@@ -179,11 +212,32 @@ class HighwayVecEnv:
         info = {"episode_return": self.ep_ret_buf, "episode_length": self.ep_len_buf}
         return self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf, info
 
+    def _step_info(self, a: torch.Tensor):
+        b = self.info_buf
+        self.step_into(a, self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf,
+                       self.ep_ret_buf, self.ep_len_buf, info=b)
+        self._keep = a
+        info = {"episode_return": self.ep_ret_buf, "episode_length": self.ep_len_buf,
+                "speed": b["speed"], "crashed": b["crashed"], "lane": b["lane"],
+                "rewards": {k: b["rewards"][:, i] for i, k in enumerate(REWARD_KEYS)},
+                "episode_stats": b["ep_stats"]}
+        return self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf, info
+
     def step_into(self, actions: torch.Tensor, obs: torch.Tensor, reward: torch.Tensor,
                   terminated: torch.Tensor, truncated: torch.Tensor,
                   ep_return: Optional[torch.Tensor] = None,
-                  ep_length: Optional[torch.Tensor] = None) -> None:
-        """step() writing straight into caller-owned rollout slices (no copies; graph-safe)."""
+                  ep_length: Optional[torch.Tensor] = None,
+                  info: Optional[Dict[str, torch.Tensor]] = None) -> None:
+        """step() writing straight into caller-owned rollout slices (no copies; graph-safe).
+        ``info``: caller-owned tensors for hwy_step_with_info's outputs, keyed by hwy_step_info's
+        fields (alloc_step_info's layout; any subset, "ep_stats" needs "acc")."""
+        if info is not None:
+            si = HwyStepInfo(*_info_ptrs(info))
+            check(lib().hwy_step_with_info(self._handle, ptr(actions), ptr(obs), ptr(reward),
+                                           ptr(terminated), ptr(truncated), ptr(ep_return),
+                                           ptr(ep_length), ctypes.byref(si), stream_ptr()),
+                  "hwy_step_with_info")
+            return
         check(lib().hwy_step(self._handle, ptr(actions), ptr(obs), ptr(reward), ptr(terminated),
                              ptr(truncated), ptr(ep_return), ptr(ep_length), stream_ptr()),
               "hwy_step")
@@ -281,10 +335,38 @@ class GroupEnvStep:
         self._nb = int(lib().hwy_step_group_table_bytes(self.n))
         self._tables: Dict[Any, Any] = {}
 
-    def launch(self, ios) -> None:
+    def _launch_info(self, ptrs, infos) -> None:
+        """launch() through hwy_step_group_info: a second device table holds the info pointers."""
+        iptrs = tuple(_info_ptrs(i) for i in infos)
+        key = (tuple((e._handle.value, e.launch_version) for e in self.envs), ptrs, iptrs)
+        hit = self._tables.get(key)
+        if hit is None:
+            arr = (HwyStepIO * self.n)(*[HwyStepIO(*p) for p in ptrs])
+            iarr = (HwyStepInfo * self.n)(*[HwyStepInfo(*p) for p in iptrs])
+            hs = (ctypes.c_void_p * self.n)(*[e._handle.value for e in self.envs])
+            dev = self.envs[0].device
+            t = torch.empty(self._nb, dtype=torch.uint8, device=dev)
+            it = torch.empty(int(lib().hwy_step_group_info_table_bytes(self.n)), dtype=torch.uint8,
+                             device=dev)
+            plan = HwyStepGroupPlan()
+            check(lib().hwy_step_group_info_prepare(hs, arr, iarr, self.n, t.data_ptr(),
+                                                    it.data_ptr(), ctypes.byref(plan),
+                                                    stream_ptr()), "hwy_step_group_info_prepare")
+            hit = (t, plan, it)
+            self._tables[key] = hit
+        check(lib().hwy_step_group_info(ctypes.byref(hit[1]), hit[0].data_ptr(),
+                                        hit[2].data_ptr(), stream_ptr()), "hwy_step_group_info")
+
+    def launch(self, ios, infos=None) -> None:
         """ios[i] = (actions, obs, reward, terminated, truncated, ep_return, ep_length) of env i,
-        as step_into takes them (the last two may be None)."""
+        as step_into takes them (the last two may be None).  ``infos[i]``: env i's step info
+        tensors as step_into's ``info`` (one dict per handle; the launch is then the info
+        variant, hwy_step_group_info)."""
         ptrs = tuple(tuple(ptr(x) for x in io) for io in ios)
+        if infos is not None:
+            if len(infos) != self.n:
+                raise ValueError("one step info dict per handle")
+            return self._launch_info(ptrs, infos)
         key = (tuple((e._handle.value, e.launch_version) for e in self.envs), ptrs)
         hit = self._tables.get(key)
         if hit is None:

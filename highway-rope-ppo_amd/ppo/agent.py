@@ -165,9 +165,14 @@ class PPOMemory:
 
 
 class RolloutBuffer:
-    """Device-resident rollout of T steps x E envs (the env kernel writes rows in place)."""
+    """Device-resident rollout of T steps x E envs (the env kernel writes rows in place).
 
-    def __init__(self, T: int, E: int, state_dim: int, action_dim: int, device: torch.device):
+    ``episode_stats``: also ``ep_stats`` [T, E, 8] (hwy_step_with_info's per-episode sums where an
+    episode finished, 0 elsewhere) and ``acc`` [E, 8] (the running sums of the current episodes,
+    carried from rollout to rollout); the rollout then issues the info variant of the step."""
+
+    def __init__(self, T: int, E: int, state_dim: int, action_dim: int, device: torch.device,
+                 episode_stats: bool = False):
         kw = dict(device=device, dtype=torch.float32)
         self.T, self.E, self.state_dim = T, E, state_dim
         self.states = torch.zeros(T + 1, E, state_dim, **kw)  # row T = bootstrap obs
@@ -182,10 +187,22 @@ class RolloutBuffer:
         self.ep_return = torch.zeros(T, E, **kw)
         self.ep_length = torch.zeros(T, E, device=device, dtype=torch.int32)
         self.noise = torch.zeros(T, E, action_dim, **kw)  # the rollout's sampling noise
+        self.ep_stats = self.acc = None
+        if episode_stats:
+            from hwy._abi import HWY_INFO_NACC
+
+            self.ep_stats = torch.zeros(T, E, HWY_INFO_NACC, **kw)
+            self.acc = torch.zeros(E, HWY_INFO_NACC, **kw)
 
     @property
     def n(self) -> int:
         return self.T * self.E
+
+    def step_info(self, t: int):
+        """step_into's ``info`` for rollout step t (None without episode_stats)."""
+        if self.ep_stats is None:
+            return None
+        return {"acc": self.acc, "ep_stats": self.ep_stats[t]}
 
     def draw_noise(self, generator: Optional[torch.Generator] = None) -> None:
         """All T steps' standard normal sampling noise in one draw (one launch per rollout

@@ -42,10 +42,13 @@ from .rollout import alloc_cut_buffers, check_episode_schedule, rollout_chunks
 class ExperimentGroup:
     def __init__(self, agents: Sequence, env, seeds: Sequence[int], envs_per_experiment: int,
                  rollout_len: int, use_graphs: bool = True, rank_tables=None,
-                 episode_schedule: str = "lockstep"):
+                 episode_schedule: str = "lockstep", episode_stats: bool = False):
         from hwy.ppo_native import GroupAct
 
         self.episode_schedule = check_episode_schedule(episode_schedule)
+        # the env steps as hwy_step_with_info, every experiment's episode sums in buf.ep_stats /
+        # buf.acc (ppo/rollout.py)
+        self.episode_stats = bool(episode_stats)
 
         self.agents = list(agents)
         self.G, self.E, self.T = len(self.agents), int(envs_per_experiment), int(rollout_len)
@@ -71,7 +74,8 @@ class ExperimentGroup:
                                                   for t in rank_tables]))
         N, Fo = self.env.obs_rows, self.env.obs_features
         self.sd = N * Fo
-        self.buf = RolloutBuffer(self.T, self.G * self.E, self.sd, 2, self.dev)
+        self.buf = RolloutBuffer(self.T, self.G * self.E, self.sd, 2, self.dev,
+                                 **({"episode_stats": True} if self.episode_stats else {}))
         self.use_graphs = bool(use_graphs)
         self.act = GroupAct(self.agents, self.E)
         GE = self.G * self.E
@@ -122,7 +126,10 @@ class ExperimentGroup:
                 buf.ep_length[t])
 
     def env_step(self, t: int) -> None:
-        self.env.step_into(*self.env_io(t))
+        if self.episode_stats:
+            self.env.step_into(*self.env_io(t), info=self.buf.step_info(t))
+        else:
+            self.env.step_into(*self.env_io(t))
 
     def cut_episodes(self) -> None:
         """The reference schedule's cut after the rollout's last step (LockstepRollout._steps)."""
@@ -401,11 +408,15 @@ class GroupBatch:
     envs per experiment and rollout length.  Each experiment stays bit-identical to its solo run: the same kernel bodies per
     learner, each group's own generator order, GAE and normalisation."""
 
-    def __init__(self, groups, use_graphs: bool = True):
+    def __init__(self, groups, use_graphs: bool = True, episode_stats: Optional[bool] = None):
         from hwy.ppo_native import GroupAct
 
         self.groups = list(groups)
         g0 = self.groups[0]
+        # the groups' steps as one hwy_step_group_info launch; the groups are built with the flag
+        self.episode_stats = g0.episode_stats if episode_stats is None else bool(episode_stats)
+        if any(g.episode_stats != self.episode_stats for g in self.groups):
+            raise ValueError("a batch's groups share episode_stats")
         if any(g.E != g0.E or g.T != g0.T for g in self.groups):
             raise ValueError("a batch's groups share envs per experiment and rollout length")
         if any(g.episode_schedule != g0.episode_schedule for g in self.groups):
@@ -440,7 +451,10 @@ class GroupBatch:
         t1 = self.T if t1 is None else t1
         for t in range(t0, t1):
             self.act.launch(self._rows(t), tiles)
-            if self.envstep is not None:
+            if self.envstep is not None and self.episode_stats:
+                self.envstep.launch([g.env_io(t) for g in self.groups],
+                                    infos=[g.buf.step_info(t) for g in self.groups])
+            elif self.envstep is not None:
                 self.envstep.launch([g.env_io(t) for g in self.groups])
             else:
                 self.groups[0].env_step(t)
@@ -478,7 +492,7 @@ class GroupBatch:
 def build_group(condition, base_config, seeds: Sequence[int], envs_per_experiment: int,
                 rollout_len: int, device: torch.device, make_agent: Callable, d_embed=None,
                 env_overrides: Optional[dict] = None, use_graphs: bool = True,
-                episode_schedule: str = "lockstep"):
+                episode_schedule: str = "lockstep", episode_stats: bool = False):
     """A group of len(seeds) experiments of one condition, each constructed as
     experiments/runner.py constructs its solo run: set_random_seeds(seed), make_env (whose RankPE
     table draws from the global torch RNG), env.to(device), then ``make_agent(state_dim)`` (the
@@ -517,7 +531,8 @@ def build_group(condition, base_config, seeds: Sequence[int], envs_per_experimen
     grp = ExperimentGroup(agents, env, seeds, E, rollout_len, use_graphs=use_graphs,
                           rank_tables=tables if rank else None,
                           **({} if episode_schedule == "lockstep"
-                             else {"episode_schedule": episode_schedule}))
+                             else {"episode_schedule": episode_schedule}),
+                          **({"episode_stats": True} if episode_stats else {}))
     grp.solo_envs = solos
     grp.group_env = env
     return grp

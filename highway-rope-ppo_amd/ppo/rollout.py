@@ -58,10 +58,15 @@ def alloc_cut_buffers(owner, E: int, sd: int, device) -> None:
 
 class LockstepRollout:
     def __init__(self, agent, env, buf, use_graph: bool = True,
-                 episode_schedule: str = "lockstep"):
+                 episode_schedule: str = "lockstep", episode_stats: bool = False):
         self.agent = agent
         self.env = env.unwrapped if hasattr(env, "unwrapped") else env
         self.buf = buf
+        # the steps as hwy_step_with_info, the episodes' sums going to buf.ep_stats / buf.acc
+        # (after a reference-schedule cut, buf.acc's rows of the cut envs hold their partial sums)
+        self.episode_stats = bool(episode_stats)
+        if self.episode_stats and buf.ep_stats is None:
+            raise ValueError("episode_stats needs a RolloutBuffer built with episode_stats=True")
         self.use_graph = bool(use_graph) and self.buf.states.is_cuda
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._key = None
@@ -102,7 +107,13 @@ class LockstepRollout:
                              noise=buf.noise[t])
             io = (buf.actions[t], buf.states[t + 1].view(E, *obs_shape), buf.rewards[t],
                   buf.terminated[t], buf.truncated[t], buf.ep_return[t], buf.ep_length[t])
-            if self._envstep is not None:
+            if self.episode_stats:
+                info = buf.step_info(t)
+                if self._envstep is not None:
+                    self._envstep.launch([io], infos=[info])
+                else:
+                    env.step_into(*io, info=info)
+            elif self._envstep is not None:
                 self._envstep.launch([io])
             else:
                 env.step_into(*io)

@@ -25,6 +25,12 @@ bootstrapped with V of its last state; the next rollout starts the schedule's ne
 the evaluation points that stream crosses are evaluated before the update, on the weights that
 collected it (:173-175).  With one env and T = ``steps_per_update`` that is the reference's
 episode stream, seeds exp_seed + episode_num.  The default, "lockstep", is the loop above.
+``episode_stats=True`` (vectorised loop, train_group, train_batch) steps the envs with
+hwy_step_with_info and books, per episode and in the order of ``episode_rewards`` (cut episodes
+included), ``episode_lengths``, ``episode_crashed``, ``episode_mean_speed`` (sum of the ego's speed
+over the episode's steps / its length) and ``episode_lane_changes`` into metrics_history, and a
+``crash_rate`` column (over the last 100 episodes) into the summary.  The training itself is
+unchanged, bit for bit.
 ``evaluate`` runs ``num_episodes`` deterministic episodes seeded exp_seed + 1000 + k (:14-29),
 as one batched env for the vectorised path.
 """
@@ -260,11 +266,51 @@ def _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_hist
         logger.warning(f"{exp_prefix} plot failed: {e}")
     csv_path = os.path.join(artifacts_dir, f"summary_{experiment_name}.csv")
     best_model_path = os.path.join(checkpoint_dir, f"ppo_highway_best_{experiment_name}.pth")
+    head, tail = "", ""
+    if "episode_crashed" in metrics_history:  # episode_stats runs only
+        head, tail = ",crash_rate", f",{crash_rate(metrics_history['episode_crashed']):.4f}"
     with open(csv_path, "w") as f:
-        f.write("experiment,final_reward,max_reward,steps,best_model,plot\n")
+        f.write(f"experiment,final_reward,max_reward,steps,best_model,plot{head}\n")
         f.write(f"{experiment_name},{avg_rewards[-1]:.4f},{max(avg_rewards):.4f},{total_steps},"
-                f"{best_model_path},{os.path.basename(plot_path)}\n")
+                f"{best_model_path},{os.path.basename(plot_path)}{tail}\n")
     logger.info(f"{exp_prefix} Summary CSV saved to {csv_path}")
+
+
+STATS_KEYS = ("episode_lengths", "episode_crashed", "episode_mean_speed", "episode_lane_changes")
+
+
+def crash_rate(crashed, last: int = 100) -> float:
+    """Share of the last ``last`` booked episodes that ended in a crash (0 with none booked)."""
+    tail = list(crashed)[-last:]
+    return float(np.mean(tail)) if tail else 0.0
+
+
+def _stats_stream(dones, ep_length, ep_stats, cut=None, cut_length=None, acc=None):
+    """The per-episode statistics of one rollout's episode stream, in _episode_ends' /
+    _episode_stream's order: for the episodes that finished in the [T, E] rollout their ep_stats
+    rows ([T, E, 8], hwy_step_with_info) and lengths, then, on the reference schedule, for the
+    episodes cut at its end the running sums ``acc`` [E, 8] as the cut left them, with the cut's
+    lengths (a cut episode has not crashed: a crash would have ended it).  Returns the [n, 8]
+    float32 sums (slot 6: crashed) and the [n] lengths."""
+    d = dones.cpu().numpy() != 0
+    sums = ep_stats.cpu().numpy()[d]
+    lens = ep_length.cpu().numpy()[d]
+    if cut is not None:
+        c = cut.cpu().numpy() != 0
+        sums = np.concatenate([sums, acc.cpu().numpy()[c]])
+        lens = np.concatenate([lens, cut_length.cpu().numpy()[c]])
+    return sums, lens
+
+
+def _book_stats(mh, sums, lens, i) -> None:
+    """Episode i of a _stats_stream into metrics_history's four lists."""
+    from hwy._abi import ACC_CRASHED, ACC_LANE_CHANGES, ACC_SPEED
+
+    n = int(lens[i])
+    mh["episode_lengths"].append(n)
+    mh["episode_crashed"].append(bool(sums[i, ACC_CRASHED] != 0))
+    mh["episode_mean_speed"].append(float(np.float64(sums[i, ACC_SPEED]) / max(n, 1)))
+    mh["episode_lane_changes"].append(int(sums[i, ACC_LANE_CHANGES]))
 
 
 class _EvalTracker:
@@ -320,8 +366,16 @@ class _EvalTracker:
 # ---------------------------------------------------------------------------------- training
 def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, log_interval=20,
                                eval_interval=50, steps_per_update=2048, experiment_name="",
-                               exp_seed: int = 0, logger=None, episode_schedule="lockstep"):
+                               exp_seed: int = 0, logger=None, episode_schedule="lockstep",
+                               episode_stats: bool = False):
     from ppo.rollout import check_episode_schedule
+
+    if episode_stats:
+        if not _is_vector(env):
+            raise ValueError("episode_stats needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                             "vector_env key for one env)")
+        if getattr(agent, "_dist", None) is not None:
+            raise ValueError("episode_stats does not run over a process group")
 
     if check_episode_schedule(episode_schedule) == "reference":
         if getattr(agent, "_dist", None) is not None:
@@ -344,6 +398,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         "eval_episode_numbers": [],
         "timestamps": [],
     }
+    if episode_stats:
+        metrics_history.update({k: [] for k in STATS_KEYS})
     start_time = time.time()
     artifacts_dir = ensure_artifacts_dir()
     checkpoint_dir = os.path.join(artifacts_dir, "checkpoints")
@@ -358,6 +414,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         raise ValueError("a process group needs the vectorised env (num_envs > 1)")
     loop = _train_vector if _is_vector(env) else _train_single
     sched_kw = {} if episode_schedule == "lockstep" else {"episode_schedule": episode_schedule}
+    if episode_stats:
+        sched_kw["episode_stats"] = True
     episode_rewards, training_episodes, total_steps = loop(
         env, agent, max_episodes, log_interval, eval_interval, steps_per_update, exp_seed, logger,
         exp_prefix, metrics_history, tracker, start_time, **sched_kw)
@@ -421,8 +479,12 @@ def _train_single(env, agent, max_episodes, log_interval, eval_interval, steps_p
 
 
 def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_per_update,
-                  exp_seed, logger, prefix, mh, tracker, start_time, episode_schedule="lockstep"):
+                  exp_seed, logger, prefix, mh, tracker, start_time, episode_schedule="lockstep",
+                  episode_stats=False):
     """E lockstep envs, device rollout of T steps, batched PPO update.
+
+    episode_stats: the rollout steps with hwy_step_with_info and every booked episode's
+    statistics go to mh's STATS_KEYS lists (read before the update and the next rollout).
 
     episode_schedule "reference": the rollout ends with the cut; its episode stream (finished,
     then cut episodes) is booked and its evaluations run before the update; the next rollout
@@ -441,19 +503,25 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
     E = base.num_envs
     sd = _flat_dim(env)
     T = max(1, math.ceil(steps_per_update / E))
-    buf = RolloutBuffer(T, E, sd, 2, base.device)
+    stats_kw = {"episode_stats": True} if episode_stats else {}
+    buf = RolloutBuffer(T, E, sd, 2, base.device, **stats_kw)
     base.set_seed_schedule(exp_seed)
     obs, _ = env.reset()
     buf.states[0].copy_(obs.reshape(E, sd))
     reference = episode_schedule == "reference"
     roll = LockstepRollout(agent, base, buf, use_graph=getattr(agent, "use_graphs", True),
-                           **({"episode_schedule": episode_schedule} if reference else {}))
+                           **({"episode_schedule": episode_schedule} if reference else {}),
+                           **stats_kw)
     episode_rewards, training_episodes = [], []
     total_steps = episode_num = 0
     while episode_num < max_episodes:
         t_update = time.time()
         roll.run()
         total_steps += T * E * world
+        if episode_stats:
+            cut_kw = ({"cut": roll.cut, "cut_length": roll.cut_length, "acc": buf.acc}
+                      if reference else {})
+            sums, lens = _stats_stream(buf.dones, buf.ep_length, buf.ep_stats, **cut_kw)
         if reference:  # the stream's evaluations run below, ahead of the update (:173-175)
             stream = _episode_stream(buf.dones, buf.ep_return, roll.cut, roll.cut_return)
             upd = None
@@ -461,7 +529,7 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
             upd = agent.update_rollout(buf, agent.value(buf.states[T]))
             # episode bookkeeping, in (step, global env) order -- identical on every rank
             stream = _episode_ends(buf.dones, buf.ep_return, group)
-        for r in stream:
+        for i, r in enumerate(stream):
             if episode_num >= max_episodes:
                 break
             episode_num += 1
@@ -470,6 +538,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
             training_episodes.append(episode_num)
             mh["episode_rewards"].append(r)
             mh["episode_numbers"].append(episode_num)
+            if episode_stats:
+                _book_stats(mh, sums, lens, i)
             _log_episode(logger, prefix, episode_num, r, episode_rewards, log_interval,
                          total_steps, start_time)
             if episode_num % eval_interval == 0 and rank == 0:
@@ -483,7 +553,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
 
 
 def train_group(group, experiment_names, exp_seeds, max_episodes=500, target_reward=0.0,
-                log_interval=20, eval_interval=50, loggers=None, episode_schedule="lockstep"):
+                log_interval=20, eval_interval=50, loggers=None, episode_schedule="lockstep",
+                episode_stats=False):
     """train_with_experiment_name for every experiment of an ExperimentGroup (ppo/group.py) at
     once: one grouped rollout + update per iteration, then each experiment's bookkeeping exactly
     as _train_vector does it on its own [T, E] slice (episode stream in (step, env) order,
@@ -496,11 +567,13 @@ def train_group(group, experiment_names, exp_seeds, max_episodes=500, target_rew
     return train_batch(group, [group], experiment_names, exp_seeds, max_episodes=max_episodes,
                        target_reward=target_reward, log_interval=log_interval,
                        eval_interval=eval_interval, loggers=loggers,
-                       episode_schedule=episode_schedule)
+                       episode_schedule=episode_schedule,
+                       **({"episode_stats": True} if episode_stats else {}))
 
 
 def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, target_reward=0.0,
-                log_interval=20, eval_interval=50, loggers=None, episode_schedule="lockstep"):
+                log_interval=20, eval_interval=50, loggers=None, episode_schedule="lockstep",
+                episode_stats=False):
     """train_group over the experiments of several ExperimentGroups stepped together: `stepper`
     is the ExperimentGroup itself (groups = [it]) or a GroupBatch over `groups` (ppo/group.py:
     the cells of one hidden width in one set of launches).  experiment_names / exp_seeds /
@@ -508,8 +581,13 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
     solo run's, on its own [T, E] slice of its group's rollout.  episode_schedule "reference"
     (the groups must have been built with it): each experiment's stream is its finished then
     its cut episodes, and the due evaluations run, still as one evaluate_many, ahead of the
-    update."""
+    update.  episode_stats (the groups must have been built with it): each experiment's
+    per-episode statistics are booked beside its returns, as _train_vector books them."""
     from ppo.rollout import check_episode_schedule
+
+    if any(bool(getattr(g, "episode_stats", False)) != bool(episode_stats) for g in groups):
+        raise ValueError(f"train_batch: every group must be built with episode_stats="
+                         f"{bool(episode_stats)}")
 
     reference = check_episode_schedule(episode_schedule) == "reference"
     if any(getattr(g, "episode_schedule", "lockstep") != episode_schedule for g in groups):
@@ -535,6 +613,8 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
         mh = {"experiment_name": name, "episode_rewards": [], "eval_rewards": [],
               "avg_eval_rewards": [], "policy_updates": [], "episode_numbers": [],
               "eval_episode_numbers": [], "timestamps": []}
+        if episode_stats:
+            mh.update({k: [] for k in STATS_KEYS})
         tracker = _EvalTracker(grp.solo_envs[j], grp.agents[j], int(exp_seeds[k]),
                                target_reward, checkpoint_dir, name, mh, logger, prefix, start_time)
         logger.info(f"{prefix} Performing initial evaluation...")
@@ -565,7 +645,12 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
                                          grp.cut[sl], grp.cut_return[sl])
             else:
                 stream = _episode_ends(grp.buf.dones[:, sl], grp.buf.ep_return[:, sl])
-            for ret in stream:
+            if episode_stats:
+                cut_kw = ({"cut": grp.cut[sl], "cut_length": grp.cut_length[sl],
+                           "acc": grp.buf.acc[sl]} if reference else {})
+                sums, lens = _stats_stream(grp.buf.dones[:, sl], grp.buf.ep_length[:, sl],
+                                           grp.buf.ep_stats[:, sl], **cut_kw)
+            for i, ret in enumerate(stream):
                 if r["episode_num"] >= max_episodes:
                     break
                 r["episode_num"] += 1
@@ -574,6 +659,8 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
                 r["training_episodes"].append(r["episode_num"])
                 r["mh"]["episode_rewards"].append(ret)
                 r["mh"]["episode_numbers"].append(r["episode_num"])
+                if episode_stats:
+                    _book_stats(r["mh"], sums, lens, i)
                 _log_episode(r["logger"], r["prefix"], r["episode_num"], ret, r["episode_rewards"],
                              log_interval, r["total_steps"], start_time)
                 if r["episode_num"] % eval_interval == 0:

@@ -14,6 +14,9 @@
  *                                (AbstractEnv.step/_simulate, HighwayEnv._reward/_is_terminated/
  *                                 _is_truncated, KinematicObservation.observe [highway-env 1.10.1])
  *                                + the PE wrapper's .observation() fused in (pe_kind != 0)
+ *   hwy_step_with_info        <- the info dict of env.step: AbstractEnv._info (speed, crashed,
+ *                                action) with HighwayEnv._rewards' four terms as "rewards"
+ *                                [highway-env 1.10.1], plus per-episode sums of them
  *   hwy_cut_episodes          <- the collection loop's cut at steps_per_update
  *                                                                        training/routine.py:125-132,153-156
  *   hwy_set_pe_table          <- RankEmbedWrapper.__init__ table        experiments/rank_embed.py:21-22
@@ -28,6 +31,7 @@
  *   hwy_step_group            <- env.step of every cell of a sweep batch (one launch)
  *                                (main.py:188-242 fans the seeds out as separate processes; here
  *                                 a cell's seeds share one handle, each with its own schedule)
+ *   hwy_step_group_info       <- the same, every cell's step with its info outputs
  *
  * Conventions
  *   - Plain pointers and sizes only; device pointers are HIP device pointers (e.g. torch
@@ -201,6 +205,40 @@ int hwy_reset(hwy_handle* h, const uint64_t* seeds, const uint8_t* mask, float* 
 int hwy_step(hwy_handle* h, const float* actions, float* obs, float* reward, uint8_t* terminated,
              uint8_t* truncated, float* ep_return, int32_t* ep_length, void* stream);
 
+/* ---- Step with info: hwy_step plus the ego's per-step info (upstream's AbstractEnv._info and
+ * HighwayEnv._rewards) and running per-episode sums.  The env computes exactly what hwy_step
+ * computes (the same kernel body; the outputs below are extra stores).  All pointers are device
+ * pointers and nullable; values are the ego's after the step's frames, before any autoreset:
+ *   speed [E] f32      Vehicle.speed
+ *   crashed [E] u8     Vehicle.crashed
+ *   lane [E] i32       the ego's lane id (lane_index[2])
+ *   rewards [E,4] f32  collision_reward, right_lane_reward, high_speed_reward, on_road_reward of
+ *                      HighwayEnv._rewards: the unweighted terms, exactly as they enter the reward
+ *   acc [E,HWY_INFO_NACC] f32, in/out, caller-owned: the current episode's running sums --
+ *                      [0] sum of speed, [1..4] sums of the four terms, [5] steps on which the
+ *                      lane id after the step differs from the one before it, [6], [7] reserved
+ *                      (written 0).  Each step does acc = acc + value in float32, as ep_return.
+ *                      An env whose step count is 0 on entry (just reset, autoreset or cut) starts
+ *                      from zero, not from the buffer, so the buffer needs no clearing.  After
+ *                      hwy_cut_episodes the rows of the cut envs hold their partial sums.
+ *   ep_stats [E,HWY_INFO_NACC] f32  where terminated|truncated: the finished episode's sums with
+ *                      [6] = the ego's crashed flag; all 0 elsewhere (as ep_return).  Needs acc.
+ * Returns HWY_EINVAL for a NULL handle, NULL info, or ep_stats without acc. */
+#define HWY_INFO_NACC 8
+typedef struct hwy_step_info {
+  float* speed;
+  uint8_t* crashed;
+  int32_t* lane;
+  float* rewards;
+  float* acc;
+  float* ep_stats;
+} hwy_step_info;
+/* sizeof(hwy_step_info) as compiled into the library (binding layout check). */
+int hwy_step_info_size(void);
+int hwy_step_with_info(hwy_handle* h, const float* actions, float* obs, float* reward,
+                       uint8_t* terminated, uint8_t* truncated, float* ep_return,
+                       int32_t* ep_length, const hwy_step_info* info, void* stream);
+
 /* End every running episode and start the next one of the schedule (the reference's collection
  * loop, training/routine.py:125-132, 153-156).  For each env whose episode has taken >= 1 policy
  * step: cut[e] = 1, ep_return[e] / ep_length[e] = its running return / steps so far, then exactly
@@ -242,6 +280,16 @@ int64_t hwy_step_group_table_bytes(int n);
 int hwy_step_group_prepare(hwy_handle* const* handles, const hwy_step_io* io, int n, void* table,
                            hwy_step_group_plan* plan, void* stream);
 int hwy_step_group(const hwy_step_group_plan* plan, const void* table, void* stream);
+/* The grouped step with info: info[i] is handle i's hwy_step_info (its pointers nullable as for
+ * hwy_step_with_info), kept in a second device table of hwy_step_group_info_table_bytes(n) bytes
+ * beside the step table (hwy_step_group_table_bytes(n), which hwy_step_group can launch too).
+ * The same rules as above: prepare is synchronous, the launch asynchronous and capturable. */
+int64_t hwy_step_group_info_table_bytes(int n);
+int hwy_step_group_info_prepare(hwy_handle* const* handles, const hwy_step_io* io,
+                                const hwy_step_info* info, int n, void* table, void* info_table,
+                                hwy_step_group_plan* plan, void* stream);
+int hwy_step_group_info(const hwy_step_group_plan* plan, const void* table, const void* info_table,
+                        void* stream);
 
 /* Copy the packed state [HWY_NFIELDS][E][HWY_MAX_VEHICLES] u32 to / from device memory. */
 int hwy_export_state(hwy_handle* h, uint32_t* dst, void* stream);
