@@ -387,6 +387,85 @@ int hwy_step_group_info(const hwy_step_group_plan* plan, const void* table, cons
   return HWY_OK;
 }
 
+// hwy_step_with_final / hwy_step_group_final_prepare: every refusal before any device call
+static int check_final(const hwy_step_info* info, const float* final_obs, const float* obs,
+                       const char* who) {
+  if (!final_obs) return fail(HWY_EINVAL, "%s: final_obs is NULL", who);
+  if (final_obs == obs) return fail(HWY_EINVAL, "%s: final_obs must not be the obs buffer", who);
+  if (info && info->ep_stats && !info->acc)
+    return fail(HWY_EINVAL, "%s: ep_stats needs acc (the episode's running sums)", who);
+  return HWY_OK;
+}
+
+int hwy_step_with_final(hwy_handle* h, const float* actions, float* obs, float* reward,
+                        uint8_t* terminated, uint8_t* truncated, float* ep_return,
+                        int32_t* ep_length, const hwy_step_info* info, float* final_obs,
+                        void* stream) {
+  if (!h) return fail(HWY_EINVAL, "handle is NULL");
+  if (!actions || !obs || !reward || !terminated || !truncated)
+    return fail(HWY_EINVAL,
+                "hwy_step_with_final: actions/obs/reward/terminated/truncated must be non-NULL");
+  if (int rc = check_final(info, final_obs, obs, "hwy_step_with_final")) return rc;
+  StepParams p = params_of(h);
+  p.actions = actions;
+  p.obs = obs;
+  p.reward = reward;
+  p.term = terminated;
+  p.trunc = truncated;
+  p.ep_ret = ep_return;
+  p.ep_len = ep_length;
+  FinalParams f;
+  memset(&f, 0, sizeof(f));
+  if (info) f.info = *info;
+  f.final_obs = final_obs;
+  if (hwy_launch_step_final(&p, &f, (hipStream_t)stream))
+    return hip_fail(hipGetLastError(), "hwy_step_final_kernel");
+  return HWY_OK;
+}
+
+int64_t hwy_step_group_final_table_bytes(int n) {
+  return n < 1 ? -1 : (int64_t)n * (int64_t)sizeof(FinalParams);
+}
+
+int hwy_step_group_final_prepare(hwy_handle* const* handles, const hwy_step_io* io,
+                                 const hwy_step_info* info, float* const* final_obs, int n,
+                                 void* table, void* final_table, hwy_step_group_plan* plan,
+                                 void* stream) {
+  if (!io || !final_obs || !final_table || n < 1)
+    return fail(HWY_EINVAL,
+                "hwy_step_group_final_prepare: io/final_obs/final_table NULL or n < 1");
+  for (int i = 0; i < n; ++i)
+    if (int rc = check_final(info ? info + i : nullptr, final_obs[i], io[i].obs,
+                             "hwy_step_group_final_prepare"))
+      return rc;
+  FinalParams* ftab = new FinalParams[n];
+  memset(ftab, 0, (size_t)n * sizeof(FinalParams));
+  for (int i = 0; i < n; ++i) {
+    if (info) ftab[i].info = info[i];
+    ftab[i].final_obs = final_obs[i];
+  }
+  int rc = hwy_step_group_prepare(handles, io, n, table, plan, stream);
+  if (rc == HWY_OK) {
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(final_table, ftab, (size_t)n * sizeof(FinalParams),
+                                  hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) rc = hip_fail(e, "hwy_step_group_final_prepare");
+  }
+  delete[] ftab;
+  return rc;
+}
+
+int hwy_step_group_final(const hwy_step_group_plan* plan, const void* table,
+                         const void* final_table, void* stream) {
+  if (!plan || !table || !final_table || plan->n < 1 || plan->blocks < 1)
+    return fail(HWY_EINVAL, "hwy_step_group_final: empty plan or NULL table");
+  if (hwy_launch_step_group_final((const StepParams*)table, (const FinalParams*)final_table,
+                                  plan->n, plan->blocks, plan->big, (hipStream_t)stream))
+    return hip_fail(hipGetLastError(), "hwy_step_grp_final_kernel");
+  return HWY_OK;
+}
+
 int hwy_export_state(hwy_handle* h, uint32_t* dst, void* stream) {
   if (!h || !dst) return fail(HWY_EINVAL, "handle/dst is NULL");
   size_t bytes = (size_t)HWY_NFIELDS * h->cfg.num_envs * HWY_MAX_VEHICLES * sizeof(uint32_t);
@@ -430,6 +509,18 @@ int hwy_gae(const float* rewards, const uint8_t* dones, const float* values,
   if (hwy_launch_gae(rewards, dones, values, last_values, gamma, lam, T, E, advantages, returns,
                      (hipStream_t)stream))
     return hip_fail(hipGetLastError(), "hwy_gae_kernel");
+  return HWY_OK;
+}
+
+int hwy_gae_boot(const float* rewards, const uint8_t* terminated, const uint8_t* truncated,
+                 const float* values, const float* last_values, const float* boot_values,
+                 double gamma, double lam, int T, int E, float* advantages, float* returns,
+                 void* stream) {
+  if (T < 0 || E < 0) return fail(HWY_EINVAL, "hwy_gae_boot: bad shape T=%d E=%d", T, E);
+  if (T == 0 || E == 0) return HWY_OK;
+  if (hwy_launch_gae_boot(rewards, terminated, truncated, values, last_values, boot_values, gamma,
+                          lam, T, E, advantages, returns, (hipStream_t)stream))
+    return hip_fail(hipGetLastError(), "hwy_gae_boot_kernel");
   return HWY_OK;
 }
 

@@ -30,6 +30,13 @@ struct StepParams {
 // the info kernels' second argument (solo) / second table's record (grouped): the ABI's struct
 typedef hwy_step_info InfoParams;
 
+// the final kernels' second argument / second table's record: the info pointers (all NULL when
+// the caller wants none) and the terminal observations' buffer [E, N, F_out]
+struct FinalParams {
+  InfoParams info;
+  float* final_obs;
+};
+
 extern "C" {
 int hwy_launch_step(const StepParams* p, hipStream_t s);
 // n handles' steps in one launch: dtab = n StepParams in device memory, blocks = the largest
@@ -39,6 +46,10 @@ int hwy_launch_step_group(const StepParams* dtab, int n, int blocks, int big, hi
 int hwy_launch_step_info(const StepParams* p, const InfoParams* info, hipStream_t s);
 int hwy_launch_step_group_info(const StepParams* dtab, const InfoParams* itab, int n, int blocks,
                                int big, hipStream_t s);
+// the final variants (their own unit): the info variants plus the terminal observation
+int hwy_launch_step_final(const StepParams* p, const FinalParams* f, hipStream_t s);
+int hwy_launch_step_group_final(const StepParams* dtab, const FinalParams* ftab, int n, int blocks,
+                                int big, hipStream_t s);
 int hwy_step_blocks(int num_envs);
 int hwy_step_big(int64_t total_envs);
 int hwy_launch_reset(const StepParams* p, hipStream_t s);
@@ -48,6 +59,9 @@ int hwy_launch_obs_pe(const float* in, float* out, int E, int N, int F, int kind
                       float max_dist, const float* table, const float* dov, hipStream_t s);
 int hwy_launch_gae(const float* rew, const uint8_t* done, const float* val, const float* last_val,
                    double gamma, double lam, int T, int E, float* adv, float* ret, hipStream_t s);
+int hwy_launch_gae_boot(const float* rew, const uint8_t* term, const uint8_t* trunc,
+                        const float* val, const float* last_val, const float* bootv, double gamma,
+                        double lam, int T, int E, float* adv, float* ret, hipStream_t s);
 int hwy_launch_math(int op, const float* in, const float* in2, float* out, int n, hipStream_t s);
 }
 #endif

@@ -1239,8 +1239,11 @@ __device__ void frame_wave(const hwy_config& C, int lane, Veh& v, float dt, floa
 // gridDim and no blockIdx.y, so a grouped launch computes every env exactly as its handle's own.
 // INFO (the info unit's kernels only, below): the ego's per-step info and the running episode
 // sums go to *I; everything inside `if constexpr (INFO)` is absent from the plain kernels.
-template <int W, bool INFO>
-__device__ __forceinline__ void step_body(const StepParams& P, const InfoParams* I) {
+// FINAL (the final unit's kernels only): the finished episode's last observation goes to
+// final_obs before the autoreset; absent from the plain and the info kernels likewise.
+template <int W, bool INFO, bool FINAL = false>
+__device__ __forceinline__ void step_body(const StepParams& P, const InfoParams* I,
+                                          [[maybe_unused]] float* final_obs = nullptr) {
   __shared__ int lds_vor[ENVS_PER_BLOCK][WAVE];
   __shared__ int lds_inv[ENVS_PER_BLOCK][WAVE];
   __shared__ CollLds lds_coll[ENVS_PER_BLOCK];
@@ -1389,6 +1392,15 @@ __device__ __forceinline__ void step_body(const StepParams& P, const InfoParams*
     }
   }
   SEC(sp, 11);
+  if constexpr (FINAL) {
+    // the terminal observation (gymnasium's final_observation): what an autoreset-off handle
+    // would observe here, from the pre-reset vehicles and this episode's step and seed.  done is
+    // wave-uniform and observe_wave's LDS rows are the wave's own, so no barrier is needed.
+    if (done && final_obs)
+      observe_wave(C, lane, v, cos_h, sin_h, step, seed, group_pe_table(P, e),
+                   final_obs + (size_t)e * C.obs_vehicles * P.fout, P.fout, lds_vor[w], lds_inv[w],
+                   lds_coll[w].imx);
+  }
   if (done && C.autoreset) {
     episode += 1;
     seed = episode_seed(P, e, episode);
@@ -1501,6 +1513,104 @@ extern "C" int hwy_launch_step_group_info(const StepParams* dtab, const InfoPara
   else
     hipLaunchKernelGGL(hwy_step_grp_info_kernel<4>, dim3(blocks, n), dim3(ENVS_PER_BLOCK * WAVE),
                        0, s, dtab, itab);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+#elif defined(HWY_FINAL_TU)
+// The final variants of the step kernels and hwy_gae_boot's kernel, likewise a unit of their own
+// (-DHWY_FINAL_TU -> hwy_final.o): step_body with INFO and FINAL on, the (nullable) info
+// pointers and the final observation's buffer a second argument (solo) or a second device table
+// (grouped).  Launch geometry and register budgets are the plain kernels'.
+template <int W>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
+hwy_step_final_kernel(StepParams P, FinalParams F) {
+  step_body<W, true, true>(P, &F.info, F.final_obs);
+}
+
+template <int W>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
+hwy_step_grp_final_kernel(const StepParams* __restrict__ tab,
+                          const FinalParams* __restrict__ ftab) {
+  const FinalParams* F = ftab + blockIdx.y;
+  step_body<W, true, true>(tab[blockIdx.y], &F->info, F->final_obs);
+}
+
+extern "C" int hwy_launch_step_final(const StepParams* p, const FinalParams* f, hipStream_t s) {
+  const int blocks = (p->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  if (hwy_step_big(p->cfg.num_envs))
+    hipLaunchKernelGGL(hwy_step_final_kernel<HWY_STEP_BIG_W>, dim3(blocks),
+                       dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p, *f);
+  else
+    hipLaunchKernelGGL(hwy_step_final_kernel<4>, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s,
+                       *p, *f);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int hwy_launch_step_group_final(const StepParams* dtab, const FinalParams* ftab, int n,
+                                           int blocks, int big, hipStream_t s) {
+  if (big)
+    hipLaunchKernelGGL(hwy_step_grp_final_kernel<HWY_STEP_BIG_W>, dim3(blocks, n),
+                       dim3(ENVS_PER_BLOCK * WAVE), 0, s, dtab, ftab);
+  else
+    hipLaunchKernelGGL(hwy_step_grp_final_kernel<4>, dim3(blocks, n), dim3(ENVS_PER_BLOCK * WAVE),
+                       0, s, dtab, ftab);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// hwy_gae_kernel with a bootstrap at truncation: a truncated, not terminated row takes
+// boot[i] = V(final observation) as its next-state value and the chain is cut there.  With no
+// such row every expression below is hwy_gae_kernel's, operation for operation.
+__global__ void __launch_bounds__(64) hwy_gae_boot_kernel(const float* __restrict__ rew,
+                                                           const uint8_t* __restrict__ term,
+                                                           const uint8_t* __restrict__ trunc,
+                                                           const float* __restrict__ val,
+                                                           const float* __restrict__ last_val,
+                                                           const float* __restrict__ bootv,
+                                                           double gamma, double lam, int T, int E,
+                                                           float* __restrict__ adv,
+                                                           float* __restrict__ ret) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  const double gl = gamma * lam;
+  float last_adv = 0.0f;
+  double v1 = (double)last_val[e];
+  constexpr int kGaeAhead = 8;  // as hwy_gae_kernel: the loads of 8 steps go ahead of their use
+  for (int t1 = T; t1 > 0; t1 -= kGaeAhead) {
+    float rv[kGaeAhead], vv[kGaeAhead], bv[kGaeAhead];
+    uint8_t tm[kGaeAhead], tr[kGaeAhead];
+#pragma unroll
+    for (int j = 0; j < kGaeAhead; ++j) {
+      const int t = t1 - 1 - j;
+      const size_t i = (size_t)(t < 0 ? 0 : t) * E + e;
+      rv[j] = rew[i], vv[j] = val[i], bv[j] = bootv[i], tm[j] = term[i], tr[j] = trunc[i];
+    }
+#pragma unroll
+    for (int j = 0; j < kGaeAhead; ++j) {
+      const int t = t1 - 1 - j;
+      if (t < 0) break;
+      const size_t i = (size_t)t * E + e;
+      const float v0f = vv[j];
+      const bool done = tm[j] | tr[j];
+      const bool boot = tr[j] && !tm[j];
+      const double vsel = boot ? (double)bv[j] : v1;
+      const double m = (done && !boot) ? 0.0 : 1.0;
+      const double nd = done ? 0.0 : 1.0;
+      const double delta = ((double)rv[j] + (gamma * vsel) * m) - (double)v0f;
+      const float a = (float)(delta + (gl * nd) * (double)last_adv);
+      adv[i] = a;
+      ret[i] = a + v0f;
+      last_adv = a;
+      v1 = (double)v0f;
+    }
+  }
+}
+
+extern "C" int hwy_launch_gae_boot(const float* rew, const uint8_t* term, const uint8_t* trunc,
+                                   const float* val, const float* last_val, const float* bootv,
+                                   double gamma, double lam, int T, int E, float* adv, float* ret,
+                                   hipStream_t s) {
+  if (E == 0) return 0;
+  const int blocks = (E + 63) / 64;
+  hipLaunchKernelGGL(hwy_gae_boot_kernel, dim3(blocks), dim3(64), 0, s, rew, term, trunc, val,
+                     last_val, bootv, gamma, lam, T, E, adv, ret);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 #else  // the main unit, to the end of the file
@@ -1742,4 +1852,4 @@ extern "C" int hwy_debug_sections(unsigned long long* out, int reset) {
   return 0;
 }
 #endif
-#endif  // HWY_CUT_TU / HWY_INFO_TU
+#endif  // HWY_CUT_TU / HWY_INFO_TU / HWY_FINAL_TU

@@ -1,6 +1,14 @@
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int row0 = blockIdx.x * kRowTile;
   const int nrows = min(kRowTile, r.B - row0);
+#ifdef HWY_PPO_VMASK_TU
+  // hwy_ppo_value_masked: a tile without a marked row stores zeros before any weight is read
+  const uint64_t vmask = vmask_tile(r, row0, nrows, lane);
+  if (!vmask) {
+    if (t < nrows) r.value[row0 + t] = 0.0f;
+    return;
+  }
+#endif
   const float* P = r.params;
   constexpr int TW = H_TW(QH, NW);
   constexpr int D = ring_depth<TW>();
@@ -45,6 +53,10 @@
     }
     const float mu0 = wave_sum_dpp(p0) + ba0, mu1 = wave_sum_dpp(p1) + ba1,
                 val = wave_sum_dpp(pv) + bcv;
+#ifdef HWY_PPO_VMASK_TU
+    if (lane == 0) r.value[b] = ((vmask >> lr) & 1ull) ? val : 0.0f;
+    (void)mu0, (void)mu1, (void)var0, (void)var1, (void)lsc0, (void)lsc1, (void)LOG_SQRT_2PI;
+#else
     if (lane == 0) {
       float z0 = mu0, z1 = mu1, lp = 0.0f;
       if (r.noise) {
@@ -63,4 +75,5 @@
       r.logp[b] = lp;
       r.value[b] = val;
     }
+#endif
   }

@@ -3,6 +3,14 @@
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int row0 = blockIdx.x * RT;
   const int nrows = min(RT, r.B - row0);
+#ifdef HWY_PPO_VMASK_TU
+  // hwy_ppo_value_masked: a tile without a marked row stores zeros before any weight is read
+  const uint64_t vmask = vmask_tile(r, row0, nrows, lane);
+  if (!vmask) {
+    if (t < nrows) r.value[row0 + t] = 0.0f;
+    return;
+  }
+#endif
   const float* P = r.params;
   constexpr int D = kRingDC;
   WRing<TW, D, 4, true, true> R;
@@ -54,6 +62,10 @@
   f32x4 dsum = HDOT[0][hr];
 #pragma unroll
   for (int ww = 1; ww < NW; ++ww) dsum += HDOT[ww][hr];
+#ifdef HWY_PPO_VMASK_TU
+  r.value[b] = ((vmask >> hr) & 1ull) ? dsum[2] + bcv : 0.0f;
+  (void)ba0, (void)ba1, (void)ls0, (void)ls1, (void)n0, (void)n1;
+#else
   const float mu0 = dsum[0] + ba0, mu1 = dsum[1] + ba1, val = dsum[2] + bcv;
   float z0 = mu0, z1 = mu1, lp = 0.0f;
   if (r.noise) {
@@ -76,3 +88,4 @@
   r.pre_tanh[2 * b + 1] = z1;
   r.logp[b] = lp;
   r.value[b] = val;
+#endif

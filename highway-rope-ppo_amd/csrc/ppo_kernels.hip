@@ -19,7 +19,7 @@
 // head kernel (ppo_head), split-K partial slabs and one deterministic reduction (ppo_reduce).
 // All GEMMs use v_mfma_f32_*_f32: exact fp32 products, fp32 accumulation.
 //
-// This file is compiled three times (Makefile).  ppo_kernels.o holds everything but the mixed-width
+// This file is compiled four times (Makefile).  ppo_kernels.o holds everything but the mixed-width
 // and scheduled grouped kernels and their entry points (hwy_ppo_mixed_*, hwy_ppo_sched_*);
 // ppo_mixed.o, compiled with -DHWY_PPO_MIXED_TU, holds only those; ppo_wide.o, compiled with
 // -DHWY_PPO_WIDE_TU, holds only the row / act kernels for S > 256 (solo, grouped, mixed and
@@ -29,7 +29,8 @@
 // beside them 27 of the 57 row / act kernels changed their VGPR counts, their source untouched):
 // in a unit of their own the mixed kernels leave every other kernel's registers, LDS and
 // occupancy as they were (profiles/r7/mixed/), and so do the wide ones
-// (profiles/r9/wide/).
+// (profiles/r9/wide/).  ppo_vmask.o, compiled with -DHWY_PPO_VMASK_TU, holds only the act kernels
+// with the masked value store and their entry point (hwy_ppo_value_masked).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -1509,7 +1510,26 @@ struct ActArgs {
   const float* noise;  // [B][2] standard normal, or null
   float *action, *pre_tanh, *logp, *value;
   const float* tiles;  // weight tile image in step with params (TL), else null
+#ifdef HWY_PPO_VMASK_TU
+  // hwy_ppo_value_masked (the masked-value unit only): row b is marked iff
+  // vm_trunc[b] && !(vm_term && vm_term[b]); only value is stored, 0 for unmarked rows
+  const uint8_t *vm_trunc, *vm_term;
+#endif
 };
+
+#ifdef HWY_PPO_VMASK_TU
+// The marks of a workgroup's rows row0 .. row0 + nrows - 1 (nrows <= 32) as bits, read by every
+// wave for itself (lane l reads row l's flags), so the result is uniform over the workgroup
+// without a barrier.
+__device__ __forceinline__ uint64_t vmask_tile(const ActArgs& r, int row0, int nrows, int lane) {
+  bool mk = false;
+  if (lane < nrows) {
+    const long b = row0 + lane;
+    mk = r.vm_trunc[b] != 0 && !(r.vm_term && r.vm_term[b] != 0);
+  }
+  return __ballot(mk);
+}
+#endif
 
 template <int QH, int NW, bool TL, bool WIDE = false>
 __device__ __forceinline__ void act_body(ActArgs r) {
@@ -2775,7 +2795,73 @@ HWY_LOCAL int hwy_ppo_wide_act_mix(int cls, int tiles, int B, int G, int lds, co
 // narrow kernels; false on a HIP error
 HWY_LOCAL bool hwy_ppo_wide_raise_lds(int kind, int cls, int tiles);
 
-#ifdef HWY_PPO_WIDE_TU
+#ifdef HWY_PPO_VMASK_TU
+// ----------------------------------------------------------------------------- masked values
+// hwy_ppo_value_masked: the act bodies with the masked store (ppo_act_body.inc /
+// ppo_act_c_body.inc under HWY_PPO_VMASK_TU) -- a tile without a marked row stores zeros and
+// returns before any weight is read, every other tile runs hwy_ppo_act's body for its dims.
+template <int QH, int NW, bool TL, bool WIDE>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_vmask(ActArgs r) {
+  act_body<QH, NW, TL, WIDE>(r);
+}
+
+template <int RT, bool WIDE>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8)))
+ppo_vmask_c(ActArgs r) {
+  act_c_body<4, 8, RT, WIDE>(r);
+}
+
+extern "C" int hwy_ppo_value_masked(const hwy_ppo_act_args* a, const uint8_t* truncated,
+                                    const uint8_t* terminated, void* stream) {
+  if (!a || !a->states || !a->params || !a->value || !truncated || a->noise) return -1;
+  const hwy_ppo_dims& d = a->dims;
+  if (!fused_ok(d) || d.A != 2 || d.B < 1) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const Layout L = make_layout(d);
+  ActArgs r = {};
+  r.B = d.B, r.S = d.S, r.states = a->states, r.params = a->params, r.noise = nullptr;
+  for (int i = 0; i < 13; ++i) r.off[i] = L.off[i];
+  r.value = a->value;
+  r.tiles = a->tiles;
+  r.vm_trunc = truncated, r.vm_term = terminated;
+  const dim3 g((d.B + kRowTile - 1) / kRowTile), b4(256), b8(512);
+  auto launch = [&](auto tl, auto wd) {
+    constexpr bool TL = decltype(tl)::value, WD = decltype(wd)::value;
+    switch (d.H / 64) {
+      case 1: hipLaunchKernelGGL((ppo_vmask<1, 4, TL, WD>), g, b4, 0, s, r); break;
+      case 2: hipLaunchKernelGGL((ppo_vmask<2, 8, TL, WD>), g, b8, 0, s, r); break;
+      case 3: hipLaunchKernelGGL((ppo_vmask<3, 4, TL, WD>), g, b4, 0, s, r); break;
+      case 4: hipLaunchKernelGGL((ppo_vmask<4, 8, TL, WD>), g, b8, 0, s, r); break;
+      case 5: hipLaunchKernelGGL((ppo_vmask<5, 4, TL, WD>), g, b4, 0, s, r); break;
+      case 6: hipLaunchKernelGGL((ppo_vmask<6, 8, TL, WD>), g, b8, 0, s, r); break;
+      case 7: hipLaunchKernelGGL((ppo_vmask<7, 4, TL, WD>), g, b4, 0, s, r); break;
+      default: hipLaunchKernelGGL((ppo_vmask<8, 8, TL, WD>), g, b8, 0, s, r); break;
+    }
+  };
+  using T = std::integral_constant<bool, true>;
+  using F = std::integral_constant<bool, false>;
+  // hwy_ppo_act's kernel choice (and hwy_ppo_wide_act's past kMaxRowS), so a marked row's value
+  // is the bits acting computes for it
+  if (wide_s(d.S)) {
+    if (r.tiles && d.H == 256)
+      hipLaunchKernelGGL((ppo_vmask_c<kRowTile, true>), g, b8, 0, s, r);
+    else if (r.tiles)
+      launch(T(), T());
+    else
+      launch(F(), T());
+  } else if (r.tiles && d.H == 256) {
+    if (d.B >= 64 * chip_geom().cus)
+      hipLaunchKernelGGL((ppo_vmask_c<32, false>), dim3((d.B + 31) / 32), b8, 0, s, r);
+    else
+      hipLaunchKernelGGL((ppo_vmask_c<16, false>), dim3((d.B + 15) / 16), b8, 0, s, r);
+  } else if (r.tiles)
+    launch(T(), F());
+  else
+    launch(F(), F());
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+#elif defined(HWY_PPO_WIDE_TU)
 static int wide_rc() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
 int hwy_ppo_wide_rows(const void* row_args, int H, int grid, hipStream_t s) {

@@ -8,7 +8,10 @@ train_with_experiment_name -> {"status": "COMPLETED"|"FAILED", ...}.  Experiment
 boundary and evaluations ahead of the update, training/routine.py; with it ``num_envs`` 1 runs
 the vectorised loop on a one-env HighwayVecEnv, which is the reference's own episode stream)
 and ``episode_stats`` (True: per-episode lengths, crashes, mean speeds and lane changes in the
-metrics and a crash rate in the summary, training/routine.py; vectorised loop only).
+metrics and a crash rate in the summary, training/routine.py; vectorised loop only) and
+``truncation`` ("terminal", the default and the reference's behaviour, or "bootstrap": GAE takes
+V(final observation) at a time limit, ppo/rollout.py; launch() on the vectorised loop only --
+a process group, launch_group and launch_batch refuse it).
 
 Launched under torchrun (WORLD_SIZE > 1) one experiment spans the ranks, one GPU each: the
 runner joins the process group (RCCL, or ``HWY_DIST_BACKEND``), gives rank r the envs
@@ -132,6 +135,14 @@ class ExperimentRunner:
                         overrides.setdefault("vector_env", True)
                     stats_kw = ({"episode_stats": True} if exp.extra.get("episode_stats")
                                 else {})
+                    from ppo.rollout import check_truncation
+
+                    truncation = check_truncation(exp.extra.get("truncation", "terminal"))
+                    if truncation != "terminal":
+                        if group is not None:
+                            raise ValueError("extra['truncation']='bootstrap' does not run over "
+                                             "a process group")
+                        stats_kw["truncation"] = truncation
                     if group is not None:
                         e = int(overrides.get("num_envs", 1))
                         if e <= 1:
@@ -208,7 +219,14 @@ class ExperimentRunner:
         import math
 
         from ppo.agent import PPOAgent
-        from ppo.rollout import check_episode_schedule
+        from ppo.rollout import check_episode_schedule, check_truncation
+
+        for exps in cells:
+            for e in exps:
+                if check_truncation(e.extra.get("truncation", "terminal")) != "terminal":
+                    raise ValueError(f"launch_group / launch_batch: extra['truncation']="
+                                     f"{e.extra['truncation']!r} is not supported by the grouped "
+                                     f"launches (experiment {e.name}); use launch()")
 
         def episode_schedule(e):
             return check_episode_schedule(e.extra.get("episode_schedule", "lockstep"))

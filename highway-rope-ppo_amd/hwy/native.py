@@ -81,6 +81,13 @@ def lib():
     L.hwy_step_group_info_prepare.argtypes = [vp, vp, vp, i32, vp, vp,
                                               ctypes.POINTER(HwyStepGroupPlan), vp]
     L.hwy_step_group_info.argtypes = [ctypes.POINTER(HwyStepGroupPlan), vp, vp, vp]
+    L.hwy_step_with_final.argtypes = [vp] * 8 + [ctypes.POINTER(HwyStepInfo), vp, vp]
+    L.hwy_step_group_final_table_bytes.argtypes = [i32]
+    L.hwy_step_group_final_table_bytes.restype = ctypes.c_int64
+    L.hwy_step_group_final_prepare.argtypes = [vp, vp, vp, vp, i32, vp, vp,
+                                               ctypes.POINTER(HwyStepGroupPlan), vp]
+    L.hwy_step_group_final.argtypes = [ctypes.POINTER(HwyStepGroupPlan), vp, vp, vp]
+    L.hwy_gae_boot.argtypes = [vp, vp, vp, vp, vp, vp, f64, f64, i32, i32, vp, vp, vp]
     L.hwy_export_state.argtypes = [vp, vp, vp]
     L.hwy_import_state.argtypes = [vp, vp, vp]
     L.hwy_obs_pe.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp]
@@ -95,7 +102,8 @@ def lib():
                  "hwy_set_seed_groups", "hwy_reset", "hwy_step", "hwy_cut_episodes",
                  "hwy_step_group_prepare",
                  "hwy_step_group", "hwy_step_with_info", "hwy_step_group_info_prepare",
-                 "hwy_step_group_info",
+                 "hwy_step_group_info", "hwy_step_with_final", "hwy_step_group_final_prepare",
+                 "hwy_step_group_final", "hwy_gae_boot",
                  "hwy_export_state", "hwy_import_state", "hwy_obs_pe", "hwy_gae",
                  "hwy_math_selftest"):
         getattr(L, name).restype = i32

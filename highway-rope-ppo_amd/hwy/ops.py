@@ -13,7 +13,7 @@ import torch
 from ._abi import PE_APPENDS, PE_DIST, PE_DIST1, PE_NONE, PE_RANK, PE_ROPE
 from .native import check, lib, ptr, require_device, stream_ptr
 
-__all__ = ["obs_pe", "gae", "math_selftest", "PE_NONE", "PE_RANK", "PE_DIST", "PE_ROPE", "PE_DIST1"]
+__all__ = ["obs_pe", "gae", "gae_boot", "math_selftest", "PE_NONE", "PE_RANK", "PE_DIST", "PE_ROPE", "PE_DIST1"]
 
 
 def obs_pe(obs: torch.Tensor, kind: int, d: int, ego_idx: int = 0, max_dist: float = 100.0,
@@ -60,6 +60,40 @@ def gae(rewards: torch.Tensor, dones: torch.Tensor, values: torch.Tensor,
                         ptr(values.float().contiguous()), ptr(last_values.float().contiguous()),
                         float(gamma), float(lam), T, E, ptr(adv), ptr(ret), stream_ptr()),
           "hwy_gae")
+    return adv, ret
+
+
+def gae_boot(rewards: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor,
+             values: torch.Tensor, last_values: torch.Tensor, boot_values: torch.Tensor,
+             gamma: float, lam: float,
+             out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gae() with a bootstrap at truncation (hwy_gae_boot): a truncated, not terminated row takes
+    ``boot_values`` (V of the episode's final observation) as its next-state value and the chain
+    is cut there.  Every array is [T, E]; without such a row the bits are gae()'s on
+    ``dones = terminated | truncated``."""
+    for t, n in ((rewards, "rewards"), (terminated, "terminated"), (truncated, "truncated"),
+                 (values, "values"), (last_values, "last_values"), (boot_values, "boot_values")):
+        require_device(t, n)
+    T, E = rewards.shape
+    for t, n in ((terminated, "terminated"), (truncated, "truncated"), (values, "values"),
+                 (boot_values, "boot_values")):
+        if tuple(t.shape) != (T, E):
+            raise ValueError(f"gae_boot: {n} must be [{T}, {E}], got {tuple(t.shape)}")
+    if terminated.dtype != torch.uint8:
+        terminated = terminated.to(torch.uint8)
+    if truncated.dtype != torch.uint8:
+        truncated = truncated.to(torch.uint8)
+    if out is None:
+        adv = torch.empty(T, E, device=rewards.device, dtype=torch.float32)
+        ret = torch.empty_like(adv)
+    else:
+        adv, ret = out
+    check(lib().hwy_gae_boot(ptr(rewards.float().contiguous()), ptr(terminated.contiguous()),
+                             ptr(truncated.contiguous()), ptr(values.float().contiguous()),
+                             ptr(last_values.float().contiguous()),
+                             ptr(boot_values.float().contiguous()), float(gamma), float(lam), T, E,
+                             ptr(adv), ptr(ret), stream_ptr()), "hwy_gae_boot")
     return adv, ret
 
 

@@ -73,6 +73,9 @@ def _bind(L):
     L.hwy_ppo_sync_params.restype = ctypes.c_int
     L.hwy_ppo_act.argtypes = [ctypes.POINTER(PpoActArgs), ctypes.c_void_p]
     L.hwy_ppo_act.restype = ctypes.c_int
+    L.hwy_ppo_value_masked.argtypes = [ctypes.POINTER(PpoActArgs), ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p]
+    L.hwy_ppo_value_masked.restype = ctypes.c_int
     L.hwy_ppo_time_kernels.argtypes = [ctypes.POINTER(PpoArgs), ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_void_p]
     L.hwy_ppo_time_kernels.restype = ctypes.c_int
@@ -293,6 +296,38 @@ def fused_act(agent, states: torch.Tensor, deterministic: bool = False,
     a.tiles = act_tiles(agent, flat, S, H)
     check(_bind(lib()).hwy_ppo_act(ctypes.byref(a), stream_ptr()), "hwy_ppo_act")
     return action, pre, logp, value
+
+
+def fused_value_masked(agent, states: torch.Tensor, truncated: torch.Tensor,
+                       terminated: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The critic's value of the rows with ``truncated & ~terminated`` and exactly 0 elsewhere
+    (hwy_ppo_value_masked): fused_act(deterministic=True)'s value bits on the marked rows, from
+    one launch whose tiles without a marked row read no weight.  ``truncated`` / ``terminated``:
+    contiguous uint8 (B,) device tensors; ``out``: a contiguous float32 (B,) tensor to write."""
+    flat = flat_params(agent)[0]
+    B, S = states.shape
+    H = agent.actor_critic.shared[0].weight.shape[0]
+    dev = states.device
+    states = states.contiguous()
+    for t, n in ((truncated, "truncated"), (terminated, "terminated")):
+        if t is not None and (tuple(t.shape) != (B,) or t.dtype != torch.uint8 or t.device != dev
+                              or not t.is_contiguous()):
+            raise ValueError(f"fused_value_masked {n} must be contiguous uint8 {(B,)} on {dev}")
+    if out is None:
+        out = torch.empty(B, device=dev)
+    elif (tuple(out.shape) != (B,) or out.dtype != torch.float32 or out.device != dev
+          or not out.is_contiguous()):
+        raise ValueError(f"fused_value_masked out must be contiguous float32 {(B,)} on {dev}")
+    a = PpoActArgs()
+    a.dims = PpoDims(B, S, H, 2)
+    a.states, a.params = states.data_ptr(), flat.data_ptr()
+    a.value = out.data_ptr()
+    a.tiles = act_tiles(agent, flat, S, H)
+    check(_bind(lib()).hwy_ppo_value_masked(ctypes.byref(a), truncated.data_ptr(),
+                                            None if terminated is None else terminated.data_ptr(),
+                                            stream_ptr()), "hwy_ppo_value_masked")
+    return out
 
 
 class FusedPPO:

@@ -18,6 +18,12 @@ of the four unweighted terms) -- and ``info["episode_stats"]`` ([E, 8]: where an
 its sums of speed and of the four terms, its lane-change count and its crashed flag; the slots
 are _abi.ACC_*).  The step then runs the info variant of the kernel (hwy_step_with_info), which
 computes the same step and stores these besides.
+
+``final_obs=True`` completes the autoreset contract: ``info["final_observation"]`` ([E, N, F_out])
+holds, where ``info["_final_observation"]`` (= terminated | truncated) is set, the last observation
+of the episode that just finished -- the row the in-kernel reset overwrote in ``obs``.  Other rows
+keep what an earlier step wrote there.  The step then runs the final variant of the kernel
+(hwy_step_with_final), with the info outputs too when ``info=True``.
 """
 
 from __future__ import annotations
@@ -58,6 +64,14 @@ def _info_ptrs(info: Dict[str, Any]) -> tuple:
     return tuple(ptr(info.get(n)) for n in INFO_FIELDS)
 
 
+def _check_final_obs(env, t: torch.Tensor) -> None:
+    """A terminal-observation buffer of ``env``: E x N x F_out contiguous float32 on its device."""
+    n = env.num_envs * env.obs_rows * env.obs_features
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+        raise ValueError(f"final_obs must be a contiguous float32 device tensor of {n} elements "
+                         f"(E x N x F_out), got {tuple(t.shape)} {t.dtype} on {t.device}")
+
+
 class HighwayVecEnv:
     """E lockstep highway-v0 envs with state resident in HBM (one wavefront per env)."""
 
@@ -67,7 +81,8 @@ class HighwayVecEnv:
                  device: Optional[torch.device] = None, autoreset: bool = True,
                  seed_base: int = 0, env_offset: int = 0, global_envs: Optional[int] = None,
                  pe_kind: int = PE_NONE, d_embed: int = 0, pe_table: Optional[np.ndarray] = None,
-                 ego_idx: int = 0, pe_max_dist: float = 100.0, info: bool = False):
+                 ego_idx: int = 0, pe_max_dist: float = 100.0, info: bool = False,
+                 final_obs: bool = False):
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         device = torch.device(device)
@@ -86,6 +101,7 @@ class HighwayVecEnv:
                                      pe_kind=pe_kind, d_embed=d_embed, ego_idx=ego_idx,
                                      pe_max_dist=pe_max_dist)
         self._pe_table = None if pe_table is None else np.ascontiguousarray(pe_table, np.float32)
+        self._final_obs = bool(final_obs)
         self._create()
         self._alloc_buffers()
         # the opt-in step info: buffers owned by the env (None: step() is the plain hwy_step)
@@ -119,6 +135,9 @@ class HighwayVecEnv:
         self.trunc_buf = torch.zeros(E, dtype=torch.uint8, **kw)
         self.ep_ret_buf = torch.zeros(E, dtype=torch.float32, **kw)
         self.ep_len_buf = torch.zeros(E, dtype=torch.int32, **kw)
+        # the opt-in terminal observations (None: step() never runs the final variant)
+        self.final_obs_buf = (torch.zeros(E, N, Fo, dtype=torch.float32, **kw)
+                              if getattr(self, "_final_obs", False) else None)
 
     def _set_obs_space(self):
         N, Fo = self.obs_rows, self.obs_features
@@ -203,6 +222,8 @@ class HighwayVecEnv:
             a = torch.as_tensor(a, device=self.device, dtype=torch.float32).contiguous()
         if a.numel() != 2 * self.num_envs:
             raise ValueError(f"actions must have {self.num_envs}x2 elements, got {tuple(a.shape)}")
+        if self.final_obs_buf is not None:
+            return self._step_final(a)
         if self.info_buf is not None:
             return self._step_info(a)
         check(lib().hwy_step(self._handle, ptr(a), ptr(self.obs_buf), ptr(self.reward_buf),
@@ -223,14 +244,42 @@ class HighwayVecEnv:
                 "episode_stats": b["ep_stats"]}
         return self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf, info
 
+    def _step_final(self, a: torch.Tensor):
+        b = self.info_buf
+        self.step_into(a, self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf,
+                       self.ep_ret_buf, self.ep_len_buf, info=b, final_obs=self.final_obs_buf)
+        self._keep = a
+        info = {"episode_return": self.ep_ret_buf, "episode_length": self.ep_len_buf,
+                "final_observation": self.final_obs_buf,
+                "_final_observation": (self.term_buf | self.trunc_buf).bool()}
+        if b is not None:
+            info.update({"speed": b["speed"], "crashed": b["crashed"], "lane": b["lane"],
+                         "rewards": {k: b["rewards"][:, i] for i, k in enumerate(REWARD_KEYS)},
+                         "episode_stats": b["ep_stats"]})
+        return self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf, info
+
     def step_into(self, actions: torch.Tensor, obs: torch.Tensor, reward: torch.Tensor,
                   terminated: torch.Tensor, truncated: torch.Tensor,
                   ep_return: Optional[torch.Tensor] = None,
                   ep_length: Optional[torch.Tensor] = None,
-                  info: Optional[Dict[str, torch.Tensor]] = None) -> None:
+                  info: Optional[Dict[str, torch.Tensor]] = None,
+                  final_obs: Optional[torch.Tensor] = None) -> None:
         """step() writing straight into caller-owned rollout slices (no copies; graph-safe).
         ``info``: caller-owned tensors for hwy_step_with_info's outputs, keyed by hwy_step_info's
-        fields (alloc_step_info's layout; any subset, "ep_stats" needs "acc")."""
+        fields (alloc_step_info's layout; any subset, "ep_stats" needs "acc").
+        ``final_obs``: a caller-owned contiguous float32 buffer of E x N x F_out floats for the
+        terminal observations of the envs that finish in this step (hwy_step_with_final; rows of
+        the other envs are not written); combines with ``info``."""
+        if final_obs is not None:
+            _check_final_obs(self, final_obs)
+            si = None if info is None else HwyStepInfo(*_info_ptrs(info))
+            check(lib().hwy_step_with_final(self._handle, ptr(actions), ptr(obs), ptr(reward),
+                                            ptr(terminated), ptr(truncated), ptr(ep_return),
+                                            ptr(ep_length),
+                                            None if si is None else ctypes.byref(si),
+                                            ptr(final_obs), stream_ptr()),
+                  "hwy_step_with_final")
+            return
         if info is not None:
             si = HwyStepInfo(*_info_ptrs(info))
             check(lib().hwy_step_with_info(self._handle, ptr(actions), ptr(obs), ptr(reward),
@@ -357,12 +406,47 @@ class GroupEnvStep:
         check(lib().hwy_step_group_info(ctypes.byref(hit[1]), hit[0].data_ptr(),
                                         hit[2].data_ptr(), stream_ptr()), "hwy_step_group_info")
 
-    def launch(self, ios, infos=None) -> None:
+    def _launch_final(self, ptrs, infos, final_obs) -> None:
+        """launch() through hwy_step_group_final: a second device table holds the (optional) info
+        pointers and the terminal-observation buffers."""
+        if len(final_obs) != self.n or (infos is not None and len(infos) != self.n):
+            raise ValueError("one final_obs buffer (and one step info dict) per handle")
+        for e, f in zip(self.envs, final_obs):
+            _check_final_obs(e, f)
+        iptrs = None if infos is None else tuple(_info_ptrs(i) for i in infos)
+        fptrs = tuple(ptr(f) for f in final_obs)
+        key = (tuple((e._handle.value, e.launch_version) for e in self.envs), ptrs, iptrs, fptrs,
+               "final")
+        hit = self._tables.get(key)
+        if hit is None:
+            arr = (HwyStepIO * self.n)(*[HwyStepIO(*p) for p in ptrs])
+            iarr = (None if iptrs is None
+                    else (HwyStepInfo * self.n)(*[HwyStepInfo(*p) for p in iptrs]))
+            farr = (ctypes.c_void_p * self.n)(*fptrs)
+            hs = (ctypes.c_void_p * self.n)(*[e._handle.value for e in self.envs])
+            dev = self.envs[0].device
+            t = torch.empty(self._nb, dtype=torch.uint8, device=dev)
+            ft = torch.empty(int(lib().hwy_step_group_final_table_bytes(self.n)),
+                             dtype=torch.uint8, device=dev)
+            plan = HwyStepGroupPlan()
+            check(lib().hwy_step_group_final_prepare(hs, arr, iarr, farr, self.n, t.data_ptr(),
+                                                     ft.data_ptr(), ctypes.byref(plan),
+                                                     stream_ptr()), "hwy_step_group_final_prepare")
+            hit = (t, plan, ft)
+            self._tables[key] = hit
+        check(lib().hwy_step_group_final(ctypes.byref(hit[1]), hit[0].data_ptr(),
+                                         hit[2].data_ptr(), stream_ptr()), "hwy_step_group_final")
+
+    def launch(self, ios, infos=None, final_obs=None) -> None:
         """ios[i] = (actions, obs, reward, terminated, truncated, ep_return, ep_length) of env i,
         as step_into takes them (the last two may be None).  ``infos[i]``: env i's step info
         tensors as step_into's ``info`` (one dict per handle; the launch is then the info
-        variant, hwy_step_group_info)."""
+        variant, hwy_step_group_info).  ``final_obs[i]``: env i's terminal-observation buffer as
+        step_into's ``final_obs`` (the launch is then the final variant, hwy_step_group_final,
+        with the info outputs too when ``infos`` is given)."""
         ptrs = tuple(tuple(ptr(x) for x in io) for io in ios)
+        if final_obs is not None:
+            return self._launch_final(ptrs, infos, final_obs)
         if infos is not None:
             if len(infos) != self.n:
                 raise ValueError("one step info dict per handle")

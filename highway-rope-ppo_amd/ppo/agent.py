@@ -169,10 +169,15 @@ class RolloutBuffer:
 
     ``episode_stats``: also ``ep_stats`` [T, E, 8] (hwy_step_with_info's per-episode sums where an
     episode finished, 0 elsewhere) and ``acc`` [E, 8] (the running sums of the current episodes,
-    carried from rollout to rollout); the rollout then issues the info variant of the step."""
+    carried from rollout to rollout); the rollout then issues the info variant of the step.
+
+    ``truncation_bootstrap``: also ``final_obs`` [E, S] (the terminal observations of the envs
+    that finished in the current step; one row set, reused every step) and ``boot_values`` [T, E]
+    (V(final observation) at the truncated, not terminated rows, 0 elsewhere), which
+    PPOAgent.update_rollout feeds to ops.gae_boot (LockstepRollout(truncation="bootstrap"))."""
 
     def __init__(self, T: int, E: int, state_dim: int, action_dim: int, device: torch.device,
-                 episode_stats: bool = False):
+                 episode_stats: bool = False, truncation_bootstrap: bool = False):
         kw = dict(device=device, dtype=torch.float32)
         self.T, self.E, self.state_dim = T, E, state_dim
         self.states = torch.zeros(T + 1, E, state_dim, **kw)  # row T = bootstrap obs
@@ -193,6 +198,10 @@ class RolloutBuffer:
 
             self.ep_stats = torch.zeros(T, E, HWY_INFO_NACC, **kw)
             self.acc = torch.zeros(E, HWY_INFO_NACC, **kw)
+        self.final_obs = self.boot_values = None
+        if truncation_bootstrap:
+            self.final_obs = torch.zeros(E, state_dim, **kw)
+            self.boot_values = torch.zeros(T, E, **kw)
 
     @property
     def n(self) -> int:
@@ -462,6 +471,27 @@ class PPOAgent:
         with torch.no_grad():
             return self.actor_critic.forward(states)[2].squeeze(-1)
 
+    def value_masked(self, states: torch.Tensor, truncated: torch.Tensor,
+                     terminated: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """V(s) at the rows with ``truncated & ~terminated`` and exactly 0 elsewhere (the
+        bootstrap values of a time limit): hwy_ppo_value_masked when acting is fused -- tiles
+        without such a row read no weight -- else the torch forward under torch.where."""
+        if self._act_fused_ok(states):
+            from hwy.ppo_native import fused_value_masked
+
+            return fused_value_masked(self, states, truncated, terminated, out=out)
+        with torch.no_grad():
+            v = self.actor_critic.forward(states)[2].squeeze(-1)
+            mark = truncated.bool()
+            if terminated is not None:
+                mark = mark & ~terminated.bool()
+            res = torch.where(mark, v, torch.zeros_like(v))
+        if out is None:
+            return res
+        out.copy_(res)
+        return out
+
     def _act_fused_ok(self, state: torch.Tensor) -> bool:
         """Batched acting runs through hwy_ppo_act (one launch) unless backend='torch'."""
         if self.backend == "torch" or not state.is_cuda:
@@ -583,7 +613,13 @@ class PPOAgent:
         from hwy import ops
 
         T, E = buf.T, buf.E
-        adv, ret = ops.gae(buf.rewards, buf.dones, buf.values, last_values, self.gamma, self.lam)
+        if getattr(buf, "boot_values", None) is not None:
+            # bootstrap at truncation: V(final observation) instead of 0 at a time limit
+            adv, ret = ops.gae_boot(buf.rewards, buf.terminated, buf.truncated, buf.values,
+                                    last_values, buf.boot_values, self.gamma, self.lam)
+        else:
+            adv, ret = ops.gae(buf.rewards, buf.dones, buf.values, last_values, self.gamma,
+                               self.lam)
         n = T * E
         states = buf.states[:T].reshape(n, -1)
         pre_tanh = buf.pre_tanh.reshape(n, -1)

@@ -18,6 +18,13 @@ partial returns in ``cut_return``.  The cut step's ``dones`` stays 0, so GAE boo
 V(states[T]).  The next rollout starts from ``next0`` (``start_next``).  A reference rollout of
 T > REFERENCE_GRAPH_CHUNK steps is issued as fixed chunk graphs of that many steps (the buffers
 are static, so each chunk replays) instead of one graph of 2T launches.
+
+``truncation="bootstrap"`` (default ``"terminal"``: a time limit is booked as terminal, as the
+reference does, training/routine.py:135): step t runs the final variant of the env step, which
+also writes the terminal observations of the envs that finished to ``buf.final_obs``, and then
+``agent.value_masked`` stores V(final observation) of the truncated, not terminated rows in
+``buf.boot_values[t]`` (0 elsewhere) with the weights that produced ``values[t]``.  Both launches
+are part of the captured graph; PPOAgent.update_rollout then runs hwy_gae_boot.
 """
 
 from __future__ import annotations
@@ -29,6 +36,7 @@ import torch
 from utils.graphs import run_or_replay, run_or_replay_chunks
 
 EPISODE_SCHEDULES = ("lockstep", "reference")
+TRUNCATIONS = ("terminal", "bootstrap")
 # steps per captured graph of a reference-schedule rollout (2 launches per step)
 REFERENCE_GRAPH_CHUNK = 256
 
@@ -38,6 +46,12 @@ def check_episode_schedule(episode_schedule: str) -> str:
         raise ValueError(f"episode_schedule must be one of {EPISODE_SCHEDULES}, "
                          f"got {episode_schedule!r}")
     return episode_schedule
+
+
+def check_truncation(truncation: str) -> str:
+    if truncation not in TRUNCATIONS:
+        raise ValueError(f"truncation must be one of {TRUNCATIONS}, got {truncation!r}")
+    return truncation
 
 
 def rollout_chunks(T: int, episode_schedule: str):
@@ -58,7 +72,8 @@ def alloc_cut_buffers(owner, E: int, sd: int, device) -> None:
 
 class LockstepRollout:
     def __init__(self, agent, env, buf, use_graph: bool = True,
-                 episode_schedule: str = "lockstep", episode_stats: bool = False):
+                 episode_schedule: str = "lockstep", episode_stats: bool = False,
+                 truncation: str = "terminal"):
         self.agent = agent
         self.env = env.unwrapped if hasattr(env, "unwrapped") else env
         self.buf = buf
@@ -67,6 +82,10 @@ class LockstepRollout:
         self.episode_stats = bool(episode_stats)
         if self.episode_stats and buf.ep_stats is None:
             raise ValueError("episode_stats needs a RolloutBuffer built with episode_stats=True")
+        self.truncation = check_truncation(truncation)
+        if self.truncation == "bootstrap" and getattr(buf, "boot_values", None) is None:
+            raise ValueError('truncation="bootstrap" needs a RolloutBuffer built with '
+                             "truncation_bootstrap=True")
         self.use_graph = bool(use_graph) and self.buf.states.is_cuda
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._key = None
@@ -93,8 +112,11 @@ class LockstepRollout:
         F = getattr(ag, "_fused", None)
         tiles = F.current_tiles(flat) if (F is not None and flat is not None) else None
         params = tuple(p.data_ptr() for p in ag.actor_critic.parameters())
-        return (env._handle.value, getattr(env, "launch_version", 0), tiles, params,
-                buf.states.data_ptr(), buf.noise.data_ptr(), buf.T, buf.E)
+        key = (env._handle.value, getattr(env, "launch_version", 0), tiles, params,
+               buf.states.data_ptr(), buf.noise.data_ptr(), buf.T, buf.E)
+        if self.truncation == "bootstrap":
+            key += (buf.final_obs.data_ptr(), buf.boot_values.data_ptr())
+        return key
 
     def _steps(self, t0: int = 0, t1: Optional[int] = None) -> None:
         ag, env, buf = self.agent, self.env, self.buf
@@ -107,7 +129,16 @@ class LockstepRollout:
                              noise=buf.noise[t])
             io = (buf.actions[t], buf.states[t + 1].view(E, *obs_shape), buf.rewards[t],
                   buf.terminated[t], buf.truncated[t], buf.ep_return[t], buf.ep_length[t])
-            if self.episode_stats:
+            if self.truncation == "bootstrap":
+                info = buf.step_info(t) if self.episode_stats else None
+                if self._envstep is not None:
+                    self._envstep.launch([io], infos=None if info is None else [info],
+                                         final_obs=[buf.final_obs])
+                else:
+                    env.step_into(*io, info=info, final_obs=buf.final_obs)
+                ag.value_masked(buf.final_obs, buf.truncated[t], buf.terminated[t],
+                                out=buf.boot_values[t])
+            elif self.episode_stats:
                 info = buf.step_info(t)
                 if self._envstep is not None:
                     self._envstep.launch([io], infos=[info])

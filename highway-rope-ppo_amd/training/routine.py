@@ -367,8 +367,16 @@ class _EvalTracker:
 def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, log_interval=20,
                                eval_interval=50, steps_per_update=2048, experiment_name="",
                                exp_seed: int = 0, logger=None, episode_schedule="lockstep",
-                               episode_stats: bool = False):
-    from ppo.rollout import check_episode_schedule
+                               episode_stats: bool = False, truncation: str = "terminal"):
+    from ppo.rollout import check_episode_schedule, check_truncation
+
+    if check_truncation(truncation) == "bootstrap":
+        if not _is_vector(env):
+            raise ValueError("truncation='bootstrap' needs a HighwayVecEnv (num_envs > 1, or "
+                             "make_env's vector_env key for one env); the one-env reference loop "
+                             "books a time limit as terminal")
+        if getattr(agent, "_dist", None) is not None:
+            raise ValueError("truncation='bootstrap' does not run over a process group")
 
     if episode_stats:
         if not _is_vector(env):
@@ -400,6 +408,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
     }
     if episode_stats:
         metrics_history.update({k: [] for k in STATS_KEYS})
+    if truncation != "terminal":  # the default's metrics stay what they were
+        metrics_history["truncation"] = truncation
     start_time = time.time()
     artifacts_dir = ensure_artifacts_dir()
     checkpoint_dir = os.path.join(artifacts_dir, "checkpoints")
@@ -416,6 +426,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
     sched_kw = {} if episode_schedule == "lockstep" else {"episode_schedule": episode_schedule}
     if episode_stats:
         sched_kw["episode_stats"] = True
+    if truncation != "terminal":
+        sched_kw["truncation"] = truncation
     episode_rewards, training_episodes, total_steps = loop(
         env, agent, max_episodes, log_interval, eval_interval, steps_per_update, exp_seed, logger,
         exp_prefix, metrics_history, tracker, start_time, **sched_kw)
@@ -480,8 +492,12 @@ def _train_single(env, agent, max_episodes, log_interval, eval_interval, steps_p
 
 def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_per_update,
                   exp_seed, logger, prefix, mh, tracker, start_time, episode_schedule="lockstep",
-                  episode_stats=False):
+                  episode_stats=False, truncation="terminal"):
     """E lockstep envs, device rollout of T steps, batched PPO update.
+
+    truncation "bootstrap": the rollout also stores V(final observation) of the truncated rows
+    (ppo/rollout.py) and the update's GAE bootstraps them (hwy_gae_boot) instead of booking a
+    time limit as terminal; not over a process group.
 
     episode_stats: the rollout steps with hwy_step_with_info and every booked episode's
     statistics go to mh's STATS_KEYS lists (read before the update and the next rollout).
@@ -499,19 +515,23 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
 
     group = getattr(agent, "_dist", None)
     rank, world = _rank_world(group)
+    bootstrap = truncation == "bootstrap"
+    if bootstrap and group is not None:
+        raise ValueError("truncation='bootstrap' does not run over a process group")
     base = env.unwrapped
     E = base.num_envs
     sd = _flat_dim(env)
     T = max(1, math.ceil(steps_per_update / E))
     stats_kw = {"episode_stats": True} if episode_stats else {}
-    buf = RolloutBuffer(T, E, sd, 2, base.device, **stats_kw)
+    buf = RolloutBuffer(T, E, sd, 2, base.device, **stats_kw,
+                        **({"truncation_bootstrap": True} if bootstrap else {}))
     base.set_seed_schedule(exp_seed)
     obs, _ = env.reset()
     buf.states[0].copy_(obs.reshape(E, sd))
     reference = episode_schedule == "reference"
     roll = LockstepRollout(agent, base, buf, use_graph=getattr(agent, "use_graphs", True),
                            **({"episode_schedule": episode_schedule} if reference else {}),
-                           **stats_kw)
+                           **stats_kw, **({"truncation": truncation} if bootstrap else {}))
     episode_rewards, training_episodes = [], []
     total_steps = episode_num = 0
     while episode_num < max_episodes:

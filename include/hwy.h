@@ -32,6 +32,14 @@
  *                                (main.py:188-242 fans the seeds out as separate processes; here
  *                                 a cell's seeds share one handle, each with its own schedule)
  *   hwy_step_group_info       <- the same, every cell's step with its info outputs
+ *   hwy_step_with_final       <- the terminal observation of an autoresetting vector env
+ *                                (gymnasium's info["final_observation"]; the reference steps one
+ *                                 env and resets it by hand, so it holds the row itself,
+ *                                 training/routine.py:134-150)
+ *   hwy_step_group_final      <- the same through the grouped launch's tables
+ *   hwy_gae_boot              <- PPOMemory.compute_advantages with the value of the final
+ *                                observation at a time limit instead of 0 (the reference books
+ *                                truncation as terminal, training/routine.py:135; opt-in)
  *
  * Conventions
  *   - Plain pointers and sizes only; device pointers are HIP device pointers (e.g. torch
@@ -291,6 +299,29 @@ int hwy_step_group_info_prepare(hwy_handle* const* handles, const hwy_step_io* i
 int hwy_step_group_info(const hwy_step_group_plan* plan, const void* table, const void* info_table,
                         void* stream);
 
+/* ---- Step with the terminal observation: hwy_step_with_info (info nullable here: NULL = no info
+ * outputs) that also writes, for every env whose episode finished in this step (terminated or
+ * truncated), the last observation of that episode to final_obs [E][N][F_out] -- what a handle
+ * with autoreset off would have written to obs: the pre-reset vehicles, the finished episode's
+ * step count and seed (the shuffled order depends on both) and the same PE table.  Rows of envs
+ * that are not done are not written.  With autoreset off the row equals the obs row.  The env
+ * computes exactly what hwy_step computes.  HWY_EINVAL for a NULL handle, a NULL final_obs,
+ * final_obs == obs, or info->ep_stats without info->acc. */
+int hwy_step_with_final(hwy_handle* h, const float* actions, float* obs, float* reward,
+                        uint8_t* terminated, uint8_t* truncated, float* ep_return,
+                        int32_t* ep_length, const hwy_step_info* info /*nullable*/,
+                        float* final_obs, void* stream);
+/* The grouped form: info (nullable; else [n], each as above) and final_obs [n] live in a second
+ * device table of hwy_step_group_final_table_bytes(n) bytes beside the step table
+ * (hwy_step_group's format).  Prepare is synchronous, the launch asynchronous and capturable. */
+int64_t hwy_step_group_final_table_bytes(int n);
+int hwy_step_group_final_prepare(hwy_handle* const* handles, const hwy_step_io* io,
+                                 const hwy_step_info* info /*nullable*/,
+                                 float* const* final_obs /*[n]*/, int n, void* table,
+                                 void* final_table, hwy_step_group_plan* plan, void* stream);
+int hwy_step_group_final(const hwy_step_group_plan* plan, const void* table,
+                         const void* final_table, void* stream);
+
 /* Copy the packed state [HWY_NFIELDS][E][HWY_MAX_VEHICLES] u32 to / from device memory. */
 int hwy_export_state(hwy_handle* h, uint32_t* dst, void* stream);
 int hwy_import_state(hwy_handle* h, const uint32_t* src, void* stream);
@@ -308,6 +339,19 @@ int hwy_obs_pe(const float* obs_in, float* obs_out, int E, int N, int F, int kin
 int hwy_gae(const float* rewards, const uint8_t* dones, const float* values,
             const float* last_values, double gamma, double lam, int T, int E, float* advantages,
             float* returns, void* stream);
+
+/* hwy_gae with a bootstrap at truncation; every array [T,E].  Per step, with v1 the next step's
+ * value (last_values past the end) and last_adv the next step's advantage:
+ *   done = term | trunc;  boot = trunc & !term;  vsel = boot ? boot_values[i] : v1
+ *   m = (done && !boot) ? 0 : 1;  nd = done ? 0 : 1
+ *   delta = (r + (gamma * vsel) * m) - v0;  a = (float)(delta + (gamma*lam * nd) * last_adv)
+ * in float64, each step rounded to float32, ret = a + v0: a truncated row's advantage is its
+ * one-step TD error against V(final observation) and the chain is cut there.  Without a boot row
+ * the result is hwy_gae's on dones = term | trunc, bit for bit. */
+int hwy_gae_boot(const float* rewards, const uint8_t* terminated, const uint8_t* truncated,
+                 const float* values, const float* last_values, const float* boot_values,
+                 double gamma, double lam, int T, int E, float* advantages, float* returns,
+                 void* stream);
 
 /* Device self-test of the deterministic math library (tests only): out[i] = op(in[i], in2[i]). */
 int hwy_math_selftest(int op, const float* in, const float* in2, float* out, int n, void* stream);

@@ -5,6 +5,10 @@
  * (reference ppo/agent.py:216-252): ActorCritic.evaluate (:76-84) on the minibatch, the
  * ratio / KL / clipped surrogate / MSE / entropy loss (:226-245), loss.backward(),
  * clip_grad_norm_(0.5) (:249-251) and Adam.step() (:252, torch.optim.Adam defaults).
+ * hwy_ppo_act replaces the acting forward and sampling on the batched rollout path (below);
+ * hwy_ppo_value_masked replaces nothing there: it is ActorCritic.forward's value (:46-54) on the final
+ * observations of the truncated rows only, for the opt-in bootstrap at a time limit that the
+ * reference, which books truncation as terminal (training/routine.py:135), does not have.
  *
  * Network (ppo/agent.py:23-42): shared = Lin(S,H)-ReLU-Lin(H,H)-ReLU; actor_mean =
  * Lin(H,H)-ReLU-Lin(H,A); log_std[A]; critic = Lin(H,H)-ReLU-Lin(H,1).  Parameters live in
@@ -110,6 +114,18 @@ typedef struct hwy_ppo_act_args {
   const float* tiles; /* optional weight tile image (see above), or NULL */
 } hwy_ppo_act_args;
 int hwy_ppo_act(const hwy_ppo_act_args* a, void* stream);
+
+/* The critic's value of the truncated rows only (replaces nothing in the reference, which books a
+ * time limit as terminal, training/routine.py:135; it is the V(final observation) that the
+ * bootstrap at truncation, hwy_gae_boot, needs).  Row b is marked iff truncated[b] &&
+ * !(terminated && terminated[b]) (both [B] u8, terminated nullable).  value[b] = the value
+ * hwy_ppo_act computes for states row b (the same kernel body for the same dims and tiles, so the
+ * same bits) for a marked row and exactly 0.0f for any other; a 16- or 32-row tile without a
+ * marked row stores its zeros and returns before it reads a weight.  Nothing else is written:
+ * a->action / pre_tanh / logp may be NULL, a->noise must be NULL.  -1 for bad arguments or dims
+ * hwy_ppo_act refuses, before any device call. */
+int hwy_ppo_value_masked(const hwy_ppo_act_args* a, const uint8_t* truncated,
+                         const uint8_t* terminated /*nullable*/, void* stream);
 
 /* ---- Grouped learners: G independent learners (a sweep cell's seeds, or the cells of one
  * hidden width; ppo/group.py, ExperimentRunner.launch_group; the reference runs them as separate processes,
