@@ -14,14 +14,18 @@ FIELD_NAMES = ["x", "y", "heading", "speed", "target_speed", "delta", "timer", "
 
 
 def make_cfg(E=32, order="sorted", pe=_abi.PE_NONE, d=0, N=None, autoreset=True, seed_base=42,
-             **overrides):
+             observation=None, ego_idx=0, **overrides):
+    """HIGHWAY_CONFIG with `overrides` on its top-level keys and `observation` (a dict) on its
+    observation block; `ego_idx` is the fused wrapper's."""
     cfg = copy.deepcopy(HIGHWAY_CONFIG)
     cfg["observation"]["order"] = order
     if N is not None:
         cfg["observation"]["vehicles_count"] = N
+    if observation:
+        cfg["observation"].update(observation)
     cfg.update(overrides)
     return _abi.config_from_dict(cfg, num_envs=E, autoreset=autoreset, seed_base=seed_base,
-                                 pe_kind=pe, d_embed=d)
+                                 pe_kind=pe, d_embed=d, ego_idx=ego_idx)
 
 
 def rope_inv_freq(rotate_dim, base=100.0):

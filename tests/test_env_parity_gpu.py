@@ -7,99 +7,13 @@ identical: any difference is a bug in the parallel formulation.
 
 import numpy as np
 import pytest
-import torch
 
+from env_util import HipEnv, run_parity
 from hwy import _abi
-from hwy.native import check, lib, ptr
 from oracle.oracle import OracleEnv
 from parity_util import diff_state, make_cfg, pe_table_for, policy_actions
 
 pytestmark = pytest.mark.gpu
-
-DEV = torch.device("cuda", 0)
-
-
-class HipEnv:
-    """Direct C-ABI driver (no Python env layer) so the test exercises exactly libhwy.so."""
-
-    def __init__(self, cfg, table=None):
-        import ctypes
-
-        self.cfg = cfg
-        self.E, self.N, self.Fo = cfg.num_envs, cfg.obs_vehicles, cfg.obs_features()
-        self.h = ctypes.c_void_p()
-        check(lib().hwy_create(ctypes.byref(cfg), 0, ctypes.byref(self.h)), "hwy_create")
-        if table is not None:
-            t = np.ascontiguousarray(table, np.float32)
-            check(lib().hwy_set_pe_table(self.h, t.ctypes.data_as(ctypes.c_void_p), t.size),
-                  "hwy_set_pe_table")
-        self.obs = torch.zeros(self.E, self.N, self.Fo, device=DEV)
-        self.rew = torch.zeros(self.E, device=DEV)
-        self.term = torch.zeros(self.E, dtype=torch.uint8, device=DEV)
-        self.trunc = torch.zeros(self.E, dtype=torch.uint8, device=DEV)
-        self.er = torch.zeros(self.E, device=DEV)
-        self.el = torch.zeros(self.E, dtype=torch.int32, device=DEV)
-
-    def reset(self, seeds=None):
-        s = None if seeds is None else torch.as_tensor(seeds.astype(np.int64), device=DEV)
-        check(lib().hwy_reset(self.h, ptr(s), None, ptr(self.obs), None), "hwy_reset")
-        torch.cuda.synchronize()
-        return self.obs.cpu().numpy()
-
-    def step(self, a):
-        at = torch.as_tensor(a, device=DEV).contiguous()
-        check(lib().hwy_step(self.h, ptr(at), ptr(self.obs), ptr(self.rew), ptr(self.term),
-                             ptr(self.trunc), ptr(self.er), ptr(self.el), None), "hwy_step")
-        torch.cuda.synchronize()
-        return (self.obs.cpu().numpy(), self.rew.cpu().numpy(), self.term.cpu().numpy(),
-                self.trunc.cpu().numpy(), self.er.cpu().numpy(), self.el.cpu().numpy())
-
-    def state(self):
-        out = torch.zeros(_abi.NFIELDS, self.E, 64, dtype=torch.int32, device=DEV)
-        check(lib().hwy_export_state(self.h, ptr(out), None), "export")
-        torch.cuda.synchronize()
-        return out.cpu().numpy().view(np.uint32)
-
-    def set_state(self, st):
-        t = torch.as_tensor(np.ascontiguousarray(st).view(np.int32), device=DEV)
-        check(lib().hwy_import_state(self.h, ptr(t), None), "import")
-        torch.cuda.synchronize()
-
-    def close(self):
-        lib().hwy_destroy(self.h)
-
-
-def run_parity(cfg, steps, table=None, seed=0, action_fn=policy_actions):
-    hip = HipEnv(cfg, table)
-    ora = OracleEnv(cfg, table)
-    V = cfg.vehicles_count + 1
-    try:
-        o_h = hip.reset()
-        o_o = ora.reset()
-        d = diff_state(hip.state(), ora.state, V)
-        assert d is None, f"reset state: {d}"
-        np.testing.assert_array_equal(o_h, o_o, err_msg="reset obs")
-        rng = np.random.default_rng(seed)
-        stats = dict(crashes=0, dones=0, lane_changes=0)
-        for t in range(steps):
-            a = action_fn(rng, cfg.num_envs, t)
-            rh = hip.step(a)
-            ro = ora.step(a)
-            d = diff_state(hip.state(), ora.state, V)
-            assert d is None, f"step {t}: {d}"
-            np.testing.assert_array_equal(rh[0], ro[0], err_msg=f"obs at step {t}")
-            np.testing.assert_array_equal(rh[1], ro[1], err_msg=f"reward at step {t}")
-            np.testing.assert_array_equal(rh[2].astype(bool), ro[2], err_msg=f"terminated at step {t}")
-            np.testing.assert_array_equal(rh[3].astype(bool), ro[3], err_msg=f"truncated at step {t}")
-            np.testing.assert_array_equal(rh[4], ro[4], err_msg=f"episode return at step {t}")
-            np.testing.assert_array_equal(rh[5], ro[5], err_msg=f"episode length at step {t}")
-            stats["dones"] += int((ro[2] | ro[3]).sum())
-            stats["crashes"] += int(ro[2].sum())
-            st = ora.state
-            stats["lane_changes"] += int((st[_abi.F_LANE, :, 1:V] != st[_abi.F_TLANE, :, 1:V]).sum())
-        return stats
-    finally:
-        hip.close()
 
 
 @pytest.mark.parametrize("order", ["sorted", "shuffled"])
