@@ -1738,9 +1738,14 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 // barrier (counted vmcnt, raw s_barrier).  The register-staged loop spent 14 us of a 75 us
 // launch in its transposing staging (timing-only build without it: 61 us).
 // The A column sums (bias gradients) come from the A operand values in registers.
+// Waves 4-7 run the same program half a chunk behind their SIMD partners (below), on the
+// row halves of the images that only they touch.
 __device__ __forceinline__ void wgrad_tile_dma(const WgArgs& a, int tile_id, int kb0, int kb1,
                                                float* part, float* wg_lds PSEC_PARAMS) {
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6, h = lane >> 5, l32 = lane & 31;
+  const int t = threadIdx.x, lane = t & 63, h = lane >> 5, l32 = lane & 31;
+  // the wave number as a scalar: the DMA bases and their LDS destinations (m0) stay on the
+  // scalar side, and the choice between the two halves' loops below is a scalar branch
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int H = a.H;
   if (kb1 <= kb0) {
     for (int i = t; i < kWgPart; i += 64 * kWgWaves) part[i] = 0.0f;
@@ -1791,6 +1796,33 @@ __device__ __forceinline__ void wgrad_tile_dma(const WgArgs& a, int tile_id, int
                                        0, 0);
     }
   };
+  // The same addresses for a chunk whose 64 rows are all in range (no clamp): a wave-uniform
+  // 64-bit base (ga / gb: this wave's first A / B row of the chunk, advanced by 64 rows per
+  // chunk on the scalar side) plus per-piece byte offsets of the lane that never change, so a
+  // piece costs one vector add instead of five vector instructions and a v_readfirstlane; its
+  // LDS destination (m0) is scalar too.
+  const char* ga = (const char*)(A + (size_t)(kb0 + 128 + 8 * w) * (size_t)lda);
+  const char* gb = (const char*)(Bm + (size_t)(kb0 + 128 + 8 * w) * (size_t)ldb);
+  uint32_t la[4], lb[2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) la[i] = ((uint32_t)((2 * i + h) * lda) + a_col) * 4u;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) lb[i] = ((uint32_t)((4 * i + rb) * ldb) + b_col) * 4u;
+  auto dma_whole = [&](float* buf, int part) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (part != i / 2) continue;
+      __builtin_amdgcn_global_load_lds((const void*)(ga + la[i]),
+                                       (lds_void_t*)(buf + (4 * w + i) * 256), 16, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      if (part != 2) continue;
+      __builtin_amdgcn_global_load_lds((const void*)(gb + lb[i]),
+                                       (lds_void_t*)(buf + kWgTM * 64 + (2 * w + i) * 256), 16,
+                                       0, 0);
+    }
+  };
   // MFMA: waves w and w + 4 (one SIMD) own the same 64 x 32 output block (two 32x32
   // accumulators sharing the B operand), over rows 0-31 / 32-63 of every chunk.
   const int kh = w >> 2, wq = w & 3;
@@ -1803,11 +1835,14 @@ __device__ __forceinline__ void wgrad_tile_dma(const WgArgs& a, int tile_id, int
 #pragma unroll
   for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.0f;
   float bs0 = 0.0f, bs1 = 0.0f;  // A column sums of this lane's features over its rows
-  // dc / dbuf: the chunk whose DMAs go out between this chunk's MFMA groups (dc < 0: none);
+  // dc / dbuf: the chunk whose DMAs go out between this chunk's MFMA groups (dma_tag 0: none,
+  // 1: the whole chunk at ga / gb, 2: chunk dc with its rows clamped, none if dc < 0);
   // issued all at once after the barrier, both waves of a SIMD issued them together (round 4:
   // 203.4 -> 201.5 us per 16,384-row step with the activation reads pinned, same weights)
-  auto compute = [&](const float* buf, int lim, auto mask_tag, int dc, float* dbuf) {
+  auto compute = [&](const float* buf, int lim, auto mask_tag, auto dma_tag, int dc,
+                     float* dbuf) {
     constexpr bool MASK = decltype(mask_tag)::value;  // rows >= lim (of the chunk) are zero
+    constexpr int DMA = decltype(dma_tag)::value;
     const float* pa0 = buf + offa0 + 32 * kh * 128;
     const float* pa1 = buf + offa1 + 32 * kh * 128;
     const float* pb = buf + offb + 32 * kh * 64;
@@ -1825,12 +1860,15 @@ __device__ __forceinline__ void wgrad_tile_dma(const WgArgs& a, int tile_id, int
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int b = g & 1;
-      // the next group's reads go out before this group's MFMAs (pinned: the scheduler would
-      // otherwise sink them to their use and wait for them there)
-      if (g + 1 < 4) rd(g + 1, b ^ 1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
+        // the next group's reads go out behind this group's first four MFMAs (pinned: the
+        // scheduler would otherwise sink them to their use and wait for them there)
+        if (j == 2) {
+          if (g + 1 < 4) rd(g + 1, b ^ 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
         float u0 = x0[b][j], u1 = x1[b][j];
         if constexpr (MASK) {
           const bool live = 32 * kh + 2 * (4 * g + j) + h < lim;
@@ -1843,7 +1881,11 @@ __device__ __forceinline__ void wgrad_tile_dma(const WgArgs& a, int tile_id, int
         acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(u1, y[b][j], acc1, 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (g < 3 && dc >= 0) {
+      if (g < 3 && DMA == 1) {
+        dma_whole(dbuf, g);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (g < 3 && DMA == 2 && dc >= 0) {
         dma(dc, dbuf, g);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1856,9 +1898,11 @@ __device__ __forceinline__ void wgrad_tile_dma(const WgArgs& a, int tile_id, int
   float* b2 = wg_lds + 2 * BUF;
   // earlier stores of this wave (a previous tile's partial) drained: the vmcnt counts are exact
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // waves 4-7, dispatched second, would lose every arbitration on their SIMD: one static raise
+  if (kh) __builtin_amdgcn_s_setprio(1);
   dma(0, b0);
-  if (nchunk > 1) dma(1, b1);
-  auto step = [&](int c, auto mask_tag) {
+  if (nchunk > 1 && !kh) dma(1, b1);  // (waves 4-7 fetch chunk 1 in their first block)
+  auto step = [&](int c, auto mask_tag, auto dma_tag) {
     // this wave's pieces of chunk c landed (chunk c + 1's 6 may still be in flight) and its
     // reads of chunk c - 1 returned; after the barrier, every wave's
     if (c + 1 < nchunk)
@@ -1868,14 +1912,129 @@ __device__ __forceinline__ void wgrad_tile_dma(const WgArgs& a, int tile_id, int
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     // chunk c + 2 into chunk c - 1's buffer, spread between this chunk's MFMA groups
-    compute(b0, kb1 - (kb0 + 64 * c), mask_tag, c + 2 < nchunk ? c + 2 : -1, b2);
+    compute(b0, kb1 - (kb0 + 64 * c), mask_tag, dma_tag, c + 2 < nchunk ? c + 2 : -1, b2);
     float* tb = b0;
     b0 = b1, b1 = b2, b2 = tb;
+    if (decltype(dma_tag)::value == 1) ga += (size_t)lda * 256, gb += (size_t)ldb * 256;
   };
   // whole chunks, then (ragged minibatches only) the last, partial one with its rows masked
+  // (the whole chunks that fetch a whole chunk two ahead take the lean DMA form; the last two
+  // fetch the ragged chunk, clamped, or nothing; the ragged chunk is the last and fetches nothing)
   const int nfull = (kb1 - kb0) / 64;
-  for (int c = 0; c < nfull; ++c) step(c, unmasked);
-  if (nfull < nchunk) step(nfull, masked);
+  const int nlean = max(nfull - 2, 0);
+  const std::integral_constant<int, 0> dma_none;
+  const std::integral_constant<int, 1> dma_lean;
+  const std::integral_constant<int, 2> dma_clamped;
+  auto run = [&]() {
+    for (int c = 0; c < nlean; ++c) step(c, unmasked, dma_lean);
+    for (int c = nlean; c < nfull; ++c) step(c, unmasked, dma_clamped);
+    if (nfull < nchunk) step(nfull, masked, dma_none);
+  };
+  // Waves 4-7 (the SIMD partners of waves 0-3) run half a chunk behind: between two barriers
+  // they take MFMA groups 2-3 of chunk c - 1, then groups 0-1 of chunk c, so the partners' read
+  // bursts and MFMA runs no longer coincide.  Same accumulators, same k order.  They read and
+  // fill only rows 32-63 of every chunk image, which waves 0-3 never touch.  Block c (after
+  // barrier c): the half of chunk c - 2's image was last read in block c - 1, so chunk c + 1 is
+  // fetched into it now (one block of flight instead of two; vmcnt(0) before every barrier).
+  // One block more than waves 0-3 (the head has no previous chunk, the tail no current one):
+  // waves 0-3 arrive at that last barrier with nothing to compute.
+  // half_tag 1: both halves, 2: the head (groups 0-1 of chunk 0; its fetch goes out at once),
+  // 3: the tail (groups 2-3 of the last chunk).  bufp / limp: the previous chunk's image / rows.
+  // The operands of a block's first group (group 2 of a chunk whose image is complete) are read
+  // at the end of the block before and cross the barrier in registers (xs0 / xs1 / ys, slot 0),
+  // so waves 4-7 open every block with MFMAs while waves 0-3 wait for their first reads.
+  float xs0[2][4], xs1[2][4], ys[2][4];
+  auto compute_st = [&](const float* bufp, const float* buf, int limp, int lim, auto mask_tag,
+                        auto dma_tag, auto half_tag, int dc, float* dbuf) {
+    constexpr bool MASK = decltype(mask_tag)::value;
+    constexpr int DMA = decltype(dma_tag)::value;
+    constexpr int HALF = decltype(half_tag)::value;
+    constexpr int K0 = HALF == 2 ? 2 : 0, K1 = HALF == 3 ? 2 : 4;  // block groups that run
+    auto& x0 = xs0;
+    auto& x1 = xs1;
+    auto& y = ys;
+    // block group k = chunk group (k + 2) & 3; k = 4: the next block's first group, from buf
+    auto rd = [&](int k, int b) {
+      const float* p = k < 2 ? bufp : buf;
+      const float* pa0 = p + offa0 + 32 * kh * 128;
+      const float* pa1 = p + offa1 + 32 * kh * 128;
+      const float* pb = p + offb + 32 * kh * 64;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int st = 4 * ((k + 2) & 3) + j;
+        x0[b][j] = pa0[st * 256];
+        x1[b][j] = pa1[st * 256];
+        y[b][j] = pb[st * 128];
+      }
+    };
+    if (HALF == 2 && DMA == 2 && dc >= 0) dma(dc, dbuf);
+    if (HALF == 2) rd(2, 0);
+#pragma unroll
+    for (int k = K0; k < K1; ++k) {
+      const int b = k & 1, g = (k + 2) & 3, l = k < 2 ? limp : lim;
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        // the next group's reads go out behind this group's first four MFMAs: its own operands
+        // were read a group ago, so no group waits for reads it has just issued
+        if (j == 2) {
+          if (k + 1 < K1 || HALF != 3) rd(k + 1, b ^ 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        float u0 = x0[b][j], u1 = x1[b][j];
+        if constexpr (MASK) {
+          const bool live = 32 * kh + 2 * (4 * g + j) + h < l;
+          u0 = live ? u0 : 0.0f;
+          u1 = live ? u1 : 0.0f;
+        }
+        bs0 += u0;
+        bs1 += u1;
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(u0, y[b][j], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(u1, y[b][j], acc1, 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (HALF == 1 && k < 3 && DMA == 1) {
+        dma_whole(dbuf, k);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (HALF == 1 && k < 3 && DMA == 2 && dc >= 0) {
+        dma(dc, dbuf, k);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  };
+  auto step_st = [&](int c, auto mask_tag, auto dma_tag, auto half_tag) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    const int lim = kb1 - (kb0 + 64 * c);
+    // b0: chunk c, b2: chunk c - 1, b1: chunk c - 2's image, chunk c + 1's now
+    compute_st(b2, b0, lim + 64, lim, mask_tag, dma_tag, half_tag, c + 1 < nchunk ? c + 1 : -1,
+               b1);
+    float* tb = b0;
+    b0 = b1, b1 = b2, b2 = tb;
+    if (decltype(dma_tag)::value == 1) ga += (size_t)lda * 256, gb += (size_t)ldb * 256;
+  };
+  const std::integral_constant<int, 1> both;
+  const std::integral_constant<int, 2> head;
+  const std::integral_constant<int, 3> tail;
+  // nchunk + 1 blocks; chunk c + 1 (fetched in block c) is whole for c < nfull - 1
+  auto run_st = [&]() {
+    step_st(0, masked, dma_clamped, head);
+    for (int c = 1; c < 1 + nlean; ++c) step_st(c, unmasked, dma_lean, both);
+    for (int c = 1 + nlean; c < nfull; ++c) step_st(c, unmasked, dma_clamped, both);
+    if (nfull < nchunk && nfull >= 1) step_st(nfull, masked, dma_none, both);
+    step_st(nchunk, masked, dma_none, tail);
+  };
+  // every wave passes nchunk + 1 barriers here, whatever its half and the minibatch's shape
+  if (kh) {
+    run_st();
+    __builtin_amdgcn_s_setprio(0);
+  } else {
+    run();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // waves 4-7's tail block
+  }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   PSEC(8);
