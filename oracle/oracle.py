@@ -10,7 +10,9 @@ Pinning (see DESIGN.md "Oracle"):
     pinned by tests/golden fixtures generated from the reference itself and by the reference's
     own RoPE tests (tests/test_rope_wrapper.py:34-113) restated as known-answer tests.
   * highway-env 1.10.1 dynamics: third-party, absent offline -> PARITY UNPINNED against
-    upstream; pinned only by hand-built known-answer cases (IDM closed form, SAT, sort order).
+    upstream itself; pinned frame by frame against tests/dyn_model.py, a float64 restatement
+    that shares no code with this library (tests/test_dyn_model.py), and by hand-built
+    known-answer cases (IDM closed form, SAT, sort order).
 """
 
 from __future__ import annotations

@@ -37,6 +37,8 @@ from hwy import _abi
 U = 2.0 ** -24        # relative error of one float32 operation, round to nearest
 SINCOS_ABS = 1e-7     # device sin / cos, absolute (test_device_math_accuracy_against_libm)
 TOL_FACTOR = 2.0      # see the module docstring
+ASIN_REL, ATAN_REL, TAN_REL = 3e-7, 2e-7, 6e-7  # device asin / atan / tan, relative (same test)
+POW_REL = 1e-5        # device pow, relative (test_device_pow_and_idm_pow_against_numpy)
 
 LANE_WIDTH = 4.0      # AbstractLane.DEFAULT_WIDTH
 ROAD_LENGTH = 10000.0  # straight_road_network
@@ -94,6 +96,58 @@ class Q:
     def where(self, mask, other):
         other = Q.of(other)
         return Q(np.where(mask, self.v, other.v), np.where(mask, self.e, other.e))
+
+    # ---- the operations of the dynamics (tests/dyn_model.py).  The library bounds are the ones
+    # test_device_math_accuracy_against_libm (asin 3e-7, atan 2e-7, tan 6e-7 relative) and
+    # test_device_pow_and_idm_pow_against_numpy (pow 1e-5 relative) pin; sqrt is correctly
+    # rounded (test_math_library_correctly_rounded_ops).
+    def sqrt(self):
+        r = np.sqrt(np.maximum(self.v, 0.0))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            # the root over [v - e, v + e]; at v <= e the whole of sqrt(v + e)
+            e = np.where(self.v > self.e, self.e / (2.0 * np.sqrt(np.maximum(self.v - self.e, 1e-300))),
+                         np.sqrt(np.maximum(self.v, 0.0) + self.e))
+        return Q(r, e + U * r)
+
+    def _through(self, fn, rel, lo=-np.inf, hi=np.inf):
+        """a monotone library function: the image of [v - e, v + e] (within the domain) plus the
+        library's relative error"""
+        r = fn(self.v)
+        a, b = fn(np.clip(self.v - self.e, lo, hi)), fn(np.clip(self.v + self.e, lo, hi))
+        return Q(r, np.maximum(np.abs(a - r), np.abs(b - r)) + rel * np.abs(r))
+
+    def asin(self):
+        return Q(np.clip(self.v, -1.0, 1.0), self.e)._through(np.arcsin, ASIN_REL, -1.0, 1.0)
+
+    def atan(self):
+        return self._through(np.arctan, ATAN_REL)
+
+    def tan(self):
+        """for |v| + e < pi / 2"""
+        return self._through(np.tan, TAN_REL)
+
+    def pow(self, p):
+        """v ** p for v >= 0 and an exact exponent p"""
+        r = np.power(self.v, p)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            d = np.where(self.v > 0, np.abs(p) * r / np.where(self.v > 0, self.v, 1.0), 0.0)
+        return Q(r, d * self.e + POW_REL * np.abs(r))
+
+    def minimum(self, o):
+        """min and max are 1-Lipschitz in the sup norm"""
+        o = Q.of(o)
+        return Q(np.minimum(self.v, o.v), np.maximum(self.e, o.e))
+
+    def maximum(self, o):
+        o = Q.of(o)
+        return Q(np.maximum(self.v, o.v), np.maximum(self.e, o.e))
+
+    def clip_sat(self, lo, hi, const_err=0.0):
+        """clip that knows when it saturates: where the value is beyond a limit by more than
+        TOL_FACTOR times its bound, a float32 evaluation returns the limit itself, whose error
+        is `const_err` (0 for a limit float32 holds exactly, one rounding for pi / 4)."""
+        sat = (self.v - TOL_FACTOR * self.e > hi) | (self.v + TOL_FACTOR * self.e < lo)
+        return Q(np.clip(self.v, lo, hi), np.where(sat, const_err, self.e + const_err))
 
     def __getitem__(self, idx):
         return Q(self.v[idx], self.e[idx])

@@ -1,5 +1,6 @@
-"""The env parity driver shared by the GPU parity tests, and the config-space case table with
-its checker against tests/env_model.py (shared by the CPU and the GPU run of the cases).
+"""The env parity driver shared by the GPU parity tests, the config-space case table with its
+checker against tests/env_model.py, and the dynamics case table with its checker against
+tests/dyn_model.py (each shared by the CPU and the GPU run of the cases).
 
 torch and libhwy.so are imported only when a HipEnv is built, so the CPU tests can import the
 case table and the checker without a GPU.
@@ -137,9 +138,12 @@ class HipEnv:
         lib().hwy_destroy(self.h)
 
 
-def run_parity(cfg, steps, table=None, seed=0, action_fn=policy_actions, hook=None):
+def run_parity(cfg, steps, table=None, seed=0, action_fn=policy_actions, hook=None,
+               init_state=None, start_hook=None):
     """hook (optional): called after every step's comparisons with
-    (cfg, hip outputs, hip state, oracle outputs)."""
+    (cfg, hip outputs, hip state, oracle outputs).  init_state (optional): a packed state both
+    sides import after the reset; start_hook (optional): called with the kernel's state before
+    the first step."""
     hip = HipEnv(cfg, table)
     ora = OracleEnv(cfg, table)
     V = cfg.vehicles_count + 1
@@ -149,6 +153,13 @@ def run_parity(cfg, steps, table=None, seed=0, action_fn=policy_actions, hook=No
         d = diff_state(hip.state(), ora.state, V)
         assert d is None, f"reset state: {d}"
         np.testing.assert_array_equal(o_h, o_o, err_msg="reset obs")
+        if init_state is not None:
+            hip.set_state(init_state)
+            ora.state[...] = init_state
+            d = diff_state(hip.state(), ora.state, V)
+            assert d is None, f"imported state: {d}"
+        if start_hook is not None:
+            start_hook(hip.state())
         rng = np.random.default_rng(seed)
         stats = dict(crashes=0, dones=0, lane_changes=0)
         for t in range(steps):
@@ -585,4 +596,308 @@ def run_case_on_oracle(case):
     for t in range(case.steps):
         out = ora.step(case.actions(rng, cfg.num_envs, t))
         ck.check(out, ora.state)
+    return ck
+
+
+# ------------------------------------------------------------------- the dynamics, frame by frame
+# The cases of tests/dyn_model.py: sim_freq == policy_freq, so a step is one simulation frame,
+# and autoreset off, so crashed vehicles keep being stepped.  Natural runs are 16 envs for 96
+# frames; a crafted case imports hand-built states (<= 8 envs, 4 frames) for what traffic does
+# not reach on its own.
+def beyond_one(rng, E, t):
+    """actions three times the usual ones: about a third of the components beyond +-1"""
+    return (3.0 * policy_actions(rng, E, t)).astype(np.float32)
+
+
+@dataclass
+class DynCase:
+    name: str
+    cfg: dict
+    need: dict                     # DynChecker counter -> the least count
+    never: tuple = ()              # counters that must stay 0
+    steps: int = 96
+    E: int = 16
+    actions: object = policy_actions
+    seed: int = 0                  # of the actions and, through seed_base, of the traffic
+    craft: object = None           # craft(cfg, reset state) -> (state, fixed actions [E, 2])
+
+    def make(self):
+        kw = dict(policy_frequency=15, seed_base=42 + 1000 * self.seed)   # the traffic's seeds
+        kw.update(self.cfg)
+        return make_cfg(E=self.E, autoreset=False, **kw)
+
+    def start(self, cfg):
+        """(the state to import after the reset or None, the action function)"""
+        if self.craft is None:
+            return None, self.actions
+        ora = OracleEnv(cfg)
+        ora.reset()
+        st, a = self.craft(cfg, ora.state.copy())
+        return st, (lambda rng, E, t: a)
+
+
+_P = _abi.FLAG_PRESENT
+
+
+def _clear(cfg, st):
+    """every vehicle slot absent and zero; the ego far down the road on the last lane"""
+    V = cfg.vehicles_count + 1
+    st[:_abi.F_ENV, :, :V] = 0
+    for e in range(st.shape[1]):
+        _put(st, e, 0, 5000.0, 4.0 * (cfg.lanes_count - 1))
+
+
+def _put(st, e, i, x, y, heading=0.0, speed=20.0, lane=None, tlane=None, tspeed=None, delta=4.0,
+         timer=0.0, flags=_P):
+    lane = int(round(y / 4.0)) if lane is None else lane
+    for f, val in ((_abi.F_X, x), (_abi.F_Y, y), (_abi.F_HEADING, heading), (_abi.F_SPEED, speed),
+                   (_abi.F_TSPEED, speed if tspeed is None else tspeed),
+                   (_abi.F_DELTA, 0.0 if i == 0 else delta), (_abi.F_TIMER, timer)):
+        st[f].view(np.float32)[e, i] = val
+    st[_abi.F_LANE][e, i] = lane
+    st[_abi.F_TLANE][e, i] = lane if tlane is None else tlane
+    st[_abi.F_FLAGS][e, i] = flags
+
+
+def craft_singles(cfg, st):
+    """one vehicle's edges: the +-40 m/s clip, |v| < 1 at a fired timer, a saturated slip,
+    headings next to +-pi, the road's two ends"""
+    _clear(cfg, st)
+    a = np.zeros((cfg.num_envs, 2), np.float32)
+    for e, (spd, thr) in enumerate(((39.9, 1.0), (40.5, 1.0), (-40.5, -1.0), (40.5, -1.0))):
+        _put(st, e, 0, 5000.0, 12.0, speed=spd)
+        a[e] = (thr, 0.1)
+    # 4: |v| < 1 behind a blocker at a fired timer stays; at 1.5 m/s it goes
+    _put(st, 4, 1, 300.0, 4.0, speed=0.5, timer=1.2)
+    _put(st, 4, 2, 308.0, 4.0, speed=0.5)
+    _put(st, 4, 3, 400.0, 8.0, speed=1.5, timer=1.2)
+    _put(st, 4, 4, 409.0, 8.0, speed=1.5)
+    # 5: two lanes from the target at 2 m/s, from either side: slip and steering saturate
+    _put(st, 5, 1, 300.0, 0.0, speed=2.0, tlane=2)
+    _put(st, 5, 2, 400.0, 12.0, speed=2.0, tlane=1)
+    _put(st, 5, 3, 500.0, 0.0, speed=0.005, tlane=2)   # not_zero(speed)
+    _put(st, 5, 4, 600.0, 8.0, tspeed=35.0)            # v0 = the speed limit
+    _put(st, 5, 5, 700.0, 4.0, speed=5.0, tspeed=-5.0)  # v0 = 0, not_zero(v0)
+    # 6: headings next to +-pi and beyond
+    for i, hd in enumerate((3.1, -3.1, 3.2, -3.2, 6.2), start=1):
+        _put(st, 6, i, 300.0 + 100.0 * i, 4.0 * (i % 4), heading=hd, speed=10.0)
+    # 7: x < 0 (on the lane down to -5, reachable from 0 on) and the last 5 m of the road
+    _put(st, 7, 1, -3.0, 4.0, timer=1.2)            # wants to leave its lane but is at x < 0
+    _put(st, 7, 2, 6.0, 4.0, speed=15.0)
+    _put(st, 7, 3, -6.0, 8.0)                        # s < -5: on no lane, so not 4's front
+    _put(st, 7, 4, -30.0, 8.0, speed=25.0)
+    _put(st, 7, 5, 9994.0, 12.0, timer=1.2)          # reachable; its front leaves the lane at 10005
+    _put(st, 7, 0, 10003.5, 12.0, speed=15.0)
+    a[7] = (0.0, 0.0)
+    return st, a
+
+
+def craft_pairs(cfg, st):
+    """two or three vehicles: not_zero's floor, the rectangles, the impact's frame, an absent
+    slot, and the MOBIL gain, braking veto and pre-check radius next to their constants"""
+    _clear(cfg, st)
+    a = np.zeros((cfg.num_envs, 2), np.float32)
+    # 0, 1: a follower at d = 0 and at d just under 0.01 (the front car 2.5 m aside: no overlap)
+    for e, d in ((0, 0.0), (1, 0.009)):
+        _put(st, e, 1, 300.0, 4.0)
+        _put(st, e, 2, 300.0 + d, 6.5, lane=2)
+    # 2: overlapping rectangles
+    _put(st, 2, 1, 300.0, 4.0)
+    _put(st, 2, 2, 303.0, 4.5)
+    # 3: will intersect within the next frame; the impact lands one frame later
+    _put(st, 3, 1, 300.0, 4.0, speed=30.0)
+    _put(st, 3, 2, 307.5, 4.0, speed=5.0)
+    # 4: an absent slot between two present ones keeps its words and is nobody's neighbour
+    _put(st, 4, 1, 300.0, 4.0)
+    _put(st, 4, 2, 310.0, 4.0, flags=0)
+    _put(st, 4, 3, 320.0, 4.0, speed=15.0)
+    # 5: a gain of 3 (40 / 154.53)^2 = 0.201: a lane change at 0.2, none at 0.202
+    _put(st, 5, 1, 300.0, 4.0, timer=1.2)
+    _put(st, 5, 2, 300.0 + 40.0 * np.sqrt(3.0 / 0.201), 4.0)
+    # 6: the new follower would brake at 3 (40 / 48.87)^2 = 2.01: vetoed at 2, allowed at 2.02
+    _put(st, 6, 1, 300.0, 4.0, timer=1.2)
+    _put(st, 6, 2, 315.0, 4.0)
+    _put(st, 6, 3, 300.0 - 40.0 / np.sqrt(2.01 / 3.0), 8.0)
+    # 7: head-on at 6.655 m after the step (both crashed already: they coast with acc = -v):
+    # outside sqrt(29) + 18.67 / 15 = 6.630, inside 1.01 sqrt(29) + 18.67 / 15 = 6.683
+    _put(st, 7, 1, 300.0, 4.0, flags=_P | _abi.FLAG_CRASHED)
+    _put(st, 7, 2, 309.3056, 4.0, heading=3.0, flags=_P | _abi.FLAG_CRASHED)
+    return st, a
+
+
+def _dyn_cases():
+    full = dict(started=1, aborts=1, crossings=1, timer_resets=1, impacts=1, new_crashes=1, slow=1)
+    some = dict(started=1, crossings=1, timer_resets=1)
+    return [
+        DynCase("dyn-default", {}, need=full),
+        # seeds 6 and 5: with seed 0 these two leave out 7.9 % and 10.9 % of their pairs, nearly all
+        # of them wrecks at rest bumper to bumper, whose will-intersect test sits on its edge
+        DynCase("dyn-5-over-5", dict(simulation_frequency=5, policy_frequency=5), need=full, seed=6),
+        DynCase("dyn-density-3", dict(vehicles_density=3), need=full, seed=5),
+        DynCase("dyn-lanes-1", dict(lanes_count=1), need=dict(timer_resets=1),
+                never=("started", "crossings")),
+        DynCase("dyn-lanes-2", dict(lanes_count=2), need=some),
+        DynCase("dyn-lanes-8", dict(lanes_count=8), need=some),
+        DynCase("dyn-limit-20", dict(speed_limit=20), need=some),
+        DynCase("dyn-V64", dict(vehicles_count=63), need=some),
+        DynCase("dyn-V2", dict(vehicles_count=1), need=dict(timer_resets=1)),
+        DynCase("dyn-actions-beyond-1", {}, need=dict(some, action_clipped=1), actions=beyond_one,
+                seed=2),
+        DynCase("dyn-crafted-singles", dict(vehicles_count=5), craft=craft_singles, E=8, steps=4,
+                need=dict(over_40=4, slow_fired=1, started=1, absent=1, timer_resets=4, v0_clipped=2)),
+        DynCase("dyn-crafted-pairs", dict(vehicles_count=5), craft=craft_pairs, E=8, steps=4,
+                need=dict(new_crashes=4, impacts=2, impact_applied=2, started=2, absent=1,
+                          timer_resets=2)),
+    ]
+
+
+DYN_CASES = _dyn_cases()
+GROUPED_DYN = ("dyn-default", "dyn-lanes-8", "dyn-crafted-pairs")  # one hwy_step_group launch
+
+
+class DynChecker:
+    """One case's frames against dyn_model.frame_model: the after-state of every step within
+    TOL_FACTOR times the model's bound of the same step's before-state (bound 0: equal), on the
+    envs the model does not call uncertain; the branch counts; the worst error per field."""
+
+    def __init__(self, case, cfg, consts=None):
+        self.case, self.cfg, self.consts = case, cfg, consts
+        self.count = {k: 0 for k in ("started", "aborts", "crossings", "timer_resets", "impacts",
+                                     "new_crashes", "slow", "v0_clipped", "action_clipped",
+                                     "over_40", "slow_fired", "absent", "impact_applied")}
+        self.pairs = self.left_out = 0
+        self.worst = {}
+        self.why = {}
+        self.t = 0
+
+    def _exact(self, what, got, want, keep):
+        bad = (got != want) & keep[:, None] if got.ndim == 2 else (got != want) & keep
+        assert not bad.any(), (f"{self.case.name} frame {self.t} {what} at "
+                               f"{np.argwhere(bad)[0].tolist()}: got {got[bad][0]!r}, model "
+                               f"{want[bad][0]!r}")
+
+    def _within(self, what, got, q, keep):
+        got = np.asarray(got, np.float64)
+        err = np.abs(got - q.v)
+        tol = TOL * q.e
+        k = keep[:, None] if got.ndim == 2 else keep
+        bad = (err > tol) & k
+        if bad.any():
+            i = tuple(np.argwhere(bad)[0])
+            raise AssertionError(f"{self.case.name} frame {self.t} {what} at {list(i)}: got "
+                                 f"{got[i]!r}, model {q.v[i]!r}, error {err[i]:.3g} > bound "
+                                 f"{tol[i]:.3g}")
+        ratio = np.where((tol > 0) & k, err / np.where(tol > 0, tol, 1.0), 0.0)
+        if ratio.size:
+            i = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+            w = self.worst.get(what, (0.0, 0.0))
+            if w[1] == 0.0 or ratio[i] > w[0] / w[1]:
+                self.worst[what] = (float(err[i]), float(tol[i]))
+
+    def check(self, before, actions, after, reward):
+        import dyn_model as dm
+
+        cfg = self.cfg
+        V = cfg.vehicles_count + 1
+        model, unc = dm.frame_model(cfg, before, actions, self.consts)
+        keep = ~unc
+        for k, n in model["why"].items():
+            self.why[k] = self.why.get(k, 0) + n
+        self.pairs += unc.size
+        self.left_out += int(unc.sum())
+        for name, f in dm.FLOAT_FIELDS.items():
+            self._within(name, after[f].view(np.float32)[:, :V], model[name], keep)
+        for name, f in dm.INT_FIELDS.items():
+            self._exact(name, after[f][:, :V].astype(np.int32).astype(np.int64), model[name], keep)
+        fl = after[_abi.F_FLAGS][:, :V].astype(np.int64)
+        self._exact("flags", fl & dm.FLAG_MASK, model["flags"], keep)
+        # the order bits are the road order of the after-state's own positions: stored words,
+        # exact, on every env
+        self._exact("road order", fl >> _abi.FLAG_ORDER_SHIFT, dm.road_order(cfg, after),
+                    np.ones_like(keep))
+        eb, ea = before[_abi.F_ENV], after[_abi.F_ENV]
+        everyone = np.ones_like(keep)
+        self._exact("step count", ea[:, _abi.E_STEP].astype(np.int64),
+                    eb[:, _abi.E_STEP].astype(np.int64) + 1, everyone)
+        for w in (_abi.E_EPISODE, _abi.E_SEED_LO, _abi.E_SEED_HI):
+            self._exact(f"env word {w}", ea[:, w], eb[:, w], everyone)
+        fa = ea.view(np.float32)
+        self._within("ego_acc", fa[:, _abi.E_EGO_ACC], model["ego_acc"], everyone)
+        self._within("ego_steer", fa[:, _abi.E_EGO_STEER], model["ego_steer"], everyone)
+        ret = em.Q(eb.view(np.float32)[:, _abi.E_RETURN].astype(np.float64)) + \
+            em.Q(np.asarray(reward, np.float32).astype(np.float64))
+        self._within("return", fa[:, _abi.E_RETURN], ret, everyone)
+        self._cover(dm.unpack(cfg, before), dm.unpack(cfg, after), actions)
+        self.t += 1
+
+    def _cover(self, b, a, actions):
+        c = self.count
+        tr = b["present"].copy()
+        tr[:, 0] = False
+        steady = tr & ~b["crashed"] & (b["lane"] == b["target_lane"])
+        fired = steady & (b["timer"] > 1.0)
+        c["started"] += int((steady & (a["target_lane"] != b["lane"])).sum())
+        c["aborts"] += int((tr & (b["lane"] != b["target_lane"]) & (a["target_lane"] == b["lane"])).sum())
+        c["crossings"] += int((tr & (a["lane"] != b["lane"])).sum())
+        c["timer_resets"] += int(fired.sum())
+        c["impacts"] += int(a["impact"].sum())
+        c["impact_applied"] += int((b["impact"] & b["present"] & a["crashed"]).sum())
+        c["new_crashes"] += int((a["crashed"] & ~b["crashed"]).sum())
+        c["slow"] += int((tr & (np.abs(b["speed"]) < 1.0)).sum())
+        c["slow_fired"] += int((fired & (np.abs(b["speed"]) < 1.0)).sum())
+        c["v0_clipped"] += int((tr & ((b["target_speed"] > float(self.cfg.speed_limit)) |
+                                        (b["target_speed"] < 0.0))).sum())
+        c["action_clipped"] += int((np.abs(actions) > 1.0).sum())
+        c["over_40"] += int((np.abs(b["speed"][:, 0]) > 40.0).sum())
+        c["absent"] += int((~b["present"]).sum())
+
+    def report(self):
+        share = self.left_out / max(self.pairs, 1)
+        worst = ", ".join(f"{k} {e:.2e}/{b:.2e}" for k, (e, b) in self.worst.items() if b > 0)
+        return (f"{self.case.name}: worst error/bound {worst}; uncertain {self.left_out}/"
+                f"{self.pairs} = {100 * share:.2f} % by { {k: v for k, v in self.why.items() if v} }; counts "
+                f"{ {k: v for k, v in self.count.items() if v} }")
+
+    def finish(self):
+        print(self.report())
+        for k, least in self.case.need.items():
+            assert self.count[k] >= least, f"{self.case.name}: {k} occurred {self.count[k]} times, need {least}"
+        for k in self.case.never:
+            assert self.count[k] == 0, f"{self.case.name}: {k} occurred {self.count[k]} times"
+        # a cap, not a target: a case over it gets another seed or other inputs
+        assert self.left_out <= 0.05 * self.pairs, self.report()
+
+
+TOL = em.TOL_FACTOR
+_TRACES = {}
+
+
+def dyn_trace(case):
+    """The case on the CPU oracle, once: [(state before, actions, state after, reward)] per
+    frame.  Shared by the tests of tests/test_dyn_model.py and left unchanged."""
+    if case.name not in _TRACES:
+        cfg = case.make()
+        init, action_fn = case.start(cfg)
+        ora = OracleEnv(cfg)
+        ora.reset()
+        if init is not None:
+            ora.state[...] = init
+        rng = np.random.default_rng(case.seed)
+        frames = []
+        for t in range(case.steps):
+            before = ora.state.copy()
+            a = np.ascontiguousarray(action_fn(rng, cfg.num_envs, t), np.float32)
+            out = ora.step(a)
+            frames.append((before, a, ora.state.copy(), out[1].copy()))
+        _TRACES[case.name] = (cfg, frames)
+    return _TRACES[case.name]
+
+
+def run_dyn_case_on_oracle(case, consts=None):
+    """The case's oracle frames against the model (with `consts` over dyn_model.CONSTS): the
+    DynChecker, not yet finished."""
+    cfg, frames = dyn_trace(case)
+    ck = DynChecker(case, cfg, consts)
+    for before, a, after, rew in frames:
+        ck.check(before, a, after, rew)
     return ck
