@@ -19,7 +19,7 @@
 // head kernel (ppo_head), split-K partial slabs and one deterministic reduction (ppo_reduce).
 // All GEMMs use v_mfma_f32_*_f32: exact fp32 products, fp32 accumulation.
 //
-// This file is compiled four times (Makefile).  ppo_kernels.o holds everything but the mixed-width
+// This file is compiled five times (Makefile).  ppo_kernels.o holds everything but the mixed-width
 // and scheduled grouped kernels and their entry points (hwy_ppo_mixed_*, hwy_ppo_sched_*);
 // ppo_mixed.o, compiled with -DHWY_PPO_MIXED_TU, holds only those; ppo_wide.o, compiled with
 // -DHWY_PPO_WIDE_TU, holds only the row / act kernels for S > 256 (solo, grouped, mixed and
@@ -30,7 +30,10 @@
 // in a unit of their own the mixed kernels leave every other kernel's registers, LDS and
 // occupancy as they were (profiles/r7/mixed/), and so do the wide ones
 // (profiles/r9/wide/).  ppo_vmask.o, compiled with -DHWY_PPO_VMASK_TU, holds only the act kernels
-// with the masked value store and their entry point (hwy_ppo_value_masked).
+// with the masked value store and their entry point (hwy_ppo_value_masked).  ppo_ctl.o, compiled
+// with -DHWY_PPO_MIXED_TU -DHWY_PPO_CTL_TU, holds only the scheduled kernels with the KL stop
+// (narrow and wide row kernels alike), the learning-rate kernel and their entry points
+// (hwy_ppo_sched_ctl_*, hwy_ppo_sched_set_lr).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -2756,6 +2759,112 @@ __global__ void __launch_bounds__(64) ppo_sched_advance(int* base, int slots) {
   if (threadIdx.x == 0) *base += slots;
 }
 
+#ifdef HWY_PPO_CTL_TU
+// ----------------------------------------------------------------------------- scheduled + control
+// The scheduled kernels with a per-learner KL stop (hwy_ppo_sched_ctl_*; ppo_ctl.o): the same
+// bodies behind one more whole-workgroup exit, so an applied step has the scheduled (= solo)
+// step's bits.  The control block holds, per learner, a CtlRec, a word stop_at (the slot that
+// tripped, -1 while running) and its copy stop_seen.
+//
+// The decision of slot s is taken in the slice-sum launch, from what EARLIER launches wrote:
+// counters[1] (the row launch of s) and the metrics row's KL (the weight-gradient launch of s).
+// Every slice-sum workgroup of learner y evaluates it for itself, so none waits for another;
+// workgroup 0 publishes stop_at[y] = s, which no workgroup of that launch reads.  The Adam launch
+// of s reads stop_at (written one launch earlier): on a trip its workgroups return, and workgroup
+// 0 copies the slot to stop_seen[y] and takes back the row kernel's increment of the Adam step
+// count.  Later slots: the row and weight-gradient launches return on stop_at, the slice-sum
+// launch on stop_seen (it may write stop_at, so it does not read it), the Adam launch on stop_at
+// (it may write stop_seen).  No launch reads a control word that it writes; both words are
+// written by one thread's ordinary store and cleared by hwy_ppo_sched_ctl_begin (a memset node).
+struct CtlRec {
+  int kl_on;
+  float kl_limit;
+};
+
+// the minibatch-mean KL of the step's metrics row, exactly as stored, against the learner's limit
+// (a NaN trips)
+__device__ __forceinline__ bool ctl_trips(const CtlRec& k, const float* __restrict__ metrics,
+                                          const int* __restrict__ counters) {
+  if (!k.kl_on) return false;
+  const float kl = metrics[(int64_t)(counters[1] - 1) * 6 + 5];
+  return !(kl <= k.kl_limit);
+}
+
+template <int NW, bool WIDE>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_rows_ctl(const RowArgs* __restrict__ tab,
+                                                           const GroupLim* __restrict__ lim,
+                                                           const int* __restrict__ qh,
+                                                           const SchedRec* __restrict__ rec,
+                                                           const int* __restrict__ base,
+                                                           const int* __restrict__ stop_at,
+                                                           int slot) {
+  const int q = qh[blockIdx.y];
+  if ((q & 1) != (NW == 4 ? 1 : 0) || (int)blockIdx.x >= lim[blockIdx.y].rows) return;
+  const SchedRec c = rec[blockIdx.y];
+  const int i = sched_minibatch(c, base, slot);
+  if (i < 0 || stop_at[blockIdx.y] >= 0) return;  // whole workgroup
+  rows_of_width<NW, WIDE>(tab[c.row0 + i], q);
+}
+
+__global__ void __launch_bounds__(512) ppo_wgrad_ctl(const WgArgs* __restrict__ tab,
+                                                     const GroupLim* __restrict__ lim,
+                                                     const SchedRec* __restrict__ rec,
+                                                     const int* __restrict__ base,
+                                                     const int* __restrict__ stop_at, int slot) {
+  if ((int)blockIdx.x >= lim[blockIdx.y].wgrad ||
+      sched_minibatch(rec[blockIdx.y], base, slot) < 0 || stop_at[blockIdx.y] >= 0)
+    return;
+  ppo_wgrad_body(tab[blockIdx.y]);
+}
+
+__global__ void __launch_bounds__(256) ppo_wsum_ctl(const WgArgs* __restrict__ tab,
+                                                    const GroupLim* __restrict__ lim,
+                                                    const SchedRec* __restrict__ rec,
+                                                    const int* __restrict__ base,
+                                                    const CtlRec* __restrict__ ctl,
+                                                    int* stop_at,
+                                                    const int* __restrict__ stop_seen, int slot) {
+  const int y = blockIdx.y;
+  if ((int)blockIdx.x >= lim[y].wsum || sched_minibatch(rec[y], base, slot) < 0 ||
+      stop_seen[y] >= 0)
+    return;
+  const WgArgs& g = tab[y];
+  if (ctl_trips(ctl[y], g.metrics, g.counters)) {  // the same answer in every workgroup
+    if (blockIdx.x == 0 && threadIdx.x == 0) stop_at[y] = *base + slot;
+    return;
+  }
+  wsum_body(g);
+}
+
+__global__ void __launch_bounds__(256) ppo_adam_tiles_ctl(const OptArgs* __restrict__ tab,
+                                                          const GroupLim* __restrict__ lim,
+                                                          const SchedRec* __restrict__ rec,
+                                                          const int* __restrict__ base,
+                                                          const int* __restrict__ stop_at,
+                                                          int* stop_seen, int slot) {
+  const int y = blockIdx.y;
+  if ((int)blockIdx.x >= lim[y].adam || sched_minibatch(rec[y], base, slot) < 0) return;
+  const int st = stop_at[y];
+  if (st >= 0) {
+    // the tripping slot: the step is discarded, so the row kernel's t += 1 is taken back
+    if (st == *base + slot && blockIdx.x == 0 && threadIdx.x == 0) {
+      stop_seen[y] = st;
+      const_cast<int32_t*>(tab[y].counters)[0] -= 1;  // OptArgs only reads them elsewhere
+    }
+    return;
+  }
+  adam_tiles_body(tab[y]);
+}
+
+// learner y's Adam learning rate from now on: its OptArgs of the scheduled table (read by the
+// Adam launches of hwy_ppo_sched_step and hwy_ppo_sched_ctl_step alike), between whole slots
+__global__ void __launch_bounds__(64) ppo_sched_set_lr(OptArgs* tab, const float* __restrict__ lr,
+                                                       int G) {
+  const int y = blockIdx.x * 64 + threadIdx.x;
+  if (y < G) tab[y].lr = lr[y];
+}
+#endif  // HWY_PPO_CTL_TU
+
 // TL: the learners carry tile images; H = 256 then runs the compact body, as hwy_ppo_act does
 template <int NW, bool TL>
 __global__ void __launch_bounds__(64 * NW, 1) ppo_act_mix(const ActArgs* __restrict__ tab,
@@ -3829,8 +3938,10 @@ int hwy_ppo_debug_sections(unsigned long long* out, int reset) {
 // ---- grouped learners of different hidden widths (include/hwy_ppo.h): the step table is the
 // grouped one plus each learner's width class, [G RowArgs | G WgArgs | G OptArgs | G GroupLim |
 // G int32 H/64]; the act table is [G ActArgs | G int32 H/64].
+#if !defined(HWY_PPO_CTL_TU)
 static int64_t mix_qh_off(int G) { return grp_lim_off(G) + align256((int64_t)G * sizeof(GroupLim)); }
 static int64_t mix_act_qh_off(int G) { return align256((int64_t)G * sizeof(ActArgs)); }
+#endif
 
 // The mixed kernels' dynamic LDS passes the 64-KB default limit: raised here, to the widest
 // learner the kernel can hold, from the prepare calls (never inside a capture).
@@ -3839,6 +3950,7 @@ static bool mix_raise_lds(const void* kernel, int bytes) {
          hipSuccess;
 }
 
+#if !defined(HWY_PPO_CTL_TU)  // the control unit (ppo_ctl.o) holds hwy_ppo_sched_ctl_* / _set_lr only
 int64_t hwy_ppo_mixed_table_bytes(const hwy_ppo_dims* d, int G) {
   if (!d || G < 1) return -1;
   for (int g = 0; g < G; ++g)
@@ -4041,6 +4153,8 @@ int hwy_ppo_mixed_act(const hwy_ppo_mixed_act_plan* plan, const void* table, voi
   return rc;
 }
 
+#endif  // !HWY_PPO_CTL_TU
+
 // ---- grouped learners with schedules of their own (include/hwy_ppo.h: hwy_ppo_sched_*).  The
 // table is [G WgArgs | G OptArgs | G GroupLim | G int32 H/64 | G SchedRec | slot base word |
 // sum(nmb) RowArgs], each section 256-byte aligned: the per-learner sections come first, so the
@@ -4054,6 +4168,7 @@ static int64_t sch_rec_off(int G) { return sch_qh_off(G) + align256((int64_t)G *
 static int64_t sch_base_off(int G) { return sch_rec_off(G) + align256((int64_t)G * sizeof(SchedRec)); }
 static int64_t sch_row_off(int G) { return sch_base_off(G) + 256; }
 
+#if !defined(HWY_PPO_CTL_TU)
 static int sched_gcd(int a, int b) {
   while (b) {
     const int t = a % b;
@@ -4061,6 +4176,8 @@ static int sched_gcd(int a, int b) {
   }
   return a;
 }
+
+#endif
 
 static bool sched_plan_ok(const hwy_ppo_sched_plan* plan) {
   if (!plan || plan->G < 1 || plan->grid_wgrad < 1 || plan->grid_wsum < 1 || plan->grid_adam < 1 ||
@@ -4073,6 +4190,7 @@ static bool sched_plan_ok(const hwy_ppo_sched_plan* plan) {
   return true;
 }
 
+#if !defined(HWY_PPO_CTL_TU)
 int64_t hwy_ppo_sched_table_bytes(const hwy_ppo_dims* d, const int32_t* nmb, int G) {
   if (!d || !nmb || G < 1) return -1;
   int64_t rows = 0;
@@ -4215,6 +4333,127 @@ int hwy_ppo_sched_advance(const hwy_ppo_sched_plan* plan, void* table, int slots
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+#else  // HWY_PPO_CTL_TU
+
+// ---- the scheduled step with a per-learner KL stop, and the device-side learning rate
+// (include/hwy_ppo.h: hwy_ppo_sched_ctl_*, hwy_ppo_sched_set_lr).  The control block is
+// [G CtlRec | G int32 stop_at | G int32 stop_seen], each section 256-byte aligned.
+static int64_t ctl_stop_off(int G) { return align256((int64_t)G * sizeof(CtlRec)); }
+static int64_t ctl_seen_off(int G) { return ctl_stop_off(G) + align256((int64_t)G * sizeof(int32_t)); }
+static int64_t ctl_bytes(int G) { return ctl_seen_off(G) + align256((int64_t)G * sizeof(int32_t)); }
+
+int64_t hwy_ppo_sched_ctl_bytes(int G) { return G < 1 ? -1 : ctl_bytes(G); }
+
+int64_t hwy_ppo_sched_ctl_stopped_offset(int G) { return G < 1 ? -1 : ctl_stop_off(G); }
+
+int hwy_ppo_sched_ctl_prepare(const hwy_ppo_sched_plan* plan, const float* kl_limit,
+                              const int32_t* kl_on, void* ctl, void* stream) {
+  if (!sched_plan_ok(plan) || !kl_limit || !kl_on || !ctl) return -1;
+  const int G = plan->G;
+  for (int g = 0; g < G; ++g)
+    if (kl_on[g] != 0 && kl_on[g] != 1) return -1;
+  const int64_t bytes = ctl_bytes(G);
+  char* host = static_cast<char*>(calloc((size_t)bytes, 1));
+  if (!host) return -2;
+  for (int g = 0; g < G; ++g) {
+    CtlRec k;
+    k.kl_on = kl_on[g], k.kl_limit = kl_limit[g];
+    reinterpret_cast<CtlRec*>(host)[g] = k;
+  }
+  memset(host + ctl_stop_off(G), 0xff, (size_t)(bytes - ctl_stop_off(G)));  // -1: running
+  int rc = 0;
+  // the row kernels' dynamic LDS limit, as hwy_ppo_sched_prepare raises the plain kernels'
+  const int l8 = 4 * rows_lds_floats<8, 8, kRowTile>(), l4 = 4 * rows_lds_floats<7, 4, kRowTile>();
+  if (plan->present[0] &&
+      !mix_raise_lds((plan->grid_rows[0] & kPlanWide) ? (const void*)ppo_rows_ctl<8, true>
+                                                      : (const void*)ppo_rows_ctl<8, false>, l8))
+    rc = -2;
+  if (rc == 0 && plan->present[1] &&
+      !mix_raise_lds((plan->grid_rows[1] & kPlanWide) ? (const void*)ppo_rows_ctl<4, true>
+                                                      : (const void*)ppo_rows_ctl<4, false>, l4))
+    rc = -2;
+  hipStream_t s = (hipStream_t)stream;
+  if (rc == 0 && (hipMemcpyAsync(ctl, host, (size_t)bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+                  hipStreamSynchronize(s) != hipSuccess))
+    rc = -2;
+  free(host);
+  return rc;
+}
+
+int hwy_ppo_sched_ctl_begin(const hwy_ppo_sched_plan* plan, void* table, void* ctl, void* stream) {
+  if (!sched_plan_ok(plan) || !table || !ctl) return -1;
+  const int G = plan->G;
+  hipStream_t s = (hipStream_t)stream;
+  char* t = static_cast<char*>(table);
+  char* k = static_cast<char*>(ctl);
+  if (hipMemsetAsync(t + sch_base_off(G), 0, sizeof(int32_t), s) != hipSuccess) return -2;
+  return hipMemsetAsync(k + ctl_stop_off(G), 0xff, (size_t)(ctl_bytes(G) - ctl_stop_off(G)), s) ==
+                 hipSuccess
+             ? 0
+             : -2;
+}
+
+int hwy_ppo_sched_ctl_step(const hwy_ppo_sched_plan* plan, const void* table, void* ctl, int slot,
+                           void* stream) {
+  if (!sched_plan_ok(plan) || !table || !ctl || slot < 0) return -1;
+  const int G = plan->G;
+  const char* t = static_cast<const char*>(table);
+  const RowArgs* tr = reinterpret_cast<const RowArgs*>(t + sch_row_off(G));
+  const WgArgs* tw = reinterpret_cast<const WgArgs*>(t + sch_wg_off(G));
+  const OptArgs* to = reinterpret_cast<const OptArgs*>(t + sch_opt_off(G));
+  const GroupLim* tl = reinterpret_cast<const GroupLim*>(t + sch_lim_off(G));
+  const int* tq = reinterpret_cast<const int*>(t + sch_qh_off(G));
+  const SchedRec* tc = reinterpret_cast<const SchedRec*>(t + sch_rec_off(G));
+  const int* tb = reinterpret_cast<const int*>(t + sch_base_off(G));
+  char* k = static_cast<char*>(ctl);
+  const CtlRec* kc = reinterpret_cast<const CtlRec*>(k);
+  int* ka = reinterpret_cast<int*>(k + ctl_stop_off(G));
+  int* ks = reinterpret_cast<int*>(k + ctl_seen_off(G));
+  hipStream_t s = (hipStream_t)stream;
+  int rc = 0;
+  if (plan->present[0]) {
+    const dim3 g(plan->grid_rows[0] & ~kPlanWide, G);
+    if (plan->grid_rows[0] & kPlanWide)
+      hipLaunchKernelGGL((ppo_rows_ctl<8, true>), g, dim3(512), plan->lds_bytes[0], s, tr, tl, tq,
+                         tc, tb, ka, slot);
+    else
+      hipLaunchKernelGGL((ppo_rows_ctl<8, false>), g, dim3(512), plan->lds_bytes[0], s, tr, tl, tq,
+                         tc, tb, ka, slot);
+    rc |= hipGetLastError() == hipSuccess ? 0 : -2;
+  }
+  if (plan->present[1]) {
+    const dim3 g(plan->grid_rows[1] & ~kPlanWide, G);
+    if (plan->grid_rows[1] & kPlanWide)
+      hipLaunchKernelGGL((ppo_rows_ctl<4, true>), g, dim3(256), plan->lds_bytes[1], s, tr, tl, tq,
+                         tc, tb, ka, slot);
+    else
+      hipLaunchKernelGGL((ppo_rows_ctl<4, false>), g, dim3(256), plan->lds_bytes[1], s, tr, tl, tq,
+                         tc, tb, ka, slot);
+    rc |= hipGetLastError() == hipSuccess ? 0 : -2;
+  }
+  hipLaunchKernelGGL(ppo_wgrad_ctl, dim3(plan->grid_wgrad, G), dim3(64 * kWgWaves), 0, s, tw, tl,
+                     tc, tb, ka, slot);
+  rc |= hipGetLastError() == hipSuccess ? 0 : -2;
+  hipLaunchKernelGGL(ppo_wsum_ctl, dim3(plan->grid_wsum, G), dim3(256), 0, s, tw, tl, tc, tb, kc,
+                     ka, ks, slot);
+  rc |= hipGetLastError() == hipSuccess ? 0 : -2;
+  hipLaunchKernelGGL(ppo_adam_tiles_ctl, dim3(plan->grid_adam, G), dim3(256), 0, s, to, tl, tc, tb,
+                     ka, ks, slot);
+  rc |= hipGetLastError() == hipSuccess ? 0 : -2;
+  return rc;
+}
+
+int hwy_ppo_sched_set_lr(const hwy_ppo_sched_plan* plan, void* table, const float* lr_dev,
+                         void* stream) {
+  if (!sched_plan_ok(plan) || !table || !lr_dev) return -1;
+  const int G = plan->G;
+  char* t = static_cast<char*>(table);
+  hipLaunchKernelGGL(ppo_sched_set_lr, dim3((G + 63) / 64), dim3(64), 0, (hipStream_t)stream,
+                     reinterpret_cast<OptArgs*>(t + sch_opt_off(G)), lr_dev, G);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+#endif  // HWY_PPO_CTL_TU
 #endif  // HWY_PPO_MIXED_TU
 
 }  // extern "C"

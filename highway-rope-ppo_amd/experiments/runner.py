@@ -95,12 +95,15 @@ class ExperimentRunner:
     def _create_agent(self, state_dim, action_dim, hp, logger, device, extra=None,
                       process_group=None, seed=None):
         extra = extra or {}
+        # the KL target and the lr schedule (PPOAgent): passed only where a cell sets them
+        control = {k: extra[k] for k in ("target_kl", "lr_anneal_updates")
+                   if extra.get(k) is not None}
         return PPOAgent(state_dim=state_dim, action_dim=action_dim, lr=hp.lr, gamma=hp.gamma,
                         lam=hp.lam, eps_clip=hp.clip_eps, value_coef=hp.value_coef,
                         entropy_coef=hp.entropy_coef, max_grad_norm=hp.max_grad_norm,
                         epochs=hp.epochs, batch_size=hp.batch_size, hidden_dim=hp.hidden_dim,
                         logger=logger, device=device, process_group=process_group,
-                        num_minibatches=extra.get("num_minibatches"), seed=seed)
+                        num_minibatches=extra.get("num_minibatches"), seed=seed, **control)
 
     def launch(self, exp: Experiment) -> Dict[str, Any]:
         results: Dict[str, Any] = {"experiment_name": exp.name, "status": "FAILED"}

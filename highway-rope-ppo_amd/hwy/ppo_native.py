@@ -731,6 +731,22 @@ def _bind_group(L):
         L.hwy_ppo_sched_step.restype = ctypes.c_int
         L.hwy_ppo_sched_advance.argtypes = [planp, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.hwy_ppo_sched_advance.restype = ctypes.c_int
+    # the scheduled step's KL stop and device-side learning rate (hwy_ppo_sched_ctl_*,
+    # hwy_ppo_sched_set_lr), likewise only where the library has them
+    if hasattr(L, "hwy_ppo_sched_ctl_step"):
+        planp = ctypes.POINTER(PpoSchedPlan)
+        vp = ctypes.c_void_p
+        for f in (L.hwy_ppo_sched_ctl_bytes, L.hwy_ppo_sched_ctl_stopped_offset):
+            f.argtypes, f.restype = [ctypes.c_int], ctypes.c_int64
+        L.hwy_ppo_sched_ctl_prepare.argtypes = [planp, ctypes.POINTER(ctypes.c_float),
+                                                ctypes.POINTER(ctypes.c_int32), vp, vp]
+        L.hwy_ppo_sched_ctl_prepare.restype = ctypes.c_int
+        L.hwy_ppo_sched_ctl_begin.argtypes = [planp, vp, vp, vp]
+        L.hwy_ppo_sched_ctl_begin.restype = ctypes.c_int
+        L.hwy_ppo_sched_ctl_step.argtypes = [planp, vp, vp, ctypes.c_int, vp]
+        L.hwy_ppo_sched_ctl_step.restype = ctypes.c_int
+        L.hwy_ppo_sched_set_lr.argtypes = [planp, vp, vp, vp]
+        L.hwy_ppo_sched_set_lr.restype = ctypes.c_int
     L._grp_bound = True
     return L
 
@@ -745,6 +761,12 @@ def _need_sched(L):
     if not hasattr(L, "hwy_ppo_sched_step"):
         raise RuntimeError("this libhwy build has no hwy_ppo_sched_* entry points (learners of "
                            "different batch_size or epochs need the product library)")
+
+
+def _need_ctl(L):
+    if not hasattr(L, "hwy_ppo_sched_ctl_step"):
+        raise RuntimeError("this libhwy build has no hwy_ppo_sched_ctl_* entry points (target_kl "
+                           "and lr_anneal_updates need the product library)")
 
 
 class GroupAct:
@@ -861,14 +883,29 @@ class GroupStep:
     (``self.sched``, hwy_ppo_sched_*): ONE table holds the whole update's schedule.  After
     ``begin()``, ``step(s)`` issues slot s -- every learner still active runs its own minibatch
     s % nmb -- for s < ``max_steps``; in a captured graph of P slots ``step(0..P-1)`` then
-    ``advance(P)`` moves the table's slot base, so the same graph replays for every P slots."""
+    ``advance(P)`` moves the table's slot base, so the same graph replays for every P slots.
+
+    A learner whose agent has a KL target (``agent.kl_limit``) or an lr schedule
+    (``agent.lr_anneal_updates``) makes the group run scheduled whatever its schedules, G = 1
+    included.  With a KL target ``begin()`` / ``step()`` take the control entry points
+    (hwy_ppo_sched_ctl_*): a learner whose minibatch KL passes its limit drops that step and sits
+    the rest of the update out; ``stopped_at`` (device int32 [G]) is the slot that tripped or
+    -1.  ``apply_lr()`` feeds every learner's current learning rate (a device float of its
+    agent) to the Adam launches (hwy_ppo_sched_set_lr), without a host round trip."""
 
     def __init__(self, fused):
         self.fused = list(fused)
         self.G = len(self.fused)
         F0 = self.fused[0]
         self.L = _bind_group(F0.L)
-        self.sched = len({(F.mb, F.nmb, F.agent.epochs) for F in self.fused}) > 1
+        self.kl_limits = [getattr(F.agent, "kl_limit", None) for F in self.fused]
+        self.ctl = any(k is not None for k in self.kl_limits)
+        self.lr_sched = any(getattr(F.agent, "lr_anneal_updates", None) for F in self.fused)
+        self.ctl_block = self.stopped_at = self._lr_buf = None
+        if self.ctl or self.lr_sched:
+            _need_ctl(self.L)
+        self.sched = (len({(F.mb, F.nmb, F.agent.epochs) for F in self.fused}) > 1
+                      or self.ctl or self.lr_sched)
         self.mixed = any(F.H != F0.H for F in self.fused)
         self.tables: List[torch.Tensor] = []
         self.plans: list = []
@@ -911,6 +948,20 @@ class GroupStep:
             self.tables, self.plans = [t], [plan]
             self.launches_per_step = plan.launches
             self.max_steps, self.period = int(plan.max_steps), int(plan.period)
+            if self.ctl:
+                G = self.G
+                lim = (ctypes.c_float * G)(*[0.0 if k is None else k for k in self.kl_limits])
+                on = (ctypes.c_int32 * G)(*[int(k is not None) for k in self.kl_limits])
+                blk = torch.empty(int(self.L.hwy_ppo_sched_ctl_bytes(G)), dtype=torch.uint8,
+                                  device=dev)
+                check(self.L.hwy_ppo_sched_ctl_prepare(ctypes.byref(plan), lim, on, blk.data_ptr(),
+                                                       stream_ptr()), "hwy_ppo_sched_ctl_prepare")
+                off = int(self.L.hwy_ppo_sched_ctl_stopped_offset(G))
+                self.ctl_block, self.stopped_at = blk, blk[off:off + 4 * G].view(torch.int32)
+            if self.lr_sched:
+                # a learner without a schedule keeps the float32 its table was prepared with
+                self._lr_buf = torch.tensor([float(arr[g].lr) for g in range(self.G)],
+                                            dtype=torch.float32, device=dev)
             return
         nmb = len(per_learner_args[0])
         for i in range(nmb):
@@ -931,8 +982,32 @@ class GroupStep:
             self.tables.append(t)
             self.plans.append(plan)
 
+    def set_lr(self, lr_dev: torch.Tensor) -> None:
+        """Scheduled mode: the Adam launches use lr_dev[g] (device float32 [G]) from now on."""
+        assert lr_dev.is_cuda and lr_dev.dtype == torch.float32 and lr_dev.numel() == self.G
+        self._lr_keep = lr_dev
+        check(self.L.hwy_ppo_sched_set_lr(ctypes.byref(self.plans[0]), self.tables[0].data_ptr(),
+                                          lr_dev.data_ptr(), stream_ptr()), "hwy_ppo_sched_set_lr")
+
+    def apply_lr(self) -> None:
+        """The learners' current learning rates (agent.lr_device(): one device float, indexed out
+        of the agent's precomputed schedule) into the table; nothing without an lr schedule."""
+        if not self.lr_sched:
+            return
+        for g, F in enumerate(self.fused):
+            src = F.agent.lr_device() if getattr(F.agent, "lr_anneal_updates", None) else None
+            if src is not None:
+                self._lr_buf[g:g + 1].copy_(src)
+        self.set_lr(self._lr_buf)
+
     def begin(self) -> None:
-        """Scheduled mode: the start of an update (slot base 0)."""
+        """Scheduled mode: the start of an update (slot base 0; the KL stops cleared)."""
+        if self.ctl:
+            check(self.L.hwy_ppo_sched_ctl_begin(ctypes.byref(self.plans[0]),
+                                                 self.tables[0].data_ptr(),
+                                                 self.ctl_block.data_ptr(), stream_ptr()),
+                  "hwy_ppo_sched_ctl_begin")
+            return
         check(self.L.hwy_ppo_sched_begin(ctypes.byref(self.plans[0]), self.tables[0].data_ptr(),
                                          stream_ptr()), "hwy_ppo_sched_begin")
 
@@ -943,6 +1018,12 @@ class GroupStep:
 
     def step(self, i: int) -> None:
         """Minibatch i of every learner; scheduled: slot (slot base + i) of the update."""
+        if self.ctl:
+            check(self.L.hwy_ppo_sched_ctl_step(ctypes.byref(self.plans[0]),
+                                                self.tables[0].data_ptr(),
+                                                self.ctl_block.data_ptr(), int(i), stream_ptr()),
+                  "hwy_ppo_sched_ctl_step")
+            return
         if self.sched:
             check(self.L.hwy_ppo_sched_step(ctypes.byref(self.plans[0]), self.tables[0].data_ptr(),
                                             int(i), stream_ptr()), "hwy_ppo_sched_step")

@@ -324,7 +324,11 @@ class _Learner:
         with graph_capture(self.g_opt):
             self._opt()
 
-    def step(self, idx: torch.Tensor):
+    def step(self, idx: torch.Tensor, kl_limit: Optional[float] = None) -> bool:
+        """One minibatch step.  With ``kl_limit`` (PPOAgent.target_kl's rule, on the host): after
+        the backward pass the minibatch's mean KL, the float32 the metrics row holds, is read
+        back, and unless kl <= kl_limit the step is dropped -- no optimizer step, the row index
+        stays on the tripping row -- and True is returned."""
         self.idx.copy_(idx)
         if self.use_graph:
             if self.g_fwd is None:
@@ -346,12 +350,21 @@ class _Learner:
                                 vv.zero_()
                     self.row.copy_(row)
             self.g_fwd.replay()
+            if kl_limit is not None and self._trips(kl_limit):
+                return True
             self._allreduce()
             self.g_opt.replay()
         else:
             self._fwd_bwd()
+            if kl_limit is not None and self._trips(kl_limit):
+                return True
             self._allreduce()
             self._opt()
+        return False
+
+    def _trips(self, kl_limit: float) -> bool:
+        kl = float(self.metrics[int(self.row), METRIC_KEYS.index("approx_kl")])  # exact float32
+        return not (kl <= kl_limit)
 
 
 class _PendingMetrics:
@@ -375,6 +388,9 @@ class _PendingMetrics:
         if self._event is not None:
             self._event.synchronize()
         vals = self._host.tolist()
+        ctl = None
+        if len(vals) > len(METRIC_KEYS) + 1:  # target_kl / lr_anneal_updates: three more values
+            ctl, vals = vals[len(METRIC_KEYS) + 1:], vals[:len(METRIC_KEYS) + 1]
         m = dict(zip(METRIC_KEYS, vals[:-1]))
         out = {
             "loss": m["loss"],
@@ -390,6 +406,10 @@ class _PendingMetrics:
             "clip_frac=%.3f kl=%.5f explained_var=%.3f", out["loss"], out["policy_loss"],
             out["value_loss"], out["entropy"], out["clip_fraction"], out["approx_kl"],
             out["explained_variance"])
+        if ctl is not None:
+            out["steps_applied"] = int(ctl[0])
+            out["kl_stopped"] = bool(ctl[1])
+            out["approx_kl_last"] = ctl[2]
         self._out = out
         return out
 
@@ -402,8 +422,31 @@ class PPOAgent:
                  logger: Optional[logging.Logger] = None,
                  device: torch.device = torch.device("cpu"),
                  num_minibatches: Optional[int] = None, use_graphs: bool = True,
-                 process_group=None, seed: Optional[int] = None, backend: str = "auto"):
+                 process_group=None, seed: Optional[int] = None, backend: str = "auto",
+                 target_kl: Optional[float] = None, lr_anneal_updates: Optional[int] = None):
+        """``target_kl`` = tau: the Stable-Baselines3 early stop, checked per minibatch -- a
+        minibatch whose mean approx_kl is not <= float32(1.5 tau) is not applied and ends the
+        update.  ``lr_anneal_updates`` = U: update u = 0, 1, ... steps with
+        float32(lr max(1 - u / U, 0)).  Both default to off, work on update_rollout (the fused
+        backend runs them inside the captured update, backend="torch" on the host) and are
+        refused with a process group and by the one-env update()."""
         self.device = torch.device(device)
+        for name, v in (("target_kl", target_kl), ("lr_anneal_updates", lr_anneal_updates)):
+            if v is not None and process_group is not None:
+                raise ValueError(f"{name} is not supported with a process group")
+        if target_kl is not None and not float(target_kl) >= 0.0:
+            raise ValueError(f"target_kl must be >= 0, got {target_kl!r}")
+        if lr_anneal_updates is not None and int(lr_anneal_updates) < 1:
+            raise ValueError(f"lr_anneal_updates must be >= 1, got {lr_anneal_updates!r}")
+        self.target_kl = None if target_kl is None else float(target_kl)
+        self.kl_limit = None if target_kl is None else float(np.float32(1.5 * float(target_kl)))
+        self.lr_anneal_updates = None if lr_anneal_updates is None else int(lr_anneal_updates)
+        self.lr0 = float(lr)
+        self._lr_table = self._lr_cell = None
+        self._ctl_runner = None
+        self._last_ctl = None
+        # table prepares / graph captures of the control path (ppo/group.py:_run_group_steps)
+        self.stats = {"update_prepare": 0, "update_capture": 0}
         if backend not in ("auto", "hip", "torch"):
             raise ValueError(f"backend must be auto|hip|torch, got {backend!r}")
         # "hip": update_rollout runs the fused HIP minibatch step (hwy/ppo_native.py);
@@ -506,13 +549,53 @@ class PPOAgent:
         return ok
 
     # ------------------------------------------------------------------ metrics
+    @property
+    def controlled(self) -> bool:
+        """A KL target or an lr schedule is set."""
+        return self.kl_limit is not None or self.lr_anneal_updates is not None
+
+    def lr_at(self, u: int) -> float:
+        """The learning rate of update u: float32(lr max(1 - u / U, 0)); lr without a schedule."""
+        U = self.lr_anneal_updates
+        if U is None:
+            return self.lr0
+        return float(np.float32(self.lr0 * max(1.0 - u / U, 0.0)))
+
+    def lr_device(self) -> Optional[torch.Tensor]:
+        """This update's learning rate as one device float: element min(updates, U) of the
+        schedule precomputed on the device (a view, no host round trip); None without one."""
+        U = self.lr_anneal_updates
+        if U is None:
+            return None
+        if self._lr_table is None:
+            self._lr_table = torch.tensor([self.lr_at(u) for u in range(U + 1)],
+                                          dtype=torch.float32, device=self.device)
+        u = min(self.updates, U)
+        return self._lr_table[u:u + 1]
+
+    def _torch_lr(self) -> None:
+        """backend="torch": this update's learning rate into agent.optimizer (a device scalar the
+        captured optimizer step reads on cuda, a float on the CPU)."""
+        if self.lr_anneal_updates is None:
+            return
+        g = self.optimizer.param_groups[0]
+        if self.device.type != "cuda":
+            g["lr"] = self.lr_at(self.updates)
+            return
+        if self._lr_cell is None:
+            self._lr_cell = torch.zeros((), dtype=torch.float32, device=self.device)
+        self._lr_cell.copy_(self.lr_device()[0])
+        g["lr"] = self._lr_cell
+
     def _finish_metrics(self, rows: torch.Tensor, sizes: List[int], values, returns,
-                        deferred: bool = False):
+                        deferred: bool = False, ctl=None):
         """Aggregate per-minibatch rows like ppo/agent.py:263-287 (epoch means, then the mean
         over epochs, in float64) plus explained variance (:272-280).  Computed on the rows'
         device with one host transfer at the end (the clip count becomes a fraction by dividing
         by each minibatch's size, as the reference's per-batch clip_frac).  ``deferred``: return
         a pending result whose host copy is still in flight (see _PendingMetrics)."""
+        if ctl is not None:
+            return self._finish_metrics_ctl(rows, sizes, values, returns, deferred, ctl)
         nb = len(sizes)
         r = torch.as_tensor(rows).to(torch.float64)[: self.epochs * nb].view(self.epochs, nb, -1)
         ci = METRIC_KEYS.index("clip_fraction")
@@ -524,6 +607,35 @@ class PPOAgent:
             ev = torch.where(var_y > 0, 1 - torch.var(returns - values) / var_y,
                              torch.zeros_like(var_y)).to(torch.float64).to(means.device)
         pending = _PendingMetrics(self.logger, torch.cat([means, ev.view(1)]))
+        return pending if deferred else pending.result()
+
+    def _finish_metrics_ctl(self, rows, sizes, values, returns, deferred, ctl):
+        """_finish_metrics with a KL target or an lr schedule: ctl = (rows_written, stopped), two
+        0-d tensors on the rows' device (the fused learner's counters[1] and stopped_at >= 0), so
+        nothing is read back before the one transfer.  An update that applied k steps wrote k rows,
+        plus the tripping row when it stopped.  The six means are float64 means over the k applied
+        rows (the tripping row's alone when k = 0); three values follow the explained variance:
+        steps_applied, kl_stopped, approx_kl_last (the last written row's KL)."""
+        nb = len(sizes)
+        steps = self.epochs * nb
+        r = torch.as_tensor(rows).to(torch.float64)[:steps]
+        ci, ki = METRIC_KEYS.index("clip_fraction"), METRIC_KEYS.index("approx_kl")
+        inv = torch.tensor([1.0 / s for s in sizes], dtype=torch.float64,
+                           device=r.device).repeat(self.epochs)
+        r = torch.cat([r[:, :ci], r[:, ci:ci + 1] * inv.view(-1, 1), r[:, ci + 1:]], -1)
+        written, stopped = ctl
+        written = written.to(torch.int64).clamp(1, steps)
+        applied = written - stopped.to(torch.int64)
+        keep = torch.arange(steps, device=r.device) < applied.clamp_min(1)
+        # where, not a product: rows past the last written one may hold anything
+        means = torch.where(keep.view(-1, 1), r, torch.zeros_like(r)).sum(0) / keep.sum()
+        kl_last = r.index_select(0, (written - 1).view(1))[0, ki]
+        with torch.no_grad():
+            var_y = torch.var(returns)
+            ev = torch.where(var_y > 0, 1 - torch.var(returns - values) / var_y,
+                             torch.zeros_like(var_y)).to(torch.float64).to(means.device)
+        tail = torch.stack([applied.to(torch.float64), stopped.to(torch.float64), kl_last])
+        pending = _PendingMetrics(self.logger, torch.cat([means, ev.view(1), tail]))
         return pending if deferred else pending.result()
 
     def _learner_for(self, n: int, mb: int, steps: int, graph: bool) -> _Learner:
@@ -550,6 +662,9 @@ class PPOAgent:
     def _run_epochs(self, states, pre_tanh, old_logp, adv, ret, batches: List[torch.Tensor]):
         self._adam_to("torch")
         self._torch_param_writes += 1  # retires every fused tile image (see __init__)
+        self._torch_lr()
+        lim = self.kl_limit
+        self._last_ctl = None
         n = states.shape[0]
         sizes = {int(b.numel()) for b in batches}
         mb = max(sizes)
@@ -562,20 +677,46 @@ class PPOAgent:
                     L = self._learner_for(n, int(b.numel()), 1, False)
                     L.bind(states, pre_tanh, old_logp, adv, ret)
                     L.row.zero_()
-                    L.step(b)
+                    tripped = L.step(b, lim)
                     rows.append(L.metrics[0].clone())
+                    if tripped:
+                        break
+                else:
+                    continue
+                break
+            if self.controlled:
+                self._last_ctl = self._host_ctl(len(rows), tripped, states.device)
+                rows += [torch.zeros_like(rows[0])] * (steps - len(rows))
             return torch.stack(rows)
         L = self._learner_for(n, mb, steps, self.use_graphs)
         L.bind(states, pre_tanh, old_logp, adv, ret)
         L.row.zero_()
+        done = tripped = 0
         for _ in range(self.epochs):
             for b in batches:
-                L.step(b)
+                tripped = L.step(b, lim)
+                done += 1
+                if tripped:
+                    break
+            if tripped:
+                break
+        if self.controlled:
+            self._last_ctl = self._host_ctl(done, tripped, states.device)
         return L.metrics
+
+    @staticmethod
+    def _host_ctl(written: int, tripped, device):
+        """(rows written, stopped) of a host-side update, as _finish_metrics_ctl takes them."""
+        return (torch.tensor(int(written), dtype=torch.int64, device=device),
+                torch.tensor(bool(tripped), device=device))
 
     # ------------------------------------------------------------------ reference update
     def update(self, last_value: float = 0.0):
         """Clipped-PPO update over the list memory (ppo/agent.py:196-308)."""
+        for name, v in (("target_kl", self.target_kl), ("lr_anneal_updates", self.lr_anneal_updates)):
+            if v is not None:
+                raise ValueError(f"{name} is not supported by the one-env update(); use "
+                                 "update_rollout")
         states, actions, pre_tanh, old_log_probs = self.memory.get_tensors()
         adv_np, ret_np = self.memory.compute_advantages(self.gamma, self.lam, last_value)
         advantages = torch.as_tensor(adv_np, device=self.device)
@@ -637,7 +778,10 @@ class PPOAgent:
             F_adv.copy_(adv)
             F_ret.copy_(ret)
             F_perm.copy_(perm)
-            rows = F.run(states, pre_tanh, old_lp, F_adv, F_ret, F_perm)
+            if self.controlled:
+                rows = self._run_fused_ctl(F, states, pre_tanh, old_lp, F_adv, F_ret, F_perm)
+            else:
+                rows = F.run(states, pre_tanh, old_lp, F_adv, F_ret, F_perm)
         else:
             # one partition for all epochs (ppo/agent.py:205); a short last minibatch takes the
             # reference's ragged path (eager torch steps at the exact sizes)
@@ -654,7 +798,61 @@ class PPOAgent:
         if not return_metrics:
             return rows
         return self._finish_metrics(rows, sizes, buf.values.reshape(n), ret,
-                                    deferred=return_metrics == "deferred")
+                                    deferred=return_metrics == "deferred",
+                                    ctl=self._last_ctl if self.controlled else None)
+
+    def _run_fused_ctl(self, F, states, pre_tanh, old_lp, adv, ret, perm) -> torch.Tensor:
+        """FusedPPO.run for a learner with a KL target or an lr schedule: the whole update as a
+        one-learner scheduled GroupStep (hwy_ppo_sched_ctl_*, hwy_ppo_sched_set_lr), captured and
+        replayed like a grouped update.  An applied step is the solo step bit for bit."""
+        from ppo.group import _run_group_steps
+
+        mb, nmb = F.mb, F.nmb
+        self.check_control_dims(mb, nmb)
+        key = (states.data_ptr(), pre_tanh.data_ptr(), old_lp.data_ptr(), adv.data_ptr(),
+               ret.data_ptr(), perm.data_ptr()) + F._scalar_key() + (self.kl_limit,
+                                                                    self.lr_anneal_updates)
+        run = self._ctl_runner
+        if run is None or run[0] != (id(F), key):
+            args = [F._args(states, pre_tanh, old_lp, adv, ret, perm.data_ptr() + i * mb * 8)
+                    for i in range(nmb)]
+            run = [(id(F), key), args, None]
+            self._ctl_runner = run
+        args = run[1]
+        F._last_args, F._last_inputs = args, (states, pre_tanh, old_lp, adv, ret, perm)
+        F.counters[1].zero_()
+        F.sync_params(args[0])
+        ctx = {"fused": [F], "args": [args], "key": key, "mb": mb, "nmb": nmb,
+               "epochs": self.epochs}
+        run[2] = _run_group_steps(self, [ctx], run[2])
+        step = run[2][1]
+        F._tiles_version = F._param_versions()
+        self._last_ctl = self._fused_ctl(F, step, 0)
+        return F.metrics
+
+    def check_control_dims(self, mb: int, nmb: int = 1) -> None:
+        """ValueError, naming the option, unless minibatches of mb rows can run the scheduled
+        step a KL target / lr schedule needs: the fused path at 16-row tiles (host-only: the
+        table-size query of the C ABI, no device call)."""
+        import ctypes
+
+        from hwy.ppo_native import PpoDims, _bind, _bind_group, lib
+
+        L = _bind_group(_bind(lib()))
+        sd = self.actor_critic.shared[0].weight
+        dims = (PpoDims * 1)(PpoDims(int(mb), sd.shape[1], sd.shape[0], 2))
+        if L.hwy_ppo_sched_table_bytes(dims, (ctypes.c_int32 * 1)(int(nmb)), 1) < 0:
+            name = "target_kl" if self.target_kl is not None else "lr_anneal_updates"
+            raise ValueError(f"{name} needs the fused step at 16-row tiles (state_dim % 4 == 0 up "
+                             f"to 1024, minibatches below 64 x CUs rows); got minibatches of "
+                             f"{mb} rows, state_dim {sd.shape[1]}")
+
+    @staticmethod
+    def _fused_ctl(F, step, g: int):
+        """(rows written, stopped) of learner g of a scheduled update, on the device."""
+        stopped = (step.stopped_at[g] >= 0 if step.stopped_at is not None
+                   else torch.zeros((), dtype=torch.bool, device=F.counters.device))
+        return F.counters[1], stopped
 
     def minibatch_sizes(self, n: int) -> List[int]:
         """The minibatch partition of an n-sample update; every sample is used once per epoch.

@@ -247,8 +247,11 @@ class ExperimentGroup:
             if return_metrics:
                 vals = buf.values[:, g * E:(g + 1) * E].contiguous().reshape(n)
                 rets = ctx["ret"][:, g * E:(g + 1) * E].contiguous().reshape(n)
+                ctl = None
+                if ag.controlled:  # a KL target / lr schedule: the applied rows only
+                    ctl = ag._fused_ctl(F, ctx["step"], ctx.get("first", 0) + g)
                 out.append(ag._finish_metrics(F.metrics, ctx["sizes"], vals, rets,
-                                              deferred=return_metrics == "deferred"))
+                                              deferred=return_metrics == "deferred", ctl=ctl))
         self.iterations += 1
         buf.states[0].copy_(self.next0 if self.episode_schedule == "reference" else buf.states[T])
         return out if return_metrics else None
@@ -356,7 +359,12 @@ def _run_group_steps(owner, ctxs, runner):
         step.prepare(args)
         runner = (key, step, None)
     _, step, graph = runner
+    first = 0
+    for c in ctxs:  # post_update reads the KL stops of learners first .. first + G from it
+        c["step"], c["first"] = step, first
+        first += len(c["fused"])
     if step.sched:
+        step.apply_lr()  # lr schedules: this update's rates, device to device (not captured)
         want = update_schedule([c["nmb"] for c in ctxs], [c["epochs"] for c in ctxs])
         if (step.max_steps, step.period) != want:
             raise RuntimeError(f"scheduled step: the table's schedule {step.max_steps, step.period} "

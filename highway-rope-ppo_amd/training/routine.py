@@ -269,11 +269,26 @@ def _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_hist
     head, tail = "", ""
     if "episode_crashed" in metrics_history:  # episode_stats runs only
         head, tail = ",crash_rate", f",{crash_rate(metrics_history['episode_crashed']):.4f}"
+    for k in CONTROL_KEYS:  # runs with a KL target / an lr schedule only
+        if k in metrics_history:
+            head, tail = f"{head},{k}", f"{tail},{metrics_history[k]}"
     with open(csv_path, "w") as f:
         f.write(f"experiment,final_reward,max_reward,steps,best_model,plot{head}\n")
         f.write(f"{experiment_name},{avg_rewards[-1]:.4f},{max(avg_rewards):.4f},{total_steps},"
                 f"{best_model_path},{os.path.basename(plot_path)}{tail}\n")
     logger.info(f"{exp_prefix} Summary CSV saved to {csv_path}")
+
+
+CONTROL_KEYS = ("target_kl", "lr_anneal_updates")
+
+
+def _book_controls(mh, agent) -> None:
+    """The agent's KL target and lr schedule into the metrics, where set (the default's metrics
+    stay what they were, as with truncation)."""
+    for k in CONTROL_KEYS:
+        v = getattr(agent, k, None)
+        if v is not None:
+            mh[k] = v
 
 
 STATS_KEYS = ("episode_lengths", "episode_crashed", "episode_mean_speed", "episode_lane_changes")
@@ -385,6 +400,11 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         if getattr(agent, "_dist", None) is not None:
             raise ValueError("episode_stats does not run over a process group")
 
+    for k in CONTROL_KEYS:
+        if getattr(agent, k, None) is not None and not _is_vector(env):
+            raise ValueError(f"{k} needs a HighwayVecEnv (num_envs > 1, or make_env's vector_env "
+                             "key for one env); the one-env reference loop does not take it")
+
     if check_episode_schedule(episode_schedule) == "reference":
         if getattr(agent, "_dist", None) is not None:
             raise ValueError("episode_schedule='reference' does not run over a process group")
@@ -410,6 +430,7 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         metrics_history.update({k: [] for k in STATS_KEYS})
     if truncation != "terminal":  # the default's metrics stay what they were
         metrics_history["truncation"] = truncation
+    _book_controls(metrics_history, agent)
     start_time = time.time()
     artifacts_dir = ensure_artifacts_dir()
     checkpoint_dir = os.path.join(artifacts_dir, "checkpoints")
@@ -635,6 +656,7 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
               "eval_episode_numbers": [], "timestamps": []}
         if episode_stats:
             mh.update({k: [] for k in STATS_KEYS})
+        _book_controls(mh, grp.agents[j])
         tracker = _EvalTracker(grp.solo_envs[j], grp.agents[j], int(exp_seeds[k]),
                                target_reward, checkpoint_dir, name, mh, logger, prefix, start_time)
         logger.info(f"{prefix} Performing initial evaluation...")

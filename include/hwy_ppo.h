@@ -247,6 +247,47 @@ int hwy_ppo_sched_begin(const hwy_ppo_sched_plan* plan, void* table, void* strea
 int hwy_ppo_sched_step(const hwy_ppo_sched_plan* plan, const void* table, int slot, void* stream);
 int hwy_ppo_sched_advance(const hwy_ppo_sched_plan* plan, void* table, int slots, void* stream);
 
+/* ---- The scheduled update with a per-learner KL stop: hwy_ppo_sched_step with a control block
+ * beside the table.  Learner y has kl_on[y] (0 / 1) and kl_limit[y].  In a slot in which y is
+ * active, after the weight-gradient launch has written the step's metrics row, kl = column 5 of
+ * that row exactly as stored; y TRIPS iff kl_on && !(kl <= kl_limit) (a NaN trips).  The tripping
+ * step is discarded: its slice-sum and Adam launches write nothing of y (params, adam_m, adam_v,
+ * tile image), and counters[0] ends as if the step had not run.  From then on y sits every slot
+ * of the update out, untouched, as a learner whose epochs are done does.  After an update that
+ * applied k steps of y: counters[0] += k, counters[1] += k + 1 (the tripping row, whose six
+ * metrics are valid; later rows are not written); without a trip, and always with kl_on == 0, y
+ * is bit for bit what hwy_ppo_sched_step makes it.  The trip state is cleared by
+ * hwy_ppo_sched_ctl_begin only: it survives graph replays and hwy_ppo_sched_advance.
+ *
+ * Control block (hwy_ppo_sched_ctl_bytes(G) bytes of device memory, sections 256-byte aligned):
+ *   byte 0                           G x { int32 kl_on; float kl_limit; }
+ *   hwy_ppo_sched_ctl_stopped_offset(G) = round_up_256(8 G)
+ *                                    G x int32 stopped_at: the slot that tripped, -1 if none
+ *   + round_up_256(4 G)              G x int32, the library's own copy of stopped_at
+ * stopped_at[y] is written by one thread's ordinary store in the tripping slot's slice-sum launch
+ * and is stable once the update's work on the stream is done: the host reads it with the copy it
+ * makes of the metrics anyway, no further synchronisation.  No step launch reads a control word
+ * that the same launch writes (a word written in launch n is read by launches after n only).
+ *
+ * hwy_ppo_sched_ctl_prepare is synchronous (host arrays; it waits for `stream`) and not
+ * capturable; begin (= hwy_ppo_sched_begin + clearing the trip state) and step are asynchronous,
+ * allocate nothing and are hipGraph-capturable; hwy_ppo_sched_advance serves both step calls.
+ *
+ * hwy_ppo_sched_set_lr: from then on (stream order) the Adam launches of hwy_ppo_sched_step and
+ * hwy_ppo_sched_ctl_step on `table` use lr_dev[y] (device floats) as learner y's learning rate --
+ * an update after it is bit for bit one whose table was prepared with args.lr = that value.
+ * Asynchronous, capturable; issue it between whole slots.
+ * -1 bad arguments (before any device call), -2 HIP error. */
+int64_t hwy_ppo_sched_ctl_bytes(int G);
+int64_t hwy_ppo_sched_ctl_stopped_offset(int G);
+int hwy_ppo_sched_ctl_prepare(const hwy_ppo_sched_plan* plan, const float* kl_limit /*[G]*/,
+                              const int32_t* kl_on /*[G]*/, void* ctl, void* stream);
+int hwy_ppo_sched_ctl_begin(const hwy_ppo_sched_plan* plan, void* table, void* ctl, void* stream);
+int hwy_ppo_sched_ctl_step(const hwy_ppo_sched_plan* plan, const void* table, void* ctl, int slot,
+                           void* stream);
+int hwy_ppo_sched_set_lr(const hwy_ppo_sched_plan* plan, void* table, const float* lr_dev /*[G]*/,
+                         void* stream);
+
 /* Build flags of this library: bit 0 = development knobs compiled in (HWY_DEV_KNOBS: the
  * HWY_WG_BAL / HWY_ROWS_RT / HWY_WG_FILL environment variables are read), bit 1 = section clocks
  * (HWY_SECTION_PROFILE).  A product build returns 0 and reads no environment variable. */
