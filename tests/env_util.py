@@ -14,6 +14,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 import env_model as em
+import rng_model as rm
 from hwy import _abi
 from oracle.oracle import OracleEnv
 from parity_util import diff_state, make_cfg, pe_table_for, policy_actions
@@ -48,12 +49,16 @@ class HipEnv:
         self.el = torch.zeros(self.E, dtype=torch.int32, device=DEV)
         self._info = None
 
-    def reset(self, seeds=None):
+    def reset(self, seeds=None, mask=None):
+        """hwy_reset: seeds [E] (any integer dtype, taken as 64-bit words) or None for the
+        schedule; mask [E] (nonzero = reset) or None for every env"""
         from hwy.native import check, lib, ptr
 
         torch = self.torch
-        s = None if seeds is None else torch.as_tensor(seeds.astype(np.int64), device=self.dev)
-        check(lib().hwy_reset(self.h, ptr(s), None, ptr(self.obs), None), "hwy_reset")
+        s = None if seeds is None else torch.as_tensor(
+            np.ascontiguousarray(seeds).astype(np.uint64).view(np.int64), device=self.dev)
+        m = None if mask is None else torch.as_tensor(np.asarray(mask).astype(np.uint8), device=self.dev)
+        check(lib().hwy_reset(self.h, ptr(s), ptr(m), ptr(self.obs), None), "hwy_reset")
         torch.cuda.synchronize()
         return self.obs.cpu().numpy()
 
@@ -114,6 +119,24 @@ class HipEnv:
                                         ptr(self.el), ctypes.byref(st) if info else None,
                                         ptr(self.final_obs), None), "hwy_step_with_final")
         return self._info_out(("final_obs",))
+
+    def set_seed_groups(self, seed_bases, envs_per_group):
+        from hwy.native import check, lib
+
+        b = np.ascontiguousarray(seed_bases, np.int64)
+        check(lib().hwy_set_seed_groups(self.h, b.ctypes.data_as(ctypes.c_void_p), len(b),
+                                        int(envs_per_group)), "hwy_set_seed_groups")
+
+    def cut_episodes(self):
+        """hwy_cut_episodes: (obs, ep_return, ep_length, cut)"""
+        from hwy.native import check, lib, ptr
+
+        if not hasattr(self, "cut"):
+            self.cut = self.torch.zeros(self.E, dtype=self.torch.uint8, device=self.dev)
+        check(lib().hwy_cut_episodes(self.h, ptr(self.obs), ptr(self.er), ptr(self.el),
+                                     ptr(self.cut), None), "hwy_cut_episodes")
+        self.torch.cuda.synchronize()
+        return tuple(x.cpu().numpy() for x in (self.obs, self.er, self.el, self.cut))
 
     def state(self):
         from hwy.native import check, lib, ptr
@@ -274,6 +297,7 @@ def _cases():
         actions=wild)
     add("N1", dict(N=1))
     add("N2-shuffled", dict(N=2, order="shuffled"))
+    add("N3-shuffled", dict(N=3, order="shuffled"))
     add("N64-V11", dict(N=64, vehicles_count=10), cover=("zero_rows",), need=dict(zero_rows=1))
     # 16 lanes: Vehicle.create_random's spacing shrinks with e^(-5/40 lanes), so the 63 others
     # start within 200 m of the ego
@@ -322,38 +346,20 @@ CASES = _cases()
 
 
 # ------------------------------------------------------------------------------- the checker
-def _perfect_matching(M):
-    """Kuhn's augmenting paths on a boolean [n, n] matrix: the column of every row if each
-    row gets its own, else None."""
-    n = M.shape[0]
-    owner = [-1] * n
-    adj = [np.nonzero(M[i])[0] for i in range(n)]
-
-    def place(i, seen):
-        for j in adj[i]:
-            if j in seen:
-                continue
-            seen.add(j)
-            if owner[j] < 0 or place(owner[j], seen):
-                owner[j] = i
-                return True
-        return False
-
-    if not all(place(i, set()) for i in range(n)):
-        return None
-    col = [0] * n
-    for j, i in enumerate(owner):
-        col[i] = j
-    return col
-
-
 class Checker:
     """One case's outputs (the kernel's or the oracle's) against the float64 model, step by
     step; collects the coverage counts, the share of (env, step) pairs `uncertain` leaves out
-    and the worst error against the derived bound."""
+    and the worst error against the derived bound.
 
-    def __init__(self, case, cfg, table):
+    `shuffled` observations are compared in order, row by row: the model's unshuffled rows are
+    moved to the rows tests/rng_model.py's `shuffle_dest` names for the seed and step in the
+    state's words, then wrapped, so the fused wrapper reads the row that really stands at
+    `ego_idx`.  That states the ordered comparison for `ego_idx >= 1` too; no case is compared
+    as a set any more.  `rng` (optional) is the RngModel to take the permutation from."""
+
+    def __init__(self, case, cfg, table, rng=None):
         self.case, self.cfg, self.table = case, cfg, table
+        self.rng = rng or rm.RngModel()
         self.count = {k: 0 for k in case.need}
         self.pairs = self.left_out = 0
         self.worst = dict(obs=(0.0, 0.0), reward=(0.0, 0.0), terms=(0.0, 0.0))  # (error, bound)
@@ -377,59 +383,27 @@ class Checker:
         if w[1] == 0.0 or ratio[k] > w[0] / w[1]:
             self.worst[what] = (float(err[k]), float(tol[k]))
 
-    def _rows_match(self, K, W):
-        """[n, m] bool: kernel row i within the bound of model row j, every column"""
-        err = np.abs(K[:, None, :].astype(np.float64) - W.v[None, :, :])
-        return (err <= em.TOL_FACTOR * W.e[None, :, :]).all(-1)
-
-    def _check_obs(self, obs, m, keep):
+    def _check_obs(self, obs, m, keep, state):
         cfg, table = self.cfg, self.table
         N, F = cfg.obs_vehicles, cfg.n_features
         rank = cfg.pe_kind == _abi.PE_RANK
         if rank:  # the appended columns are the table's row for the position, exactly
             t = np.asarray(table, np.float32).reshape(N, cfg.d_embed)
             np.testing.assert_array_equal(obs[:, :, F:], np.broadcast_to(t, obs[:, :, F:].shape))
-        if not (cfg.order == _abi.ORDER_SHUFFLED and N > 2):
-            w = em.wrap_model(cfg, m, table)
-            self._within("obs", obs[keep], w[keep])
-            return
-        # shuffled: as a set.  Row 0 is the ego; every other kernel row matches exactly one model
-        # row (so the zero-row counts are equal too).  The wrapper measures distances from the
-        # row at ego_idx, so with ego_idx >= 1 the model row standing there is searched for.
-        eg = int(cfg.ego_idx)
-        for e in np.nonzero(keep)[0]:
-            me = m[e]
-            K = obs[e, :, :F] if rank else obs[e]
-            zero = np.nonzero(~me.v[1:].any(-1))[0] + 1
-            cands = [0] if eg == 0 else [j for j in range(1, N) if j not in zero[1:]]
-            ok = False
-            for c in cands:
-                ref = em.Q(np.broadcast_to(me.v[c], me.v.shape), np.broadcast_to(me.e[c], me.e.shape))
-                W = me if rank else em.wrap_rows(cfg, me, ref, table)
-                M = self._rows_match(K, W)
-                if not M[0, 0]:
-                    continue
-                M = M[1:, 1:].copy()
-                if eg >= 1:  # position ego_idx holds model row c
-                    keep_cell = M[eg - 1, c - 1]
-                    M[eg - 1, :] = False
-                    M[:, c - 1] = False
-                    M[eg - 1, c - 1] = keep_cell
-                col = _perfect_matching(M)
-                if col is not None:
-                    ok = True
-                    # the figure reported is each row against the nearest model row it may be
-                    # (rows closer to each other than the bound are interchangeable)
-                    err = np.abs(K[:, None, :].astype(np.float64) - W.v[None]).sum(-1)
-                    err[1:, 1:][~M] = np.inf
-                    err[0, 1:] = err[1:, 0] = np.inf
-                    self._within("obs", K, W[np.argmin(err, 1)])
-                    break
-            assert ok, (f"{self.case.name} step {self.t} env {e}: the kernel's rows are not a "
-                        f"permutation of the model's rows within the bound\nkernel\n{obs[e]}\n"
-                        f"model (before the wrapper)\n{me.v}")
-            if cfg.pe_kind in (_abi.PE_NONE, _abi.PE_RANK):
-                assert int((K[1:] == 0).all(-1).sum()) == len(zero), "zero-row counts differ"
+        if cfg.order == _abi.ORDER_SHUFFLED and N > 2:
+            m = self._shuffled(m, state)
+        w = em.wrap_model(cfg, m, table)
+        self._within("obs", obs[keep], w[keep])
+
+    def _shuffled(self, m, state):
+        """the model's rows in the kernel's order: slot q (row 1 + q) moved to the row
+        rng_model's shuffle_dest gives for the seed and the step count in the state's words"""
+        E, N = m.v.shape[:2]
+        dest = self.rng.shuffle_dest(N, rm.state_seeds(state), state[_abi.F_ENV][:, _abi.E_STEP])
+        ar = np.arange(E)[:, None]
+        v, e = m.v.copy(), m.e.copy()
+        v[ar, dest], e[ar, dest] = m.v[:, 1:], m.e[:, 1:]
+        return em.Q(v, e)
 
     def check(self, out, state):
         """out: (obs, reward, terminated, truncated, ...) of one step; state: the packed state
@@ -440,7 +414,7 @@ class Checker:
         self.pairs += unc.size
         self.left_out += int(unc.sum())
         m = em.observe_model(cfg, state)
-        self._check_obs(obs, m, ~unc)
+        self._check_obs(obs, m, ~unc, state)
         # the reward is of the state before an autoreset, which a reset env no longer holds
         done = term.astype(bool) | trunc.astype(bool)
         keep = ~unc & ~(done & bool(cfg.autoreset))
