@@ -19,7 +19,7 @@
 // head kernel (ppo_head), split-K partial slabs and one deterministic reduction (ppo_reduce).
 // All GEMMs use v_mfma_f32_*_f32: exact fp32 products, fp32 accumulation.
 //
-// This file is compiled five times (Makefile).  ppo_kernels.o holds everything but the mixed-width
+// This file is compiled six times (Makefile).  ppo_kernels.o holds everything but the mixed-width
 // and scheduled grouped kernels and their entry points (hwy_ppo_mixed_*, hwy_ppo_sched_*);
 // ppo_mixed.o, compiled with -DHWY_PPO_MIXED_TU, holds only those; ppo_wide.o, compiled with
 // -DHWY_PPO_WIDE_TU, holds only the row / act kernels for S > 256 (solo, grouped, mixed and
@@ -33,7 +33,9 @@
 // with the masked value store and their entry point (hwy_ppo_value_masked).  ppo_ctl.o, compiled
 // with -DHWY_PPO_MIXED_TU -DHWY_PPO_CTL_TU, holds only the scheduled kernels with the KL stop
 // (narrow and wide row kernels alike), the learning-rate kernel and their entry points
-// (hwy_ppo_sched_ctl_*, hwy_ppo_sched_set_lr).
+// (hwy_ppo_sched_ctl_*, hwy_ppo_sched_set_lr).  ppo_igrad.o, compiled with
+// -DHWY_PPO_IGRAD_TU, holds only the input-gradient kernels, narrow and wide, and
+// their entry point (hwy_ppo_input_grad).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -3013,6 +3015,212 @@ __global__ void __launch_bounds__(64 * NW, 1) ppo_act_mix_w(const ActArgs* __res
   }
 }
 #endif  // HWY_PPO_WIDE_TU
+#ifdef HWY_PPO_IGRAD_TU
+// ----------------------------------------------------------------------------- input gradients
+// ppo_igrad (hwy_ppo_input_grad): for 16 rows of states per workgroup, the forward of ppo_act
+// without a tile image (act_body's rows_forward call and per-row head, so mean / value are
+// hwy_ppo_act's bits), then K backward passes down to the states:
+//   dac = relu'(a1 | c1) * (cot_0 wa2[0] + cot_1 wa2[1] | cot_v wc2)
+//   dh2 = relu'(h2) * (dac [Wa1; Wc1])      dh1 = relu'(h1) * (dh2 W2)      dS = dh1 W1
+// The forward runs once.  Its four ReLU decisions stay in registers as bits of the lane's C
+// elements (bit 4 t + r: row 4 g + r, column n_base + 16 t + c), so the backward passes are free
+// to overwrite the forward's images: dac goes to [a1 | c1]'s, dh2 to h2's, dh1 to h1's -- no LDS
+// beyond act_body's.  The backward weights are params read k-major (the ring's segments 4-6, as
+// ppo_rows' general layout); dS reads W1 [H][S] the same way, 16 state columns per MFMA tile, two
+// tiles per wave at a time, and goes from the accumulators to global memory.
+struct IgArgs {
+  int B, S, K;
+  const float* states;  // [B][S]
+  const float* params;
+  int64_t off[13];
+  const float* cot;     // [K][B][3]
+  float* dstates;       // [K][B][S]
+  float *mean, *value;  // nullable [B][2], [B]
+  uint32_t* relu_bits;  // nullable [B][4][H / 32]
+};
+
+template <int QH, int NW, bool WIDE>
+__device__ __forceinline__ void igrad_body(const IgArgs& r) {
+  constexpr int H = 64 * QH;
+  constexpr int RPW = kRowTile / NW;
+  constexpr int NT = 64 * NW;
+  constexpr int PH = lds_pitch(H), PA = lds_pitch(2 * H), PXMAX = lds_pitch(kMaxRowS);
+  __shared__ __attribute__((aligned(16))) float X[kRowTile * PXMAX];
+  __shared__ __attribute__((aligned(16))) float H1[kRowTile * PH];
+  __shared__ __attribute__((aligned(16))) float H2[kRowTile * PH];
+  __shared__ __attribute__((aligned(16))) float AC[kRowTile * PA];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int g = lane >> 4, c = lane & 15;
+  const int S = r.S, B = r.B;
+  const int row0 = blockIdx.x * kRowTile;
+  const int nrows = min(kRowTile, B - row0);
+  const float* P = r.params;
+  constexpr int TW = H_TW(QH, NW);
+  constexpr int D = ring_depth<TW>();
+  const int nb = w * (H / NW);  // this wave's output columns of an H-wide layer
+  WRing<TW, D, 7, false> R;
+  ring_setup(R, P, r.off, S, H, nb, nullptr);
+  R.prime();
+#ifdef HWY_SECTION_PROFILE
+  uint64_t _pt = 0, _pacc[16];
+#endif
+  {
+    f32x4 unused_a[1][TW], unused_c[1][TW];
+    uint32_t unused_m[2];
+    rows_forward<QH, NW, kRowTile, false, D, 7, false, false, false, WIDE>(
+        R, r.states, nullptr, S, nrows, row0, P, r.off, X, H1, H2, AC, nullptr, nullptr, nullptr,
+        unused_m, unused_a, unused_c PSEC_ARGS);
+  }
+  // ---- mean / value: ppo_act's head (lane owns columns lane + 64 q, fixed-order wave sums)
+  if (r.mean || r.value) {
+    float wa0[QH], wa1[QH], wc[QH];
+#pragma unroll
+    for (int q = 0; q < QH; ++q) {
+      const int col = lane + 64 * q;
+      wa0[q] = P[r.off[P_WA2] + col];
+      wa1[q] = P[r.off[P_WA2] + H + col];
+      wc[q] = P[r.off[P_WC2] + col];
+    }
+    const float ba0 = P[r.off[P_BA2]], ba1 = P[r.off[P_BA2] + 1], bcv = P[r.off[P_BC2]];
+    for (int rr = 0; rr < RPW; ++rr) {
+      const int lr = RPW * w + rr;
+      if (lr >= nrows) break;
+      const long b = row0 + lr;
+      const float* arow = AC + lr * PA;
+      float p0 = 0.0f, p1 = 0.0f, pv = 0.0f;
+#pragma unroll
+      for (int q = 0; q < QH; ++q) {
+        const int col = lane + 64 * q;
+        const float a = arow[col], cc = arow[H + col];
+        p0 += a * wa0[q];
+        p1 += a * wa1[q];
+        pv += cc * wc[q];
+      }
+      const float mu0 = wave_sum_dpp(p0) + ba0, mu1 = wave_sum_dpp(p1) + ba1,
+                  val = wave_sum_dpp(pv) + bcv;
+      if (lane == 0) {
+        if (r.mean) r.mean[2 * b] = mu0, r.mean[2 * b + 1] = mu1;
+        if (r.value) r.value[b] = val;
+      }
+    }
+  }
+  // ---- the ReLU decisions: an output is > 0 iff its pre-activation is.  Words of 32 units for
+  // the caller (layers z1, z2, za, zc), and the bits of this lane's C elements for the backward.
+  if (r.relu_bits) {
+    constexpr int WPL = H / 32;
+    for (int e = t; e < nrows * 4 * WPL; e += NT) {
+      const int row = e / (4 * WPL), rem = e - row * (4 * WPL);
+      const int layer = rem / WPL, wi = rem - layer * WPL;
+      const float* src = layer == 0   ? H1 + row * PH
+                         : layer == 1 ? H2 + row * PH
+                                      : AC + row * PA + (layer - 2) * H;
+      src += 32 * wi;
+      uint32_t m = 0u;
+#pragma unroll
+      for (int i = 0; i < 32; ++i) m |= (src[i] > 0.0f ? 1u : 0u) << i;
+      r.relu_bits[((long)(row0 + row) * 4 + layer) * WPL + wi] = m;
+    }
+  }
+  uint32_t mb[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int u = 0; u < TW; ++u)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int row = 4 * g + q, col = nb + 16 * u + c, sh = 4 * u + q;
+      mb[0] |= (H1[row * PH + col] > 0.0f ? 1u : 0u) << sh;
+      mb[1] |= (H2[row * PH + col] > 0.0f ? 1u : 0u) << sh;
+      mb[2] |= (AC[row * PA + col] > 0.0f ? 1u : 0u) << sh;
+      mb[3] |= (AC[row * PA + H + col] > 0.0f ? 1u : 0u) << sh;
+    }
+  // the head weights of this wave's columns (dac's factors)
+  float ha0[TW], ha1[TW], hc[TW];
+#pragma unroll
+  for (int u = 0; u < TW; ++u) {
+    const int col = nb + 16 * u + c;
+    ha0[u] = P[r.off[P_WA2] + col];
+    ha1[u] = P[r.off[P_WA2] + H + col];
+    hc[u] = P[r.off[P_WC2] + col];
+  }
+  const float* W1 = P + r.off[P_W1];
+  const int nct = (S + 15) / 16;  // 16-column tiles of dS
+  f32x4 acc[1][TW];
+  for (int k = 0; k < r.K; ++k) {
+    // this lane's rows' cotangents (rows past nrows: 0)
+    float c0[4], c1[4], c2[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int row = 4 * g + q;
+      c0[q] = c1[q] = c2[q] = 0.0f;
+      if (row < nrows) {
+        const float* cp = r.cot + ((long)k * B + row0 + row) * 3;
+        c0[q] = cp[0], c1[q] = cp[1], c2[q] = cp[2];
+      }
+    }
+    // the ring ends a pass on a spare block: refill it with the first blocks of segment 4
+    if (k > 0) {
+#pragma unroll
+      for (int d = 0; d < D; ++d) R.template load_ahead<4>(d, R.buf[d]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();  // every wave is done with the images (the forward's, or the last pass's)
+#pragma unroll
+    for (int u = 0; u < TW; ++u)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int row = 4 * g + q, col = nb + 16 * u + c, sh = 4 * u + q;
+        AC[row * PA + col] = ((mb[2] >> sh) & 1u) ? (c0[q] * ha0[u] + c1[q] * ha1[u]) : 0.0f;
+        AC[row * PA + H + col] = ((mb[3] >> sh) & 1u) ? c2[q] * hc[u] : 0.0f;
+      }
+    __syncthreads();
+    // dh2 = (dac [Wa1; Wc1]) * (z2 > 0): the two halves of K = 2H in one accumulator
+    zero_acc(acc);
+    R.template run<4>(AC, PA, acc);
+    R.template run<5>(AC + H, PA, acc);
+    row_epi_maskbits(acc, mb[1], H2, PH, nb);
+    __syncthreads();
+    // dh1 = (dh2 W2) * (z1 > 0)
+    zero_acc(acc);
+    R.template run<6>(H2, PH, acc);
+    row_epi_maskbits(acc, mb[0], H1, PH, nb);
+    __syncthreads();
+    // dS = dh1 W1: wave w takes the column tiles w, w + NW, ..., two at a time; a column past S
+    // is clamped onto S - 1 for the loads and not stored
+    float* out = r.dstates + ((long)k * B + row0) * S;
+    const float* arow = H1 + c * PH + 4 * g;
+    for (int ct = w; ct < nct; ct += 2 * NW) {
+      const int na = 16 * ct + c, nbb = 16 * (ct + NW) + c;
+      const int la = min(na, S - 1), lb = min(nbb, S - 1);
+      f32x4 da = {0.0f, 0.0f, 0.0f, 0.0f}, db = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 2
+      for (int kb = 0; kb < H; kb += 16) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(arow + kb);
+        const float* wp = W1 + (long)(kb + 4 * g) * S;
+        float wa[4], wb[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wa[j] = wp[(long)j * S + la], wb[j] = wp[(long)j * S + lb];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          da = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], wa[j], da, 0, 0, 0);
+          db = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], wb[j], db, 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int row = 4 * g + q;
+        if (row < nrows) {
+          if (na < S) out[(long)row * S + na] = da[q];
+          if (nbb < S) out[(long)row * S + nbb] = db[q];
+        }
+      }
+    }
+  }
+}
+
+template <int QH, int NW, bool WIDE>
+__global__ void __launch_bounds__(64 * NW, 1) ppo_igrad(IgArgs r) {
+  igrad_body<QH, NW, WIDE>(r);
+}
+#endif  // HWY_PPO_IGRAD_TU
 
 // Set in a plan's grid_rows (hwy_ppo_mixed_act_plan: lds_bytes) by the prepare calls when the
 // table holds a learner with wide states: the launch calls then run the wide unit's kernels
@@ -3063,7 +3271,46 @@ HWY_LOCAL int hwy_ppo_wide_act_mix(int cls, int tiles, int B, int G, int lds, co
 // narrow kernels; false on a HIP error
 HWY_LOCAL bool hwy_ppo_wide_raise_lds(int kind, int cls, int tiles);
 
-#ifdef HWY_PPO_VMASK_TU
+#if defined(HWY_PPO_IGRAD_TU)
+// ----------------------------------------------------------------------------- input gradients
+// hwy_ppo_input_grad (include/hwy_ppo.h): one launch of ppo_igrad, narrow or (S > kMaxRowS) with
+// the chunked first layer, at hwy_ppo_act's wave counts per H.
+extern "C" int hwy_ppo_input_grad_args_size(void) { return (int)sizeof(hwy_ppo_input_grad_args); }
+
+extern "C" int hwy_ppo_input_grad(const hwy_ppo_input_grad_args* a, void* stream) {
+  if (!a || !a->states || !a->params || !a->cot || !a->dstates) return -1;
+  if (a->K < 1 || a->K > 4) return -1;
+  const hwy_ppo_dims& d = a->dims;
+  if (!fused_ok(d) || d.S < 4 || d.A != 2 || d.B < 1) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const Layout L = make_layout(d);
+  IgArgs r = {};
+  r.B = d.B, r.S = d.S, r.K = a->K, r.states = a->states, r.params = a->params;
+  for (int i = 0; i < 13; ++i) r.off[i] = L.off[i];
+  r.cot = a->cot, r.dstates = a->dstates;
+  r.mean = a->mean, r.value = a->value, r.relu_bits = a->relu_bits;
+  const dim3 g((d.B + kRowTile - 1) / kRowTile), b4(256), b8(512);
+  auto launch = [&](auto wd) {
+    constexpr bool WD = decltype(wd)::value;
+    switch (d.H / 64) {
+      case 1: hipLaunchKernelGGL((ppo_igrad<1, 4, WD>), g, b4, 0, s, r); break;
+      case 2: hipLaunchKernelGGL((ppo_igrad<2, 8, WD>), g, b8, 0, s, r); break;
+      case 3: hipLaunchKernelGGL((ppo_igrad<3, 4, WD>), g, b4, 0, s, r); break;
+      case 4: hipLaunchKernelGGL((ppo_igrad<4, 8, WD>), g, b8, 0, s, r); break;
+      case 5: hipLaunchKernelGGL((ppo_igrad<5, 4, WD>), g, b4, 0, s, r); break;
+      case 6: hipLaunchKernelGGL((ppo_igrad<6, 8, WD>), g, b8, 0, s, r); break;
+      case 7: hipLaunchKernelGGL((ppo_igrad<7, 4, WD>), g, b4, 0, s, r); break;
+      default: hipLaunchKernelGGL((ppo_igrad<8, 8, WD>), g, b8, 0, s, r); break;
+    }
+  };
+  if (wide_s(d.S))
+    launch(std::integral_constant<bool, true>());
+  else
+    launch(std::integral_constant<bool, false>());
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+#elif defined(HWY_PPO_VMASK_TU)
 // ----------------------------------------------------------------------------- masked values
 // hwy_ppo_value_masked: the act bodies with the masked store (ppo_act_body.inc /
 // ppo_act_c_body.inc under HWY_PPO_VMASK_TU) -- a tile without a marked row stores zeros and

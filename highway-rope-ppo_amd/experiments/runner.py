@@ -11,7 +11,12 @@ and ``episode_stats`` (True: per-episode lengths, crashes, mean speeds and lane 
 metrics and a crash rate in the summary, training/routine.py; vectorised loop only) and
 ``truncation`` ("terminal", the default and the reference's behaviour, or "bootstrap": GAE takes
 V(final observation) at a time limit, ppo/rollout.py; launch() on the vectorised loop only --
-a process group, launch_group and launch_batch refuse it).
+a process group, launch_group and launch_batch refuse it) and ``attribution`` (True: after
+training, training/routine.py's attribution() at the final weights on the evaluations' seeds goes
+into the metrics JSON as ``attribution`` -- mean |input gradient| of acceleration, steering and
+value per observed row, per distance rank and per feature column, with the share on the embedding
+columns and on the ego row; training, rewards and weights are bit for bit those without it;
+launch() on the vectorised loop only -- launch_group and launch_batch refuse it).
 
 Launched under torchrun (WORLD_SIZE > 1) one experiment spans the ranks, one GPU each: the
 runner joins the process group (RCCL, or ``HWY_DIST_BACKEND``), gives rank r the envs
@@ -146,6 +151,8 @@ class ExperimentRunner:
                             raise ValueError("extra['truncation']='bootstrap' does not run over "
                                              "a process group")
                         stats_kw["truncation"] = truncation
+                    if exp.extra.get("attribution"):
+                        stats_kw["attribution"] = True
                     if group is not None:
                         e = int(overrides.get("num_envs", 1))
                         if e <= 1:
@@ -230,6 +237,11 @@ class ExperimentRunner:
                     raise ValueError(f"launch_group / launch_batch: extra['truncation']="
                                      f"{e.extra['truncation']!r} is not supported by the grouped "
                                      f"launches (experiment {e.name}); use launch()")
+
+                if e.extra.get("attribution"):
+                    raise ValueError(f"launch_group / launch_batch: extra['attribution'] is not "
+                                     f"supported by the grouped launches (experiment {e.name}); "
+                                     f"use launch()")
 
         def episode_schedule(e):
             return check_episode_schedule(e.extra.get("episode_schedule", "lockstep"))

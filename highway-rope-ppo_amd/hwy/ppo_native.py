@@ -330,6 +330,75 @@ def fused_value_masked(agent, states: torch.Tensor, truncated: torch.Tensor,
     return out
 
 
+class PpoInputGradArgs(ctypes.Structure):
+    _fields_ = [
+        ("dims", PpoDims),
+        ("states", ctypes.c_void_p), ("params", ctypes.c_void_p), ("K", ctypes.c_int32),
+        ("cot", ctypes.c_void_p), ("dstates", ctypes.c_void_p), ("mean", ctypes.c_void_p),
+        ("value", ctypes.c_void_p), ("relu_bits", ctypes.c_void_p),
+    ]
+
+
+def _bind_input_grad(L):
+    if getattr(L, "_ppo_igrad_bound", False):
+        return L
+    L.hwy_ppo_input_grad.argtypes = [ctypes.POINTER(PpoInputGradArgs), ctypes.c_void_p]
+    L.hwy_ppo_input_grad.restype = ctypes.c_int
+    L.hwy_ppo_input_grad_args_size.argtypes = []
+    L.hwy_ppo_input_grad_args_size.restype = ctypes.c_int
+    if L.hwy_ppo_input_grad_args_size() != ctypes.sizeof(PpoInputGradArgs):
+        raise RuntimeError("hwy_ppo_input_grad_args: the library's layout differs from the binding's")
+    L._ppo_igrad_bound = True
+    return L
+
+
+MAX_INPUT_GRAD_COTANGENTS = 4
+
+
+def fused_input_grad(agent, states: torch.Tensor, cot: torch.Tensor, *,
+                     want_outputs: bool = False, want_relu_bits: bool = False):
+    """Input gradients of the policy's outputs through hwy_ppo_input_grad: for ``states`` (B, S)
+    and ``cot`` (K, B, 3), K <= 4, the weights of (mean_0, mean_1, value) per row,
+    ``dstates[k, b] = sum_o cot[k, b, o] * d out_o(states[b]) / d states[b]`` as (K, B, S).
+    mean is the pre-tanh actor mean (fused_act(deterministic=True)'s pre_tanh).  Returns dstates,
+    then with ``want_outputs`` the kernel's own mean (B, 2) and value (B,), then with
+    ``want_relu_bits`` its ReLU decisions as int32 words (B, 4, H // 32): layers z1, z2, za, zc,
+    bit c % 32 of word c // 32 set iff pre-activation c is > 0.  One launch; no parameter, gradient
+    or version counter is touched."""
+    flat = flat_params(agent)[0]
+    H = agent.actor_critic.shared[0].weight.shape[0]
+    dev = flat.device
+    if (states.dim() != 2 or states.dtype != torch.float32 or states.device != dev
+            or not states.is_contiguous()):
+        raise ValueError(f"fused_input_grad states must be contiguous float32 (B, S) on {dev}")
+    B, S = states.shape
+    if not act_supported(S, H, 2) or B < 1:
+        raise ValueError(f"fused_input_grad does not support B={B} S={S} H={H}")
+    if (cot.dim() != 3 or cot.shape[1:] != (B, 3) or not 1 <= cot.shape[0] <= MAX_INPUT_GRAD_COTANGENTS
+            or cot.dtype != torch.float32 or cot.device != dev or not cot.is_contiguous()):
+        raise ValueError(f"fused_input_grad cot must be contiguous float32 (K, {B}, 3), "
+                         f"1 <= K <= {MAX_INPUT_GRAD_COTANGENTS}, on {dev}")
+    K = cot.shape[0]
+    dstates = torch.empty(K, B, S, device=dev)
+    a = PpoInputGradArgs()
+    a.dims = PpoDims(B, S, H, 2)
+    a.states, a.params, a.K = states.data_ptr(), flat.data_ptr(), K
+    a.cot, a.dstates = cot.data_ptr(), dstates.data_ptr()
+    out = [dstates]
+    if want_outputs:
+        mean = torch.empty(B, 2, device=dev)
+        value = torch.empty(B, device=dev)
+        a.mean, a.value = mean.data_ptr(), value.data_ptr()
+        out += [mean, value]
+    if want_relu_bits:
+        bits = torch.empty(B, 4, H // 32, device=dev, dtype=torch.int32)
+        a.relu_bits = bits.data_ptr()
+        out.append(bits)
+    check(_bind_input_grad(lib()).hwy_ppo_input_grad(ctypes.byref(a), stream_ptr()),
+          "hwy_ppo_input_grad")
+    return dstates if len(out) == 1 else tuple(out)
+
+
 class FusedPPO:
     def __init__(self, agent, mb: int, nmb: int, group=None, use_graphs: bool = True):
         ac = agent.actor_critic

@@ -535,6 +535,34 @@ class PPOAgent:
         out.copy_(res)
         return out
 
+    _INPUT_GRAD_NAMES = ("acceleration", "steering", "value")
+
+    def input_gradients(self, states: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """What the policy's outputs depend on in a batch of observations (B, S): the gradients
+        of the pre-tanh actor means -- action 0, the longitudinal command ("acceleration"), and
+        action 1, the lateral one ("steering"; ContinuousAction's order) -- and of the critic's
+        "value" with respect to the state row, each (B, S).  One hwy_ppo_input_grad launch with
+        the three one-hot cotangents where acting is fused, else (always with backend="torch" and
+        on the CPU) torch autograd on the module.  Parameters, their .grad and their version
+        counters are left as they are."""
+        if states.dim() != 2:
+            raise ValueError("input_gradients takes a (B, S) batch of states")
+        B = states.shape[0]
+        if self._act_fused_ok(states):
+            from hwy.ppo_native import fused_input_grad
+
+            cot = torch.eye(3, device=states.device).unsqueeze(1).expand(3, B, 3).contiguous()
+            g = fused_input_grad(self, states.float().contiguous(), cot)
+            return {n: g[k] for k, n in enumerate(self._INPUT_GRAD_NAMES)}
+        with torch.enable_grad():
+            x = states.detach().clone().requires_grad_(True)
+            mean, _, value = self.actor_critic.forward(x)
+            outs = (mean[:, 0].sum(), mean[:, 1].sum(), value.sum())
+            # with respect to the states only: no parameter's .grad is read or written
+            grads = [torch.autograd.grad(o, x, retain_graph=(k < 2))[0]
+                     for k, o in enumerate(outs)]
+        return {n: g.detach() for n, g in zip(self._INPUT_GRAD_NAMES, grads)}
+
     def _act_fused_ok(self, state: torch.Tensor) -> bool:
         """Batched acting runs through hwy_ppo_act (one launch) unless backend='torch'."""
         if self.backend == "torch" or not state.is_cuda:

@@ -33,6 +33,11 @@ over the episode's steps / its length) and ``episode_lane_changes`` into metrics
 unchanged, bit for bit.
 ``evaluate`` runs ``num_episodes`` deterministic episodes seeded exp_seed + 1000 + k (:14-29),
 as one batched env for the vectorised path.
+``attribution`` runs the same episodes and reports what the policy looks at: the mean |input
+gradient| of acceleration, steering and value per observed row, per distance rank and per feature
+column (PPOAgent.input_gradients at every step).  ``attribution=True`` books it, at the final
+weights on the evaluations' seeds, as ``attribution`` in the metrics; it runs after training and
+draws no random number, so the training is unchanged, bit for bit.
 """
 
 from __future__ import annotations
@@ -136,6 +141,178 @@ def _run_eval_vector(env, agent, num_episodes, exp_seed):
         if k % 8 == 7 and not bool(alive.any()):
             break
     return float(total.mean().item())
+
+
+# ---------------------------------------------------------------------------------- attribution
+ATTRIBUTION_OUTPUTS = ("acceleration", "steering", "value")
+
+
+def attribution_from(base_obs, grads, alive, n_base_features, ego_idx=0, features=None,
+                     absolute=False):
+    """One step's contribution to the attribution statistic, on torch tensors of any device.
+
+    ``base_obs`` (B, N, F): the un-embedded Kinematics rows the policy saw (before any RankPE /
+    DistPE / RoPE wrapper); ``grads`` (3, B, N * F_out): the input gradients of (acceleration,
+    steering, value) with respect to the wrapped, flattened observation
+    (PPOAgent.input_gradients); ``alive`` (B,) bool: the samples that count; ``n_base_features``
+    = F.  Returns float64 sums and the sample count, so that steps add up:
+
+      by_row[k][n][f]   sum over alive samples of |grad_k[n, f]|, rows as observed
+      by_rank[k][r][f]  the same with each sample's rows reordered by rank: rank 0 is row
+                        ``ego_idx``; every other non-empty row follows by (sqrt(x^2 + y^2) in
+                        float64, row index) ascending, x and y being base columns 0 and 1; rows
+                        whose F base features are all exactly 0.0 (absent vehicles) come last, by
+                        row index.  None unless the base features begin with x, y (``features``,
+                        the observation config's list; None: they do) and are relative to the ego
+                        (``absolute`` False)
+      count             alive samples (int64 tensor)
+
+    attribution_stats turns summed results into the reported numbers."""
+    B, N, F = base_obs.shape
+    if F != n_base_features:
+        raise ValueError(f"base_obs has {F} features per row, n_base_features says {n_base_features}")
+    if grads.dim() != 3 or grads.shape[0] != 3 or grads.shape[1] != B or grads.shape[2] % N:
+        raise ValueError(f"grads must be (3, {B}, {N} * F_out), got {tuple(grads.shape)}")
+    Fo = grads.shape[2] // N
+    if Fo < F:
+        raise ValueError(f"grads have {Fo} columns per row, fewer than the {F} base features")
+    if not 0 <= ego_idx < N:
+        raise ValueError(f"ego_idx {ego_idx} outside the {N} rows")
+    g = grads.reshape(3, B, N, Fo).abs().double()
+    w = alive.to(g.device).reshape(1, B, 1, 1).double()
+    g = g * w
+    out = {"by_row": g.sum(dim=1), "by_rank": None,
+           "count": alive.to(torch.int64).sum()}
+    ranked = (F >= 2 and not absolute
+              and (features is None or list(features[:2]) == ["x", "y"]))
+    if ranked:
+        b = base_obs.double()
+        dist = torch.sqrt(b[..., 0] * b[..., 0] + b[..., 1] * b[..., 1])
+        cls = torch.where((base_obs == 0).all(dim=-1), 2, 1)
+        cls[:, ego_idx] = 0
+        dist = torch.where(cls == 1, dist, torch.zeros_like(dist))
+        # (class, distance, row index) ascending: two stable sorts, the minor key first
+        by_dist = torch.argsort(dist, dim=1, stable=True)
+        by_cls = torch.argsort(torch.gather(cls, 1, by_dist), dim=1, stable=True)
+        order = torch.gather(by_dist, 1, by_cls)  # order[b, r]: the row at rank r
+        idx = order.to(g.device).reshape(1, B, N, 1).expand(3, B, N, Fo)
+        out["by_rank"] = torch.gather(g, 2, idx).sum(dim=1)
+    return out
+
+
+def attribution_add(total, part):
+    """Sum of two attribution_from results (``total`` may be None)."""
+    if total is None:
+        return dict(part)
+    return {"by_row": total["by_row"] + part["by_row"],
+            "by_rank": (None if total["by_rank"] is None or part["by_rank"] is None
+                        else total["by_rank"] + part["by_rank"]),
+            "count": total["count"] + part["count"]}
+
+
+def attribution_stats(sums, n_base_features, ego_idx=0):
+    """The reported numbers of summed attribution_from results, as plain Python: ``by_row`` and
+    ``by_rank`` divided by the sample count (mean |gradient| per observed row / rank and feature
+    column, nested lists [3][N][F_out]; zeros without a sample), ``pe_share[k]`` the mass on the
+    embedding columns f >= F over the total mass (None when the observation has none, F_out == F)
+    and ``ego_share[k]`` row ``ego_idx``'s mass over the total (shares are None where the total
+    is 0), ``samples`` the count; k indexes ATTRIBUTION_OUTPUTS."""
+    n = int(sums["count"])
+    by_row = sums["by_row"].detach().cpu()
+    F = n_base_features
+    Fo = by_row.shape[2]
+    mean = (lambda t: (t / n if n else torch.zeros_like(t)).tolist())
+    # total = base + embedding mass, so that a share is exactly 1.0 when the rest is exactly 0
+    pe = by_row[:, :, F:].sum(dim=(1, 2))
+    total = by_row[:, :, :F].sum(dim=(1, 2)) + pe
+    share = (lambda part: [float(p / t) if float(t) > 0.0 else None
+                           for p, t in zip(part, total)])
+    return {
+        "outputs": list(ATTRIBUTION_OUTPUTS),
+        "by_row": mean(by_row),
+        "by_rank": None if sums["by_rank"] is None else mean(sums["by_rank"].detach().cpu()),
+        "pe_share": None if Fo == F else share(pe),
+        "ego_share": share(by_row[:, ego_idx, :].sum(dim=1)),
+        "samples": n,
+    }
+
+
+def _attribution_env_like(env, num_episodes: int):
+    """_eval_env_like without the fused observation wrapper: the env emits the un-embedded rows,
+    and attribution applies the wrapper with the stand-alone op (hwy.ops.obs_pe), whose rows are
+    the fused env's bit for bit."""
+    from hwy.vec_env import HighwayVecEnv
+
+    base = env.unwrapped
+    return HighwayVecEnv(base.config, num_envs=num_episodes, device=base.device, autoreset=False)
+
+
+def _obs_wrapper_of(env):
+    """env's fused observation wrapper as a function of un-embedded rows (..., N, F): the
+    stand-alone op with the env's kind, width, ego row, distance scale and table."""
+    from hwy import ops
+
+    base = env.unwrapped
+    cfg = base.hwy_config
+    kind, d = int(cfg.pe_kind), int(cfg.d_embed)
+    if kind == ops.PE_NONE:
+        return lambda b: b
+    table = None if base._pe_table is None else torch.as_tensor(base._pe_table, device=base.device)
+    ego, max_dist = int(cfg.ego_idx), float(cfg.pe_max_dist)
+    return lambda b: ops.obs_pe(b, kind, d, ego, max_dist, table)
+
+
+def attribution(env, agent, num_episodes=10, exp_seed: int = 0, tape=None):
+    """What the policy looks at, over exactly evaluate()'s episodes (seeds exp_seed + 1000 + k,
+    deterministic acting): at every step of every running episode the input gradients of
+    (acceleration, steering, value) (PPOAgent.input_gradients), accumulated as mean |gradient|
+    per observed row and per distance rank and feature column (attribution_from /
+    attribution_stats).  Returns attribution_stats' dict plus ``mean_reward``, which equals
+    evaluate(env, agent, num_episodes, exp_seed).  Vector envs only.  ``tape``: a list that
+    receives every step's (base_obs, observation, alive) clones (tests)."""
+    if not _is_vector(env):
+        raise ValueError("attribution needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                         "vector_env key for one env)")
+    base = env.unwrapped
+    cfg = base.hwy_config
+    cache = getattr(base, "_attr_envs", None)
+    if cache is None:
+        cache = base._attr_envs = {}
+    ev = cache.get(num_episodes)
+    if ev is None:
+        ev = cache[num_episodes] = _attribution_env_like(env, num_episodes)
+    dev = ev.device
+    wrap = _obs_wrapper_of(env)
+    from hwy._abi import _OBS_DEFAULTS
+
+    features = (base.config.get("observation") or {}).get("features") or _OBS_DEFAULTS["features"]
+    F = ev.obs_features
+    seeds = torch.arange(num_episodes, device=dev, dtype=torch.int64) + (exp_seed + 1000)
+    base_obs, _ = ev.reset(seeds=seeds)
+    alive = torch.ones(num_episodes, dtype=torch.bool, device=dev)
+    total = torch.zeros(num_episodes, dtype=torch.float64, device=dev)
+    sums = None
+    for k in range(ev.max_episode_steps + 1):
+        obs = wrap(base_obs).reshape(num_episodes, -1)
+        g = agent.input_gradients(obs)
+        grads = torch.stack([g[n] for n in ATTRIBUTION_OUTPUTS])
+        sums = attribution_add(sums, attribution_from(
+            base_obs, grads, alive, F, int(cfg.ego_idx), features=features,
+            absolute=bool(cfg.absolute)))
+        if tape is not None:
+            tape.append((base_obs.clone(), obs.clone(), alive.clone()))
+        a, _, _, _ = agent.select_action(obs, deterministic=True)
+        base_obs, r, te, tr, _ = ev.step(a.contiguous())
+        total += torch.where(alive, r.double(), torch.zeros_like(total))
+        alive &= ~(te.bool() | tr.bool())
+        if k % 8 == 7 and not bool(alive.any()):  # as _run_eval_vector: later steps add nothing
+            break
+    out = attribution_stats(sums, F, int(cfg.ego_idx))
+    out["mean_reward"] = float(total.mean().item())
+    return out
+
+
+_attribution = attribution  # train_with_experiment_name's keyword shadows the name
 
 
 def evaluate_many(items, num_episodes=5):
@@ -382,8 +559,13 @@ class _EvalTracker:
 def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, log_interval=20,
                                eval_interval=50, steps_per_update=2048, experiment_name="",
                                exp_seed: int = 0, logger=None, episode_schedule="lockstep",
-                               episode_stats: bool = False, truncation: str = "terminal"):
+                               episode_stats: bool = False, truncation: str = "terminal",
+                               attribution: bool = False):
     from ppo.rollout import check_episode_schedule, check_truncation
+
+    if attribution and not _is_vector(env):
+        raise ValueError("attribution needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                         "vector_env key for one env)")
 
     if check_truncation(truncation) == "bootstrap":
         if not _is_vector(env):
@@ -454,6 +636,9 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         exp_prefix, metrics_history, tracker, start_time, **sched_kw)
     if rank != 0:
         return tracker.rewards, tracker.avg_rewards, metrics_history
+    if attribution:  # after training, at the final weights, on the evaluations' seeds
+        metrics_history["attribution"] = _attribution(env, agent, num_episodes=5,
+                                                      exp_seed=exp_seed)
     _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_history,
                     training_episodes, episode_rewards, tracker.eval_episodes, tracker.rewards,
                     tracker.avg_rewards, target_reward, total_steps, logger, exp_prefix)

@@ -288,6 +288,41 @@ int hwy_ppo_sched_ctl_step(const hwy_ppo_sched_plan* plan, const void* table, vo
 int hwy_ppo_sched_set_lr(const hwy_ppo_sched_plan* plan, void* table, const float* lr_dev /*[G]*/,
                          void* stream);
 
+/* ---- Input gradients: what the policy's outputs depend on in its observation.  For B rows of
+ * states and K cotangents per row (1 <= K <= 4)
+ *   dstates[k][b][:] = sum_o cot[k][b][o] * d out_o(states[b]) / d states[b],
+ *   out = (mean_0, mean_1, value):
+ * mean is the pre-tanh actor mean (hwy_ppo_act's pre_tanh with noise == NULL), value the critic's
+ * output; log_std does not enter.  The forward is hwy_ppo_act's without a tile image (16-row
+ * tiles; past S = 256 the chunked first layer), run once per tile; mean / value, when given, are
+ * bit for bit hwy_ppo_act(noise = NULL, tiles = NULL)'s pre_tanh / value on the same inputs.  Per
+ * cotangent the backward is
+ *   dac = relu'(a1 | c1) * (cot_0 wa2[0] + cot_1 wa2[1] | cot_v wc2)
+ *   dh2 = relu'(h2) * (dac [Wa1; Wc1])    dh1 = relu'(h1) * (dh2 W2)    dS = dh1 W1
+ * with relu' = 1 iff the kernel's own fp32 pre-activation is > 0 (torch's convention, 0 at 0); the
+ * products are fp32 MFMA over params read in place (no tile image is used or needed).
+ * Exact by construction: a row whose cotangent is all zero gets a zero dstates row; a state column
+ * whose W1 column is all zero gets zeros; cotangent k of a K-cotangent call has the bits of a
+ * one-cotangent call; a row's results do not depend on B or on the other rows.  Nothing outside
+ * dstates, mean, value and relu_bits is written.  Needs S % 4 == 0, 0 < S <= 1024,
+ * H in {64, 128, ..., 512}, A == 2.  Asynchronous, allocates nothing, hipGraph-capturable.
+ * -1 bad arguments (a NULL states / params / cot / dstates, K outside 1..4, dims outside the range),
+ * before any device call; -2 HIP error. */
+typedef struct hwy_ppo_input_grad_args {
+  hwy_ppo_dims dims;
+  const float* states;    /* [B][S] contiguous */
+  const float* params;    /* flat, hwy_ppo_param_layout order */
+  int32_t K;              /* 1..4 */
+  const float* cot;       /* [K][B][3] device: weights of (mean_0, mean_1, value) per row */
+  float* dstates;         /* [K][B][S] */
+  float* mean;            /* nullable [B][2] */
+  float* value;           /* nullable [B] */
+  uint32_t* relu_bits;    /* nullable [B][4][H/32]: layers z1, z2, za, zc; bit (c % 32) of word
+                             c / 32 set iff the kernel's own pre-activation of unit c is > 0 */
+} hwy_ppo_input_grad_args;
+int hwy_ppo_input_grad(const hwy_ppo_input_grad_args* a, void* stream);
+int hwy_ppo_input_grad_args_size(void); /* sizeof(hwy_ppo_input_grad_args), for a binding's check */
+
 /* Build flags of this library: bit 0 = development knobs compiled in (HWY_DEV_KNOBS: the
  * HWY_WG_BAL / HWY_ROWS_RT / HWY_WG_FILL environment variables are read), bit 1 = section clocks
  * (HWY_SECTION_PROFILE).  A product build returns 0 and reads no environment variable. */
