@@ -18,6 +18,9 @@ struct hwy_handle {
   float* pe_table;  // [HWY_MAX_PE_TABLE]
   int64_t* group_seed;  // [n_groups] (hwy_set_seed_groups), or null
   int n_groups, group_envs, pe_group_stride;
+  // the per-group RankPE tables no longer match the groups (hwy_set_seed_groups changed their
+  // geometry): every launch and prepare is refused until hwy_set_pe_table loads a table again
+  int pe_invalid;
 };
 
 static thread_local char g_err[512];
@@ -173,6 +176,7 @@ int hwy_set_pe_table(hwy_handle* h, const float* table_host, int n) {
   hipError_t e = hipMemcpy(h->pe_table, table_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
   if (e != hipSuccess) return hip_fail(e, "hipMemcpy(pe_table)");
   h->pe_group_stride = stride;
+  h->pe_invalid = 0;
   return HWY_OK;
 }
 
@@ -182,6 +186,7 @@ int hwy_set_seed_groups(hwy_handle* h, const int64_t* seed_bases, int n_groups, 
   if (n_groups == 0) {
     if (h->group_seed) (void)hipFree(h->group_seed);
     h->group_seed = nullptr;
+    if (h->pe_group_stride) h->pe_invalid = 1;  // per-group tables without groups
     h->n_groups = h->group_envs = h->pe_group_stride = 0;
     return HWY_OK;
   }
@@ -199,9 +204,14 @@ int hwy_set_seed_groups(hwy_handle* h, const int64_t* seed_bases, int n_groups, 
   }
   if (h->group_seed) (void)hipFree(h->group_seed);
   h->group_seed = dev;
+  // per-group RankPE tables (hwy_set_pe_table after the groups) stay with groups of the same
+  // geometry: group g keeps reading table g.  Any other geometry leaves them meaningless.
+  if (h->pe_group_stride && (n_groups != h->n_groups || envs_per_group != h->group_envs)) {
+    h->pe_group_stride = 0;
+    h->pe_invalid = 1;
+  }
   h->n_groups = n_groups;
   h->group_envs = envs_per_group;
-  h->pe_group_stride = 0;  // a grouped RankPE table is set after the groups
   return HWY_OK;
 }
 
@@ -211,6 +221,13 @@ int hwy_set_seed_schedule(hwy_handle* h, int64_t seed_base, int32_t env_offset, 
   h->cfg.seed_base = seed_base;
   h->cfg.env_offset = env_offset;
   h->cfg.seed_stride = seed_stride;
+  return HWY_OK;
+}
+
+static int check_pe(const hwy_handle* h, const char* who) {
+  if (h->pe_invalid)
+    return fail(HWY_EINVAL, "%s: the per-group PE tables were loaded for other seed groups; call "
+                            "hwy_set_pe_table again", who);
   return HWY_OK;
 }
 
@@ -229,6 +246,7 @@ static StepParams params_of(hwy_handle* h) {
 
 int hwy_reset(hwy_handle* h, const uint64_t* seeds, const uint8_t* mask, float* obs, void* stream) {
   if (!h) return fail(HWY_EINVAL, "handle is NULL");
+  if (int rc = check_pe(h, "hwy_reset")) return rc;
   StepParams p = params_of(h);
   p.seeds = seeds;
   p.mask = mask;
@@ -242,6 +260,7 @@ int hwy_step(hwy_handle* h, const float* actions, float* obs, float* reward, uin
   if (!h) return fail(HWY_EINVAL, "handle is NULL");
   if (!actions || !obs || !reward || !terminated || !truncated)
     return fail(HWY_EINVAL, "hwy_step: actions/obs/reward/terminated/truncated must be non-NULL");
+  if (int rc = check_pe(h, "hwy_step")) return rc;
   StepParams p = params_of(h);
   p.actions = actions;
   p.obs = obs;
@@ -271,6 +290,7 @@ int hwy_step_with_info(hwy_handle* h, const float* actions, float* obs, float* r
     return fail(HWY_EINVAL,
                 "hwy_step_with_info: actions/obs/reward/terminated/truncated must be non-NULL");
   if (int rc = check_info(info, "hwy_step_with_info")) return rc;
+  if (int rc = check_pe(h, "hwy_step_with_info")) return rc;
   StepParams p = params_of(h);
   p.actions = actions;
   p.obs = obs;
@@ -288,6 +308,7 @@ int hwy_cut_episodes(hwy_handle* h, float* obs, float* ep_return, int32_t* ep_le
                      uint8_t* cut, void* stream) {
   if (!h) return fail(HWY_EINVAL, "handle is NULL");
   if (!obs) return fail(HWY_EINVAL, "hwy_cut_episodes: obs must be non-NULL");
+  if (int rc = check_pe(h, "hwy_cut_episodes")) return rc;
   StepParams p = params_of(h);
   p.obs = obs;
   p.ep_ret = ep_return;
@@ -322,6 +343,10 @@ int hwy_step_group_prepare(hwy_handle* const* handles, const hwy_step_io* io, in
                   h->device);
     }
     dev = h->device;
+    if (int rc = check_pe(h, "hwy_step_group_prepare")) {
+      delete[] tab;
+      return rc;
+    }
     StepParams p = params_of(h);
     p.actions = a.actions;
     p.obs = a.obs;
@@ -406,6 +431,7 @@ int hwy_step_with_final(hwy_handle* h, const float* actions, float* obs, float* 
     return fail(HWY_EINVAL,
                 "hwy_step_with_final: actions/obs/reward/terminated/truncated must be non-NULL");
   if (int rc = check_final(info, final_obs, obs, "hwy_step_with_final")) return rc;
+  if (int rc = check_pe(h, "hwy_step_with_final")) return rc;
   StepParams p = params_of(h);
   p.actions = actions;
   p.obs = obs;

@@ -872,9 +872,10 @@ class GroupAct:
         for ag, S, H in zip(self.agents, self.S, self.Hs):
             flat = flat_params(ag)[0]
             out.append(act_tiles(ag, flat, S, H))
-        if self.mixed and any(t is None for t in out) and any(t is not None for t in out):
+        if any(t is None for t in out) and any(t is not None for t in out):
             # one launch streams tile images for every learner or for none: the learners that
-            # have no image in step yet (only H = 256 keeps an acting-only one) get one
+            # have no image in step (only H = 256 keeps an acting-only one; a learner whose
+            # weights were written since its last fused update has a retired one) get one
             out = [_act_tiles(ag, flat_params(ag)[0], S, H) if t is None else t
                    for ag, S, H, t in zip(self.agents, self.S, self.Hs, out)]
         return out

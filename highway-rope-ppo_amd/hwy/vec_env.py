@@ -314,13 +314,23 @@ class HighwayVecEnv:
               "hwy_set_seed_schedule")
         self.launch_version += 1
 
-    def set_seed_groups(self, seed_bases, envs_per_group: int) -> None:
+    def set_seed_groups(self, seed_bases, envs_per_group: int = 1) -> None:
         """Split the E envs into experiment groups of ``envs_per_group`` consecutive envs, group
         g seeded as a solo handle of that many envs with ``set_seed_schedule(seed_bases[g])``
         would be: seed(env l of group g, episode k) = seed_bases[g] + l + 1 + envs_per_group*k
-        (hwy_set_seed_groups; experiments/sweep.py).  ``seed_bases=None`` turns grouping off."""
+        (hwy_set_seed_groups; experiments/sweep.py).  ``seed_bases=None`` turns grouping off and
+        puts back the seed stride the grouping replaced.  Per-group RankPE tables stay with groups
+        of the same geometry; after any other call the handle refuses to run until set_pe_table
+        is called again (include/hwy.h)."""
         if seed_bases is None:
             check(lib().hwy_set_seed_groups(self._handle, None, 0, 1), "hwy_set_seed_groups")
+            if getattr(self, "_groups", None) is not None:
+                # back to the stride the grouping replaced: with envs_per_group left in place the
+                # envs of an ungrouped handle would reuse each other's episode seeds
+                c = self._cfg
+                c.seed_stride = int(self._ungrouped_stride)
+                check(lib().hwy_set_seed_schedule(self._handle, c.seed_base, c.env_offset,
+                                                  c.seed_stride), "hwy_set_seed_schedule")
             self._groups = None
         else:
             b = np.ascontiguousarray(np.asarray(seed_bases, dtype=np.int64))
@@ -328,6 +338,8 @@ class HighwayVecEnv:
                                             int(b.size), int(envs_per_group)),
                   "hwy_set_seed_groups")
             c = self._cfg
+            if getattr(self, "_groups", None) is None:
+                self._ungrouped_stride = int(c.seed_stride)
             c.seed_stride = int(envs_per_group)
             check(lib().hwy_set_seed_schedule(self._handle, c.seed_base, c.env_offset,
                                               c.seed_stride), "hwy_set_seed_schedule")

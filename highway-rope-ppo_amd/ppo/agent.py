@@ -455,9 +455,11 @@ class PPOAgent:
         self._fused = None
         self.actor_critic = ActorCritic(state_dim, action_dim, hidden_dim, device=self.device)
         self._dist = process_group
+        written = False
         if process_group is not None:  # identical initial weights on every rank
             for p in self.actor_critic.parameters():
                 torch.distributed.broadcast(p.data, src=0, group=process_group)
+            written = True
         capturable = self.device.type == "cuda"
         self.optimizer = torch.optim.Adam(self.actor_critic.parameters(), lr=lr,
                                           capturable=capturable)
@@ -480,6 +482,8 @@ class PPOAgent:
         # place without bumping their version counters, so the fused path's weight tile images
         # key their staleness on this count too (hwy/ppo_native.py)
         self._torch_param_writes = 0
+        if written:  # the broadcast above wrote through .data
+            self.params_written()
         self.generator = None
         if self.device.type == "cuda":
             self.generator = torch.Generator(device=self.device)
@@ -909,13 +913,74 @@ class PPOAgent:
             raise ValueError("backend='hip' needs action_dim 2 and hidden_dim in {64,128,...,512}")
         return ok
 
+    def _optimizer_follows(self, old, new) -> None:
+        """agent.optimizer steps the Parameter objects `new` (layout order) from now on, with
+        the Adam state it held for `old`: a writer that replaced the module's Parameters
+        (load_state_dict(assign=True), a new module) left it stepping objects nobody reads."""
+        swap = {id(o): n for o, n in zip(old, new) if o is not n}
+        if not swap:
+            return
+        opt = self.optimizer
+        for o, n in zip(old, new):
+            if o is not n and o in opt.state:
+                opt.state[n] = opt.state.pop(o)
+        for g in opt.param_groups:
+            g["params"] = [swap.get(id(p), p) for p in g["params"]]
+
+    def params_written(self) -> None:
+        """Tell the agent that its parameters were written in place through ``.data``
+        (``p.data.copy_()``, ``p.data.mul_()``, ``torch._foreach_*`` on ``.data`` tensors, a
+        ``torch.distributed.broadcast(p.data)``): such a write bumps no version counter, so
+        nothing else can see it.  Retires what was derived from the old weights -- the weight
+        tile images acting and the fused step stream, the grouped acting tables and captured
+        rollouts keyed on them, the torch-path learners and the evaluation memo -- exactly as a
+        torch-path update does.  Every other way of writing the parameters needs no call."""
+        self._torch_param_writes += 1
+        self._learners = {}
+
+    def __deepcopy__(self, memo):
+        """A copy with its own weights, optimizer state and generator state and none of the
+        original's device caches (flat buffer, FusedPPO, tile images, captured learners): it
+        rebuilds them on first use, over its own storage."""
+        import copy
+
+        if self._fused is not None and self._adam_owner == "fused":
+            self._fused.export_torch_state()  # the copy starts from agent.optimizer's state
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        fresh = {"_fused": None, "_flat": None, "_flat_guard": None, "_act_tile_image": None,
+                 "_static_bufs": None, "_ctl_runner": None, "_last_ctl": None}
+        for k, v in self.__dict__.items():
+            if k in fresh:
+                new.__dict__[k] = fresh[k]
+            elif k == "_learners":
+                new.__dict__[k] = {}
+            elif k in ("logger", "_dist"):
+                new.__dict__[k] = v
+            elif k == "generator" and v is not None:
+                g = torch.Generator(device=v.device)
+                g.set_state(v.get_state())
+                new.__dict__[k] = g
+            else:
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        new._adam_owner = "torch"
+        return new
+
     def _fused_for(self, mb: int, nmb: int, n: int):
-        from hwy.ppo_native import FusedPPO
+        from hwy.ppo_native import FusedPPO, flat_params
 
         F = self._fused
-        if F is None or F.mb != mb or F.nmb != nmb or F.metrics.shape[0] != self.epochs * nmb:
+        # the parameters may have been rebound to other storage since F was built (p.data = ...,
+        # vector_to_parameters, load_state_dict(assign=True), a .cpu()/.to(device) round trip, a
+        # new module): flat_params then made a new flat buffer, and F would train the old one,
+        # which nothing reads any more
+        moved = F is not None and F.flat is not flat_params(self)[0]
+        if (F is None or moved or F.mb != mb or F.nmb != nmb
+                or F.metrics.shape[0] != self.epochs * nmb):
             if F is not None and self._adam_owner == "fused":
                 F.export_torch_state()  # carry Adam's moments and step count to the new instance
+            if moved:
+                self._optimizer_follows(F.params, flat_params(self)[3])
             self._adam_owner = "torch"  # the new instance imports agent.optimizer's state
             F = FusedPPO(self, mb, nmb, group=self._dist, use_graphs=self.use_graphs)
             self._fused = F

@@ -105,12 +105,18 @@ class LockstepRollout:
             alloc_cut_buffers(self, buf.E, buf.states.shape[-1], buf.states.device)
 
     def _launch_key(self):
-        from hwy.ppo_native import flat_params
+        from hwy.ppo_native import act_tiles, flat_params
 
         ag, env, buf = self.agent, self.env, self.buf
         flat = flat_params(ag)[0] if ag.backend != "torch" else None
-        F = getattr(ag, "_fused", None)
-        tiles = F.current_tiles(flat) if (F is not None and flat is not None) else None
+        tiles = None
+        if flat is not None and ag._act_fused_ok(buf.states[0]):
+            # the image acting streams, brought in step with the parameters here, outside any
+            # capture (as ExperimentGroup.rollout's act.tiles()): a replayed graph reads the
+            # image's memory, so a write that retired an acting-only image (H = 256 before the
+            # first fused update, where no address in this key moves) must be applied before it
+            sd = ag.actor_critic.shared[0].weight
+            tiles = act_tiles(ag, flat, sd.shape[1], sd.shape[0])
         params = tuple(p.data_ptr() for p in ag.actor_critic.parameters())
         key = (env._handle.value, getattr(env, "launch_version", 0), tiles, params,
                buf.states.data_ptr(), buf.noise.data_ptr(), buf.T, buf.E)

@@ -102,7 +102,9 @@ def _eval_key(agent, num_episodes, exp_seed):
     # (the fused optimizer, a copy into it) bump only the buffer's counter
     flat = getattr(agent, "_flat", None)
     flat_v = (flat[0].data_ptr(), flat[0]._version) if flat is not None else None
-    return (getattr(agent, "updates", None), params, flat_v, num_episodes, exp_seed)
+    # in-place writes through .data bump neither: PPOAgent.params_written() counts them
+    writes = getattr(agent, "_torch_param_writes", 0)
+    return (getattr(agent, "updates", None), params, flat_v, num_episodes, exp_seed, writes)
 
 
 def _evaluate_vector(env, agent, num_episodes, exp_seed):

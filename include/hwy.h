@@ -197,7 +197,10 @@ int hwy_set_seed_schedule(hwy_handle* h, int64_t seed_base, int32_t env_offset, 
  * (set seed_stride = envs_per_group for the solo schedule of each group: the same seeds, so each
  * group's envs step bit for bit as a solo handle of envs_per_group envs would).  seed_bases
  * (host, [E / envs_per_group]) is copied; n_groups = 0 turns grouping off.  With a fused RankPE,
- * hwy_set_pe_table may then take n_groups tables back to back (group g reads table g).
+ * hwy_set_pe_table may then take n_groups tables back to back (group g reads table g).  A later
+ * call with the same n_groups and envs_per_group keeps them (group g still reads table g); any
+ * other call, n_groups = 0 included, leaves them without meaning: every reset, step, cut and
+ * prepare then returns HWY_EINVAL until hwy_set_pe_table is called again.
  * Synchronous (setup time only). */
 int hwy_set_seed_groups(hwy_handle* h, const int64_t* seed_bases, int n_groups, int envs_per_group);
 
