@@ -506,6 +506,47 @@ int hwy_import_state(hwy_handle* h, const uint32_t* src, void* stream) {
   return e == hipSuccess ? HWY_OK : hip_fail(e, "hwy_import_state");
 }
 
+int hwy_render_args_size(void) { return (int)sizeof(hwy_render_args); }
+
+// hwy_render's checks that need no handle; on failure the message is set and -1 returned
+static int64_t render_bytes(const hwy_render_args* a) {
+  if (!a) return fail(HWY_EINVAL, "hwy_render: args is NULL");
+  if (a->width < 1 || a->width > 4096 || a->height < 1 || a->height > 4096)
+    return fail(HWY_EINVAL, "hwy_render: width and height must be in [1, 4096], got %d x %d",
+                a->width, a->height);
+  if (a->channels != 1 && a->channels != 3)
+    return fail(HWY_EINVAL, "hwy_render: channels must be 1 or 3, got %d", a->channels);
+  if (a->n < 1 || a->n > (1 << 22))
+    return fail(HWY_EINVAL, "hwy_render: n must be in [1, 2^22], got %d", a->n);
+  const float inf = __builtin_inff();
+  if (!(a->scaling > 0.0f && a->scaling < inf))
+    return fail(HWY_EINVAL, "hwy_render: scaling must be finite and > 0");
+  for (int i = 0; i < 2; ++i)
+    if (!(a->centering[i] > -inf && a->centering[i] < inf))
+      return fail(HWY_EINVAL, "hwy_render: centering must be finite");
+  if (!a->frames || ((uintptr_t)a->frames & 15u))
+    return fail(HWY_EINVAL, "hwy_render: frames must be a 16-byte aligned device pointer");
+  return (int64_t)a->n * a->height * a->width * a->channels;
+}
+
+int64_t hwy_render_frame_bytes(const hwy_render_args* a) { return render_bytes(a); }
+
+int hwy_render(hwy_handle* h, const hwy_render_args* a, void* stream) {
+  if (!h) return fail(HWY_EINVAL, "hwy_render: handle is NULL");
+  if (render_bytes(a) < 0) return HWY_EINVAL;
+  if (!a->env_ids && a->n > h->cfg.num_envs)
+    return fail(HWY_EINVAL, "hwy_render: n = %d frames of a handle of %d envs need env_ids", a->n,
+                h->cfg.num_envs);
+  RenderParams p;
+  p.a = *a;
+  p.state = h->state;
+  p.num_envs = h->cfg.num_envs;
+  p.lanes_count = h->cfg.lanes_count;
+  if (hwy_launch_render(&p, (hipStream_t)stream))
+    return hip_fail(hipGetLastError(), "hwy_render_kernel");
+  return HWY_OK;
+}
+
 int hwy_obs_pe(const float* obs_in, float* obs_out, int E, int N, int F, int kind, int d,
                int ego_idx, float max_dist, const float* table, const float* dist_override,
                void* stream) {

@@ -37,7 +37,15 @@ struct FinalParams {
   float* final_obs;
 };
 
+// hwy_render's launch parameters (hwy_render.hip): the checked arguments and the handle's state
+struct RenderParams {
+  hwy_render_args a;
+  const uint32_t* state;  // [HWY_NFIELDS][E][64]
+  int num_envs, lanes_count;
+};
+
 extern "C" {
+int hwy_launch_render(const RenderParams* p, hipStream_t s);
 int hwy_launch_step(const StepParams* p, hipStream_t s);
 // n handles' steps in one launch: dtab = n StepParams in device memory, blocks = the largest
 // handle's hwy_step_blocks, big = hwy_step_big(total envs) (the register budget of the launch)

@@ -19,6 +19,8 @@ Extra (native-only) keys read from the merged config, all optional:
   ``autoreset``       vector env only, default True
   ``env_offset``, ``global_envs``   episode-seed schedule for env-sharded multi-GPU runs
   ``max_episode_steps``             horizon override (see hwy/_abi.py)
+  ``render_mode``     one-env facade only: "rgb_array" makes ``env.render()`` return the frame
+                      (a HighwayVecEnv's ``render()`` needs no mode)
 """
 
 from __future__ import annotations
@@ -34,7 +36,8 @@ from .dist_embed import DistanceEmbedWrapper
 from .rank_embed import RankEmbedWrapper
 from .rope_embed import RotaryEmbedWrapper
 
-_NATIVE_KEYS = ("num_envs", "device", "autoreset", "env_offset", "global_envs", "vector_env")
+_NATIVE_KEYS = ("num_envs", "device", "autoreset", "env_offset", "global_envs", "vector_env",
+                "render_mode")
 
 _SHUFFLED_FAMILY = (
     Condition.SHUFFLED,
@@ -89,7 +92,7 @@ def make_env(exp_condition: Condition, base_cfg: Dict[str, Any], d_embed: Option
                             env_offset=int(native.get("env_offset", 0)),
                             global_envs=native.get("global_envs"))
     else:
-        env = HighwayEnv(cfg, device=native.get("device"))
+        env = HighwayEnv(cfg, device=native.get("device"), render_mode=native.get("render_mode"))
 
     F = env.observation_space.shape[1]
     if exp_condition is Condition.SHUFFLED_ROPE and d_embed is not None:

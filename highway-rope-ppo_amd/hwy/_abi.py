@@ -63,6 +63,38 @@ class HwyStepInfo(ctypes.Structure):
                                                "ep_stats")]
 
 
+class RenderArgs(ctypes.Structure):
+    """hwy_render_args (include/hwy.h): one hwy_render launch's view, frame list and buffers."""
+    _fields_ = [
+        ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("channels", ctypes.c_int32),
+        ("n", ctypes.c_int32),
+        ("scaling", ctypes.c_float),
+        ("centering", ctypes.c_float * 2),
+        ("env_ids", ctypes.c_void_p),
+        ("shade", ctypes.c_void_p),
+        ("frames", ctypes.c_void_p),
+    ]
+
+
+# the view hwy_render draws by default: upstream's AbstractEnv.default_config screen_width,
+# screen_height, scaling and centering_position [highway-env 1.10.1]
+RENDER_DEFAULTS = {"screen_width": 600, "screen_height": 150, "scaling": 5.5,
+                   "centering_position": [0.3, 0.5]}
+
+
+def render_view(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The config's view keys over RENDER_DEFAULTS, as (width, height, scaling, centering)."""
+    v = dict(RENDER_DEFAULTS)
+    v.update({k: cfg[k] for k in RENDER_DEFAULTS if cfg.get(k) is not None})
+    cen = list(v["centering_position"])
+    if len(cen) != 2:
+        raise ValueError(f"centering_position must have two entries, got {cen!r}")
+    return {"width": int(v["screen_width"]), "height": int(v["screen_height"]),
+            "scaling": float(v["scaling"]), "centering": (float(cen[0]), float(cen[1]))}
+
+
 class HwyConfig(ctypes.Structure):
     _fields_ = [
         ("num_envs", ctypes.c_int32),

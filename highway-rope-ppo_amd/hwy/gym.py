@@ -54,6 +54,7 @@ except ImportError:
         observation_space: Any = None
         action_space: Any = None
         metadata: dict = {"render_modes": []}
+        render_mode = None
         spec = None
 
         def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):
@@ -61,6 +62,9 @@ except ImportError:
 
         def step(self, action):
             raise NotImplementedError
+
+        def render(self):
+            return None
 
         def close(self):
             pass
@@ -80,6 +84,9 @@ except ImportError:
 
         def step(self, action):
             return self.env.step(action)
+
+        def render(self):
+            return self.env.render()
 
         def close(self):
             return self.env.close()

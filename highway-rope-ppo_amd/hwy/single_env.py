@@ -22,10 +22,15 @@ from .vec_env import HighwayVecEnv
 class HighwayEnv(Env):
     """gymnasium-style single highway-v0 env backed by libhwy.so."""
 
-    metadata = {"render_modes": []}
+    metadata = {"render_modes": ["rgb_array"]}
 
     def __init__(self, config: Dict[str, Any], device: Optional[torch.device] = None,
-                 info: bool = False):
+                 info: bool = False, render_mode: Optional[str] = None):
+        if render_mode is not None and render_mode not in self.metadata["render_modes"]:
+            # "human" included: there is no display to draw on
+            raise ValueError(f"render_mode {render_mode!r} is not supported; supported: "
+                             f"{self.metadata['render_modes']} (or None)")
+        self.render_mode = render_mode
         self._vec = HighwayVecEnv(config, num_envs=1, device=device, autoreset=False, info=info)
         self._info = bool(info)
         self.config = self._vec.config
@@ -82,6 +87,14 @@ class HighwayEnv(Env):
                     "action": np.asarray(action, dtype=np.float32).reshape(2).copy(),
                     "rewards": {k: float(host[5 + i]) for i, k in enumerate(REWARD_KEYS)}}
         return (obs[0].cpu().numpy(), float(host[0]), bool(host[1] > 0), bool(host[2] > 0), info)
+
+    def render(self):
+        """The current frame as an H x W x 3 uint8 numpy array with render_mode="rgb_array"
+        (HighwayVecEnv.render: the frame rule of include/hwy.h at the config's view), None
+        without a render mode, as gymnasium's envs do."""
+        if self.render_mode is None:
+            return None
+        return self._vec.render()[0].cpu().numpy()
 
     def close(self):
         self._vec.close()

@@ -24,6 +24,10 @@ holds, where ``info["_final_observation"]`` (= terminated | truncated) is set, t
 of the episode that just finished -- the row the in-kernel reset overwrote in ``obs``.  Other rows
 keep what an earlier step wrote there.  The step then runs the final variant of the kernel
 (hwy_step_with_final), with the info outputs too when ``info=True``.
+
+``render`` draws the envs' current states as uint8 frames on the device (hwy_render: the frame
+rule of include/hwy.h at the config's ``screen_width`` / ``screen_height`` / ``scaling`` /
+``centering_position``), one launch for any number of envs.
 """
 
 from __future__ import annotations
@@ -363,6 +367,64 @@ class HighwayVecEnv:
             raise ValueError("state has the wrong size")
         check(lib().hwy_import_state(self._handle, ptr(st), stream_ptr()), "hwy_import_state")
         self._keep = st
+
+    def render(self, envs=None, *, width: Optional[int] = None, height: Optional[int] = None,
+               channels: int = 3, shade: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Frames of the envs' current states as a uint8 device tensor [n, H, W, C] (hwy_render:
+        the frame rule of include/hwy.h; one launch, no synchronisation, graph-capturable when
+        ``envs`` is None or a device tensor).
+
+        ``envs``: None for all E envs, a device int32 tensor of env ids (read by the kernel; an id
+        outside 0..E-1 gives an all-background frame) or a sequence of ids (copied to the device).
+        ``width`` / ``height`` default to the config's ``screen_width`` / ``screen_height`` (600,
+        150); ``scaling`` and ``centering_position`` come from the config too (5.5, [0.3, 0.5]).
+        ``channels``: 3 for RGB, 1 for luma.  ``shade``: a float32 device tensor of E x 64 values
+        in vehicle order, tinting each vehicle toward (255, 220, 0).  ``out``: a contiguous uint8
+        device tensor of n*H*W*C elements, 16-byte aligned, to write instead of a new one."""
+        view = _abi.render_view(self.config)
+        a = _abi.RenderArgs()
+        a.width = int(view["width"] if width is None else width)
+        a.height = int(view["height"] if height is None else height)
+        a.channels = int(channels)
+        a.scaling = view["scaling"]
+        a.centering[0], a.centering[1] = view["centering"]
+        ids = None
+        if envs is None:
+            a.n = self.num_envs
+        else:
+            ids = envs
+            if not isinstance(ids, torch.Tensor):
+                ids = torch.as_tensor(np.asarray(ids, dtype=np.int32).reshape(-1),
+                                      device=self.device)
+            if not (ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous()
+                    and ids.dim() == 1):
+                raise ValueError("envs must be a contiguous 1-D int32 device tensor, a sequence "
+                                 f"of env ids or None, got {tuple(ids.shape)} {ids.dtype} on "
+                                 f"{ids.device}")
+            a.n = int(ids.numel())
+            a.env_ids = ptr(ids)
+        if shade is not None:
+            if not (shade.is_cuda and shade.dtype == torch.float32 and shade.is_contiguous()
+                    and shade.numel() == self.num_envs * HWY_MAX_VEHICLES):
+                raise ValueError(f"shade must be a contiguous float32 device tensor of "
+                                 f"{self.num_envs} x {HWY_MAX_VEHICLES} elements, got "
+                                 f"{tuple(shade.shape)} {shade.dtype} on {shade.device}")
+            a.shade = ptr(shade)
+        shape = (int(a.n), int(a.height), int(a.width), int(a.channels))
+        if out is None:
+            a.frames = 16  # any aligned address: the size check reads no memory
+            nbytes = int(lib().hwy_render_frame_bytes(ctypes.byref(a)))
+            check(0 if nbytes >= 0 else -1, "hwy_render")
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+                  and out.numel() == shape[0] * shape[1] * shape[2] * shape[3]):
+            raise ValueError(f"out must be a contiguous uint8 device tensor of {shape} elements, "
+                             f"got {tuple(out.shape)} {out.dtype} on {out.device}")
+        a.frames = ptr(out)
+        check(lib().hwy_render(self._handle, ctypes.byref(a), stream_ptr()), "hwy_render")
+        self._keep_render = (ids, shade, out)
+        return out.view(shape)
 
     def close(self) -> None:
         if self._handle:

@@ -38,6 +38,8 @@ gradient| of acceleration, steering and value per observed row, per distance ran
 column (PPOAgent.input_gradients at every step).  ``attribution=True`` books it, at the final
 weights on the evaluations' seeds, as ``attribution`` in the metrics; it runs after training and
 draws no random number, so the training is unchanged, bit for bit.
+``visualize_agent`` (:32-58) runs deterministic episodes seeded exp_seed + 2000 + k and, with
+``out_dir``, records their frames (HighwayVecEnv.render, one launch per step); there is no window.
 """
 
 from __future__ import annotations
@@ -143,6 +145,90 @@ def _run_eval_vector(env, agent, num_episodes, exp_seed):
         if k % 8 == 7 and not bool(alive.any()):
             break
     return float(total.mean().item())
+
+
+# ---------------------------------------------------------------------------------- visualisation
+def _vec_base(env):
+    """The HighwayVecEnv behind env: itself, or the one inside the one-env facade."""
+    base = env.unwrapped
+    return getattr(base, "vec_env", base)
+
+
+def save_frames(path_stem: str, frames: np.ndarray, fps: int = 15) -> list:
+    """One episode's frames [T + 1, H, W, 3] as ``<stem>.npy``, and as an animated
+    ``<stem>.gif`` when PIL is importable (MP4 is not offered: no encoder is a dependency).
+    Returns the paths written."""
+    np.save(path_stem + ".npy", frames)
+    paths = [path_stem + ".npy"]
+    try:
+        from PIL import Image
+    except ImportError:
+        return paths
+    imgs = [Image.fromarray(f) for f in frames]
+    imgs[0].save(path_stem + ".gif", save_all=True, append_images=imgs[1:],
+                 duration=max(1, int(round(1000 / fps))), loop=0)
+    return paths + [path_stem + ".gif"]
+
+
+def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, out_dir=None):
+    """Deterministic episodes of a trained agent, seeded exp_seed + 2000 + ep, on a fresh env of
+    ``env``'s config and fused wrapper (reference training/routine.py:32-58, which opens a
+    render_mode="human" window; there is no display here).  All ``num_episodes`` run as one
+    vector env without autoreset, stepped as evaluate() steps its episodes.  With ``out_dir``
+    every step's frames are drawn in one launch (HighwayVecEnv.render) and episode ep's frames --
+    the reset frame and one per step up to its own end, [T + 1, H, W, 3] -- are written to
+    ``out_dir/viz_episode_<ep + 1>.npy`` (and ``.gif`` when PIL is importable).  Logs
+    ``viz_episode=%d reward=%.2f`` per episode and returns the rewards."""
+    from hwy.vec_env import HighwayVecEnv
+
+    if logger is None:
+        logger = logging.getLogger(__name__)
+    logger.info("Visualizing agent...")
+    n = int(num_episodes)
+    if n < 1:
+        return []
+    base = _vec_base(env)
+    cfg = base.hwy_config
+    ev = HighwayVecEnv(base.config, num_envs=n, device=base.device, autoreset=False,
+                       pe_kind=cfg.pe_kind, d_embed=cfg.d_embed, ego_idx=cfg.ego_idx,
+                       pe_max_dist=cfg.pe_max_dist, pe_table=base._pe_table)
+    try:
+        dev = ev.device
+        seeds = torch.arange(n, device=dev, dtype=torch.int64) + (exp_seed + 2000)
+        obs, _ = ev.reset(seeds=seeds)
+        alive = torch.ones(n, dtype=torch.bool, device=dev)
+        total = torch.zeros(n, dtype=torch.float64, device=dev)
+        frames = [[] for _ in range(n)]
+        running = [True] * n
+
+        def grab():
+            host = ev.render().cpu().numpy()
+            for ep in range(n):
+                if running[ep]:
+                    frames[ep].append(host[ep])
+
+        if out_dir is not None:
+            grab()
+        for _ in range(ev.max_episode_steps + 1):
+            a, _, _, _ = agent.select_action(obs.reshape(n, -1), deterministic=True)
+            obs, r, te, tr, _ = ev.step(a.contiguous())
+            total += torch.where(alive, r.double(), torch.zeros_like(total))
+            if out_dir is not None:
+                grab()  # the frame after this step, for the episodes that took it
+            alive &= ~(te.bool() | tr.bool())
+            running = alive.cpu().tolist()
+            if not any(running):
+                break
+        rewards = [float(x) for x in total.cpu().tolist()]
+    finally:
+        ev.close()
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+    for ep, rew in enumerate(rewards):
+        if out_dir is not None:
+            save_frames(os.path.join(out_dir, f"viz_episode_{ep + 1}"), np.stack(frames[ep]))
+        logger.info("viz_episode=%d reward=%.2f", ep + 1, rew)
+    return rewards
 
 
 # ---------------------------------------------------------------------------------- attribution

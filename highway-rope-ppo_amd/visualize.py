@@ -1,0 +1,141 @@
+"""Record episodes of trained checkpoints as frames (the reference's visualize.py role).
+
+    python visualize.py --model artifacts/highway-ppo/checkpoints/ppo_highway_best_<exp>.pth \
+        --episodes 3 --out demo_frames
+    python visualize.py --models-file best_checkpoints.txt --out demo_frames
+
+For every checkpoint the network's dimensions are read from the saved weights
+(``shared.0.weight`` is [hidden_dim, state_dim], ``actor_mean.2.weight`` [action_dim,
+hidden_dim]), the condition and ``d_embed`` from the checkpoint's name
+(``ppo_highway_{best,solved}_<experiment name>.pth``: the name begins with the condition and a
+positional-embedding condition carries ``_d_embed<k>``), the condition's env is rebuilt with
+``make_env`` and ``--episodes`` deterministic episodes are recorded with
+training.routine.visualize_agent into ``--out/<checkpoint stem>/``: per episode a ``.npy`` of
+[T + 1, H, W, 3] uint8 frames, and an animated GIF when PIL is importable.  The frames are drawn
+on the GPU by hwy_render (include/hwy.h: this project's frame rule at upstream's view geometry,
+not pygame's pixels).  There is no live window and no MP4: neither a display nor an encoder is a
+dependency.
+"""
+
+from __future__ import annotations
+
+import argparse
+import os
+import re
+import sys
+from typing import Iterable, List, Optional, Tuple
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)
+
+from experiments.config import Condition  # noqa: E402
+
+CHECKPOINT_RE = re.compile(r"^ppo_highway_(?:best|solved)_(?P<exp>.+)\.pth$")
+# longest prefix first: every positional-embedding condition's name begins with "shuffled"
+_PREFIXES = (("shuffled_rankpe", Condition.SHUFFLED_RANKPE),
+             ("shuffled_distpe", Condition.SHUFFLED_DISTPE),
+             ("shuffled_rope", Condition.SHUFFLED_ROPE),
+             ("shuffled", Condition.SHUFFLED),
+             ("sorted", Condition.SORTED))
+_PE_CONDITIONS = (Condition.SHUFFLED_RANKPE, Condition.SHUFFLED_DISTPE, Condition.SHUFFLED_ROPE)
+
+
+def experiment_name(path: str) -> str:
+    """The experiment name inside a checkpoint's file name (the bare stem when the file is not
+    named as training/routine.py names its checkpoints)."""
+    base = os.path.basename(path)
+    m = CHECKPOINT_RE.match(base)
+    return m.group("exp") if m else os.path.splitext(base)[0]
+
+
+def parse_name(exp_name: str) -> Tuple[Condition, Optional[int]]:
+    """(condition, d_embed) of an experiment name; d_embed is None for the conditions without a
+    positional embedding.  ValueError when the name tells neither."""
+    low = exp_name.lower()
+    cond = next((c for prefix, c in _PREFIXES if low.startswith(prefix)), None)
+    if cond is None:
+        raise ValueError(f"cannot infer the condition from experiment name {exp_name!r}")
+    if cond not in _PE_CONDITIONS:
+        return cond, None
+    m = re.search(r"_d_embed(\d+)", low)
+    if not m:
+        raise ValueError(f"cannot parse d_embed from experiment name {exp_name!r}")
+    return cond, int(m.group(1))
+
+
+def infer_dims(state_dict) -> Tuple[int, int, int]:
+    """(state_dim, hidden_dim, action_dim) of a saved ActorCritic."""
+    hidden_dim, state_dim = state_dict["shared.0.weight"].shape
+    action_dim = state_dict["actor_mean.2.weight"].shape[0]
+    return int(state_dim), int(hidden_dim), int(action_dim)
+
+
+def load_agent(path: str, device=None):
+    """A PPOAgent of the checkpoint's dimensions holding its weights, on ``device``."""
+    import torch
+
+    from ppo.agent import PPOAgent
+
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    state_dim, hidden_dim, action_dim = infer_dims(ckpt["model"])
+    agent = PPOAgent(state_dim, action_dim, hidden_dim=hidden_dim, device=torch.device(device))
+    agent.load(path, load_optimizer=False)
+    agent.actor_critic.eval()
+    return agent
+
+
+def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=None) -> List[float]:
+    """Record ``episodes`` episodes of one checkpoint into out_dir/<checkpoint stem>/; returns
+    their rewards."""
+    from config.base_config import HIGHWAY_CONFIG
+    from experiments.wrappers import make_env
+    from training.routine import visualize_agent
+
+    cond, d_embed = parse_name(experiment_name(path))
+    agent = load_agent(path, device=device)
+    env = make_env(cond, HIGHWAY_CONFIG, d_embed=d_embed,
+                   env_overrides={"vector_env": True, "device": agent.device})
+    try:
+        have = int(env.observation_space.shape[0] * env.observation_space.shape[1])
+        want = infer_dims(agent.actor_critic.state_dict())[0]
+        if have != want:
+            raise ValueError(f"{os.path.basename(path)}: the checkpoint takes {want} inputs, the "
+                             f"{cond.name} env (d_embed={d_embed}) gives {have}")
+        dest = os.path.join(out_dir, os.path.splitext(os.path.basename(path))[0])
+        rewards = visualize_agent(env, agent, num_episodes=episodes, exp_seed=seed, out_dir=dest)
+    finally:
+        env.close()
+    for ep, r in enumerate(rewards):
+        print(f"{os.path.basename(path)} episode {ep + 1}/{len(rewards)} reward={r:.2f}")
+    print(f"frames written to {dest}")
+    return rewards
+
+
+def models_from_file(path: str) -> Iterable[str]:
+    with open(path) as f:
+        for line in f:
+            if line.strip():
+                yield line.strip()
+
+
+def main(argv=None) -> int:
+    p = argparse.ArgumentParser(description="Record episodes of trained PPO checkpoints.")
+    g = p.add_mutually_exclusive_group(required=True)
+    g.add_argument("--model", help="one .pth checkpoint")
+    g.add_argument("--models-file", help="text file with one checkpoint path per line")
+    p.add_argument("--episodes", type=int, default=1)
+    p.add_argument("--out", default="demo_frames", help="directory for the recordings")
+    p.add_argument("--seed", type=int, default=0,
+                   help="episode ep is seeded seed + 2000 + ep, as visualize_agent")
+    args = p.parse_args(argv)
+    models = [args.model] if args.model else list(models_from_file(args.models_file))
+    for m in models:
+        record(m, args.out, episodes=args.episodes, seed=args.seed)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

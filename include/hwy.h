@@ -40,6 +40,8 @@
  *   hwy_gae_boot              <- PPOMemory.compute_advantages with the value of the final
  *                                observation at a time limit instead of 0 (the reference books
  *                                truncation as terminal, training/routine.py:135; opt-in)
+ *   hwy_render                <- env.render() of a render_mode="rgb_array" env  visualize.py:146
+ *                                (this project's own frame rule, not pygame's pixels)
  *
  * Conventions
  *   - Plain pointers and sizes only; device pointers are HIP device pointers (e.g. torch
@@ -328,6 +330,72 @@ int hwy_step_group_final(const hwy_step_group_plan* plan, const void* table,
 /* Copy the packed state [HWY_NFIELDS][E][HWY_MAX_VEHICLES] u32 to / from device memory. */
 int hwy_export_state(hwy_handle* h, uint32_t* dst, void* stream);
 int hwy_import_state(hwy_handle* h, const uint32_t* src, void* stream);
+
+/* ---- Frames of the env states (the reference's render_mode="rgb_array" envs, visualize.py and
+ * training/routine.py:visualize_agent; upstream draws with pygame, whose pixels are NOT
+ * reproduced: the frame is defined by the rule below, with upstream's view geometry -- 600x150,
+ * 5.5 px/m, the ego at 0.3 / 0.5 of the frame -- as the Python layer's defaults).
+ *
+ * Frame i shows env e = env_ids[i] (e = i when env_ids is NULL), drawn from the state words as
+ * they stand: after an autoreset that is the new episode, as the obs row the step wrote.  An
+ * env_ids entry outside 0..E-1 gives an all-background frame (the state is never indexed with it).
+ * All geometry is relative to the ego (vehicle 0, at (xe, ye)) and computed in binary32.
+ *
+ * Pixel centre of row r, column c, in metres from the ego (x right along the road, y down toward
+ * higher lane ids):
+ *   px = ((c + 0.5) - centering[0] * width)  / scaling
+ *   py = ((r + 0.5) - centering[1] * height) / scaling
+ * Layers, the later one wins:
+ *   1. background
+ *   2. road surface where -xe <= px <= 10000 - xe (ROAD_LENGTH) and y_0 <= py < y_L, with
+ *      y_k = (4k - 2) - ye for k = 0..L, L = lanes_count
+ *   3. lane lines, inside the road's x extent only, where |py - y_k| <= LINE_HALF; k = 0 and
+ *      k = L solid, 0 < k < L dashed and anchored to the world: with ph = xe - 8 floor(xe / 8)
+ *      (exact in binary32) and u = px + ph, a dash is drawn where u - 8 floor(u / 8) < DASH_ON
+ *   4. vehicles 1..63 in ascending index (a later one paints over an earlier one), each iff its
+ *      flags carry HWY_FLAG_PRESENT: with dx = px - (x_v - xe), dy = py - (y_v - ye) (the two
+ *      differences in parentheses taken first) and (sh, ch) = hm_sincosf(heading_v), the pixel
+ *      is covered iff |dx ch + dy sh| <= 2.5 and |dy ch - dx sh| <= 1.0 (VEH_LENGTH / 2,
+ *      VEH_WIDTH / 2)
+ *   5. the ego, by the same test, on top
+ * A comparison with a NaN is false: a vehicle at a non-finite position is not drawn, and a frame
+ * whose ego is non-finite is all background.
+ *
+ *   constant      value            meaning
+ *   BACKGROUND    ( 60,  60,  60)  layer 1
+ *   ROAD          (100, 100, 100)  layer 2
+ *   LINE          (255, 255, 255)  layer 3
+ *   VEHICLE       (100, 200, 255)  layer 4
+ *   EGO           ( 50, 200,   0)  layer 5
+ *   CRASHED       (255, 100, 100)  any vehicle, the ego included, with HWY_FLAG_CRASHED
+ *   HOT           (255, 220,   0)  what `shade` tints toward
+ *   LINE_HALF     0.15 m           half width of a lane line
+ *   DASH_ON       3 m of every 8   drawn part of a dashed line
+ * (the palette, LINE_HALF and DASH_ON are this project's constants, not upstream's).
+ *
+ * shade (nullable; device float [E][64], vehicle order) tints vehicle v of env e toward HOT in
+ * integer arithmetic: s8 = (int)(clamp(s, 0, 1) * 256), NaN giving 0, and per channel
+ * (base (256 - s8) + HOT s8 + 128) >> 8 -- the base colour at s = 0 and HOT at s = 1, exactly.
+ * channels == 1 writes the luma (77 R + 150 G + 29 B + 128) >> 8 of the RGB pixel.
+ *
+ * hwy_render is asynchronous, allocates nothing, is hipGraph-capturable, reads the state and
+ * writes nothing but `frames`.  Bad arguments return HWY_EINVAL before any device call. */
+typedef struct hwy_render_args {
+  int32_t width, height;   /* pixels, each 1..4096 */
+  int32_t channels;        /* 3 = RGB, 1 = luma */
+  int32_t n;               /* frames, 1..2^22 */
+  float scaling;           /* pixels per metre: finite, > 0 */
+  float centering[2];      /* finite */
+  const int32_t* env_ids;  /* device [n] in 0..E-1, nullable (then n <= E) */
+  const float* shade;      /* device [E][64], nullable */
+  uint8_t* frames;         /* device [n][height][width][channels], 16-byte aligned */
+} hwy_render_args;
+/* sizeof(hwy_render_args) as compiled into the library (binding layout check). */
+int hwy_render_args_size(void);
+/* n * height * width * channels, or -1 for arguments hwy_render refuses (every check that needs
+ * no handle); pure, no device call. */
+int64_t hwy_render_frame_bytes(const hwy_render_args* a);
+int hwy_render(hwy_handle* h, const hwy_render_args* a, void* stream);
 
 /* Stand-alone observation wrapper on [E,N,F] f32 -> [E,N,F_out] f32 (foreign envs).
  *   kind = enum hwy_pe_kind, d = appended width (rank/dist) or rotate_dim (rope),
