@@ -547,6 +547,37 @@ int hwy_render(hwy_handle* h, const hwy_render_args* a, void* stream) {
   return HWY_OK;
 }
 
+int hwy_observe_args_size(void) { return (int)sizeof(hwy_observe_args); }
+
+int hwy_observe_check(const hwy_observe_args* a) {
+  if (!a) return fail(HWY_EINVAL, "hwy_observe: args is NULL");
+  if (a->order != -1 && a->order != HWY_ORDER_SORTED && a->order != HWY_ORDER_SHUFFLED)
+    return fail(HWY_EINVAL, "hwy_observe: order must be -1 (the handle's), sorted or shuffled, "
+                            "got %d", a->order);
+  if (!a->obs && !a->row_vehicle && !a->veh_values)
+    return fail(HWY_EINVAL, "hwy_observe: obs, row_vehicle and veh_values are all NULL");
+  if ((a->row_values != nullptr) != (a->veh_values != nullptr))
+    return fail(HWY_EINVAL, "hwy_observe: row_values and veh_values go together");
+  return HWY_OK;
+}
+
+int hwy_observe(hwy_handle* h, const hwy_observe_args* a, void* stream) {
+  if (!h) return fail(HWY_EINVAL, "hwy_observe: handle is NULL");
+  if (int rc = hwy_observe_check(a)) return rc;
+  if (int rc = check_pe(h, "hwy_observe")) return rc;
+  ObserveParams p;
+  memset(&p, 0, sizeof(p));
+  p.p = params_of(h);
+  if (a->order >= 0) p.p.cfg.order = a->order;
+  p.p.obs = a->obs;
+  p.row_vehicle = a->row_vehicle;
+  p.row_values = a->row_values;
+  p.veh_values = a->veh_values;
+  if (hwy_launch_observe(&p, (hipStream_t)stream))
+    return hip_fail(hipGetLastError(), "hwy_observe_kernel");
+  return HWY_OK;
+}
+
 int hwy_obs_pe(const float* obs_in, float* obs_out, int E, int N, int F, int kind, int d,
                int ego_idx, float max_dist, const float* table, const float* dist_override,
                void* stream) {

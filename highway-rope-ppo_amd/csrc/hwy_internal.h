@@ -44,7 +44,18 @@ struct RenderParams {
   int num_envs, lanes_count;
 };
 
+// hwy_observe's launch parameters (the observe unit of hwy_kernels.hip): p.cfg is the handle's
+// config with the order the call asked for, p.obs the (nullable) observation output; the rest of
+// the outputs as in hwy_observe_args
+struct ObserveParams {
+  StepParams p;
+  int32_t* row_vehicle;
+  const float* row_values;
+  float* veh_values;
+};
+
 extern "C" {
+int hwy_launch_observe(const ObserveParams* p, hipStream_t s);
 int hwy_launch_render(const RenderParams* p, hipStream_t s);
 int hwy_launch_step(const StepParams* p, hipStream_t s);
 // n handles' steps in one launch: dtab = n StepParams in device memory, blocks = the largest

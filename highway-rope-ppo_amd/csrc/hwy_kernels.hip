@@ -514,9 +514,14 @@ __device__ __forceinline__ void write_pe_row(const float* vals, int F, int kind,
 // KinematicObservation.observe + fused wrapper for the env of this wave.
 // ch / sh: hm_cosf / hm_sinf of v.h (the step carries them from the last frame)
 // lds_key: WAVE 64-bit words of per-wave LDS scratch (the distance ranking)
+// MAP (the observe unit's kernel only, below): *row_map receives the vehicle shown in row `lane`
+// (0 for the ego's row, -1 for an empty row and for lanes past the N rows) and a NULL obs_env
+// skips the row's store; everything inside `if constexpr (MAP)` is absent from every other caller.
+template <bool MAP = false>
 __device__ void observe_wave(const hwy_config& C, int lane, const Veh& v, float ch, float sh,
                              int step, uint64_t seed, const float* pe_table, float* obs_env,
-                             int fout, int* lds_vor, int* lds_inv, unsigned long long* lds_key) {
+                             int fout, int* lds_vor, int* lds_inv, unsigned long long* lds_key,
+                             [[maybe_unused]] int* row_map = nullptr) {
   const int V = C.vehicles_count + 1;
   const int N = C.obs_vehicles, F = C.n_features;
   const float ex = rdlf(v.x, 0), ey = rdlf(v.y, 0), eh = rdlf(v.h, 0), espd = rdlf(v.spd, 0);
@@ -608,6 +613,10 @@ __device__ void observe_wave(const hwy_config& C, int lane, const Veh& v, float 
   }
   const int eg = C.ego_idx;
   const float ex0 = rdlf(vals[0], eg), ex1 = rdlf(vals[1], eg);
+  if constexpr (MAP) {
+    *row_map = kind == 0 ? -1 : src;  // kind 1 (the ego's row) holds src = 0
+    if (!obs_env) return;             // wave-uniform
+  }
   if (lane < N)
     write_pe_row(vals, F, C.pe_kind, C.d_embed, lane, ex0, ex1, C.pe_max_dist, pe_table, false,
                  0.0f, obs_env + (size_t)lane * fout);
@@ -1613,6 +1622,63 @@ extern "C" int hwy_launch_gae_boot(const float* rew, const uint8_t* term, const 
                      last_val, bootv, gamma, lam, T, E, adv, ret);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#elif defined(HWY_OBSERVE_TU)
+// hwy_observe's kernel, likewise a unit of its own (-DHWY_OBSERVE_TU -> hwy_observe.o): the
+// observation of the stored state, through the step's own observe_wave (its MAP instantiation,
+// which exists in this unit only), with the row -> vehicle map and the scatter of per-row values
+// to per-vehicle ones.  One wave per env, lane = vehicle, as the step; it loads the five fields
+// the observation reads (x, y, heading, speed, flags) and the env words, 1,536 B per env, and
+// writes nothing but its outputs.  P.p.cfg.order is the order the call asked for.
+__global__ void __launch_bounds__(256) hwy_observe_kernel(ObserveParams P) {
+  __shared__ int lds_vor[ENVS_PER_BLOCK][WAVE];
+  __shared__ int lds_inv[ENVS_PER_BLOCK][WAVE];
+  __shared__ unsigned long long lds_key[ENVS_PER_BLOCK][WAVE];
+  __shared__ uint32_t lds_val[ENVS_PER_BLOCK][WAVE];
+  const hwy_config& C = P.p.cfg;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int w = threadIdx.x / WAVE;
+  const int e = blockIdx.x * ENVS_PER_BLOCK + w;
+  if (e >= C.num_envs) return;  // whole wave
+  const int V = C.vehicles_count + 1;
+  const int N = C.obs_vehicles;
+  const size_t fstride = (size_t)C.num_envs * WAVE;
+  const uint32_t idx = (uint32_t)e * WAVE + lane;  // < 2^32: hwy_create bounds num_envs
+  const uint32_t* st = P.p.state;
+  Veh v{};  // the fields the observation does not read stay zero
+  v.x = hm_bits2f((st + HWY_F_X * fstride)[idx]);
+  v.y = hm_bits2f((st + HWY_F_Y * fstride)[idx]);
+  v.h = hm_bits2f((st + HWY_F_HEADING * fstride)[idx]);
+  v.spd = hm_bits2f((st + HWY_F_SPEED * fstride)[idx]);
+  const uint32_t fl = (st + HWY_F_FLAGS * fstride)[idx];
+  const uint32_t ew = (st + HWY_F_ENV * fstride)[idx];
+  v.present = ((fl & HWY_FLAG_PRESENT) != 0u) && lane < V;  // load_veh's rule
+  const int step = rdli((int)ew, HWY_E_STEP);
+  const uint64_t seed = (uint64_t)(uint32_t)rdli((int)ew, HWY_E_SEED_LO) |
+                        ((uint64_t)(uint32_t)rdli((int)ew, HWY_E_SEED_HI) << 32);
+  float cos_h, sin_h;
+  hm_sincosf(v.h, &sin_h, &cos_h);
+  int rv;
+  observe_wave<true>(C, lane, v, cos_h, sin_h, step, seed, group_pe_table(P.p, e),
+                     P.p.obs ? P.p.obs + (size_t)e * N * P.p.fout : nullptr, P.p.fout, lds_vor[w],
+                     lds_inv[w], lds_key[w], &rv);
+  if (P.row_vehicle && lane < N) P.row_vehicle[(size_t)e * N + lane] = rv;
+  if (P.veh_values) {
+    // the scatter in LDS, zeros first and the rows after a wave barrier, then one coalesced
+    // store of the env's 64 words: every entry is written exactly once
+    const uint32_t bits = (lane < N && rv >= 0) ? hm_f2bits(P.row_values[(size_t)e * N + lane]) : 0u;
+    lds_val[w][lane] = 0u;
+    wave_lds_sync();
+    if (lane < N && rv >= 0) lds_val[w][rv] = bits;  // rv in 0..63, distinct over the rows
+    wave_lds_sync();
+    ((uint32_t*)P.veh_values)[idx] = lds_val[w][lane];
+  }
+}
+
+extern "C" int hwy_launch_observe(const ObserveParams* p, hipStream_t s) {
+  const int blocks = (p->p.cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  hipLaunchKernelGGL(hwy_observe_kernel, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 #else  // the main unit, to the end of the file
 template <int W>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
@@ -1852,4 +1918,4 @@ extern "C" int hwy_debug_sections(unsigned long long* out, int reset) {
   return 0;
 }
 #endif
-#endif  // HWY_CUT_TU / HWY_INFO_TU / HWY_FINAL_TU
+#endif  // HWY_CUT_TU / HWY_INFO_TU / HWY_FINAL_TU / HWY_OBSERVE_TU

@@ -16,7 +16,12 @@ training, training/routine.py's attribution() at the final weights on the evalua
 into the metrics JSON as ``attribution`` -- mean |input gradient| of acceleration, steering and
 value per observed row, per distance rank and per feature column, with the share on the embedding
 columns and on the ego row; training, rewards and weights are bit for bit those without it;
-launch() on the vectorised loop only -- launch_group and launch_batch refuse it).
+launch() on the vectorised loop only -- launch_group and launch_batch refuse it) and
+``eval_orders`` (a list of "sorted" / "shuffled": after training, evaluate(num_episodes=10,
+order=name) at the final weights goes into the metrics JSON as ``order_rewards[name]`` -- the
+evaluation's episodes with the policy acting on the same worlds observed under that row order,
+whatever order it trained on; it draws no random number, so everything else is bit for bit the
+run without it; launch() on the vectorised loop only, refused by the grouped launches likewise).
 
 Launched under torchrun (WORLD_SIZE > 1) one experiment spans the ranks, one GPU each: the
 runner joins the process group (RCCL, or ``HWY_DIST_BACKEND``), gives rank r the envs
@@ -153,6 +158,8 @@ class ExperimentRunner:
                         stats_kw["truncation"] = truncation
                     if exp.extra.get("attribution"):
                         stats_kw["attribution"] = True
+                    if exp.extra.get("eval_orders"):
+                        stats_kw["eval_orders"] = list(exp.extra["eval_orders"])
                     if group is not None:
                         e = int(overrides.get("num_envs", 1))
                         if e <= 1:
@@ -240,6 +247,10 @@ class ExperimentRunner:
 
                 if e.extra.get("attribution"):
                     raise ValueError(f"launch_group / launch_batch: extra['attribution'] is not "
+                                     f"supported by the grouped launches (experiment {e.name}); "
+                                     f"use launch()")
+                if e.extra.get("eval_orders"):
+                    raise ValueError(f"launch_group / launch_batch: extra['eval_orders'] is not "
                                      f"supported by the grouped launches (experiment {e.name}); "
                                      f"use launch()")
 

@@ -78,6 +78,29 @@ class RenderArgs(ctypes.Structure):
     ]
 
 
+class ObserveArgs(ctypes.Structure):
+    """hwy_observe_args (include/hwy.h): one hwy_observe launch's order override and outputs."""
+    _fields_ = [
+        ("order", ctypes.c_int32),
+        ("obs", ctypes.c_void_p),
+        ("row_vehicle", ctypes.c_void_p),
+        ("row_values", ctypes.c_void_p),
+        ("veh_values", ctypes.c_void_p),
+    ]
+
+
+# hwy_observe's `order`: None = the handle's own (-1)
+OBSERVE_ORDERS = {None: -1, "sorted": 0, "shuffled": 1}
+
+
+def observe_order(order) -> int:
+    """hwy_observe_args.order of ``order`` (None, "sorted" or "shuffled")."""
+    try:
+        return OBSERVE_ORDERS[order]
+    except (KeyError, TypeError):
+        raise ValueError(f"order must be None, 'sorted' or 'shuffled', got {order!r}") from None
+
+
 # the view hwy_render draws by default: upstream's AbstractEnv.default_config screen_width,
 # screen_height, scaling and centering_position [highway-env 1.10.1]
 RENDER_DEFAULTS = {"screen_width": 600, "screen_height": 150, "scaling": 5.5,

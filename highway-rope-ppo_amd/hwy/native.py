@@ -13,7 +13,7 @@ import os
 import subprocess
 from typing import Optional
 
-from ._abi import HWY_ABI_VERSION, HwyConfig, HwyStepInfo, RenderArgs
+from ._abi import HWY_ABI_VERSION, HwyConfig, HwyStepInfo, ObserveArgs, RenderArgs
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhwy.so")
@@ -92,6 +92,9 @@ def lib():
     L.hwy_render_frame_bytes.argtypes = [ctypes.POINTER(RenderArgs)]
     L.hwy_render_frame_bytes.restype = ctypes.c_int64
     L.hwy_render.argtypes = [vp, ctypes.POINTER(RenderArgs), vp]
+    L.hwy_observe_args_size.restype = i32
+    L.hwy_observe_check.argtypes = [ctypes.POINTER(ObserveArgs)]
+    L.hwy_observe.argtypes = [vp, ctypes.POINTER(ObserveArgs), vp]
     L.hwy_export_state.argtypes = [vp, vp, vp]
     L.hwy_import_state.argtypes = [vp, vp, vp]
     L.hwy_obs_pe.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp]
@@ -108,6 +111,7 @@ def lib():
                  "hwy_step_group", "hwy_step_with_info", "hwy_step_group_info_prepare",
                  "hwy_step_group_info", "hwy_step_with_final", "hwy_step_group_final_prepare",
                  "hwy_step_group_final", "hwy_gae_boot", "hwy_render",
+                 "hwy_observe_check", "hwy_observe",
                  "hwy_export_state", "hwy_import_state", "hwy_obs_pe", "hwy_gae",
                  "hwy_math_selftest"):
         getattr(L, name).restype = i32
@@ -115,6 +119,8 @@ def lib():
         raise HwyNativeError("libhwy.so's hwy_step_info differs from the python mirror; rebuild")
     if L.hwy_render_args_size() != ctypes.sizeof(RenderArgs):
         raise HwyNativeError("libhwy.so's hwy_render_args differs from the python mirror; rebuild")
+    if L.hwy_observe_args_size() != ctypes.sizeof(ObserveArgs):
+        raise HwyNativeError("libhwy.so's hwy_observe_args differs from the python mirror; rebuild")
     if L.hwy_abi_version() != HWY_ABI_VERSION:
         raise HwyNativeError(
             f"libhwy.so ABI {L.hwy_abi_version()} != python ABI {HWY_ABI_VERSION}; rebuild"

@@ -96,5 +96,10 @@ class HighwayEnv(Env):
             return None
         return self._vec.render()[0].cpu().numpy()
 
+    def row_vehicles(self):
+        """The vehicle index each row of the current observation shows, an [N] int32 numpy array
+        (HighwayVecEnv.row_vehicles: 0 in row 0, -1 for an empty row)."""
+        return self._vec.row_vehicles()[0].cpu().numpy()
+
     def close(self):
         self._vec.close()

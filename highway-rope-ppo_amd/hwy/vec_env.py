@@ -76,6 +76,34 @@ def _check_final_obs(env, t: torch.Tensor) -> None:
                          f"(E x N x F_out), got {tuple(t.shape)} {t.dtype} on {t.device}")
 
 
+def observe_args(num_envs: int, rows: int, fout: int, device, order=None, *, obs=None,
+                 row_vehicle=None, row_values=None, veh_values=None) -> _abi.ObserveArgs:
+    """hwy_observe_args for an env of ``num_envs`` x ``rows`` x ``fout`` on ``device`` from
+    caller-owned tensors, every refusal a ValueError (no device call, no library call)."""
+    a = _abi.ObserveArgs()
+    a.order = _abi.observe_order(order)
+    E, N = int(num_envs), int(rows)
+    spec = (("obs", obs, torch.float32, E * N * int(fout), "E x N x F_out"),
+            ("row_vehicle", row_vehicle, torch.int32, E * N, "E x N"),
+            ("row_values", row_values, torch.float32, E * N, "E x N"),
+            ("veh_values", veh_values, torch.float32, E * HWY_MAX_VEHICLES, "E x 64"))
+    for name, t, dtype, n, what in spec:
+        if t is None:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
+                and t.numel() == n and t.device == torch.device(device)):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements "
+                             f"({what}) on {device}, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} "
+                             f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
+        setattr(a, name, t.data_ptr())
+    if obs is None and row_vehicle is None and veh_values is None:
+        raise ValueError("observe_into needs at least one of obs, row_vehicle and veh_values")
+    if (row_values is None) != (veh_values is None):
+        raise ValueError("row_values and veh_values go together")
+    return a
+
+
 class HighwayVecEnv:
     """E lockstep highway-v0 envs with state resident in HBM (one wavefront per env)."""
 
@@ -425,6 +453,51 @@ class HighwayVecEnv:
         check(lib().hwy_render(self._handle, ctypes.byref(a), stream_ptr()), "hwy_render")
         self._keep_render = (ids, shade, out)
         return out.view(shape)
+
+    def observe_into(self, order: Optional[str] = None, *, obs: Optional[torch.Tensor] = None,
+                     row_vehicle: Optional[torch.Tensor] = None,
+                     row_values: Optional[torch.Tensor] = None,
+                     veh_values: Optional[torch.Tensor] = None) -> None:
+        """Re-observe the envs' current states into caller-owned device tensors (hwy_observe:
+        one launch, no synchronisation, graph-capturable).  ``order``: None for the env's own
+        row order -- ``obs`` is then bit for bit what the last step / reset / cut wrote -- or
+        "sorted" / "shuffled" to observe the same states under that order instead.
+        ``obs`` [E, N, F_out] float32; ``row_vehicle`` [E, N] int32, the vehicle each row shows
+        (-1 for an empty row, 0 in row 0); ``row_values`` [E, N] float32 in and ``veh_values``
+        [E, 64] float32 out (both or neither), the per-row values scattered to the vehicles in
+        ``render``'s ``shade`` layout, 0 for vehicles no row shows."""
+        a = observe_args(self.num_envs, self.obs_rows, self.obs_features, self.device, order,
+                         obs=obs, row_vehicle=row_vehicle, row_values=row_values,
+                         veh_values=veh_values)
+        check(lib().hwy_observe(self._handle, ctypes.byref(a), stream_ptr()), "hwy_observe")
+        self._keep_observe = (obs, row_vehicle, row_values, veh_values)
+
+    def observe(self, order: Optional[str] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The current observation [E, N, F_out] under ``order`` (observe_into's ``obs``)."""
+        if out is None:
+            out = torch.empty(self.num_envs, self.obs_rows, self.obs_features,
+                              dtype=torch.float32, device=self.device)
+        self.observe_into(order, obs=out)
+        return out.view(self.num_envs, self.obs_rows, self.obs_features)
+
+    def row_vehicles(self, order: Optional[str] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The vehicle index each observation row shows, [E, N] int32 (-1: an empty row)."""
+        if out is None:
+            out = torch.empty(self.num_envs, self.obs_rows, dtype=torch.int32, device=self.device)
+        self.observe_into(order, row_vehicle=out)
+        return out.view(self.num_envs, self.obs_rows)
+
+    def rows_to_vehicles(self, row_values: torch.Tensor, order: Optional[str] = None,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-row values [E, N] scattered to the vehicles the rows show, [E, 64] float32 (0 for
+        the others): ready to pass as ``render(shade=...)``."""
+        if out is None:
+            out = torch.empty(self.num_envs, HWY_MAX_VEHICLES, dtype=torch.float32,
+                              device=self.device)
+        self.observe_into(order, row_values=row_values, veh_values=out)
+        return out.view(self.num_envs, HWY_MAX_VEHICLES)
 
     def close(self) -> None:
         if self._handle:

@@ -40,6 +40,11 @@ weights on the evaluations' seeds, as ``attribution`` in the metrics; it runs af
 draws no random number, so the training is unchanged, bit for bit.
 ``visualize_agent`` (:32-58) runs deterministic episodes seeded exp_seed + 2000 + k and, with
 ``out_dir``, records their frames (HighwayVecEnv.render, one launch per step); there is no window.
+``attribution="value"`` (or another of ATTRIBUTION_OUTPUTS) tints every vehicle of every frame by
+the policy's input-gradient mass on the observation row that shows it (``attribution_shade``).
+``evaluate(..., order="sorted" | "shuffled")`` runs the evaluation's episodes with the policy acting
+on the same worlds observed under that row order (HighwayVecEnv.observe), whatever the env's own
+order is; ``eval_orders`` books both at the final weights as ``order_rewards`` in the metrics.
 """
 
 from __future__ import annotations
@@ -65,8 +70,15 @@ def _flat_dim(env) -> int:
 
 
 # ---------------------------------------------------------------------------------- evaluation
-def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0):
-    """Mean return of deterministic episodes seeded exp_seed + 1000 + k."""
+def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order=None):
+    """Mean return of deterministic episodes seeded exp_seed + 1000 + k.  ``order`` ("sorted" or
+    "shuffled"; vector envs only): the same episodes with the policy acting on the states
+    re-observed under that row order (HighwayVecEnv.observe) instead of the step's own rows."""
+    if order is not None:
+        if not _is_vector(env):
+            raise ValueError("evaluate(order=...) needs a HighwayVecEnv (num_envs > 1, or "
+                             "make_env's vector_env key for one env)")
+        return _evaluate_vector_order(env, agent, num_episodes, exp_seed, order)
     if _is_vector(env):
         return _evaluate_vector(env, agent, num_episodes, exp_seed)
     totals = []
@@ -122,7 +134,25 @@ def _evaluate_vector(env, agent, num_episodes, exp_seed):
     return r
 
 
-def _run_eval_vector(env, agent, num_episodes, exp_seed):
+def _evaluate_vector_order(env, agent, num_episodes, exp_seed, order):
+    """_evaluate_vector for evaluate(order=...), with a memo of its own keyed by the order too
+    (the order=None memo is neither read nor written)."""
+    from hwy._abi import observe_order
+
+    observe_order(order)  # ValueError for anything but None / "sorted" / "shuffled"
+    key = _eval_key(agent, num_episodes, exp_seed) + (order,)
+    memo = getattr(env.unwrapped, "_eval_order_memo", None)
+    if memo is None:
+        memo = env.unwrapped._eval_order_memo = {}
+    hit = memo.get(order)
+    if hit is not None and hit[0] == key and key[0] is not None:
+        return hit[1]
+    r = _run_eval_vector(env, agent, num_episodes, exp_seed, order=order)
+    memo[order] = (key, r)
+    return r
+
+
+def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None):
     cache = getattr(env.unwrapped, "_eval_envs", None)
     if cache is None:
         cache = {}
@@ -135,7 +165,10 @@ def _run_eval_vector(env, agent, num_episodes, exp_seed):
     obs, _ = ev.reset(seeds=seeds)
     alive = torch.ones(num_episodes, dtype=torch.bool, device=dev)
     total = torch.zeros(num_episodes, dtype=torch.float64, device=dev)
+    seen = None  # order given: the states as observed under it, in a buffer of its own
     for k in range(ev.max_episode_steps + 1):
+        if order is not None:
+            obs = seen = ev.observe(order=order, out=seen)
         a, _, _, _ = agent.select_action(obs.reshape(num_episodes, -1), deterministic=True)
         obs, r, te, tr, _ = ev.step(a.contiguous())
         total += torch.where(alive, r.double(), torch.zeros_like(total))
@@ -170,7 +203,21 @@ def save_frames(path_stem: str, frames: np.ndarray, fps: int = 15) -> list:
     return paths + [path_stem + ".gif"]
 
 
-def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, out_dir=None):
+def attribution_shade(vec_env, grad, order=None):
+    """Per-vehicle tint [E, 64] float32 (HighwayVecEnv.render's ``shade``) from one output's input
+    gradients ``grad`` [E, N * F_out] (PPOAgent.input_gradients(obs)[name]) at ``vec_env``'s
+    current states: per env, the row mass is the sum over the row's F_out columns of |grad|
+    divided by the env's largest row mass (0 where that largest mass is 0), scattered to the
+    vehicles the rows show (rows_to_vehicles under ``order``; None: the env's own)."""
+    E, N = vec_env.num_envs, vec_env.obs_rows
+    mass = grad.detach().reshape(E, N, -1).abs().sum(dim=2)
+    top = mass.max(dim=1, keepdim=True).values
+    rel = torch.where(top > 0, mass / top, torch.zeros_like(mass))
+    return vec_env.rows_to_vehicles(rel.to(torch.float32).contiguous(), order=order)
+
+
+def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, out_dir=None,
+                    attribution=None, tape=None):
     """Deterministic episodes of a trained agent, seeded exp_seed + 2000 + ep, on a fresh env of
     ``env``'s config and fused wrapper (reference training/routine.py:32-58, which opens a
     render_mode="human" window; there is no display here).  All ``num_episodes`` run as one
@@ -178,8 +225,16 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
     every step's frames are drawn in one launch (HighwayVecEnv.render) and episode ep's frames --
     the reset frame and one per step up to its own end, [T + 1, H, W, 3] -- are written to
     ``out_dir/viz_episode_<ep + 1>.npy`` (and ``.gif`` when PIL is importable).  Logs
-    ``viz_episode=%d reward=%.2f`` per episode and returns the rewards."""
+    ``viz_episode=%d reward=%.2f`` per episode and returns the rewards.  ``attribution``: None, or
+    one of ATTRIBUTION_OUTPUTS to tint each frame's vehicles by that output's input-gradient mass
+    at the frame's own observation (attribution_shade; both are the state after the step).
+    ``tape``: a list that receives, per grabbed step, (observation, exported state, the episodes
+    still recording) as clones (tests)."""
     from hwy.vec_env import HighwayVecEnv
+
+    if attribution is not None and attribution not in ATTRIBUTION_OUTPUTS:
+        raise ValueError(f"attribution must be None or one of {ATTRIBUTION_OUTPUTS}, got "
+                         f"{attribution!r}")
 
     if logger is None:
         logger = logging.getLogger(__name__)
@@ -202,7 +257,13 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
         running = [True] * n
 
         def grab():
-            host = ev.render().cpu().numpy()
+            shade = None
+            if attribution is not None:
+                g = agent.input_gradients(obs.reshape(n, -1))[attribution]
+                shade = attribution_shade(ev, g)
+            host = ev.render(shade=shade).cpu().numpy()
+            if tape is not None:
+                tape.append((obs.clone(), ev.export_state(), list(running)))
             for ep in range(n):
                 if running[ep]:
                     frames[ep].append(host[ep])
@@ -648,11 +709,15 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
                                eval_interval=50, steps_per_update=2048, experiment_name="",
                                exp_seed: int = 0, logger=None, episode_schedule="lockstep",
                                episode_stats: bool = False, truncation: str = "terminal",
-                               attribution: bool = False):
+                               attribution: bool = False, eval_orders=None):
     from ppo.rollout import check_episode_schedule, check_truncation
 
     if attribution and not _is_vector(env):
         raise ValueError("attribution needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                         "vector_env key for one env)")
+    eval_orders = check_eval_orders(eval_orders)
+    if eval_orders and not _is_vector(env):
+        raise ValueError("eval_orders needs a HighwayVecEnv (num_envs > 1, or make_env's "
                          "vector_env key for one env)")
 
     if check_truncation(truncation) == "bootstrap":
@@ -727,10 +792,24 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
     if attribution:  # after training, at the final weights, on the evaluations' seeds
         metrics_history["attribution"] = _attribution(env, agent, num_episodes=5,
                                                       exp_seed=exp_seed)
+    if eval_orders:  # likewise: the final weights under each row order, evaluate()'s episodes
+        metrics_history["order_rewards"] = {
+            name: evaluate(env, agent, num_episodes=10, exp_seed=exp_seed, order=name)
+            for name in eval_orders}
     _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_history,
                     training_episodes, episode_rewards, tracker.eval_episodes, tracker.rewards,
                     tracker.avg_rewards, target_reward, total_steps, logger, exp_prefix)
     return tracker.rewards, tracker.avg_rewards, metrics_history
+
+
+def check_eval_orders(eval_orders) -> list:
+    """``eval_orders`` as a list of row-order names (None or empty: none), each "sorted" or
+    "shuffled" and none twice; ValueError otherwise."""
+    names = [] if eval_orders is None else list(eval_orders)
+    if any(n not in ("sorted", "shuffled") for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"eval_orders must list 'sorted' and / or 'shuffled' once each, got "
+                         f"{eval_orders!r}")
+    return names
 
 
 def _log_episode(logger, prefix, episode_num, ep_reward, episode_rewards, log_interval,

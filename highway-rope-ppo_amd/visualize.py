@@ -3,6 +3,7 @@
     python visualize.py --model artifacts/highway-ppo/checkpoints/ppo_highway_best_<exp>.pth \
         --episodes 3 --out demo_frames
     python visualize.py --models-file best_checkpoints.txt --out demo_frames
+    python visualize.py --model <checkpoint> --attribution value     # what the critic looks at
 
 For every checkpoint the network's dimensions are read from the saved weights
 (``shared.0.weight`` is [hidden_dim, state_dim], ``actor_mean.2.weight`` [action_dim,
@@ -13,7 +14,9 @@ positional-embedding condition carries ``_d_embed<k>``), the condition's env is 
 training.routine.visualize_agent into ``--out/<checkpoint stem>/``: per episode a ``.npy`` of
 [T + 1, H, W, 3] uint8 frames, and an animated GIF when PIL is importable.  The frames are drawn
 on the GPU by hwy_render (include/hwy.h: this project's frame rule at upstream's view geometry,
-not pygame's pixels).  There is no live window and no MP4: neither a display nor an encoder is a
+not pygame's pixels).  ``--attribution`` tints every vehicle toward yellow by the share of the
+chosen output's input-gradient mass on the observation row that shows it (hwy_observe's row ->
+vehicle map; training.routine.attribution_shade).  There is no live window and no MP4: neither a display nor an encoder is a
 dependency.
 """
 
@@ -87,9 +90,11 @@ def load_agent(path: str, device=None):
     return agent
 
 
-def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=None) -> List[float]:
+def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=None,
+           attribution: Optional[str] = None) -> List[float]:
     """Record ``episodes`` episodes of one checkpoint into out_dir/<checkpoint stem>/; returns
-    their rewards."""
+    their rewards.  ``attribution`` ("acceleration", "steering" or "value"): tint every vehicle by
+    the policy's input-gradient mass on the row that shows it (visualize_agent)."""
     from config.base_config import HIGHWAY_CONFIG
     from experiments.wrappers import make_env
     from training.routine import visualize_agent
@@ -105,7 +110,8 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
             raise ValueError(f"{os.path.basename(path)}: the checkpoint takes {want} inputs, the "
                              f"{cond.name} env (d_embed={d_embed}) gives {have}")
         dest = os.path.join(out_dir, os.path.splitext(os.path.basename(path))[0])
-        rewards = visualize_agent(env, agent, num_episodes=episodes, exp_seed=seed, out_dir=dest)
+        rewards = visualize_agent(env, agent, num_episodes=episodes, exp_seed=seed, out_dir=dest,
+                                  attribution=attribution)
     finally:
         env.close()
     for ep, r in enumerate(rewards):
@@ -130,10 +136,12 @@ def main(argv=None) -> int:
     p.add_argument("--out", default="demo_frames", help="directory for the recordings")
     p.add_argument("--seed", type=int, default=0,
                    help="episode ep is seeded seed + 2000 + ep, as visualize_agent")
+    p.add_argument("--attribution", choices=("acceleration", "steering", "value"), default=None,
+                   help="tint each vehicle by |input gradient| of this output on its row")
     args = p.parse_args(argv)
     models = [args.model] if args.model else list(models_from_file(args.models_file))
     for m in models:
-        record(m, args.out, episodes=args.episodes, seed=args.seed)
+        record(m, args.out, episodes=args.episodes, seed=args.seed, attribution=args.attribution)
     return 0
 
 

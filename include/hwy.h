@@ -42,6 +42,8 @@
  *                                truncation as terminal, training/routine.py:135; opt-in)
  *   hwy_render                <- env.render() of a render_mode="rgb_array" env  visualize.py:146
  *                                (this project's own frame rule, not pygame's pixels)
+ *   hwy_observe               <- env.unwrapped.observation_type.observe() on the current road, under
+ *                                either "order", plus the row -> vehicle assignment it drops
  *
  * Conventions
  *   - Plain pointers and sizes only; device pointers are HIP device pointers (e.g. torch
@@ -396,6 +398,49 @@ int hwy_render_args_size(void);
  * no handle); pure, no device call. */
 int64_t hwy_render_frame_bytes(const hwy_render_args* a);
 int hwy_render(hwy_handle* h, const hwy_render_args* a, void* stream);
+
+/* ---- Re-observe the env states: the observation as a function of the stored state, the vehicle
+ * each row shows, the other row order, and per-row values scattered to the vehicles.
+ *
+ * hwy_observe observes all E envs from the state words as they stand, with the step's own
+ * observation code (the same function hwy_step / hwy_reset / hwy_cut_episodes run on exactly what
+ * they then store: the vehicles' x, y, heading, speed and flags and the env's step and seed words;
+ * sin / cos are hm_sincosf of the stored heading).
+ *
+ *   order -1, or the handle's own order: obs [E][N][F_out] is bit for bit the row the last
+ *     hwy_step* / hwy_reset / hwy_cut_episodes wrote for that env -- after an autoreset the new
+ *     episode's first observation -- for every fused wrapper and for seed groups with their
+ *     per-group RankPE tables.
+ *   the other order: obs is what that same call would have written had the handle's `order` been
+ *     the other one, everything else as the handle's config, the fused wrapper included: RankPE
+ *     appends table[row position], the distance wrappers see the reordered rows.  `shuffled` is
+ *     the step's permutation: Philox over (slot, step word, seed words), N - 1 slots, empty slots
+ *     shuffled along with the full ones, identity for N <= 2.
+ *   row_vehicle [E][N] i32: the vehicle index (0..63) shown in row r, -1 for an empty (all-zero)
+ *     row; row 0 is always 0 (the ego).  Non-negative entries of an env are distinct.
+ *   row_values [E][N] f32 in, veh_values [E][64] f32 out (hwy_render's `shade` layout), both or
+ *     neither: veh_values[e][row_vehicle[e][r]] = row_values[e][r], bits copied, for every row
+ *     with a vehicle; every other entry of the 64 is written +0.0.
+ *
+ * All pointers are device pointers and nullable, but at least one output must be given.
+ * hwy_observe is asynchronous, allocates nothing, is hipGraph-capturable, reads the state and
+ * writes nothing but the outputs it was given.  It returns HWY_EINVAL before any device call for
+ * a NULL handle or NULL args, an order outside {-1, HWY_ORDER_SORTED, HWY_ORDER_SHUFFLED}, all of
+ * obs / row_vehicle / veh_values NULL, row_values without veh_values or the reverse, and a handle
+ * whose per-group PE tables are without meaning (hwy_set_seed_groups). */
+typedef struct hwy_observe_args {
+  int32_t order;            /* -1: the handle's own; else enum hwy_order */
+  float* obs;               /* device [E][N][F_out], nullable */
+  int32_t* row_vehicle;     /* device [E][N], nullable */
+  const float* row_values;  /* device [E][N], nullable; needs veh_values */
+  float* veh_values;        /* device [E][64], nullable; needs row_values */
+} hwy_observe_args;
+/* sizeof(hwy_observe_args) as compiled into the library (binding layout check). */
+int hwy_observe_args_size(void);
+/* HWY_OK, or HWY_EINVAL for arguments hwy_observe refuses (every check that needs no handle);
+ * pure, no device call. */
+int hwy_observe_check(const hwy_observe_args* a);
+int hwy_observe(hwy_handle* h, const hwy_observe_args* a, void* stream);
 
 /* Stand-alone observation wrapper on [E,N,F] f32 -> [E,N,F_out] f32 (foreign envs).
  *   kind = enum hwy_pe_kind, d = appended width (rank/dist) or rotate_dim (rope),
