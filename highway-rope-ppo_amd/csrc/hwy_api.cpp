@@ -578,6 +578,40 @@ int hwy_observe(hwy_handle* h, const hwy_observe_args* a, void* stream) {
   return HWY_OK;
 }
 
+int hwy_traffic_args_size(void) { return (int)sizeof(hwy_traffic_args); }
+
+int hwy_traffic_check(const hwy_traffic_args* a) {
+  if (!a) return fail(HWY_EINVAL, "hwy_traffic: args is NULL");
+  if (!a->front && !a->rear && !a->gap && !a->closing && !a->ttc && !a->thw && !a->risk &&
+      !a->ego && !a->acc)
+    return fail(HWY_EINVAL, "hwy_traffic: no output given (front, rear, gap, closing, ttc, thw, "
+                            "risk, ego and acc are all NULL)");
+  if (a->ep_stats && !a->acc) return fail(HWY_EINVAL, "hwy_traffic: ep_stats needs acc");
+  for (int k = 0; k < 3; ++k)
+    if (a->restart[k] && !a->acc)
+      return fail(HWY_EINVAL, "hwy_traffic: restart[%d] needs acc", k);
+  const float inf = __builtin_inff();
+  const float vals[4] = {a->ttc_thresh, a->thw_thresh, a->risk_horizon, a->near_range};
+  const char* names[4] = {"ttc_thresh", "thw_thresh", "risk_horizon", "near_range"};
+  for (int i = 0; i < 4; ++i)
+    if (!(vals[i] > 0.0f && vals[i] < inf))
+      return fail(HWY_EINVAL, "hwy_traffic: %s must be finite and > 0, got %g", names[i],
+                  (double)vals[i]);
+  return HWY_OK;
+}
+
+int hwy_traffic(hwy_handle* h, const hwy_traffic_args* a, void* stream) {
+  if (!h) return fail(HWY_EINVAL, "hwy_traffic: handle is NULL");
+  if (int rc = hwy_traffic_check(a)) return rc;
+  TrafficParams p;
+  p.a = *a;
+  p.state = h->state;
+  p.cfg = h->cfg;
+  if (hwy_launch_traffic(&p, (hipStream_t)stream))
+    return hip_fail(hipGetLastError(), "hwy_traffic_kernel");
+  return HWY_OK;
+}
+
 int hwy_obs_pe(const float* obs_in, float* obs_out, int E, int N, int F, int kind, int d,
                int ego_idx, float max_dist, const float* table, const float* dist_override,
                void* stream) {

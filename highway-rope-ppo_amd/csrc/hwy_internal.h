@@ -54,7 +54,16 @@ struct ObserveParams {
   float* veh_values;
 };
 
+// hwy_traffic's launch parameters (the traffic unit of hwy_kernels.hip): the checked arguments,
+// the handle's state and its config (the neighbour search takes the config it takes in the step)
+struct TrafficParams {
+  hwy_traffic_args a;
+  const uint32_t* state;  // [HWY_NFIELDS][E][64]
+  hwy_config cfg;
+};
+
 extern "C" {
+int hwy_launch_traffic(const TrafficParams* p, hipStream_t s);
 int hwy_launch_observe(const ObserveParams* p, hipStream_t s);
 int hwy_launch_render(const RenderParams* p, hipStream_t s);
 int hwy_launch_step(const StepParams* p, hipStream_t s);

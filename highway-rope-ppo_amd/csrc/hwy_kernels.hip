@@ -1679,6 +1679,140 @@ extern "C" int hwy_launch_observe(const ObserveParams* p, hipStream_t s) {
   hipLaunchKernelGGL(hwy_observe_kernel, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#elif defined(HWY_TRAFFIC_TU)
+// hwy_traffic's kernel, likewise a unit of its own (-DHWY_TRAFFIC_TU -> hwy_traffic.o): the
+// neighbours of every vehicle through the step's own road_order / lane_scan /
+// neighbours_ordered, and from them the gap, time-to-collision and headway of include/hwy.h, the
+// ego row and the running per-episode reduction.  One wave per env, lane = vehicle, as the step;
+// it loads six fields (x, y, heading, speed, lane, flags), 1,536 B per env, and writes nothing
+// but the outputs it was given.  Every cross-lane read runs with all 64 lanes active; the
+// per-lane index of a gather is a road-order entry or the lane itself, so it is in 0..63.
+
+// 0 where gap <= 0, else gap / den where den > 0, else +inf (ttc: den = closing; thw: den = vx)
+__device__ __forceinline__ float gap_over(float gap, float den) {
+  return gap <= 0.0f ? 0.0f : (den > 0.0f ? gap / den : hm_bits2f(0x7f800000u));
+}
+
+__global__ void __launch_bounds__(256) hwy_traffic_kernel(TrafficParams P) {
+  const hwy_config& C = P.cfg;
+  const hwy_traffic_args& A = P.a;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int w = threadIdx.x / WAVE;
+  const int e = blockIdx.x * ENVS_PER_BLOCK + w;
+  if (e >= C.num_envs) return;  // whole wave
+  const int V = C.vehicles_count + 1;
+  const size_t fstride = (size_t)C.num_envs * WAVE;
+  const uint32_t idx = (uint32_t)e * WAVE + lane;  // < 2^32: hwy_create bounds num_envs
+  const uint32_t* st = P.state;
+  const float inf = hm_bits2f(0x7f800000u);
+  Veh v{};  // the fields the neighbour search does not read stay zero
+  v.x = hm_bits2f((st + HWY_F_X * fstride)[idx]);
+  v.y = hm_bits2f((st + HWY_F_Y * fstride)[idx]);
+  v.h = hm_bits2f((st + HWY_F_HEADING * fstride)[idx]);
+  v.spd = hm_bits2f((st + HWY_F_SPEED * fstride)[idx]);
+  v.ln = (int)(st + HWY_F_LANE * fstride)[idx];
+  const uint32_t fl = (st + HWY_F_FLAGS * fstride)[idx];
+  v.present = ((fl & HWY_FLAG_PRESENT) != 0u) && lane < V;  // load_veh's rule
+  const uint64_t pres = ballot(v.present);
+
+  // Road.neighbour_vehicles on lanes ln - 1, ln, ln + 1 (slot s <-> lane ln - 1 + s), as
+  // frame_wave asks for them
+  RoadOrder ro;
+  ro.rk = 0;
+  ro.ord = 0;
+  ro.valid = false;
+  road_order(lane, v, pres, ro);
+  const float xq = shf(v.x, ro.ord);
+  int fi[3], ri[3], qfp[3];
+  neighbours_ordered(C, lane, v, pres, ro, xq, fi, ri, qfp);
+
+  float sin_h, cos_h;
+  hm_sincosf(v.h, &sin_h, &cos_h);
+  const float vx = v.spd * cos_h;
+
+  // gaps towards the front / the rear of slot s: (x_f - x_i) - 5 and (x_i - x_r) - 5, +inf for none
+  float fgap[3], rgap[3];
+  bool hasf[3], hasr[3];
+  float vxf = 0.0f, vxr = 0.0f;  // vx of the own lane's front / rear (this vehicle's without one)
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    hasf[s] = v.present && fi[s] >= 0;
+    hasr[s] = v.present && ri[s] >= 0;
+    const int fsrc = hasf[s] ? fi[s] : lane, rsrc = hasr[s] ? ri[s] : lane;
+    const float xf = shf(v.x, fsrc), xr = shf(v.x, rsrc);
+    fgap[s] = hasf[s] ? (xf - v.x) - VEH_LENGTH : inf;
+    rgap[s] = hasr[s] ? (v.x - xr) - VEH_LENGTH : inf;
+    if (s == 1) {
+      vxf = shf(vx, fsrc);
+      vxr = shf(vx, rsrc);
+    }
+  }
+  const float gap = fgap[1];
+  const float closing = hasf[1] ? vx - vxf : 0.0f;
+  const float ttc = v.present ? gap_over(gap, closing) : inf;
+  const float thw = v.present ? gap_over(gap, vx) : inf;
+  const float risk = ttc < A.risk_horizon ? 1.0f - ttc / A.risk_horizon : 0.0f;
+  if (A.front) A.front[idx] = hasf[1] ? fi[1] : -1;
+  if (A.rear) A.rear[idx] = hasr[1] ? ri[1] : -1;
+  if (A.gap) A.gap[idx] = gap;
+  if (A.closing) A.closing[idx] = closing;
+  if (A.ttc) A.ttc[idx] = ttc;
+  if (A.thw) A.thw[idx] = thw;
+  if (A.risk) A.risk[idx] = risk;
+  if (!A.ego && !A.acc) return;  // wave-uniform
+
+  // ---- the ego row: vehicle 0's values, broadcast, lane s of the first 16 holding slot s
+  const float rclos = hasr[1] ? vxr - vx : 0.0f;
+  const float rttc = gap_over(rgap[1], rclos);
+  const float ex = rdlf(v.x, 0), ey = rdlf(v.y, 0);
+  const float dx = v.x - ex, dy = v.y - ey;
+  const bool other = v.present && lane != 0;
+  // the least dx*dx + dy*dy as the greatest of the negated squares (exact either way)
+  const float dist = __builtin_sqrtf(-wave_max_f(other ? -(dx * dx + dy * dy) : -inf));
+  const uint64_t nearm = ballot(other) & ballot(0.0f <= dx) & ballot(dx <= A.near_range);
+  const float off = lane_lat(v.y, v.ln);
+  const float gap0 = rdlf(gap, 0), ttc0 = rdlf(ttc, 0), thw0 = rdlf(thw, 0);
+  const float slot[HWY_TRAFFIC_NEGO] = {
+      gap0, rdlf(closing, 0), ttc0, thw0, rdlf(rgap[1], 0), rdlf(rclos, 0), rdlf(rttc, 0),
+      rdlf(fgap[0], 0), rdlf(rgap[0], 0), rdlf(fgap[2], 0), rdlf(rgap[2], 0), dist,
+      (float)__popcll(nearm), rdlf(off, 0), rdlf(vx, 0), rdlf(risk, 0)};
+  if (A.ego) {
+    float ev = 0.0f;
+#pragma unroll
+    for (int s = 0; s < HWY_TRAFFIC_NEGO; ++s) ev = lane == s ? slot[s] : ev;
+    if (lane < HWY_TRAFFIC_NEGO) A.ego[(size_t)e * HWY_TRAFFIC_NEGO + lane] = ev;
+  }
+  if (!A.acc) return;
+
+  // ---- the running reduction: lane s of the first 8 holds slot s of the env's row
+  bool restart = false;  // wave-uniform
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    if (A.restart[k]) restart = restart || A.restart[k][e] != 0;
+  const float one_if_front = rdli((int)hasf[1], 0) ? 1.0f : 0.0f;
+  const float now[HWY_TRAFFIC_NACC] = {1.0f, ttc0, thw0, gap0, dist,
+                                       ttc0 < A.ttc_thresh ? 1.0f : 0.0f,
+                                       thw0 < A.thw_thresh ? 1.0f : 0.0f, one_if_front};
+  float sv = 0.0f;
+#pragma unroll
+  for (int s = 0; s < HWY_TRAFFIC_NACC; ++s) sv = lane == s ? now[s] : sv;
+  const bool mine = lane < HWY_TRAFFIC_NACC;
+  const size_t ai = (size_t)e * HWY_TRAFFIC_NACC + (mine ? lane : 0);
+  const float old = mine ? A.acc[ai] : 0.0f;
+  const bool fresh = restart || rdlf(old, 0) == 0.0f;
+  const bool is_min = lane >= 1 && lane <= 4;
+  const float merged = is_min ? hm_minf(old, sv) : old + sv;
+  if (mine) {
+    A.acc[ai] = fresh ? sv : merged;
+    if (A.ep_stats) A.ep_stats[ai] = restart ? old : 0.0f;
+  }
+}
+
+extern "C" int hwy_launch_traffic(const TrafficParams* p, hipStream_t s) {
+  const int blocks = (p->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  hipLaunchKernelGGL(hwy_traffic_kernel, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 #else  // the main unit, to the end of the file
 template <int W>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
@@ -1918,4 +2052,4 @@ extern "C" int hwy_debug_sections(unsigned long long* out, int reset) {
   return 0;
 }
 #endif
-#endif  // HWY_CUT_TU / HWY_INFO_TU / HWY_FINAL_TU / HWY_OBSERVE_TU
+#endif  // HWY_CUT_TU / HWY_INFO_TU / HWY_FINAL_TU / HWY_OBSERVE_TU / HWY_TRAFFIC_TU

@@ -9,6 +9,10 @@ boundary and evaluations ahead of the update, training/routine.py; with it ``num
 the vectorised loop on a one-env HighwayVecEnv, which is the reference's own episode stream)
 and ``episode_stats`` (True: per-episode lengths, crashes, mean speeds and lane changes in the
 metrics and a crash rate in the summary, training/routine.py; vectorised loop only) and
+``safety_stats`` (True: one hwy_traffic launch per env step books every episode's least
+time-to-collision, headway, gap and distance and its shares of critical and tailgating states in
+the metrics, and a near-miss rate in the summary, training/routine.py; vectorised loop only, not
+over a process group; training, rewards and weights are bit for bit those without it) and
 ``truncation`` ("terminal", the default and the reference's behaviour, or "bootstrap": GAE takes
 V(final observation) at a time limit, ppo/rollout.py; launch() on the vectorised loop only --
 a process group, launch_group and launch_batch refuse it) and ``attribution`` (True: after
@@ -156,6 +160,11 @@ class ExperimentRunner:
                             raise ValueError("extra['truncation']='bootstrap' does not run over "
                                              "a process group")
                         stats_kw["truncation"] = truncation
+                    if exp.extra.get("safety_stats"):
+                        if group is not None:
+                            raise ValueError("extra['safety_stats'] does not run over a process "
+                                             "group")
+                        stats_kw["safety_stats"] = True
                     if exp.extra.get("attribution"):
                         stats_kw["attribution"] = True
                     if exp.extra.get("eval_orders"):
@@ -270,6 +279,8 @@ class ExperimentRunner:
             raise ValueError("launch_batch: the cells must share extra['episode_schedule']")
         if len({bool(e.extra.get("episode_stats", False)) for e in first}) != 1:
             raise ValueError("launch_batch: the cells must share extra['episode_stats']")
+        if len({bool(e.extra.get("safety_stats", False)) for e in first}) != 1:
+            raise ValueError("launch_batch: the cells must share extra['safety_stats']")
 
         def shared(e):
             return (int(e.extra.get("num_envs", 1)), e.hp.steps_per_update, e.max_episodes,
@@ -329,6 +340,8 @@ class ExperimentRunner:
         sched_kw = {} if schedule == "lockstep" else {"episode_schedule": schedule}
         if first[0].extra.get("episode_stats"):
             sched_kw["episode_stats"] = True
+        if first[0].extra.get("safety_stats"):
+            sched_kw["safety_stats"] = True
         results = [[{"experiment_name": e.name, "status": "FAILED"} for e in exps]
                    for exps in cells]
         loggers = []

@@ -89,6 +89,30 @@ class ObserveArgs(ctypes.Structure):
     ]
 
 
+# hwy_traffic (include/hwy.h): floats per env of the ego row and of the running reduction, their
+# slots, and the defaults of the four thresholds (seconds, seconds, seconds, metres)
+HWY_TRAFFIC_NEGO = 16
+HWY_TRAFFIC_NACC = 8
+(EGO_GAP, EGO_CLOSING, EGO_TTC, EGO_THW, EGO_REAR_GAP, EGO_REAR_CLOSING, EGO_REAR_TTC,
+ EGO_LEFT_FRONT_GAP, EGO_LEFT_REAR_GAP, EGO_RIGHT_FRONT_GAP, EGO_RIGHT_REAR_GAP, EGO_MIN_DISTANCE,
+ EGO_NEAR_COUNT, EGO_LANE_OFFSET, EGO_VX, EGO_RISK) = range(16)
+(TACC_N, TACC_MIN_TTC, TACC_MIN_THW, TACC_MIN_GAP, TACC_MIN_DISTANCE, TACC_TTC_CRITICAL,
+ TACC_TAILGATING, TACC_WITH_FRONT) = range(8)
+TRAFFIC_VEHICLE_OUTPUTS = ("front", "rear", "gap", "closing", "ttc", "thw", "risk")
+TRAFFIC_DEFAULTS = {"ttc_thresh": 2.0, "thw_thresh": 1.0, "risk_horizon": 4.0, "near_range": 50.0}
+
+
+class TrafficArgs(ctypes.Structure):
+    """hwy_traffic_args (include/hwy.h): one hwy_traffic launch's outputs, masks and thresholds."""
+    _fields_ = [(n, ctypes.c_void_p) for n in TRAFFIC_VEHICLE_OUTPUTS + ("ego", "acc", "ep_stats")] + [
+        ("restart", ctypes.c_void_p * 3),
+        ("ttc_thresh", ctypes.c_float),
+        ("thw_thresh", ctypes.c_float),
+        ("risk_horizon", ctypes.c_float),
+        ("near_range", ctypes.c_float),
+    ]
+
+
 # hwy_observe's `order`: None = the handle's own (-1)
 OBSERVE_ORDERS = {None: -1, "sorted": 0, "shuffled": 1}
 

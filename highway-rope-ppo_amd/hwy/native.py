@@ -13,7 +13,7 @@ import os
 import subprocess
 from typing import Optional
 
-from ._abi import HWY_ABI_VERSION, HwyConfig, HwyStepInfo, ObserveArgs, RenderArgs
+from ._abi import HWY_ABI_VERSION, HwyConfig, HwyStepInfo, ObserveArgs, RenderArgs, TrafficArgs
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhwy.so")
@@ -95,6 +95,9 @@ def lib():
     L.hwy_observe_args_size.restype = i32
     L.hwy_observe_check.argtypes = [ctypes.POINTER(ObserveArgs)]
     L.hwy_observe.argtypes = [vp, ctypes.POINTER(ObserveArgs), vp]
+    L.hwy_traffic_args_size.restype = i32
+    L.hwy_traffic_check.argtypes = [ctypes.POINTER(TrafficArgs)]
+    L.hwy_traffic.argtypes = [vp, ctypes.POINTER(TrafficArgs), vp]
     L.hwy_export_state.argtypes = [vp, vp, vp]
     L.hwy_import_state.argtypes = [vp, vp, vp]
     L.hwy_obs_pe.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp]
@@ -111,7 +114,7 @@ def lib():
                  "hwy_step_group", "hwy_step_with_info", "hwy_step_group_info_prepare",
                  "hwy_step_group_info", "hwy_step_with_final", "hwy_step_group_final_prepare",
                  "hwy_step_group_final", "hwy_gae_boot", "hwy_render",
-                 "hwy_observe_check", "hwy_observe",
+                 "hwy_observe_check", "hwy_observe", "hwy_traffic_check", "hwy_traffic",
                  "hwy_export_state", "hwy_import_state", "hwy_obs_pe", "hwy_gae",
                  "hwy_math_selftest"):
         getattr(L, name).restype = i32
@@ -121,6 +124,8 @@ def lib():
         raise HwyNativeError("libhwy.so's hwy_render_args differs from the python mirror; rebuild")
     if L.hwy_observe_args_size() != ctypes.sizeof(ObserveArgs):
         raise HwyNativeError("libhwy.so's hwy_observe_args differs from the python mirror; rebuild")
+    if L.hwy_traffic_args_size() != ctypes.sizeof(TrafficArgs):
+        raise HwyNativeError("libhwy.so's hwy_traffic_args differs from the python mirror; rebuild")
     if L.hwy_abi_version() != HWY_ABI_VERSION:
         raise HwyNativeError(
             f"libhwy.so ABI {L.hwy_abi_version()} != python ABI {HWY_ABI_VERSION}; rebuild"

@@ -101,5 +101,11 @@ class HighwayEnv(Env):
         (HighwayVecEnv.row_vehicles: 0 in row 0, -1 for an empty row)."""
         return self._vec.row_vehicles()[0].cpu().numpy()
 
+    def traffic(self, **thresholds):
+        """Gaps, time-to-collision and headway of the current state (HighwayVecEnv.traffic) as
+        numpy: ``ego`` [16] float32 (hwy._abi.EGO_* slots) and the per-vehicle ``front``, ``rear``
+        [64] int32 and ``gap``, ``closing``, ``ttc``, ``thw``, ``risk`` [64] float32."""
+        return {k: t[0].cpu().numpy() for k, t in self._vec.traffic(**thresholds).items()}
+
     def close(self):
         self._vec.close()

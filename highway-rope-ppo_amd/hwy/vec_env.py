@@ -104,6 +104,74 @@ def observe_args(num_envs: int, rows: int, fout: int, device, order=None, *, obs
     return a
 
 
+TRAFFIC_OUTPUTS = _abi.TRAFFIC_VEHICLE_OUTPUTS + ("ego", "acc", "ep_stats")
+
+
+def alloc_traffic(num_envs: int, device) -> Dict[str, torch.Tensor]:
+    """Device tensors for every output of hwy_traffic, keyed by hwy_traffic_args' fields; ``acc``
+    is zero-filled as the running reduction's contract asks."""
+    E, kw = int(num_envs), dict(device=device)
+    out = {n: torch.zeros(E, HWY_MAX_VEHICLES, dtype=torch.int32 if n in ("front", "rear")
+                          else torch.float32, **kw) for n in _abi.TRAFFIC_VEHICLE_OUTPUTS}
+    out["ego"] = torch.zeros(E, _abi.HWY_TRAFFIC_NEGO, dtype=torch.float32, **kw)
+    out["acc"] = torch.zeros(E, _abi.HWY_TRAFFIC_NACC, dtype=torch.float32, **kw)
+    out["ep_stats"] = torch.zeros(E, _abi.HWY_TRAFFIC_NACC, dtype=torch.float32, **kw)
+    return out
+
+
+def traffic_args(num_envs: int, device, *, restart=(), ttc_thresh=None, thw_thresh=None,
+                 risk_horizon=None, near_range=None, **outputs) -> _abi.TrafficArgs:
+    """hwy_traffic_args for ``num_envs`` envs on ``device`` from caller-owned tensors (``outputs``
+    by hwy_traffic_args' field names, None = not wanted; ``restart`` up to three [E] uint8 masks),
+    every refusal a ValueError (no device call, no library call)."""
+    unknown = set(outputs) - set(TRAFFIC_OUTPUTS)
+    if unknown:
+        raise ValueError(f"unknown traffic outputs {sorted(unknown)}; known: {TRAFFIC_OUTPUTS}")
+    a = _abi.TrafficArgs()
+    E = int(num_envs)
+
+    def dev_tensor(name, t, dtype, n, what):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
+                and t.numel() == n and t.device == torch.device(device)):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements "
+                             f"({what}) on {device}, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} "
+                             f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
+        return t.data_ptr()
+
+    for name in TRAFFIC_OUTPUTS:
+        t = outputs.get(name)
+        if t is None:
+            continue
+        if name in _abi.TRAFFIC_VEHICLE_OUTPUTS:
+            dtype = torch.int32 if name in ("front", "rear") else torch.float32
+            n, what = E * HWY_MAX_VEHICLES, "E x 64"
+        else:
+            width = _abi.HWY_TRAFFIC_NEGO if name == "ego" else _abi.HWY_TRAFFIC_NACC
+            dtype, n, what = torch.float32, E * width, f"E x {width}"
+        setattr(a, name, dev_tensor(name, t, dtype, n, what))
+    if all(outputs.get(n) is None for n in TRAFFIC_OUTPUTS if n != "ep_stats"):
+        raise ValueError("traffic_into needs at least one output besides ep_stats")
+    masks = [m for m in (restart or ()) if m is not None]
+    if len(masks) > 3:
+        raise ValueError(f"at most three restart masks, got {len(masks)}")
+    has_acc = outputs.get("acc") is not None
+    if outputs.get("ep_stats") is not None and not has_acc:
+        raise ValueError("ep_stats needs acc")
+    if masks and not has_acc:
+        raise ValueError("restart masks need acc")
+    for k, m in enumerate(masks):
+        a.restart[k] = dev_tensor(f"restart[{k}]", m, torch.uint8, E, "E")
+    given = {"ttc_thresh": ttc_thresh, "thw_thresh": thw_thresh, "risk_horizon": risk_horizon,
+             "near_range": near_range}
+    for name, default in _abi.TRAFFIC_DEFAULTS.items():
+        val = default if given[name] is None else float(given[name])
+        if not (0.0 < ctypes.c_float(val).value < float("inf")):  # as the float32 the call takes
+            raise ValueError(f"{name} must be finite and > 0, got {val!r}")
+        setattr(a, name, val)
+    return a
+
+
 class HighwayVecEnv:
     """E lockstep highway-v0 envs with state resident in HBM (one wavefront per env)."""
 
@@ -498,6 +566,34 @@ class HighwayVecEnv:
                               device=self.device)
         self.observe_into(order, row_values=row_values, veh_values=out)
         return out.view(self.num_envs, HWY_MAX_VEHICLES)
+
+    def traffic_into(self, *, restart=(), ttc_thresh: Optional[float] = None,
+                     thw_thresh: Optional[float] = None, risk_horizon: Optional[float] = None,
+                     near_range: Optional[float] = None, **outputs) -> None:
+        """Neighbours, gaps, time-to-collision and headway of the envs' current states into
+        caller-owned device tensors (hwy_traffic: one launch, no synchronisation,
+        graph-capturable).  ``outputs`` by name, each optional: ``front`` / ``rear`` [E, 64] int32
+        (the vehicle in front of / behind each vehicle on its own lane, -1 for none), ``gap``,
+        ``closing``, ``ttc``, ``thw``, ``risk`` [E, 64] float32 (``risk`` is ready to pass as
+        ``render(shade=...)``), ``ego`` [E, 16] float32 (_abi.EGO_* slots), ``acc`` [E, 8] float32
+        in/out (the running per-episode reduction, _abi.TACC_* slots, zero-filled once by the
+        caller) and ``ep_stats`` [E, 8] float32 (the finished episodes' rows).  ``restart``: up
+        to three [E] uint8 masks, OR-ed, of the envs whose episode ended with the call that
+        produced this state (a step's terminated and truncated, cut_episodes' cut).  Call it once
+        per state the policy acts on: after reset, after every step, after a cut."""
+        a = traffic_args(self.num_envs, self.device, restart=restart, ttc_thresh=ttc_thresh,
+                         thw_thresh=thw_thresh, risk_horizon=risk_horizon, near_range=near_range,
+                         **outputs)
+        check(lib().hwy_traffic(self._handle, ctypes.byref(a), stream_ptr()), "hwy_traffic")
+        self._keep_traffic = (outputs, restart)
+
+    def traffic(self, **thresholds) -> Dict[str, torch.Tensor]:
+        """The per-vehicle arrays and the ego row of the current states, a dict of fresh device
+        tensors (traffic_into's ``front`` .. ``risk`` and ``ego``)."""
+        out = alloc_traffic(self.num_envs, self.device)
+        del out["acc"], out["ep_stats"]
+        self.traffic_into(**thresholds, **out)
+        return out
 
     def close(self) -> None:
         if self._handle:

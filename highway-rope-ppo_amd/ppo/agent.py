@@ -174,10 +174,17 @@ class RolloutBuffer:
     ``truncation_bootstrap``: also ``final_obs`` [E, S] (the terminal observations of the envs
     that finished in the current step; one row set, reused every step) and ``boot_values`` [T, E]
     (V(final observation) at the truncated, not terminated rows, 0 elsewhere), which
-    PPOAgent.update_rollout feeds to ops.gae_boot (LockstepRollout(truncation="bootstrap"))."""
+    PPOAgent.update_rollout feeds to ops.gae_boot (LockstepRollout(truncation="bootstrap")).
+
+    ``safety_stats``: also ``traffic_stats`` [T, E, 8] (hwy_traffic's per-episode reduction of the
+    ego's time-to-collision, headway, gap and distance where an episode finished -- on the
+    reference schedule row T - 1 also holds the rows of the episodes the cut ended -- 0
+    elsewhere) and ``traffic_acc`` [E, 8] (the running reduction of the current episodes, carried
+    from rollout to rollout); the rollout then issues one hwy_traffic launch per env step."""
 
     def __init__(self, T: int, E: int, state_dim: int, action_dim: int, device: torch.device,
-                 episode_stats: bool = False, truncation_bootstrap: bool = False):
+                 episode_stats: bool = False, truncation_bootstrap: bool = False,
+                 safety_stats: bool = False):
         kw = dict(device=device, dtype=torch.float32)
         self.T, self.E, self.state_dim = T, E, state_dim
         self.states = torch.zeros(T + 1, E, state_dim, **kw)  # row T = bootstrap obs
@@ -202,6 +209,12 @@ class RolloutBuffer:
         if truncation_bootstrap:
             self.final_obs = torch.zeros(E, state_dim, **kw)
             self.boot_values = torch.zeros(T, E, **kw)
+        self.traffic_stats = self.traffic_acc = None
+        if safety_stats:
+            from hwy._abi import HWY_TRAFFIC_NACC
+
+            self.traffic_stats = torch.zeros(T, E, HWY_TRAFFIC_NACC, **kw)
+            self.traffic_acc = torch.zeros(E, HWY_TRAFFIC_NACC, **kw)
 
     @property
     def n(self) -> int:

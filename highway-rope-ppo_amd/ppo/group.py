@@ -36,16 +36,21 @@ from utils.graphs import run_or_replay as _graph_run
 from utils.graphs import run_or_replay_chunks as _graph_run_chunks
 
 from .agent import RolloutBuffer
-from .rollout import alloc_cut_buffers, check_episode_schedule, rollout_chunks
+from .rollout import (alloc_cut_buffers, check_episode_schedule, rollout_chunks,
+                      traffic_after_reset, traffic_after_step)
 
 
 class ExperimentGroup:
     def __init__(self, agents: Sequence, env, seeds: Sequence[int], envs_per_experiment: int,
                  rollout_len: int, use_graphs: bool = True, rank_tables=None,
-                 episode_schedule: str = "lockstep", episode_stats: bool = False):
+                 episode_schedule: str = "lockstep", episode_stats: bool = False,
+                 safety_stats: bool = False):
         from hwy.ppo_native import GroupAct
 
         self.episode_schedule = check_episode_schedule(episode_schedule)
+        # one hwy_traffic launch on the group's handle after every env step, every experiment's
+        # per-episode reduction in buf.traffic_stats / buf.traffic_acc (ppo/rollout.py)
+        self.safety_stats = bool(safety_stats)
         # the env steps as hwy_step_with_info, every experiment's episode sums in buf.ep_stats /
         # buf.acc (ppo/rollout.py)
         self.episode_stats = bool(episode_stats)
@@ -75,7 +80,8 @@ class ExperimentGroup:
         N, Fo = self.env.obs_rows, self.env.obs_features
         self.sd = N * Fo
         self.buf = RolloutBuffer(self.T, self.G * self.E, self.sd, 2, self.dev,
-                                 **({"episode_stats": True} if self.episode_stats else {}))
+                                 **({"episode_stats": True} if self.episode_stats else {}),
+                                 **({"safety_stats": True} if self.safety_stats else {}))
         self.use_graphs = bool(use_graphs)
         self.act = GroupAct(self.agents, self.E)
         GE = self.G * self.E
@@ -97,6 +103,8 @@ class ExperimentGroup:
                       "update_prepare": 0, "update_capture": 0}
         obs, _ = self.env.reset()
         self.buf.states[0].copy_(obs.reshape(GE, self.sd))
+        if self.safety_stats:
+            traffic_after_reset(self.env, self.buf)
 
     # ------------------------------------------------------------------ rollout
     def _draw_noise(self) -> None:
@@ -131,12 +139,20 @@ class ExperimentGroup:
         else:
             self.env.step_into(*self.env_io(t))
 
+    def env_traffic(self, t: int) -> None:
+        """safety_stats: hwy_traffic on the states step t left (LockstepRollout._steps: on the
+        reference schedule the last step's launch follows the cut)."""
+        if self.safety_stats and not (self.episode_schedule == "reference" and t == self.T - 1):
+            traffic_after_step(self.env, self.buf, t)
+
     def cut_episodes(self) -> None:
         """The reference schedule's cut after the rollout's last step (LockstepRollout._steps)."""
         obs_shape = self.env.obs_buf.shape[1:]
         self.next0.copy_(self.buf.states[self.T])
         self.env.cut_episodes(self.next0.view(self.G * self.E, *obs_shape), self.cut_return,
                               self.cut_length, self.cut)
+        if self.safety_stats:
+            traffic_after_step(self.env, self.buf, self.T - 1, cut=self.cut)
 
     def finish_rollout(self) -> None:
         self.buf.finish_dones()
@@ -148,6 +164,7 @@ class ExperimentGroup:
         for t in range(t0, t1):
             self.act.launch(self.act_rows(t), tiles)
             self.env_step(t)
+            self.env_traffic(t)
         if t1 == self.T:
             self.finish_rollout()
 
@@ -425,6 +442,10 @@ class GroupBatch:
         self.episode_stats = g0.episode_stats if episode_stats is None else bool(episode_stats)
         if any(g.episode_stats != self.episode_stats for g in self.groups):
             raise ValueError("a batch's groups share episode_stats")
+        # one hwy_traffic launch per handle and step (a grouped launch does not exist)
+        self.safety_stats = g0.safety_stats
+        if any(g.safety_stats != self.safety_stats for g in self.groups):
+            raise ValueError("a batch's groups share safety_stats")
         if any(g.E != g0.E or g.T != g0.T for g in self.groups):
             raise ValueError("a batch's groups share envs per experiment and rollout length")
         if any(g.episode_schedule != g0.episode_schedule for g in self.groups):
@@ -466,6 +487,8 @@ class GroupBatch:
                 self.envstep.launch([g.env_io(t) for g in self.groups])
             else:
                 self.groups[0].env_step(t)
+            for g in self.groups:
+                g.env_traffic(t)
         if t1 == self.T:
             for g in self.groups:
                 g.finish_rollout()  # the reference schedule's cut: once per handle
@@ -500,7 +523,8 @@ class GroupBatch:
 def build_group(condition, base_config, seeds: Sequence[int], envs_per_experiment: int,
                 rollout_len: int, device: torch.device, make_agent: Callable, d_embed=None,
                 env_overrides: Optional[dict] = None, use_graphs: bool = True,
-                episode_schedule: str = "lockstep", episode_stats: bool = False):
+                episode_schedule: str = "lockstep", episode_stats: bool = False,
+                safety_stats: bool = False):
     """A group of len(seeds) experiments of one condition, each constructed as
     experiments/runner.py constructs its solo run: set_random_seeds(seed), make_env (whose RankPE
     table draws from the global torch RNG), env.to(device), then ``make_agent(state_dim)`` (the
@@ -540,7 +564,8 @@ def build_group(condition, base_config, seeds: Sequence[int], envs_per_experimen
                           rank_tables=tables if rank else None,
                           **({} if episode_schedule == "lockstep"
                              else {"episode_schedule": episode_schedule}),
-                          **({"episode_stats": True} if episode_stats else {}))
+                          **({"episode_stats": True} if episode_stats else {}),
+                          **({"safety_stats": True} if safety_stats else {}))
     grp.solo_envs = solos
     grp.group_env = env
     return grp

@@ -25,6 +25,16 @@ also writes the terminal observations of the envs that finished to ``buf.final_o
 ``agent.value_masked`` stores V(final observation) of the truncated, not terminated rows in
 ``buf.boot_values[t]`` (0 elsewhere) with the weights that produced ``values[t]``.  Both launches
 are part of the captured graph; PPOAgent.update_rollout then runs hwy_gae_boot.
+
+``safety_stats=True``: one hwy_traffic launch after the reset that precedes the first rollout and
+one after every env step, inside the captured graph, with that step's terminated / truncated as
+restart masks: ``buf.traffic_acc`` carries the running per-episode reduction of the ego's
+time-to-collision, headway, gap and distance, ``buf.traffic_stats[t]`` receives the rows of the
+episodes that finished in step t (``traffic_after_reset`` / ``traffic_after_step``).  On the
+reference schedule the launch of the last step waits for the cut and takes its ``cut`` as a
+third mask, so the state the cut throws away is not measured, the cut episodes' rows land in
+``traffic_stats[T - 1]`` beside the finished ones' (no env is both), and an env that had just
+restarted is not counted twice.
 """
 
 from __future__ import annotations
@@ -70,10 +80,22 @@ def alloc_cut_buffers(owner, E: int, sd: int, device) -> None:
     owner.cut = torch.zeros(E, dtype=torch.uint8, device=device)
 
 
+def traffic_after_reset(env, buf) -> None:
+    """hwy_traffic on the reset states: the zero-filled running reduction starts from them."""
+    env.traffic_into(acc=buf.traffic_acc)
+
+
+def traffic_after_step(env, buf, t: int, cut=None) -> None:
+    """hwy_traffic on the states rollout step t left (``cut``: and the cut after it), the
+    finished episodes' rows going to buf.traffic_stats[t]."""
+    masks = (buf.terminated[t], buf.truncated[t]) + (() if cut is None else (cut,))
+    env.traffic_into(acc=buf.traffic_acc, ep_stats=buf.traffic_stats[t], restart=masks)
+
+
 class LockstepRollout:
     def __init__(self, agent, env, buf, use_graph: bool = True,
                  episode_schedule: str = "lockstep", episode_stats: bool = False,
-                 truncation: str = "terminal"):
+                 truncation: str = "terminal", safety_stats: bool = False):
         self.agent = agent
         self.env = env.unwrapped if hasattr(env, "unwrapped") else env
         self.buf = buf
@@ -82,6 +104,10 @@ class LockstepRollout:
         self.episode_stats = bool(episode_stats)
         if self.episode_stats and buf.ep_stats is None:
             raise ValueError("episode_stats needs a RolloutBuffer built with episode_stats=True")
+        # one hwy_traffic launch per env step (and one now, on the reset states the caller left)
+        self.safety_stats = bool(safety_stats)
+        if self.safety_stats and getattr(buf, "traffic_stats", None) is None:
+            raise ValueError("safety_stats needs a RolloutBuffer built with safety_stats=True")
         self.truncation = check_truncation(truncation)
         if self.truncation == "bootstrap" and getattr(buf, "boot_values", None) is None:
             raise ValueError('truncation="bootstrap" needs a RolloutBuffer built with '
@@ -103,6 +129,8 @@ class LockstepRollout:
         self.stats = {"rollout_replay": 0, "rollout_eager": 0, "rollout_capture": 0}
         if self.episode_schedule == "reference":
             alloc_cut_buffers(self, buf.E, buf.states.shape[-1], buf.states.device)
+        if self.safety_stats:
+            traffic_after_reset(self.env, buf)
 
     def _launch_key(self):
         from hwy.ppo_native import act_tiles, flat_params
@@ -122,6 +150,8 @@ class LockstepRollout:
                buf.states.data_ptr(), buf.noise.data_ptr(), buf.T, buf.E)
         if self.truncation == "bootstrap":
             key += (buf.final_obs.data_ptr(), buf.boot_values.data_ptr())
+        if self.safety_stats:
+            key += (buf.traffic_stats.data_ptr(), buf.traffic_acc.data_ptr())
         return key
 
     def _steps(self, t0: int = 0, t1: Optional[int] = None) -> None:
@@ -154,6 +184,8 @@ class LockstepRollout:
                 self._envstep.launch([io])
             else:
                 env.step_into(*io)
+            if self.safety_stats and not (self.episode_schedule == "reference" and t == buf.T - 1):
+                traffic_after_step(env, buf, t)
         if t1 < buf.T:
             return
         buf.finish_dones()
@@ -161,6 +193,8 @@ class LockstepRollout:
             self.next0.copy_(buf.states[buf.T])
             env.cut_episodes(self.next0.view(E, *obs_shape), self.cut_return, self.cut_length,
                              self.cut)
+            if self.safety_stats:
+                traffic_after_step(env, buf, buf.T - 1, cut=self.cut)
 
     def start_next(self) -> None:
         """states[0] of the next rollout: the last observation, or, on the reference schedule,

@@ -31,6 +31,16 @@ included), ``episode_lengths``, ``episode_crashed``, ``episode_mean_speed`` (sum
 over the episode's steps / its length) and ``episode_lane_changes`` into metrics_history, and a
 ``crash_rate`` column (over the last 100 episodes) into the summary.  The training itself is
 unchanged, bit for bit.
+``safety_stats=True`` (vectorised loop, train_group, train_batch; not over a process group) issues
+one hwy_traffic launch per env step (ppo/rollout.py) and books, per episode and in the order of
+``episode_rewards`` (cut episodes included), ``episode_min_ttc``, ``episode_min_headway``,
+``episode_min_gap``, ``episode_min_distance`` (the least time-to-collision, time headway,
+bumper-to-bumper gap to the front vehicle and centre distance to any vehicle over the states the
+policy acted on; +inf, written to the JSON as null, where the episode never had a front
+vehicle), ``episode_ttc_critical_share`` and ``episode_tailgating_share`` (the share of those
+states with ttc < 2 s and headway < 1 s), and a ``near_miss_rate`` column (the share of the last
+100 episodes whose least ttc was below 2 s) into the summary.  The training itself is unchanged,
+bit for bit.  ``safety_profile`` measures the same over evaluate()'s episodes.
 ``evaluate`` runs ``num_episodes`` deterministic episodes seeded exp_seed + 1000 + k (:14-29),
 as one batched env for the vectorised path.
 ``attribution`` runs the same episodes and reports what the policy looks at: the mean |input
@@ -42,6 +52,7 @@ draws no random number, so the training is unchanged, bit for bit.
 ``out_dir``, records their frames (HighwayVecEnv.render, one launch per step); there is no window.
 ``attribution="value"`` (or another of ATTRIBUTION_OUTPUTS) tints every vehicle of every frame by
 the policy's input-gradient mass on the observation row that shows it (``attribution_shade``).
+``tint="ttc"`` tints them by hwy_traffic's ``risk`` instead (1 - ttc / 4 s below 4 s, else 0).
 ``evaluate(..., order="sorted" | "shuffled")`` runs the evaluation's episodes with the policy acting
 on the same worlds observed under that row order (HighwayVecEnv.observe), whatever the env's own
 order is; ``eval_orders`` books both at the final weights as ``order_rewards`` in the metrics.
@@ -216,8 +227,11 @@ def attribution_shade(vec_env, grad, order=None):
     return vec_env.rows_to_vehicles(rel.to(torch.float32).contiguous(), order=order)
 
 
+VISUALIZE_TINTS = ("ttc",)
+
+
 def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, out_dir=None,
-                    attribution=None, tape=None):
+                    attribution=None, tape=None, tint=None):
     """Deterministic episodes of a trained agent, seeded exp_seed + 2000 + ep, on a fresh env of
     ``env``'s config and fused wrapper (reference training/routine.py:32-58, which opens a
     render_mode="human" window; there is no display here).  All ``num_episodes`` run as one
@@ -228,6 +242,8 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
     ``viz_episode=%d reward=%.2f`` per episode and returns the rewards.  ``attribution``: None, or
     one of ATTRIBUTION_OUTPUTS to tint each frame's vehicles by that output's input-gradient mass
     at the frame's own observation (attribution_shade; both are the state after the step).
+    ``tint``: None, or "ttc" to tint each frame's vehicles by their time-to-collision risk at the
+    frame's state (HighwayVecEnv.traffic_into's ``risk``); not together with ``attribution``.
     ``tape``: a list that receives, per grabbed step, (observation, exported state, the episodes
     still recording) as clones (tests)."""
     from hwy.vec_env import HighwayVecEnv
@@ -235,6 +251,10 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
     if attribution is not None and attribution not in ATTRIBUTION_OUTPUTS:
         raise ValueError(f"attribution must be None or one of {ATTRIBUTION_OUTPUTS}, got "
                          f"{attribution!r}")
+    if tint is not None and tint not in VISUALIZE_TINTS:
+        raise ValueError(f"tint must be None or one of {VISUALIZE_TINTS}, got {tint!r}")
+    if tint is not None and attribution is not None:
+        raise ValueError("tint and attribution both shade the vehicles: give one of them")
 
     if logger is None:
         logger = logging.getLogger(__name__)
@@ -261,6 +281,9 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
             if attribution is not None:
                 g = agent.input_gradients(obs.reshape(n, -1))[attribution]
                 shade = attribution_shade(ev, g)
+            elif tint == "ttc":
+                shade = torch.empty(n, 64, dtype=torch.float32, device=dev)
+                ev.traffic_into(risk=shade)
             host = ev.render(shade=shade).cpu().numpy()
             if tape is not None:
                 tape.append((obs.clone(), ev.export_state(), list(running)))
@@ -464,6 +487,116 @@ def attribution(env, agent, num_episodes=10, exp_seed: int = 0, tape=None):
 _attribution = attribution  # train_with_experiment_name's keyword shadows the name
 
 
+# ---------------------------------------------------------------------------------- safety
+SAFETY_KEYS = ("episode_min_ttc", "episode_min_headway", "episode_min_gap", "episode_min_distance",
+               "episode_ttc_critical_share", "episode_tailgating_share")
+
+
+def safety_row(row) -> tuple:
+    """One episode's SAFETY_KEYS values from its hwy_traffic reduction row [8] (float32): the
+    four minima as they are, the two counts over the states counted (0 of 0 states: 0)."""
+    from hwy._abi import (TACC_MIN_DISTANCE, TACC_MIN_GAP, TACC_MIN_THW, TACC_MIN_TTC, TACC_N,
+                          TACC_TAILGATING, TACC_TTC_CRITICAL)
+
+    n = max(float(row[TACC_N]), 1.0)
+    return (float(row[TACC_MIN_TTC]), float(row[TACC_MIN_THW]), float(row[TACC_MIN_GAP]),
+            float(row[TACC_MIN_DISTANCE]), float(row[TACC_TTC_CRITICAL]) / n,
+            float(row[TACC_TAILGATING]) / n)
+
+
+def near_miss_rate(min_ttc, ttc_thresh=None, last: int = 100) -> float:
+    """Share of the last ``last`` booked episodes whose least time-to-collision was below
+    ``ttc_thresh`` (default: hwy_traffic's, 2 s); 0 with none booked."""
+    from hwy._abi import TRAFFIC_DEFAULTS
+
+    thresh = TRAFFIC_DEFAULTS["ttc_thresh"] if ttc_thresh is None else float(ttc_thresh)
+    tail = [v for v in list(min_ttc)[-last:]]
+    return float(np.mean([v is not None and v < thresh for v in tail])) if tail else 0.0
+
+
+def _safety_stream(dones, traffic_stats, cut=None):
+    """The hwy_traffic reduction rows of one rollout's episode stream, in _episode_ends' /
+    _episode_stream's order: the rows of the episodes that finished in the [T, E] rollout
+    (traffic_stats [T, E, 8]), then, on the reference schedule, those of the episodes cut at its
+    end, which the last step's launch wrote to traffic_stats[T - 1] (ppo/rollout.py)."""
+    d = dones.cpu().numpy() != 0
+    stats = traffic_stats.cpu().numpy()
+    rows = stats[d]
+    if cut is not None:
+        rows = np.concatenate([rows, stats[-1][cut.cpu().numpy() != 0]])
+    return rows
+
+
+def _book_safety(mh, rows, i) -> None:
+    """Episode i of a _safety_stream into metrics_history's SAFETY_KEYS lists."""
+    for k, v in zip(SAFETY_KEYS, safety_row(rows[i])):
+        mh[k].append(v)
+
+
+def _json_ready(mh: dict) -> dict:
+    """metrics_history as it is written: a non-finite SAFETY_KEYS entry (an episode without a
+    front vehicle has no least ttc) becomes null; everything else is the dict's own."""
+    if not any(k in mh for k in SAFETY_KEYS):
+        return mh
+    out = dict(mh)
+    for k in SAFETY_KEYS:
+        if k in out:
+            out[k] = [v if math.isfinite(v) else None for v in out[k]]
+    return out
+
+
+def safety_profile(env, agent, num_episodes=10, exp_seed: int = 0):
+    """How close the policy drives, over exactly evaluate()'s episodes (seeds exp_seed + 1000 +
+    k, deterministic acting): hwy_traffic on every state the policy acts on, reduced per episode.
+    Returns ``episodes`` -- a dict of SAFETY_KEYS (without the ``episode_`` prefix) plus
+    ``states`` and ``reward``, each a list with one value per episode -- their means as
+    ``mean_<key>`` (+inf where an episode's value is), ``near_miss_rate`` and ``mean_reward``,
+    which equals evaluate(env, agent, num_episodes, exp_seed).  It runs on an env of its own and
+    leaves evaluate()'s memo alone.  Vector envs only."""
+    if not _is_vector(env):
+        raise ValueError("safety_profile needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                         "vector_env key for one env)")
+    from hwy._abi import HWY_TRAFFIC_NACC, TACC_N
+
+    base = env.unwrapped
+    cache = getattr(base, "_safety_envs", None)
+    if cache is None:
+        cache = base._safety_envs = {}
+    ev = cache.get(num_episodes)
+    if ev is None:
+        ev = cache[num_episodes] = _eval_env_like(env, num_episodes)
+    dev = ev.device
+    seeds = torch.arange(num_episodes, device=dev, dtype=torch.int64) + (exp_seed + 1000)
+    obs, _ = ev.reset(seeds=seeds)
+    alive = torch.ones(num_episodes, dtype=torch.bool, device=dev)
+    total = torch.zeros(num_episodes, dtype=torch.float64, device=dev)
+    acc = torch.zeros(num_episodes, HWY_TRAFFIC_NACC, dtype=torch.float32, device=dev)
+    rows = torch.zeros_like(acc)
+    for k in range(ev.max_episode_steps + 1):
+        # the state the policy is about to act on; a finished episode's row stays as it ended
+        ev.traffic_into(acc=acc)
+        rows = torch.where(alive[:, None], acc, rows)
+        a, _, _, _ = agent.select_action(obs.reshape(num_episodes, -1), deterministic=True)
+        obs, r, te, tr, _ = ev.step(a.contiguous())
+        total += torch.where(alive, r.double(), torch.zeros_like(total))
+        alive &= ~(te.bool() | tr.bool())
+        if k % 8 == 7 and not bool(alive.any()):  # as _run_eval_vector: later steps add nothing
+            break
+    host = rows.cpu().numpy()
+    names = [k[len("episode_"):] for k in SAFETY_KEYS]
+    per = {n: [] for n in names}
+    for row in host:
+        for n, v in zip(names, safety_row(row)):
+            per[n].append(v)
+    per["states"] = [int(x) for x in host[:, TACC_N]]
+    per["reward"] = [float(x) for x in total.cpu().tolist()]
+    out = {"episodes": per}
+    out.update({f"mean_{n}": float(np.mean(per[n])) for n in names})
+    out["near_miss_rate"] = near_miss_rate(per["min_ttc"], last=num_episodes)
+    out["mean_reward"] = float(total.mean().item())
+    return out
+
+
 def evaluate_many(items, num_episodes=5):
     """evaluate(env, agent, num_episodes, exp_seed) for every (env, agent, exp_seed) of `items`,
     each result exactly what evaluate returns for it alone: the evaluations that are not memoised
@@ -563,7 +696,7 @@ def _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_hist
                     target_reward, total_steps, logger, exp_prefix):
     metrics_path = os.path.join(artifacts_dir, f"training_metrics_{experiment_name}.json")
     with open(metrics_path, "w") as f:
-        json.dump(metrics_history, f, indent=2)
+        json.dump(_json_ready(metrics_history), f, indent=2)
     logger.info(f"{exp_prefix} Metrics saved to {metrics_path}")
     plot_path = os.path.join(artifacts_dir, f"ppo_highway_rewards_{experiment_name}.png")
     try:
@@ -595,6 +728,9 @@ def _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_hist
     head, tail = "", ""
     if "episode_crashed" in metrics_history:  # episode_stats runs only
         head, tail = ",crash_rate", f",{crash_rate(metrics_history['episode_crashed']):.4f}"
+    if "episode_min_ttc" in metrics_history:  # safety_stats runs only
+        head = f"{head},near_miss_rate"
+        tail = f"{tail},{near_miss_rate(metrics_history['episode_min_ttc']):.4f}"
     for k in CONTROL_KEYS:  # runs with a KL target / an lr schedule only
         if k in metrics_history:
             head, tail = f"{head},{k}", f"{tail},{metrics_history[k]}"
@@ -709,7 +845,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
                                eval_interval=50, steps_per_update=2048, experiment_name="",
                                exp_seed: int = 0, logger=None, episode_schedule="lockstep",
                                episode_stats: bool = False, truncation: str = "terminal",
-                               attribution: bool = False, eval_orders=None):
+                               attribution: bool = False, eval_orders=None,
+                               safety_stats: bool = False):
     from ppo.rollout import check_episode_schedule, check_truncation
 
     if attribution and not _is_vector(env):
@@ -734,6 +871,13 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
                              "vector_env key for one env)")
         if getattr(agent, "_dist", None) is not None:
             raise ValueError("episode_stats does not run over a process group")
+
+    if safety_stats:
+        if not _is_vector(env):
+            raise ValueError("safety_stats needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                             "vector_env key for one env)")
+        if getattr(agent, "_dist", None) is not None:
+            raise ValueError("safety_stats does not run over a process group")
 
     for k in CONTROL_KEYS:
         if getattr(agent, k, None) is not None and not _is_vector(env):
@@ -763,6 +907,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
     }
     if episode_stats:
         metrics_history.update({k: [] for k in STATS_KEYS})
+    if safety_stats:
+        metrics_history.update({k: [] for k in SAFETY_KEYS})
     if truncation != "terminal":  # the default's metrics stay what they were
         metrics_history["truncation"] = truncation
     _book_controls(metrics_history, agent)
@@ -784,6 +930,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         sched_kw["episode_stats"] = True
     if truncation != "terminal":
         sched_kw["truncation"] = truncation
+    if safety_stats:
+        sched_kw["safety_stats"] = True
     episode_rewards, training_episodes, total_steps = loop(
         env, agent, max_episodes, log_interval, eval_interval, steps_per_update, exp_seed, logger,
         exp_prefix, metrics_history, tracker, start_time, **sched_kw)
@@ -865,8 +1013,12 @@ def _train_single(env, agent, max_episodes, log_interval, eval_interval, steps_p
 
 def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_per_update,
                   exp_seed, logger, prefix, mh, tracker, start_time, episode_schedule="lockstep",
-                  episode_stats=False, truncation="terminal"):
+                  episode_stats=False, truncation="terminal", safety_stats=False):
     """E lockstep envs, device rollout of T steps, batched PPO update.
+
+    safety_stats: the rollout issues one hwy_traffic launch per env step and every booked
+    episode's reduction row goes to mh's SAFETY_KEYS lists (read before the next rollout); not
+    over a process group.
 
     truncation "bootstrap": the rollout also stores V(final observation) of the truncated rows
     (ppo/rollout.py) and the update's GAE bootstraps them (hwy_gae_boot) instead of booking a
@@ -891,12 +1043,15 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
     bootstrap = truncation == "bootstrap"
     if bootstrap and group is not None:
         raise ValueError("truncation='bootstrap' does not run over a process group")
+    if safety_stats and group is not None:
+        raise ValueError("safety_stats does not run over a process group")
     base = env.unwrapped
     E = base.num_envs
     sd = _flat_dim(env)
     T = max(1, math.ceil(steps_per_update / E))
     stats_kw = {"episode_stats": True} if episode_stats else {}
-    buf = RolloutBuffer(T, E, sd, 2, base.device, **stats_kw,
+    safety_kw = {"safety_stats": True} if safety_stats else {}
+    buf = RolloutBuffer(T, E, sd, 2, base.device, **stats_kw, **safety_kw,
                         **({"truncation_bootstrap": True} if bootstrap else {}))
     base.set_seed_schedule(exp_seed)
     obs, _ = env.reset()
@@ -904,7 +1059,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
     reference = episode_schedule == "reference"
     roll = LockstepRollout(agent, base, buf, use_graph=getattr(agent, "use_graphs", True),
                            **({"episode_schedule": episode_schedule} if reference else {}),
-                           **stats_kw, **({"truncation": truncation} if bootstrap else {}))
+                           **stats_kw, **safety_kw,
+                           **({"truncation": truncation} if bootstrap else {}))
     episode_rewards, training_episodes = [], []
     total_steps = episode_num = 0
     while episode_num < max_episodes:
@@ -915,6 +1071,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
             cut_kw = ({"cut": roll.cut, "cut_length": roll.cut_length, "acc": buf.acc}
                       if reference else {})
             sums, lens = _stats_stream(buf.dones, buf.ep_length, buf.ep_stats, **cut_kw)
+        if safety_stats:
+            safety = _safety_stream(buf.dones, buf.traffic_stats, roll.cut if reference else None)
         if reference:  # the stream's evaluations run below, ahead of the update (:173-175)
             stream = _episode_stream(buf.dones, buf.ep_return, roll.cut, roll.cut_return)
             upd = None
@@ -933,6 +1091,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
             mh["episode_numbers"].append(episode_num)
             if episode_stats:
                 _book_stats(mh, sums, lens, i)
+            if safety_stats:
+                _book_safety(mh, safety, i)
             _log_episode(logger, prefix, episode_num, r, episode_rewards, log_interval,
                          total_steps, start_time)
             if episode_num % eval_interval == 0 and rank == 0:
@@ -947,7 +1107,7 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
 
 def train_group(group, experiment_names, exp_seeds, max_episodes=500, target_reward=0.0,
                 log_interval=20, eval_interval=50, loggers=None, episode_schedule="lockstep",
-                episode_stats=False):
+                episode_stats=False, safety_stats=False):
     """train_with_experiment_name for every experiment of an ExperimentGroup (ppo/group.py) at
     once: one grouped rollout + update per iteration, then each experiment's bookkeeping exactly
     as _train_vector does it on its own [T, E] slice (episode stream in (step, env) order,
@@ -961,12 +1121,13 @@ def train_group(group, experiment_names, exp_seeds, max_episodes=500, target_rew
                        target_reward=target_reward, log_interval=log_interval,
                        eval_interval=eval_interval, loggers=loggers,
                        episode_schedule=episode_schedule,
-                       **({"episode_stats": True} if episode_stats else {}))
+                       **({"episode_stats": True} if episode_stats else {}),
+                       **({"safety_stats": True} if safety_stats else {}))
 
 
 def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, target_reward=0.0,
                 log_interval=20, eval_interval=50, loggers=None, episode_schedule="lockstep",
-                episode_stats=False):
+                episode_stats=False, safety_stats=False):
     """train_group over the experiments of several ExperimentGroups stepped together: `stepper`
     is the ExperimentGroup itself (groups = [it]) or a GroupBatch over `groups` (ppo/group.py:
     the cells of one hidden width in one set of launches).  experiment_names / exp_seeds /
@@ -975,8 +1136,17 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
     (the groups must have been built with it): each experiment's stream is its finished then
     its cut episodes, and the due evaluations run, still as one evaluate_many, ahead of the
     update.  episode_stats (the groups must have been built with it): each experiment's
-    per-episode statistics are booked beside its returns, as _train_vector books them."""
+    per-episode statistics are booked beside its returns, as _train_vector books them.
+    safety_stats (likewise): each experiment's hwy_traffic reduction rows, from its own slice of
+    its group's traffic_stats."""
     from ppo.rollout import check_episode_schedule
+
+    if any(bool(getattr(g, "safety_stats", False)) != bool(safety_stats) for g in groups):
+        raise ValueError(f"train_batch: every group must be built with safety_stats="
+                         f"{bool(safety_stats)}")
+    if safety_stats and any(getattr(a, "_dist", None) is not None
+                            for g in groups for a in g.agents):
+        raise ValueError("safety_stats does not run over a process group")
 
     if any(bool(getattr(g, "episode_stats", False)) != bool(episode_stats) for g in groups):
         raise ValueError(f"train_batch: every group must be built with episode_stats="
@@ -1008,6 +1178,8 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
               "eval_episode_numbers": [], "timestamps": []}
         if episode_stats:
             mh.update({k: [] for k in STATS_KEYS})
+        if safety_stats:
+            mh.update({k: [] for k in SAFETY_KEYS})
         _book_controls(mh, grp.agents[j])
         tracker = _EvalTracker(grp.solo_envs[j], grp.agents[j], int(exp_seeds[k]),
                                target_reward, checkpoint_dir, name, mh, logger, prefix, start_time)
@@ -1044,6 +1216,9 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
                            "acc": grp.buf.acc[sl]} if reference else {})
                 sums, lens = _stats_stream(grp.buf.dones[:, sl], grp.buf.ep_length[:, sl],
                                            grp.buf.ep_stats[:, sl], **cut_kw)
+            if safety_stats:
+                safety = _safety_stream(grp.buf.dones[:, sl], grp.buf.traffic_stats[:, sl],
+                                        grp.cut[sl] if reference else None)
             for i, ret in enumerate(stream):
                 if r["episode_num"] >= max_episodes:
                     break
@@ -1055,6 +1230,8 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
                 r["mh"]["episode_numbers"].append(r["episode_num"])
                 if episode_stats:
                     _book_stats(r["mh"], sums, lens, i)
+                if safety_stats:
+                    _book_safety(r["mh"], safety, i)
                 _log_episode(r["logger"], r["prefix"], r["episode_num"], ret, r["episode_rewards"],
                              log_interval, r["total_steps"], start_time)
                 if r["episode_num"] % eval_interval == 0:

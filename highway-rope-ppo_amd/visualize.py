@@ -4,6 +4,7 @@
         --episodes 3 --out demo_frames
     python visualize.py --models-file best_checkpoints.txt --out demo_frames
     python visualize.py --model <checkpoint> --attribution value     # what the critic looks at
+    python visualize.py --model <checkpoint> --tint ttc              # who is about to be hit
 
 For every checkpoint the network's dimensions are read from the saved weights
 (``shared.0.weight`` is [hidden_dim, state_dim], ``actor_mean.2.weight`` [action_dim,
@@ -16,7 +17,9 @@ training.routine.visualize_agent into ``--out/<checkpoint stem>/``: per episode 
 on the GPU by hwy_render (include/hwy.h: this project's frame rule at upstream's view geometry,
 not pygame's pixels).  ``--attribution`` tints every vehicle toward yellow by the share of the
 chosen output's input-gradient mass on the observation row that shows it (hwy_observe's row ->
-vehicle map; training.routine.attribution_shade).  There is no live window and no MP4: neither a display nor an encoder is a
+vehicle map; training.routine.attribution_shade); ``--tint ttc`` tints them by their
+time-to-collision risk instead (hwy_traffic's ``risk``: 1 - ttc / 4 s below 4 s), and the two
+exclude each other.  There is no live window and no MP4: neither a display nor an encoder is a
 dependency.
 """
 
@@ -91,10 +94,13 @@ def load_agent(path: str, device=None):
 
 
 def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=None,
-           attribution: Optional[str] = None) -> List[float]:
+           attribution: Optional[str] = None, tint: Optional[str] = None) -> List[float]:
     """Record ``episodes`` episodes of one checkpoint into out_dir/<checkpoint stem>/; returns
     their rewards.  ``attribution`` ("acceleration", "steering" or "value"): tint every vehicle by
-    the policy's input-gradient mass on the row that shows it (visualize_agent)."""
+    the policy's input-gradient mass on the row that shows it (visualize_agent).  ``tint``
+    ("ttc"): tint them by their time-to-collision risk instead; not together with it."""
+    if tint is not None and attribution is not None:
+        raise ValueError("tint and attribution both shade the vehicles: give one of them")
     from config.base_config import HIGHWAY_CONFIG
     from experiments.wrappers import make_env
     from training.routine import visualize_agent
@@ -111,7 +117,7 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
                              f"{cond.name} env (d_embed={d_embed}) gives {have}")
         dest = os.path.join(out_dir, os.path.splitext(os.path.basename(path))[0])
         rewards = visualize_agent(env, agent, num_episodes=episodes, exp_seed=seed, out_dir=dest,
-                                  attribution=attribution)
+                                  attribution=attribution, **({"tint": tint} if tint else {}))
     finally:
         env.close()
     for ep, r in enumerate(rewards):
@@ -138,10 +144,15 @@ def main(argv=None) -> int:
                    help="episode ep is seeded seed + 2000 + ep, as visualize_agent")
     p.add_argument("--attribution", choices=("acceleration", "steering", "value"), default=None,
                    help="tint each vehicle by |input gradient| of this output on its row")
+    p.add_argument("--tint", choices=("ttc",), default=None,
+                   help="tint each vehicle by its time-to-collision risk (not with --attribution)")
     args = p.parse_args(argv)
+    if args.tint and args.attribution:
+        p.error("--tint and --attribution both shade the vehicles: give one of them")
     models = [args.model] if args.model else list(models_from_file(args.models_file))
     for m in models:
-        record(m, args.out, episodes=args.episodes, seed=args.seed, attribution=args.attribution)
+        record(m, args.out, episodes=args.episodes, seed=args.seed, attribution=args.attribution,
+               tint=args.tint)
     return 0
 
 

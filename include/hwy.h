@@ -44,6 +44,8 @@
  *                                (this project's own frame rule, not pygame's pixels)
  *   hwy_observe               <- env.unwrapped.observation_type.observe() on the current road, under
  *                                either "order", plus the row -> vehicle assignment it drops
+ *   hwy_traffic               <- env.unwrapped.road.neighbour_vehicles(v) for every vehicle, and the
+ *                                gap / time-to-collision / headway a driving study derives from it
  *
  * Conventions
  *   - Plain pointers and sizes only; device pointers are HIP device pointers (e.g. torch
@@ -441,6 +443,98 @@ int hwy_observe_args_size(void);
  * pure, no device call. */
 int hwy_observe_check(const hwy_observe_args* a);
 int hwy_observe(hwy_handle* h, const hwy_observe_args* a, void* stream);
+
+/* ---- Traffic measures of the env states: who drives in front of and behind whom, the
+ * bumper-to-bumper gap, the time-to-collision (TTC) and the time headway (THW), an ego row, and a
+ * running per-episode reduction of the ego's.
+ *
+ * hwy_traffic reads the state words as they stand (x, y, heading, speed, the lane word and the
+ * flags) with the step's own neighbour search, so "front" is the vehicle IDM would brake for.
+ *
+ * Neighbour rule (Road.neighbour_vehicles).  The candidates for vehicle i on lane c are the other
+ * present vehicles k with |y_k - 4c| <= 3 (one float32 subtraction) and -5 <= x_k < 10005.
+ *   front = the nearest candidate with x_i <= x_k; among equal x the last in vehicle order
+ *   rear  = the nearest candidate with x_k < x_i;  among equal x the first in vehicle order
+ * A vehicle's own lane is its stored HWY_F_LANE word (no neighbour on a lane outside the road).
+ *
+ * Per-vehicle outputs, [E][64] in hwy_render's `shade` layout, vx = speed * cos(heading) with
+ * hm_sincosf's cosine:
+ *   front, rear (i32)  vehicle index on the own lane, -1 for none
+ *   gap     (x_f - x_i) - 5.0f, the two float32 subtractions in that order; +inf without a front
+ *   closing vx_i - vx_f; 0 without a front
+ *   ttc     0 where gap <= 0, else gap / closing where closing > 0, else +inf
+ *   thw     0 where gap <= 0, else gap / vx_i where vx_i > 0, else +inf
+ *   risk    1 - ttc / risk_horizon where ttc < risk_horizon, else 0 (in [0, 1]: usable as
+ *           hwy_render's shade as it is)
+ * Absent slots and lanes >= vehicles_count + 1 are written the "none" values: front = rear = -1,
+ * gap = ttc = thw = +inf, closing = risk = 0.  No entry is left unwritten.
+ *
+ * ego [E][HWY_TRAFFIC_NEGO] f32, of vehicle 0 (x_e, y_e, vx_e, lane word ln):
+ *   0-3   front gap, closing, ttc, thw (vehicle 0's entries above)
+ *   4     rear gap (x_e - x_r) - 5.0f, +inf without a rear
+ *   5     rear closing vx_r - vx_e, 0 without a rear
+ *   6     rear ttc, from slots 4 and 5 by the front ttc's rule
+ *   7-10  front gap and rear gap on lane ln - 1, then on lane ln + 1: the same expressions towards
+ *         that lane's front / rear of the ego; +inf where the lane or the vehicle does not exist.
+ *         They may be negative (down to -5 in front) when a car is alongside.
+ *   11    the least centre distance to any other present vehicle: sqrt of the least
+ *         dx*dx + dy*dy (two products and a sum, no fused multiply-add); +inf with none
+ *   12    the count of other present vehicles with 0 <= x_k - x_e <= near_range
+ *   13    y_e - 4 ln
+ *   14    vx_e
+ *   15    risk of the ego
+ *
+ * acc [E][HWY_TRAFFIC_NACC] f32, in/out, caller-owned, zero-filled once by the caller: the running
+ * reduction of the ego's measures over the states of the current episode,
+ *   0 states counted n        1 min front ttc      2 min front thw     3 min front gap
+ *   4 min centre distance     5 states with ttc < ttc_thresh           6 states with thw <
+ *   thw_thresh                7 states with a front vehicle
+ * restart[0..2]: up to three nullable [E] u8 masks, OR-ed (meant for a step's terminated and
+ * truncated and hwy_cut_episodes' cut).  For a marked env ep_stats[e] ([E][8], nullable, needs
+ * acc) receives the old acc row and the row restarts from this state alone; every unmarked env's
+ * ep_stats row is written all 0.  A row with n = 0 also starts from this state alone, without a
+ * flush.  Otherwise the state is folded in: min for slots 1-4, +1 for n and for each count that
+ * applies.
+ *
+ * The contract: call it once per state the policy acts on -- after hwy_reset (no mask), after
+ * every step with that step's terminated / truncated, after a cut with its `cut`.  Under autoreset
+ * the post-step state of a finished env is already the next episode's first state, so an episode's
+ * measured states are s_0 .. s_{L-1}: its terminal state is not measured (the step's crashed flag,
+ * hwy_step_with_info's episode sums, say how it ended).
+ *
+ * All pointers are device pointers and nullable, but at least one output (front, rear, gap,
+ * closing, ttc, thw, risk, ego, acc) must be given.  hwy_traffic is asynchronous, allocates
+ * nothing, is hipGraph-capturable, reads the state and writes nothing but the outputs it was
+ * given.  It returns HWY_EINVAL before any device call for a NULL handle or NULL args, no output
+ * at all, ep_stats or a restart mask without acc, and a ttc_thresh, thw_thresh, risk_horizon or
+ * near_range that is not finite and positive.  On non-finite state words the neighbours are
+ * whatever the step's neighbour rule gives for them and the values are not specified; the kernel
+ * terminates and stays inside its outputs. */
+#define HWY_TRAFFIC_NEGO 16
+#define HWY_TRAFFIC_NACC 8
+typedef struct hwy_traffic_args {
+  int32_t* front;             /* device [E][64], nullable */
+  int32_t* rear;              /* device [E][64], nullable */
+  float* gap;                 /* device [E][64], nullable */
+  float* closing;             /* device [E][64], nullable */
+  float* ttc;                 /* device [E][64], nullable */
+  float* thw;                 /* device [E][64], nullable */
+  float* risk;                /* device [E][64], nullable */
+  float* ego;                 /* device [E][HWY_TRAFFIC_NEGO], nullable */
+  float* acc;                 /* device [E][HWY_TRAFFIC_NACC], in/out, nullable */
+  float* ep_stats;            /* device [E][HWY_TRAFFIC_NACC], nullable; needs acc */
+  const uint8_t* restart[3];  /* device [E] each, nullable; need acc */
+  float ttc_thresh;           /* s, finite and > 0 */
+  float thw_thresh;           /* s, finite and > 0 */
+  float risk_horizon;         /* s, finite and > 0 */
+  float near_range;           /* m, finite and > 0 */
+} hwy_traffic_args;
+/* sizeof(hwy_traffic_args) as compiled into the library (binding layout check). */
+int hwy_traffic_args_size(void);
+/* HWY_OK, or HWY_EINVAL for arguments hwy_traffic refuses (every check that needs no handle);
+ * pure, no device call. */
+int hwy_traffic_check(const hwy_traffic_args* a);
+int hwy_traffic(hwy_handle* h, const hwy_traffic_args* a, void* stream);
 
 /* Stand-alone observation wrapper on [E,N,F] f32 -> [E,N,F_out] f32 (foreign envs).
  *   kind = enum hwy_pe_kind, d = appended width (rank/dist) or rotate_dim (rope),
