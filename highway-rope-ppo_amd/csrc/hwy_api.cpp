@@ -612,6 +612,51 @@ int hwy_traffic(hwy_handle* h, const hwy_traffic_args* a, void* stream) {
   return HWY_OK;
 }
 
+int hwy_sense_args_size(void) { return (int)sizeof(hwy_sense_args); }
+
+int hwy_sense_check(const hwy_sense_args* a) {
+  if (!a) return fail(HWY_EINVAL, "hwy_sense: args is NULL");
+  if (a->order != -1 && a->order != HWY_ORDER_SORTED && a->order != HWY_ORDER_SHUFFLED)
+    return fail(HWY_EINVAL, "hwy_sense: order must be -1 (the handle's), sorted or shuffled, "
+                            "got %d", a->order);
+  const float inf = __builtin_inff();
+  if (!(a->range_m > 0.0f))  // +inf passes, a NaN does not
+    return fail(HWY_EINVAL, "hwy_sense: range_m must be > 0 (+inf: no range limit), got %g",
+                (double)a->range_m);
+  if (!(a->p_drop >= 0.0f && a->p_drop <= 1.0f))
+    return fail(HWY_EINVAL, "hwy_sense: p_drop must lie in [0, 1], got %g", (double)a->p_drop);
+  for (int c = 0; c < 3; ++c)
+    if (!(a->sigma[c] >= 0.0f && a->sigma[c] < inf))
+      return fail(HWY_EINVAL, "hwy_sense: sigma[%d] must be finite and >= 0, got %g", c,
+                  (double)a->sigma[c]);
+  if (a->salt < 0 || a->salt > 65535)
+    return fail(HWY_EINVAL, "hwy_sense: salt must lie in 0..65535, got %d", a->salt);
+  if (!a->obs && !a->row_vehicle && !a->visible && !a->hidden && !a->counts)
+    return fail(HWY_EINVAL, "hwy_sense: no output given (obs, row_vehicle, visible, hidden and "
+                            "counts are all NULL)");
+  return HWY_OK;
+}
+
+int hwy_sense(hwy_handle* h, const hwy_sense_args* a, void* stream) {
+  if (!h) return fail(HWY_EINVAL, "hwy_sense: handle is NULL");
+  if (int rc = hwy_sense_check(a)) return rc;
+  if (int rc = check_pe(h, "hwy_sense")) return rc;
+  SenseParams p;
+  memset(&p, 0, sizeof(p));
+  p.p = params_of(h);
+  if (a->order >= 0) p.p.cfg.order = a->order;
+  p.p.obs = a->obs;
+  p.a = *a;
+  p.salt_word = HWY_SENSE_SALT + (uint32_t)a->salt;
+  p.range2 = a->range_m * a->range_m;
+  // 4 m over the 2.7 m half diagonal, and 1e-4 of the range over what binary32 rounds of it
+  const float far = (a->range_m + 4.0f) * 1.0001f;
+  p.cull2 = far * far;
+  if (hwy_launch_sense(&p, (hipStream_t)stream))
+    return hip_fail(hipGetLastError(), "hwy_sense_kernel");
+  return HWY_OK;
+}
+
 int hwy_obs_pe(const float* obs_in, float* obs_out, int E, int N, int F, int kind, int d,
                int ego_idx, float max_dist, const float* table, const float* dist_override,
                void* stream) {

@@ -62,7 +62,19 @@ struct TrafficParams {
   hwy_config cfg;
 };
 
+// hwy_sense's launch parameters (the sense unit of hwy_kernels.hip): p as in ObserveParams
+// (p.obs = a.obs), a the checked arguments, salt_word = HWY_SENSE_SALT + a.salt, range2 =
+// a.range_m * a.range_m (+inf for +inf)
+struct SenseParams {
+  StepParams p;
+  hwy_sense_args a;
+  uint32_t salt_word;
+  float range2;
+  float cull2;  // ((a.range_m + 4) * 1.0001)^2: a body farther from the ego blocks nothing in range
+};
+
 extern "C" {
+int hwy_launch_sense(const SenseParams* p, hipStream_t s);
 int hwy_launch_traffic(const TrafficParams* p, hipStream_t s);
 int hwy_launch_observe(const ObserveParams* p, hipStream_t s);
 int hwy_launch_render(const RenderParams* p, hipStream_t s);

@@ -1813,6 +1813,146 @@ extern "C" int hwy_launch_traffic(const TrafficParams* p, hipStream_t s) {
   hipLaunchKernelGGL(hwy_traffic_kernel, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#elif defined(HWY_SENSE_TU)
+// hwy_sense's kernel, likewise a unit of its own (-DHWY_SENSE_TU -> hwy_sense.o): the sensor
+// model of include/hwy.h as a front end to the step's own observe_wave (its MAP instantiation, as
+// in the observe unit), which is handed a perceived copy of the vehicles: not visible -> not
+// present, x / y / speed perturbed.  One wave per env, lane = vehicle, as the step; it loads the
+// five fields the observation reads and the env words, 1,536 B per env, and writes nothing but
+// the outputs it was given.  Every cross-lane operation runs with all 64 lanes active; the
+// branches around the line-of-sight loop, the draws and the observation are wave-uniform.
+
+// one Philox draw of the sensor's stream: counter (vehicle, step word, channel, salt word)
+__device__ __forceinline__ hm_u32x4 sense_draw(int lane, int step, uint32_t ch, uint32_t salt_word,
+                                               uint64_t seed) {
+  return hm_philox4x32_10((uint32_t)lane, (uint32_t)step, ch, salt_word,
+                          (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32));
+}
+
+// the unit-variance draw of channel ch: four uniforms summed pairwise, centred and scaled
+__device__ __forceinline__ float sense_z(int lane, int step, uint32_t ch, uint32_t salt_word,
+                                         uint64_t seed) {
+  const hm_u32x4 w = sense_draw(lane, step, ch, salt_word, seed);
+  const float u0 = hm_u01(w.v[0]), u1 = hm_u01(w.v[1]), u2 = hm_u01(w.v[2]), u3 = hm_u01(w.v[3]);
+  return (((u0 + u1) + (u2 + u3)) - 2.0f) * 1.7320508f;
+}
+
+__global__ void __launch_bounds__(256) hwy_sense_kernel(SenseParams P) {
+  __shared__ int lds_vor[ENVS_PER_BLOCK][WAVE];
+  __shared__ int lds_inv[ENVS_PER_BLOCK][WAVE];
+  __shared__ unsigned long long lds_key[ENVS_PER_BLOCK][WAVE];
+  // the blockers' image: (x, y, cos h, sin h) and the ego's centre in the blocker's frame
+  __shared__ float4 lds_body[ENVS_PER_BLOCK][WAVE];
+  __shared__ float2 lds_ego[ENVS_PER_BLOCK][WAVE];
+  const hwy_config& C = P.p.cfg;
+  const hwy_sense_args& A = P.a;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int w = threadIdx.x / WAVE;
+  const int e = blockIdx.x * ENVS_PER_BLOCK + w;
+  if (e >= C.num_envs) return;  // whole wave
+  const int V = C.vehicles_count + 1;
+  const int N = C.obs_vehicles;
+  const size_t fstride = (size_t)C.num_envs * WAVE;
+  const uint32_t idx = (uint32_t)e * WAVE + lane;  // < 2^32: hwy_create bounds num_envs
+  const uint32_t* st = P.p.state;
+  Veh v{};  // the fields the observation does not read stay zero
+  v.x = hm_bits2f((st + HWY_F_X * fstride)[idx]);
+  v.y = hm_bits2f((st + HWY_F_Y * fstride)[idx]);
+  v.h = hm_bits2f((st + HWY_F_HEADING * fstride)[idx]);
+  v.spd = hm_bits2f((st + HWY_F_SPEED * fstride)[idx]);
+  const uint32_t fl = (st + HWY_F_FLAGS * fstride)[idx];
+  const uint32_t ew = (st + HWY_F_ENV * fstride)[idx];
+  v.present = ((fl & HWY_FLAG_PRESENT) != 0u) && lane < V;  // load_veh's rule
+  const int step = rdli((int)ew, HWY_E_STEP);
+  const uint64_t seed = (uint64_t)(uint32_t)rdli((int)ew, HWY_E_SEED_LO) |
+                        ((uint64_t)(uint32_t)rdli((int)ew, HWY_E_SEED_HI) << 32);
+  float cos_h, sin_h;
+  hm_sincosf(v.h, &sin_h, &cos_h);
+
+  // ---- visibility, on the true positions
+  const float ex = rdlf(v.x, 0), ey = rdlf(v.y, 0);
+  const bool other = v.present && lane >= 1;
+  const uint64_t otherm = ballot(other);
+  const float dx = v.x - ex, dy = v.y - ey;
+  const float d2 = dx * dx + dy * dy;
+  const bool in_range = d2 <= P.range2;
+  bool blocked = false;
+  if (A.los) {
+    // Only an in-range vehicle's blocked bit reaches an output, and its sight segment lies inside
+    // the range circle.  A body whose centre is more than (range_m + 4 m) * 1.0001 from the ego
+    // (its half diagonal is 2.7 m) has no point within a metre of that circle, so it cannot meet such a
+    // segment and is left out of the loop: wave-uniformly, and never with range_m = +inf
+    // (cull2 = +inf) or a NaN distance (the comparison is false).
+    const uint64_t bodym = otherm & ~ballot(d2 > P.cull2);
+    // lane j lays out its body and the ego's centre in its frame (u0, w0: the same for every k);
+    // lane k then reads blocker j's six words at one address (broadcast)
+    const float ax = ex - v.x, ay = ey - v.y;
+    lds_body[w][lane] = make_float4(v.x, v.y, cos_h, sin_h);
+    lds_ego[w][lane] = make_float2(ax * cos_h + ay * sin_h, ay * cos_h - ax * sin_h);
+    wave_lds_sync();
+    for (int j = 1; j < V; ++j) {
+      if (!((bodym >> j) & 1ull)) continue;  // wave-uniform: an absent slot is no body
+      const float4 b = lds_body[w][j];
+      const float2 eo = lds_ego[w][j];
+      const float u0 = eo.x, w0 = eo.y;
+      const float bx = v.x - b.x, by = v.y - b.y;
+      const float u1 = bx * b.z + by * b.w;
+      const float w1 = by * b.z - bx * b.w;
+      const bool hit = hm_minf(u0, u1) <= 0.5f * VEH_LENGTH && hm_maxf(u0, u1) >= -0.5f * VEH_LENGTH &&
+                       hm_minf(w0, w1) <= 0.5f * VEH_WIDTH && hm_maxf(w0, w1) >= -0.5f * VEH_WIDTH &&
+                       hm_absf(u0 * w1 - u1 * w0) <= (0.5f * VEH_LENGTH) * hm_absf(w1 - w0) +
+                                                         (0.5f * VEH_WIDTH) * hm_absf(u1 - u0);
+      blocked = blocked || (hit && j != lane);
+    }
+  }
+  bool dropped = false;
+  if (A.p_drop > 0.0f)  // u < 0 never holds
+    dropped = hm_u01(sense_draw(lane, step, 3u, P.salt_word, seed).v[0]) < A.p_drop;
+  const bool visible = lane == 0 ? v.present : (other && in_range && !blocked && !dropped);
+
+  if (A.visible) A.visible[idx] = visible ? 1 : 0;
+  if (A.hidden) A.hidden[idx] = (v.present && !visible) ? 1.0f : 0.0f;
+  if (A.counts) {
+    const uint64_t outm = ballot(other && !in_range);
+    const uint64_t blkm = ballot(other && in_range && blocked);
+    const uint64_t drpm = ballot(other && in_range && !blocked && dropped);
+    int cv = __popcll(otherm);
+    cv = lane == 1 ? __popcll(outm) : cv;
+    cv = lane == 2 ? __popcll(blkm) : cv;
+    cv = lane == 3 ? __popcll(drpm) : cv;
+    if (lane < 4) A.counts[(size_t)e * 4 + lane] = cv;
+  }
+
+  // ---- the observation of the perceived vehicles
+  if (P.p.obs || A.row_vehicle) {  // wave-uniform
+    Veh pv = v;
+    pv.present = v.present && visible;
+    // a sigma of exactly 0 skips its addition; the ego is never perturbed
+    if (A.sigma[0] != 0.0f) {
+      const float z = sense_z(lane, step, 0u, P.salt_word, seed);
+      if (lane >= 1) pv.x = v.x + A.sigma[0] * z;
+    }
+    if (A.sigma[1] != 0.0f) {
+      const float z = sense_z(lane, step, 1u, P.salt_word, seed);
+      if (lane >= 1) pv.y = v.y + A.sigma[1] * z;
+    }
+    if (A.sigma[2] != 0.0f) {
+      const float z = sense_z(lane, step, 2u, P.salt_word, seed);
+      if (lane >= 1) pv.spd = v.spd + A.sigma[2] * z;
+    }
+    int rv;
+    observe_wave<true>(C, lane, pv, cos_h, sin_h, step, seed, group_pe_table(P.p, e),
+                       P.p.obs ? P.p.obs + (size_t)e * N * P.p.fout : nullptr, P.p.fout,
+                       lds_vor[w], lds_inv[w], lds_key[w], &rv);
+    if (A.row_vehicle && lane < N) A.row_vehicle[(size_t)e * N + lane] = rv;
+  }
+}
+
+extern "C" int hwy_launch_sense(const SenseParams* p, hipStream_t s) {
+  const int blocks = (p->p.cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  hipLaunchKernelGGL(hwy_sense_kernel, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 #else  // the main unit, to the end of the file
 template <int W>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
@@ -2052,4 +2192,4 @@ extern "C" int hwy_debug_sections(unsigned long long* out, int reset) {
   return 0;
 }
 #endif
-#endif  // HWY_CUT_TU / HWY_INFO_TU / HWY_FINAL_TU / HWY_OBSERVE_TU / HWY_TRAFFIC_TU
+#endif  // HWY_CUT_TU / HWY_INFO_TU / HWY_FINAL_TU / HWY_OBSERVE_TU / HWY_TRAFFIC_TU / HWY_SENSE_TU

@@ -25,7 +25,15 @@ launch() on the vectorised loop only -- launch_group and launch_batch refuse it)
 order=name) at the final weights goes into the metrics JSON as ``order_rewards[name]`` -- the
 evaluation's episodes with the policy acting on the same worlds observed under that row order,
 whatever order it trained on; it draws no random number, so everything else is bit for bit the
-run without it; launch() on the vectorised loop only, refused by the grouped launches likewise).
+run without it; launch() on the vectorised loop only, refused by the grouped launches likewise)
+and ``eval_sensors`` ({name: sensor dict}, hwy.SensorModel's fields ``los``, ``range``,
+``dropout``, ``noise``, ``salt``: after training, evaluate(num_episodes=10, sensor=...) at the
+final weights goes into the metrics JSON as ``sensor_rewards[name]`` -- the policy acting on what
+that sensor perceives; the training is likewise unchanged, and the grouped launches refuse it) and
+``sensor`` (one such dict: the run *trains* under it -- every state the policy acts on is sensed,
+its own evaluations use the same sensor, the metrics carry it as ``sensor``; launch() on the
+vectorised loop only, not over a process group, not with truncation "bootstrap" or the reference
+schedule, refused by the grouped launches).
 
 Launched under torchrun (WORLD_SIZE > 1) one experiment spans the ranks, one GPU each: the
 runner joins the process group (RCCL, or ``HWY_DIST_BACKEND``), gives rank r the envs
@@ -169,6 +177,12 @@ class ExperimentRunner:
                         stats_kw["attribution"] = True
                     if exp.extra.get("eval_orders"):
                         stats_kw["eval_orders"] = list(exp.extra["eval_orders"])
+                    if exp.extra.get("eval_sensors"):
+                        stats_kw["eval_sensors"] = dict(exp.extra["eval_sensors"])
+                    if exp.extra.get("sensor") is not None:
+                        if group is not None:
+                            raise ValueError("extra['sensor'] does not run over a process group")
+                        stats_kw["sensor"] = exp.extra["sensor"]
                     if group is not None:
                         e = int(overrides.get("num_envs", 1))
                         if e <= 1:
@@ -260,6 +274,14 @@ class ExperimentRunner:
                                      f"use launch()")
                 if e.extra.get("eval_orders"):
                     raise ValueError(f"launch_group / launch_batch: extra['eval_orders'] is not "
+                                     f"supported by the grouped launches (experiment {e.name}); "
+                                     f"use launch()")
+                if e.extra.get("eval_sensors"):
+                    raise ValueError(f"launch_group / launch_batch: extra['eval_sensors'] is not "
+                                     f"supported by the grouped launches (experiment {e.name}); "
+                                     f"use launch()")
+                if e.extra.get("sensor") is not None:  # any sensor, the null one ({}) too
+                    raise ValueError(f"launch_group / launch_batch: extra['sensor'] is not "
                                      f"supported by the grouped launches (experiment {e.name}); "
                                      f"use launch()")
 

@@ -16,6 +16,7 @@ from ._abi import (  # noqa: F401
     PE_RANK,
     PE_ROPE,
     HwyConfig,
+    SensorModel,
     config_from_dict,
 )
 from .native import HwyNativeError, build  # noqa: F401

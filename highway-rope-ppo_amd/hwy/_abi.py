@@ -125,6 +125,115 @@ def observe_order(order) -> int:
         raise ValueError(f"order must be None, 'sorted' or 'shuffled', got {order!r}") from None
 
 
+class SenseArgs(ctypes.Structure):
+    """hwy_sense_args (include/hwy.h): one hwy_sense launch's order, sensor and outputs."""
+    _fields_ = [
+        ("order", ctypes.c_int32),
+        ("los", ctypes.c_int32),
+        ("range_m", ctypes.c_float),
+        ("p_drop", ctypes.c_float),
+        ("sigma", ctypes.c_float * 3),
+        ("salt", ctypes.c_int32),
+        ("obs", ctypes.c_void_p),
+        ("row_vehicle", ctypes.c_void_p),
+        ("visible", ctypes.c_void_p),
+        ("hidden", ctypes.c_void_p),
+        ("counts", ctypes.c_void_p),
+    ]
+
+
+SENSE_OUTPUTS = ("obs", "row_vehicle", "visible", "hidden", "counts")
+HWY_SENSE_SALT = 0x53454E53
+
+
+class SensorModel:
+    """The sensor of hwy_sense (include/hwy.h), an immutable, hashable value.
+
+    ``los``: line-of-sight occlusion by the other vehicles' bodies; ``range``: sensing range in
+    metres (None: unlimited); ``dropout``: probability of a missed detection per vehicle and
+    step, in [0, 1]; ``noise``: the standard deviations of the perceived x (m), y (m) and speed
+    (m/s); ``salt``: 0..65535, selects the stream of the draws.  Everything hwy_sense_check
+    refuses is a ValueError here."""
+
+    __slots__ = ("los", "range", "dropout", "noise", "salt")
+
+    def __init__(self, los: bool = False, range: Optional[float] = None, dropout: float = 0.0,
+                 noise=(0, 0, 0), salt: int = 0):
+        try:
+            rng = None if range is None else float(range)
+            drop = float(dropout)
+            sig = tuple(float(s) for s in noise)
+            slt = int(salt)
+        except (TypeError, ValueError):
+            raise ValueError(f"bad sensor fields: range={range!r} dropout={dropout!r} "
+                             f"noise={noise!r} salt={salt!r}") from None
+        if rng is not None and math.isinf(rng) and rng > 0:
+            rng = None
+        if rng is not None and not (rng > 0.0 and math.isfinite(rng)):
+            raise ValueError(f"range must be None (unlimited) or finite and > 0, got {range!r}")
+        if not 0.0 <= drop <= 1.0:
+            raise ValueError(f"dropout must lie in [0, 1], got {dropout!r}")
+        if len(sig) != 3 or not all(s >= 0.0 and math.isfinite(s) for s in sig):
+            raise ValueError(f"noise must be three finite values >= 0 (x, y, speed), got {noise!r}")
+        if slt != salt or not 0 <= slt <= 65535:
+            raise ValueError(f"salt must be an integer in 0..65535, got {salt!r}")
+        object.__setattr__(self, "los", bool(los))
+        object.__setattr__(self, "range", rng)
+        object.__setattr__(self, "dropout", drop)
+        object.__setattr__(self, "noise", sig)
+        object.__setattr__(self, "salt", slt)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("SensorModel is immutable")
+
+    def _key(self):
+        return (self.los, self.range, self.dropout, self.noise, self.salt)
+
+    def __eq__(self, other):
+        return isinstance(other, SensorModel) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return (f"SensorModel(los={self.los}, range={self.range}, dropout={self.dropout}, "
+                f"noise={self.noise}, salt={self.salt})")
+
+    @property
+    def is_null(self) -> bool:
+        """No occlusion, no range limit, no dropout and no noise: hwy_sense is hwy_observe."""
+        return (not self.los and self.range is None and self.dropout == 0.0
+                and self.noise == (0.0, 0.0, 0.0))
+
+    def to_dict(self) -> Dict[str, Any]:
+        """JSON-ready (the metrics file): range None = unlimited."""
+        return {"los": self.los, "range": self.range, "dropout": self.dropout,
+                "noise": list(self.noise), "salt": self.salt}
+
+    @classmethod
+    def from_dict(cls, d) -> "SensorModel":
+        """A SensorModel from ``to_dict``'s form (missing keys: the defaults), or ``d`` itself
+        when it already is one; unknown keys are a ValueError."""
+        if isinstance(d, cls):
+            return d
+        if not isinstance(d, dict):
+            raise ValueError(f"a sensor is a SensorModel or a dict of its fields, got {d!r}")
+        unknown = set(d) - set(cls.__slots__)
+        if unknown:
+            raise ValueError(f"unknown sensor keys {sorted(unknown)}; known: {list(cls.__slots__)}")
+        return cls(**d)
+
+    def fill(self, a: SenseArgs) -> SenseArgs:
+        """Write the sensor's fields into hwy_sense_args ``a``."""
+        a.los = int(self.los)
+        a.range_m = math.inf if self.range is None else self.range
+        a.p_drop = self.dropout
+        for c in range(3):
+            a.sigma[c] = self.noise[c]
+        a.salt = self.salt
+        return a
+
+
 # the view hwy_render draws by default: upstream's AbstractEnv.default_config screen_width,
 # screen_height, scaling and centering_position [highway-env 1.10.1]
 RENDER_DEFAULTS = {"screen_width": 600, "screen_height": 150, "scaling": 5.5,

@@ -13,7 +13,8 @@ import os
 import subprocess
 from typing import Optional
 
-from ._abi import HWY_ABI_VERSION, HwyConfig, HwyStepInfo, ObserveArgs, RenderArgs, TrafficArgs
+from ._abi import (HWY_ABI_VERSION, HwyConfig, HwyStepInfo, ObserveArgs, RenderArgs, SenseArgs,
+                   TrafficArgs)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhwy.so")
@@ -98,6 +99,9 @@ def lib():
     L.hwy_traffic_args_size.restype = i32
     L.hwy_traffic_check.argtypes = [ctypes.POINTER(TrafficArgs)]
     L.hwy_traffic.argtypes = [vp, ctypes.POINTER(TrafficArgs), vp]
+    L.hwy_sense_args_size.restype = i32
+    L.hwy_sense_check.argtypes = [ctypes.POINTER(SenseArgs)]
+    L.hwy_sense.argtypes = [vp, ctypes.POINTER(SenseArgs), vp]
     L.hwy_export_state.argtypes = [vp, vp, vp]
     L.hwy_import_state.argtypes = [vp, vp, vp]
     L.hwy_obs_pe.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp]
@@ -115,6 +119,7 @@ def lib():
                  "hwy_step_group_info", "hwy_step_with_final", "hwy_step_group_final_prepare",
                  "hwy_step_group_final", "hwy_gae_boot", "hwy_render",
                  "hwy_observe_check", "hwy_observe", "hwy_traffic_check", "hwy_traffic",
+                 "hwy_sense_check", "hwy_sense",
                  "hwy_export_state", "hwy_import_state", "hwy_obs_pe", "hwy_gae",
                  "hwy_math_selftest"):
         getattr(L, name).restype = i32
@@ -126,6 +131,8 @@ def lib():
         raise HwyNativeError("libhwy.so's hwy_observe_args differs from the python mirror; rebuild")
     if L.hwy_traffic_args_size() != ctypes.sizeof(TrafficArgs):
         raise HwyNativeError("libhwy.so's hwy_traffic_args differs from the python mirror; rebuild")
+    if L.hwy_sense_args_size() != ctypes.sizeof(SenseArgs):
+        raise HwyNativeError("libhwy.so's hwy_sense_args differs from the python mirror; rebuild")
     if L.hwy_abi_version() != HWY_ABI_VERSION:
         raise HwyNativeError(
             f"libhwy.so ABI {L.hwy_abi_version()} != python ABI {HWY_ABI_VERSION}; rebuild"

@@ -107,5 +107,10 @@ class HighwayEnv(Env):
         [64] int32 and ``gap``, ``closing``, ``ttc``, ``thw``, ``risk`` [64] float32."""
         return {k: t[0].cpu().numpy() for k, t in self._vec.traffic(**thresholds).items()}
 
+    def sense(self, sensor):
+        """The current observation through ``sensor`` (HighwayVecEnv.sense: a hwy.SensorModel or
+        its dict), an [N, F_out] float32 numpy array."""
+        return self._vec.sense(sensor)[0].cpu().numpy()
+
     def close(self):
         self._vec.close()

@@ -172,6 +172,35 @@ def traffic_args(num_envs: int, device, *, restart=(), ttc_thresh=None, thw_thre
     return a
 
 
+def sense_args(num_envs: int, rows: int, fout: int, device, sensor, order=None, *, obs=None,
+               row_vehicle=None, visible=None, hidden=None, counts=None) -> _abi.SenseArgs:
+    """hwy_sense_args for an env of ``num_envs`` x ``rows`` x ``fout`` on ``device`` from a
+    SensorModel (or its dict) and caller-owned tensors, every refusal a ValueError (no device
+    call, no library call)."""
+    a = _abi.SensorModel.from_dict(sensor).fill(_abi.SenseArgs())
+    a.order = _abi.observe_order(order)
+    E, N = int(num_envs), int(rows)
+    spec = (("obs", obs, torch.float32, E * N * int(fout), "E x N x F_out"),
+            ("row_vehicle", row_vehicle, torch.int32, E * N, "E x N"),
+            ("visible", visible, torch.uint8, E * HWY_MAX_VEHICLES, "E x 64"),
+            ("hidden", hidden, torch.float32, E * HWY_MAX_VEHICLES, "E x 64"),
+            ("counts", counts, torch.int32, E * 4, "E x 4"))
+    for name, t, dtype, n, what in spec:
+        if t is None:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
+                and t.numel() == n and t.device == torch.device(device)):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements "
+                             f"({what}) on {device}, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} "
+                             f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
+        setattr(a, name, t.data_ptr())
+    if all(t is None for _, t, _, _, _ in spec):
+        raise ValueError("sense_into needs at least one of obs, row_vehicle, visible, hidden and "
+                         "counts")
+    return a
+
+
 class HighwayVecEnv:
     """E lockstep highway-v0 envs with state resident in HBM (one wavefront per env)."""
 
@@ -594,6 +623,44 @@ class HighwayVecEnv:
         del out["acc"], out["ep_stats"]
         self.traffic_into(**thresholds, **out)
         return out
+
+    def sense_into(self, sensor, order: Optional[str] = None, *,
+                   obs: Optional[torch.Tensor] = None, row_vehicle: Optional[torch.Tensor] = None,
+                   visible: Optional[torch.Tensor] = None, hidden: Optional[torch.Tensor] = None,
+                   counts: Optional[torch.Tensor] = None) -> None:
+        """Observe the envs' current states through ``sensor`` (a SensorModel or its dict) into
+        caller-owned device tensors (hwy_sense: one launch, no synchronisation,
+        graph-capturable).  ``order`` as in observe_into.  ``obs`` [E, N, F_out] float32 and
+        ``row_vehicle`` [E, N] int32: observe_into's, of the vehicles as the sensor perceives
+        them (hidden ones absent, x / y / speed with the sensor's noise); ``visible`` [E, 64]
+        uint8; ``hidden`` [E, 64] float32, 1 where a present vehicle is not visible (ready to
+        pass as ``render(shade=...)``); ``counts`` [E, 4] int32: present others, out of range,
+        blocked, dropped.  With the null sensor ``obs`` and ``row_vehicle`` are observe_into's
+        bit for bit."""
+        a = sense_args(self.num_envs, self.obs_rows, self.obs_features, self.device, sensor,
+                       order, obs=obs, row_vehicle=row_vehicle, visible=visible, hidden=hidden,
+                       counts=counts)
+        check(lib().hwy_sense(self._handle, ctypes.byref(a), stream_ptr()), "hwy_sense")
+        self._keep_sense = (obs, row_vehicle, visible, hidden, counts)
+
+    def sense(self, sensor, order: Optional[str] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The current observation [E, N, F_out] through ``sensor`` under ``order`` (sense_into's
+        ``obs``)."""
+        if out is None:
+            out = torch.empty(self.num_envs, self.obs_rows, self.obs_features,
+                              dtype=torch.float32, device=self.device)
+        self.sense_into(sensor, order, obs=out)
+        return out.view(self.num_envs, self.obs_rows, self.obs_features)
+
+    def hidden_vehicles(self, sensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[E, 64] float32, 1 where a present vehicle is hidden from ``sensor`` (sense_into's
+        ``hidden``): ready to pass as ``render(shade=...)``."""
+        if out is None:
+            out = torch.empty(self.num_envs, HWY_MAX_VEHICLES, dtype=torch.float32,
+                              device=self.device)
+        self.sense_into(sensor, hidden=out)
+        return out.view(self.num_envs, HWY_MAX_VEHICLES)
 
     def close(self) -> None:
         if self._handle:

@@ -35,6 +35,13 @@ reference schedule the launch of the last step waits for the cut and takes its `
 third mask, so the state the cut throws away is not measured, the cut episodes' rows land in
 ``traffic_stats[T - 1]`` beside the finished ones' (no env is both), and an env that had just
 restarted is not counted twice.
+
+``sensor=`` (a hwy.SensorModel or its dict): the policy acts on the states as that sensor
+perceives them.  One hwy_sense launch after every env step, inside the captured graph, overwrites
+``buf.states[t + 1]`` with the sensed observation of the state the step left, and one on the
+reset states the caller left overwrites ``buf.states[0]``; the env step itself is unchanged.  Not
+with ``truncation="bootstrap"`` (``final_obs`` would not be sensed) and not on the reference
+schedule (the cut's first observations would not be).
 """
 
 from __future__ import annotations
@@ -62,6 +69,22 @@ def check_truncation(truncation: str) -> str:
     if truncation not in TRUNCATIONS:
         raise ValueError(f"truncation must be one of {TRUNCATIONS}, got {truncation!r}")
     return truncation
+
+
+def check_sensor(sensor, truncation: str = "terminal", episode_schedule: str = "lockstep"):
+    """``sensor`` as a hwy.SensorModel (None: none), refusing what a sensed rollout does not do."""
+    if sensor is None:
+        return None
+    from hwy._abi import SensorModel
+
+    sensor = SensorModel.from_dict(sensor)
+    if truncation == "bootstrap":
+        raise ValueError('sensor does not go with truncation="bootstrap": the terminal '
+                         "observations (final_obs) would not be sensed")
+    if episode_schedule == "reference":
+        raise ValueError('sensor does not go with episode_schedule="reference": the first '
+                         "observations after the cut would not be sensed")
+    return sensor
 
 
 def rollout_chunks(T: int, episode_schedule: str):
@@ -95,10 +118,12 @@ def traffic_after_step(env, buf, t: int, cut=None) -> None:
 class LockstepRollout:
     def __init__(self, agent, env, buf, use_graph: bool = True,
                  episode_schedule: str = "lockstep", episode_stats: bool = False,
-                 truncation: str = "terminal", safety_stats: bool = False):
+                 truncation: str = "terminal", safety_stats: bool = False, sensor=None):
         self.agent = agent
         self.env = env.unwrapped if hasattr(env, "unwrapped") else env
         self.buf = buf
+        # one hwy_sense launch per env step (and one now, on the reset states the caller left)
+        self.sensor = check_sensor(sensor, truncation, episode_schedule)
         # the steps as hwy_step_with_info, the episodes' sums going to buf.ep_stats / buf.acc
         # (after a reference-schedule cut, buf.acc's rows of the cut envs hold their partial sums)
         self.episode_stats = bool(episode_stats)
@@ -131,6 +156,8 @@ class LockstepRollout:
             alloc_cut_buffers(self, buf.E, buf.states.shape[-1], buf.states.device)
         if self.safety_stats:
             traffic_after_reset(self.env, buf)
+        if self.sensor is not None:
+            self.env.sense_into(self.sensor, obs=buf.states[0])
 
     def _launch_key(self):
         from hwy.ppo_native import act_tiles, flat_params
@@ -152,6 +179,8 @@ class LockstepRollout:
             key += (buf.final_obs.data_ptr(), buf.boot_values.data_ptr())
         if self.safety_stats:
             key += (buf.traffic_stats.data_ptr(), buf.traffic_acc.data_ptr())
+        if self.sensor is not None:
+            key += (self.sensor,)
         return key
 
     def _steps(self, t0: int = 0, t1: Optional[int] = None) -> None:
@@ -184,6 +213,8 @@ class LockstepRollout:
                 self._envstep.launch([io])
             else:
                 env.step_into(*io)
+            if self.sensor is not None:
+                env.sense_into(self.sensor, obs=buf.states[t + 1])
             if self.safety_stats and not (self.episode_schedule == "reference" and t == buf.T - 1):
                 traffic_after_step(env, buf, t)
         if t1 < buf.T:

@@ -52,10 +52,17 @@ draws no random number, so the training is unchanged, bit for bit.
 ``out_dir``, records their frames (HighwayVecEnv.render, one launch per step); there is no window.
 ``attribution="value"`` (or another of ATTRIBUTION_OUTPUTS) tints every vehicle of every frame by
 the policy's input-gradient mass on the observation row that shows it (``attribution_shade``).
-``tint="ttc"`` tints them by hwy_traffic's ``risk`` instead (1 - ttc / 4 s below 4 s, else 0).
+``tint="ttc"`` tints them by hwy_traffic's ``risk`` instead (1 - ttc / 4 s below 4 s, else 0),
+``tint="hidden"`` with ``sensor=`` the vehicles that sensor does not see (hwy_sense's ``hidden``).
 ``evaluate(..., order="sorted" | "shuffled")`` runs the evaluation's episodes with the policy acting
 on the same worlds observed under that row order (HighwayVecEnv.observe), whatever the env's own
 order is; ``eval_orders`` books both at the final weights as ``order_rewards`` in the metrics.
+``evaluate(..., sensor=S)`` (a hwy.SensorModel or its dict; it combines with ``order``) runs them
+with the policy acting on what that sensor perceives (HighwayVecEnv.sense: line-of-sight
+occlusion, a sensing range, missed detections, position and speed noise); ``eval_sensors``
+({name: sensor}) books each at the final weights as ``sensor_rewards``.  ``sensor`` trains under
+one: the rollout senses every state the policy acts on (ppo/rollout.py), the run's own
+evaluations use the same sensor and the metrics carry it as ``sensor``.
 """
 
 from __future__ import annotations
@@ -81,10 +88,18 @@ def _flat_dim(env) -> int:
 
 
 # ---------------------------------------------------------------------------------- evaluation
-def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order=None):
+def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order=None,
+             sensor=None):
     """Mean return of deterministic episodes seeded exp_seed + 1000 + k.  ``order`` ("sorted" or
     "shuffled"; vector envs only): the same episodes with the policy acting on the states
-    re-observed under that row order (HighwayVecEnv.observe) instead of the step's own rows."""
+    re-observed under that row order (HighwayVecEnv.observe) instead of the step's own rows.
+    ``sensor`` (a hwy.SensorModel or its dict; vector envs only): the policy acts on the states as
+    that sensor perceives them (HighwayVecEnv.sense), under ``order`` when that is given too."""
+    if sensor is not None:
+        if not _is_vector(env):
+            raise ValueError("evaluate(sensor=...) needs a HighwayVecEnv (num_envs > 1, or "
+                             "make_env's vector_env key for one env)")
+        return _evaluate_vector_sensor(env, agent, num_episodes, exp_seed, sensor, order)
     if order is not None:
         if not _is_vector(env):
             raise ValueError("evaluate(order=...) needs a HighwayVecEnv (num_envs > 1, or "
@@ -163,7 +178,28 @@ def _evaluate_vector_order(env, agent, num_episodes, exp_seed, order):
     return r
 
 
-def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None):
+def _evaluate_vector_sensor(env, agent, num_episodes, exp_seed, sensor, order):
+    """_evaluate_vector for evaluate(sensor=...), with a memo of its own keyed by the sensor and
+    the order too (the plain memo and the order memo are neither read nor written)."""
+    from hwy._abi import SensorModel, observe_order
+
+    sensor = SensorModel.from_dict(sensor)
+    observe_order(order)
+    key = _eval_key(agent, num_episodes, exp_seed) + (sensor, order)
+    # one (key, value) pair per (sensor, order) ever evaluated on this env, never dropped: a
+    # handful for eval_sensors; a caller sweeping many sensors may clear env._eval_sensor_memo
+    memo = getattr(env.unwrapped, "_eval_sensor_memo", None)
+    if memo is None:
+        memo = env.unwrapped._eval_sensor_memo = {}
+    hit = memo.get((sensor, order))
+    if hit is not None and hit[0] == key and key[0] is not None:
+        return hit[1]
+    r = _run_eval_vector(env, agent, num_episodes, exp_seed, order=order, sensor=sensor)
+    memo[(sensor, order)] = (key, r)
+    return r
+
+
+def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None):
     cache = getattr(env.unwrapped, "_eval_envs", None)
     if cache is None:
         cache = {}
@@ -176,9 +212,11 @@ def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None):
     obs, _ = ev.reset(seeds=seeds)
     alive = torch.ones(num_episodes, dtype=torch.bool, device=dev)
     total = torch.zeros(num_episodes, dtype=torch.float64, device=dev)
-    seen = None  # order given: the states as observed under it, in a buffer of its own
+    seen = None  # order / sensor given: the states as observed under it, in a buffer of its own
     for k in range(ev.max_episode_steps + 1):
-        if order is not None:
+        if sensor is not None:
+            obs = seen = ev.sense(sensor, order=order, out=seen)
+        elif order is not None:
             obs = seen = ev.observe(order=order, out=seen)
         a, _, _, _ = agent.select_action(obs.reshape(num_episodes, -1), deterministic=True)
         obs, r, te, tr, _ = ev.step(a.contiguous())
@@ -227,11 +265,11 @@ def attribution_shade(vec_env, grad, order=None):
     return vec_env.rows_to_vehicles(rel.to(torch.float32).contiguous(), order=order)
 
 
-VISUALIZE_TINTS = ("ttc",)
+VISUALIZE_TINTS = ("ttc", "hidden")
 
 
 def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, out_dir=None,
-                    attribution=None, tape=None, tint=None):
+                    attribution=None, tape=None, tint=None, sensor=None):
     """Deterministic episodes of a trained agent, seeded exp_seed + 2000 + ep, on a fresh env of
     ``env``'s config and fused wrapper (reference training/routine.py:32-58, which opens a
     render_mode="human" window; there is no display here).  All ``num_episodes`` run as one
@@ -243,7 +281,10 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
     one of ATTRIBUTION_OUTPUTS to tint each frame's vehicles by that output's input-gradient mass
     at the frame's own observation (attribution_shade; both are the state after the step).
     ``tint``: None, or "ttc" to tint each frame's vehicles by their time-to-collision risk at the
-    frame's state (HighwayVecEnv.traffic_into's ``risk``); not together with ``attribution``.
+    frame's state (HighwayVecEnv.traffic_into's ``risk``), or "hidden" to tint the vehicles
+    ``sensor`` does not see at the frame's state (HighwayVecEnv.sense_into's ``hidden``); not
+    together with ``attribution``.  ``sensor`` (a hwy.SensorModel or its dict): the policy acts on
+    what that sensor perceives, as in evaluate(sensor=...); "hidden" needs it.
     ``tape``: a list that receives, per grabbed step, (observation, exported state, the episodes
     still recording) as clones (tests)."""
     from hwy.vec_env import HighwayVecEnv
@@ -255,6 +296,12 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
         raise ValueError(f"tint must be None or one of {VISUALIZE_TINTS}, got {tint!r}")
     if tint is not None and attribution is not None:
         raise ValueError("tint and attribution both shade the vehicles: give one of them")
+    if sensor is not None:
+        from hwy._abi import SensorModel
+
+        sensor = SensorModel.from_dict(sensor)
+    elif tint == "hidden":
+        raise ValueError('tint="hidden" needs a sensor')
 
     if logger is None:
         logger = logging.getLogger(__name__)
@@ -271,6 +318,8 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
         dev = ev.device
         seeds = torch.arange(n, device=dev, dtype=torch.int64) + (exp_seed + 2000)
         obs, _ = ev.reset(seeds=seeds)
+        if sensor is not None:
+            obs = ev.sense(sensor)
         alive = torch.ones(n, dtype=torch.bool, device=dev)
         total = torch.zeros(n, dtype=torch.float64, device=dev)
         frames = [[] for _ in range(n)]
@@ -284,6 +333,8 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
             elif tint == "ttc":
                 shade = torch.empty(n, 64, dtype=torch.float32, device=dev)
                 ev.traffic_into(risk=shade)
+            elif tint == "hidden":
+                shade = ev.hidden_vehicles(sensor)
             host = ev.render(shade=shade).cpu().numpy()
             if tape is not None:
                 tape.append((obs.clone(), ev.export_state(), list(running)))
@@ -296,6 +347,8 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
         for _ in range(ev.max_episode_steps + 1):
             a, _, _, _ = agent.select_action(obs.reshape(n, -1), deterministic=True)
             obs, r, te, tr, _ = ev.step(a.contiguous())
+            if sensor is not None:
+                obs = ev.sense(sensor)
             total += torch.where(alive, r.double(), torch.zeros_like(total))
             if out_dir is not None:
                 grab()  # the frame after this step, for the episodes that took it
@@ -794,8 +847,9 @@ class _EvalTracker:
     """Eval / moving-average / checkpoint bookkeeping of routine.py:172-222."""
 
     def __init__(self, env, agent, exp_seed, target_reward, checkpoint_dir, experiment_name,
-                 metrics_history, logger, exp_prefix, start_time):
+                 metrics_history, logger, exp_prefix, start_time, sensor=None):
         self.env, self.agent, self.exp_seed = env, agent, exp_seed
+        self.sensor = sensor  # the sensor the run trains under: its own evaluations use it too
         self.target_reward = target_reward
         self.checkpoint_dir, self.name = checkpoint_dir, experiment_name
         self.mh, self.logger, self.prefix, self.t0 = metrics_history, logger, exp_prefix, start_time
@@ -805,7 +859,8 @@ class _EvalTracker:
 
     def initial(self, r=None):
         if r is None:
-            r = evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed)
+            r = evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed,
+                         **({} if self.sensor is None else {"sensor": self.sensor}))
         self.rewards.append(r)
         self.avg_rewards.append(r)
         self.mh["eval_rewards"].append(r)
@@ -818,7 +873,8 @@ class _EvalTracker:
         """r: the evaluation's result when the caller ran it (evaluate_many), else evaluated here."""
         self.logger.info(f"{self.prefix} Evaluating at episode {episode_num}...")
         if r is None:
-            r = evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed)
+            r = evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed,
+                         **({} if self.sensor is None else {"sensor": self.sensor}))
         self.rewards.append(r)
         self.eval_episodes.append(episode_num)
         elapsed = time.time() - self.t0
@@ -846,8 +902,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
                                exp_seed: int = 0, logger=None, episode_schedule="lockstep",
                                episode_stats: bool = False, truncation: str = "terminal",
                                attribution: bool = False, eval_orders=None,
-                               safety_stats: bool = False):
-    from ppo.rollout import check_episode_schedule, check_truncation
+                               safety_stats: bool = False, sensor=None, eval_sensors=None):
+    from ppo.rollout import check_episode_schedule, check_sensor, check_truncation
 
     if attribution and not _is_vector(env):
         raise ValueError("attribution needs a HighwayVecEnv (num_envs > 1, or make_env's "
@@ -856,6 +912,19 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
     if eval_orders and not _is_vector(env):
         raise ValueError("eval_orders needs a HighwayVecEnv (num_envs > 1, or make_env's "
                          "vector_env key for one env)")
+
+    eval_sensors = check_eval_sensors(eval_sensors)
+    if eval_sensors and not _is_vector(env):
+        raise ValueError("eval_sensors needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                         "vector_env key for one env)")
+    sensor = check_sensor(sensor, check_truncation(truncation),
+                          check_episode_schedule(episode_schedule))
+    if sensor is not None:
+        if not _is_vector(env):
+            raise ValueError("sensor needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                             "vector_env key for one env)")
+        if getattr(agent, "_dist", None) is not None:
+            raise ValueError("sensor does not run over a process group")
 
     if check_truncation(truncation) == "bootstrap":
         if not _is_vector(env):
@@ -911,13 +980,15 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         metrics_history.update({k: [] for k in SAFETY_KEYS})
     if truncation != "terminal":  # the default's metrics stay what they were
         metrics_history["truncation"] = truncation
+    if sensor is not None:
+        metrics_history["sensor"] = sensor.to_dict()
     _book_controls(metrics_history, agent)
     start_time = time.time()
     artifacts_dir = ensure_artifacts_dir()
     checkpoint_dir = os.path.join(artifacts_dir, "checkpoints")
     os.makedirs(checkpoint_dir, exist_ok=True)
     tracker = _EvalTracker(env, agent, exp_seed, target_reward, checkpoint_dir, experiment_name,
-                           metrics_history, logger, exp_prefix, start_time)
+                           metrics_history, logger, exp_prefix, start_time, sensor=sensor)
     rank, _ = _rank_world(getattr(agent, "_dist", None))
     if rank == 0:
         logger.info(f"{exp_prefix} Performing initial evaluation...")
@@ -932,6 +1003,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         sched_kw["truncation"] = truncation
     if safety_stats:
         sched_kw["safety_stats"] = True
+    if sensor is not None:
+        sched_kw["sensor"] = sensor
     episode_rewards, training_episodes, total_steps = loop(
         env, agent, max_episodes, log_interval, eval_interval, steps_per_update, exp_seed, logger,
         exp_prefix, metrics_history, tracker, start_time, **sched_kw)
@@ -944,6 +1017,10 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         metrics_history["order_rewards"] = {
             name: evaluate(env, agent, num_episodes=10, exp_seed=exp_seed, order=name)
             for name in eval_orders}
+    if eval_sensors:  # likewise, under each sensor
+        metrics_history["sensor_rewards"] = {
+            name: evaluate(env, agent, num_episodes=10, exp_seed=exp_seed, sensor=s)
+            for name, s in eval_sensors.items()}
     _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_history,
                     training_episodes, episode_rewards, tracker.eval_episodes, tracker.rewards,
                     tracker.avg_rewards, target_reward, total_steps, logger, exp_prefix)
@@ -958,6 +1035,18 @@ def check_eval_orders(eval_orders) -> list:
         raise ValueError(f"eval_orders must list 'sorted' and / or 'shuffled' once each, got "
                          f"{eval_orders!r}")
     return names
+
+
+def check_eval_sensors(eval_sensors) -> dict:
+    """``eval_sensors`` as {name: hwy.SensorModel} (None or empty: none) from a dict of names to
+    sensors or their dicts; ValueError otherwise."""
+    from hwy._abi import SensorModel
+
+    if eval_sensors is None:
+        return {}
+    if not isinstance(eval_sensors, dict) or not all(isinstance(n, str) for n in eval_sensors):
+        raise ValueError(f"eval_sensors must be a dict of names to sensors, got {eval_sensors!r}")
+    return {name: SensorModel.from_dict(s) for name, s in eval_sensors.items()}
 
 
 def _log_episode(logger, prefix, episode_num, ep_reward, episode_rewards, log_interval,
@@ -1013,8 +1102,12 @@ def _train_single(env, agent, max_episodes, log_interval, eval_interval, steps_p
 
 def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_per_update,
                   exp_seed, logger, prefix, mh, tracker, start_time, episode_schedule="lockstep",
-                  episode_stats=False, truncation="terminal", safety_stats=False):
+                  episode_stats=False, truncation="terminal", safety_stats=False, sensor=None):
     """E lockstep envs, device rollout of T steps, batched PPO update.
+
+    sensor: the rollout senses the reset states and the state every env step leaves into the
+    rows the policy acts on (one hwy_sense launch each, ppo/rollout.py); not over a process
+    group, not with truncation "bootstrap" or the reference schedule.
 
     safety_stats: the rollout issues one hwy_traffic launch per env step and every booked
     episode's reduction row goes to mh's SAFETY_KEYS lists (read before the next rollout); not
@@ -1045,6 +1138,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
         raise ValueError("truncation='bootstrap' does not run over a process group")
     if safety_stats and group is not None:
         raise ValueError("safety_stats does not run over a process group")
+    if sensor is not None and group is not None:
+        raise ValueError("sensor does not run over a process group")
     base = env.unwrapped
     E = base.num_envs
     sd = _flat_dim(env)
@@ -1060,7 +1155,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
     roll = LockstepRollout(agent, base, buf, use_graph=getattr(agent, "use_graphs", True),
                            **({"episode_schedule": episode_schedule} if reference else {}),
                            **stats_kw, **safety_kw,
-                           **({"truncation": truncation} if bootstrap else {}))
+                           **({"truncation": truncation} if bootstrap else {}),
+                           **({"sensor": sensor} if sensor is not None else {}))
     episode_rewards, training_episodes = [], []
     total_steps = episode_num = 0
     while episode_num < max_episodes:

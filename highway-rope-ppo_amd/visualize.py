@@ -5,6 +5,7 @@
     python visualize.py --models-file best_checkpoints.txt --out demo_frames
     python visualize.py --model <checkpoint> --attribution value     # what the critic looks at
     python visualize.py --model <checkpoint> --tint ttc              # who is about to be hit
+    python visualize.py --model <checkpoint> --tint hidden --sensor '{"los": true, "range": 80}'
 
 For every checkpoint the network's dimensions are read from the saved weights
 (``shared.0.weight`` is [hidden_dim, state_dim], ``actor_mean.2.weight`` [action_dim,
@@ -19,7 +20,9 @@ not pygame's pixels).  ``--attribution`` tints every vehicle toward yellow by th
 chosen output's input-gradient mass on the observation row that shows it (hwy_observe's row ->
 vehicle map; training.routine.attribution_shade); ``--tint ttc`` tints them by their
 time-to-collision risk instead (hwy_traffic's ``risk``: 1 - ttc / 4 s below 4 s), and the two
-exclude each other.  There is no live window and no MP4: neither a display nor an encoder is a
+exclude each other.  ``--sensor JSON`` (hwy.SensorModel's fields) lets the policy act on what that
+sensor perceives (hwy_sense), and ``--tint hidden`` with it tints the vehicles the sensor does not
+see.  There is no live window and no MP4: neither a display nor an encoder is a
 dependency.
 """
 
@@ -94,13 +97,18 @@ def load_agent(path: str, device=None):
 
 
 def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=None,
-           attribution: Optional[str] = None, tint: Optional[str] = None) -> List[float]:
+           attribution: Optional[str] = None, tint: Optional[str] = None,
+           sensor=None) -> List[float]:
     """Record ``episodes`` episodes of one checkpoint into out_dir/<checkpoint stem>/; returns
     their rewards.  ``attribution`` ("acceleration", "steering" or "value"): tint every vehicle by
     the policy's input-gradient mass on the row that shows it (visualize_agent).  ``tint``
-    ("ttc"): tint them by their time-to-collision risk instead; not together with it."""
+    ("ttc"): tint them by their time-to-collision risk instead; not together with it.  ``sensor``
+    (a hwy.SensorModel or its dict): the policy acts on what it perceives, and ``tint`` "hidden"
+    tints the vehicles it does not see."""
     if tint is not None and attribution is not None:
         raise ValueError("tint and attribution both shade the vehicles: give one of them")
+    if tint == "hidden" and sensor is None:
+        raise ValueError('tint "hidden" needs a sensor')
     from config.base_config import HIGHWAY_CONFIG
     from experiments.wrappers import make_env
     from training.routine import visualize_agent
@@ -117,7 +125,8 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
                              f"{cond.name} env (d_embed={d_embed}) gives {have}")
         dest = os.path.join(out_dir, os.path.splitext(os.path.basename(path))[0])
         rewards = visualize_agent(env, agent, num_episodes=episodes, exp_seed=seed, out_dir=dest,
-                                  attribution=attribution, **({"tint": tint} if tint else {}))
+                                  attribution=attribution, **({"tint": tint} if tint else {}),
+                                  **({"sensor": sensor} if sensor is not None else {}))
     finally:
         env.close()
     for ep, r in enumerate(rewards):
@@ -144,15 +153,31 @@ def main(argv=None) -> int:
                    help="episode ep is seeded seed + 2000 + ep, as visualize_agent")
     p.add_argument("--attribution", choices=("acceleration", "steering", "value"), default=None,
                    help="tint each vehicle by |input gradient| of this output on its row")
-    p.add_argument("--tint", choices=("ttc",), default=None,
-                   help="tint each vehicle by its time-to-collision risk (not with --attribution)")
+    p.add_argument("--tint", choices=("ttc", "hidden"), default=None,
+                   help="tint each vehicle by its time-to-collision risk, or (hidden, with "
+                        "--sensor) the vehicles the sensor does not see (not with --attribution)")
+    p.add_argument("--sensor", default=None, metavar="JSON",
+                   help='the policy acts through this sensor, e.g. \'{"los": true, "range": 80, '
+                        '"dropout": 0.1, "noise": [0.5, 0.2, 0.5]}\'')
     args = p.parse_args(argv)
     if args.tint and args.attribution:
         p.error("--tint and --attribution both shade the vehicles: give one of them")
+    sensor = None
+    if args.sensor is not None:
+        import json
+
+        from hwy._abi import SensorModel
+
+        try:
+            sensor = SensorModel.from_dict(json.loads(args.sensor))
+        except ValueError as e:   # json.JSONDecodeError is a ValueError too
+            p.error(f"--sensor: {e}")
+    if args.tint == "hidden" and sensor is None:
+        p.error("--tint hidden needs --sensor")
     models = [args.model] if args.model else list(models_from_file(args.models_file))
     for m in models:
         record(m, args.out, episodes=args.episodes, seed=args.seed, attribution=args.attribution,
-               tint=args.tint)
+               tint=args.tint, **({"sensor": sensor} if sensor is not None else {}))
     return 0
 
 

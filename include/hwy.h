@@ -44,6 +44,8 @@
  *                                (this project's own frame rule, not pygame's pixels)
  *   hwy_observe               <- env.unwrapped.observation_type.observe() on the current road, under
  *                                either "order", plus the row -> vehicle assignment it drops
+ *   hwy_sense                 <- nothing upstream: observation_type.observe() of the vehicles a sensor
+ *                                on the ego perceives (range, line of sight, dropout, noise)
  *   hwy_traffic               <- env.unwrapped.road.neighbour_vehicles(v) for every vehicle, and the
  *                                gap / time-to-collision / headway a driving study derives from it
  *
@@ -535,6 +537,81 @@ int hwy_traffic_args_size(void);
  * pure, no device call. */
 int hwy_traffic_check(const hwy_traffic_args* a);
 int hwy_traffic(hwy_handle* h, const hwy_traffic_args* a, void* stream);
+
+/* ---- A sensor model in front of the observation: range, line of sight, missed detections and
+ * measurement noise.
+ *
+ * hwy_sense observes all E envs from the state words as they stand, as hwy_observe does and
+ * with the same observation code, but of the vehicles as a sensor on the ego perceives them: a
+ * vehicle that is not `visible` is handed to the observation as absent, a visible one with a
+ * perturbed x, y and speed.  Ranking, the 200 m perception test, see_behind, the shuffle and the
+ * fused wrapper therefore act on the perceived vehicles, as they would on a tracker's list.  With
+ * the null sensor (los 0, range_m +inf, p_drop 0, sigma 0 0 0) obs and row_vehicle are bit for
+ * bit hwy_observe's.
+ *
+ * All arithmetic is binary32 without contraction, each product rounded before the sum it
+ * enters; a comparison with a NaN is false.  The ego is vehicle 0 at (xe, ye), V =
+ * vehicles_count + 1.  For vehicle k, 1 <= k < V, carrying HWY_FLAG_PRESENT:
+ *   in range: dx = x_k - xe, dy = y_k - ye; in range iff dx*dx + dy*dy <= range_m*range_m
+ *     (range_m = +inf: always).
+ *   blocked (los != 0 only): some present j, 1 <= j < V, j != k, has its 5.0 x 2.0 rectangle at
+ *     heading h_j meeting the segment from the ego's centre to k's centre.  A blocker is a body:
+ *     it blocks whether or not it is visible itself.  In j's frame, by separating axes:
+ *       (sj, cj) = hm_sincosf(h_j)
+ *       ax = xe - x_j, ay = ye - y_j, bx = x_k - x_j, by = y_k - y_j
+ *       u0 = ax*cj + ay*sj   w0 = ay*cj - ax*sj
+ *       u1 = bx*cj + by*sj   w1 = by*cj - bx*sj
+ *       blocked by j iff  min(u0,u1) <= 2.5 && max(u0,u1) >= -2.5
+ *                      && min(w0,w1) <= 1.0 && max(w0,w1) >= -1.0
+ *                      && |u0*w1 - u1*w0| <= 2.5*|w1 - w0| + 1.0*|u1 - u0|
+ *   dropped: hm_u01(philox(k, step, 3, SALT, seed_lo, seed_hi).v[0]) < p_drop, with the env's
+ *     step and seed words, philox = hm_philox4x32_10 (counter words, then key words) and
+ *     SALT = 0x53454E53 + salt in uint32 (the shuffle's stream is 0x53485546).
+ *   visible[k] = present && in range && !blocked && !dropped.  visible[0] is the ego's present
+ *     bit; absent slots and k >= V give 0.
+ *   noise, for channel c in {0: x, 1: y, 2: speed}: w = philox(k, step, c, SALT, seed_lo, seed_hi),
+ *     u_i = hm_u01(w.v[i]), z_c = (((u_0 + u_1) + (u_2 + u_3)) - 2.0f) * 1.7320508f (zero mean,
+ *     unit variance, |z| <= 2 sqrt 3); x' = x + sigma[0]*z_0, y' = y + sigma[1]*z_1,
+ *     spd' = spd + sigma[2]*z_2.  A sigma of exactly 0 skips its addition (the bits of -0.0
+ *     survive).  The heading and the ego are never perturbed.  Range and line of sight are
+ *     decided on the true positions; the perceived ones enter the observation.
+ *
+ *   obs [E][N][F_out], row_vehicle [E][N] i32: as hwy_observe's, of the perceived vehicles,
+ *     under `order` (-1: the handle's own).
+ *   visible [E][64] u8: 1 / 0 as above.
+ *   hidden [E][64] f32: 1.0 where present and not visible, else +0.0 (the ego: +0.0); hwy_render's
+ *     `shade` layout.
+ *   counts [E][4] i32: present others (1 <= k < V); of them out of range; in range but blocked;
+ *     in range, not blocked but dropped.  The three and the visible others add up to the first.
+ *
+ * All output pointers are device pointers and nullable, but at least one must be given.
+ * hwy_sense is asynchronous, allocates nothing, is hipGraph-capturable, reads the state and
+ * writes nothing but the outputs it was given.  It returns HWY_EINVAL before any device call for
+ * a NULL handle or NULL args, an order outside {-1, HWY_ORDER_SORTED, HWY_ORDER_SHUFFLED}, a
+ * range_m that is neither +inf nor finite and > 0, a p_drop outside [0, 1], a sigma that is not
+ * finite and >= 0, a salt outside 0..65535, no output at all, and a handle whose per-group PE
+ * tables are without meaning (hwy_set_seed_groups).  On non-finite state words the values are
+ * not specified; the kernel terminates and stays inside its outputs. */
+#define HWY_SENSE_SALT 0x53454E53u
+typedef struct hwy_sense_args {
+  int32_t order;         /* -1: the handle's own; else enum hwy_order */
+  int32_t los;           /* != 0: line-of-sight occlusion */
+  float range_m;         /* m, finite and > 0, or +inf */
+  float p_drop;          /* in [0, 1] */
+  float sigma[3];        /* x (m), y (m), speed (m/s): finite and >= 0 */
+  int32_t salt;          /* 0..65535 */
+  float* obs;            /* device [E][N][F_out], nullable */
+  int32_t* row_vehicle;  /* device [E][N], nullable */
+  uint8_t* visible;      /* device [E][64], nullable */
+  float* hidden;         /* device [E][64], nullable */
+  int32_t* counts;       /* device [E][4], nullable */
+} hwy_sense_args;
+/* sizeof(hwy_sense_args) as compiled into the library (binding layout check). */
+int hwy_sense_args_size(void);
+/* HWY_OK, or HWY_EINVAL for arguments hwy_sense refuses (every check that needs no handle);
+ * pure, no device call. */
+int hwy_sense_check(const hwy_sense_args* a);
+int hwy_sense(hwy_handle* h, const hwy_sense_args* a, void* stream);
 
 /* Stand-alone observation wrapper on [E,N,F] f32 -> [E,N,F_out] f32 (foreign envs).
  *   kind = enum hwy_pe_kind, d = appended width (rank/dist) or rotate_dim (rope),
