@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "hwy.h"
 #include "hwy_internal.h"
@@ -36,6 +37,13 @@ static int fail(int code, const char* fmt, ...) {
 static int hip_fail(hipError_t e, const char* what) {
   return fail(HWY_EDEVICE, "%s: %s", what, hipGetErrorString(e));
 }
+
+// the end of every compute entry point: rc is a hwy_launch_*'s return
+static int launched(int rc, const char* kernel) {
+  return rc ? hip_fail(hipGetLastError(), kernel) : HWY_OK;
+}
+
+static bool finite_pos(float x) { return x > 0.0f && x < __builtin_inff(); }
 
 static int pe_extra(const hwy_config* c) {
   return (c->pe_kind == HWY_PE_RANK || c->pe_kind == HWY_PE_DIST || c->pe_kind == HWY_PE_DIST1)
@@ -101,6 +109,10 @@ static int validate(const hwy_config* c) {
   return HWY_OK;
 }
 
+static size_t state_bytes(const hwy_handle* h) {
+  return (size_t)HWY_NFIELDS * (size_t)h->cfg.num_envs * HWY_MAX_VEHICLES * sizeof(uint32_t);
+}
+
 extern "C" {
 
 int hwy_abi_version(void) { return HWY_ABI_VERSION; }
@@ -120,38 +132,34 @@ int hwy_create(const hwy_config* cfg, int device, hwy_handle** out) {
   h->cfg = *cfg;
   h->device = device;
   h->fout = cfg->n_features + pe_extra(cfg);
-  size_t words = (size_t)HWY_NFIELDS * (size_t)cfg->num_envs * HWY_MAX_VEHICLES;
-  e = hipMalloc(&h->state, words * sizeof(uint32_t));
-  if (e != hipSuccess) {
-    delete h;
-    return hip_fail(e, "hipMalloc(state)");
+  const char* what = "hipMalloc(state)";
+  e = hipMalloc(&h->state, state_bytes(h));
+  if (e == hipSuccess) {
+    what = "hipMalloc(pe_table)";
+    e = hipMalloc(&h->pe_table, HWY_MAX_PE_TABLE * sizeof(float));
   }
-  e = hipMalloc(&h->pe_table, HWY_MAX_PE_TABLE * sizeof(float));
-  if (e != hipSuccess) {
-    (void)hipFree(h->state);
-    delete h;
-    return hip_fail(e, "hipMalloc(pe_table)");
+  if (e == hipSuccess) {
+    what = "hipMemset";
+    (void)hipMemset(h->state, 0, state_bytes(h));
+    (void)hipMemset(h->pe_table, 0, HWY_MAX_PE_TABLE * sizeof(float));
+    e = hipDeviceSynchronize();
   }
-  (void)hipMemset(h->state, 0, words * sizeof(uint32_t));
-  (void)hipMemset(h->pe_table, 0, HWY_MAX_PE_TABLE * sizeof(float));
-  e = hipDeviceSynchronize();
   if (e != hipSuccess) {
-    (void)hipFree(h->state);
-    (void)hipFree(h->pe_table);
-    delete h;
-    return hip_fail(e, "hipMemset");
+    hwy_destroy(h);  // frees what exists of h
+    return hip_fail(e, what);
   }
   *out = h;
   return HWY_OK;
 }
 
+// also hwy_create's error path: h may be partly built (hipFree(NULL) does nothing)
 void hwy_destroy(hwy_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
   (void)hipFree(h->state);
   (void)hipFree(h->pe_table);
-  if (h->group_seed) (void)hipFree(h->group_seed);
+  (void)hipFree(h->group_seed);
   delete h;
 }
 
@@ -244,6 +252,37 @@ static StepParams params_of(hwy_handle* h) {
   return p;
 }
 
+static bool step_io_ok(const hwy_step_io& a) {
+  return a.actions && a.obs && a.reward && a.terminated && a.truncated;
+}
+
+static int check_step_io(const char* who, const hwy_step_io& a) {
+  if (!step_io_ok(a))
+    return fail(HWY_EINVAL, "%s: actions/obs/reward/terminated/truncated must be non-NULL", who);
+  return HWY_OK;
+}
+
+// params_of(h) with one step's buffers
+static StepParams step_params(hwy_handle* h, const hwy_step_io& a) {
+  StepParams p = params_of(h);
+  p.actions = a.actions;
+  p.obs = a.obs;
+  p.reward = a.reward;
+  p.term = a.terminated;
+  p.trunc = a.truncated;
+  p.ep_ret = a.ep_return;
+  p.ep_len = a.ep_length;
+  return p;
+}
+
+// a grouped variant's second device table, after hwy_step_group_prepare filled the first
+static int upload_table(void* dst, const void* src, size_t bytes, void* stream, const char* who) {
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return e == hipSuccess ? HWY_OK : hip_fail(e, who);
+}
+
 int hwy_reset(hwy_handle* h, const uint64_t* seeds, const uint8_t* mask, float* obs, void* stream) {
   if (!h) return fail(HWY_EINVAL, "handle is NULL");
   if (int rc = check_pe(h, "hwy_reset")) return rc;
@@ -251,57 +290,43 @@ int hwy_reset(hwy_handle* h, const uint64_t* seeds, const uint8_t* mask, float* 
   p.seeds = seeds;
   p.mask = mask;
   p.obs = obs;
-  if (hwy_launch_reset(&p, (hipStream_t)stream)) return hip_fail(hipGetLastError(), "hwy_reset_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_reset(&p, (hipStream_t)stream), "hwy_reset_kernel");
 }
 
 int hwy_step(hwy_handle* h, const float* actions, float* obs, float* reward, uint8_t* terminated,
              uint8_t* truncated, float* ep_return, int32_t* ep_length, void* stream) {
   if (!h) return fail(HWY_EINVAL, "handle is NULL");
-  if (!actions || !obs || !reward || !terminated || !truncated)
-    return fail(HWY_EINVAL, "hwy_step: actions/obs/reward/terminated/truncated must be non-NULL");
+  const hwy_step_io io = {actions, obs, reward, terminated, truncated, ep_return, ep_length};
+  if (int rc = check_step_io("hwy_step", io)) return rc;
   if (int rc = check_pe(h, "hwy_step")) return rc;
-  StepParams p = params_of(h);
-  p.actions = actions;
-  p.obs = obs;
-  p.reward = reward;
-  p.term = terminated;
-  p.trunc = truncated;
-  p.ep_ret = ep_return;
-  p.ep_len = ep_length;
-  if (hwy_launch_step(&p, (hipStream_t)stream)) return hip_fail(hipGetLastError(), "hwy_step_kernel");
-  return HWY_OK;
+  const StepParams p = step_params(h, io);
+  return launched(hwy_launch_step(&p, (hipStream_t)stream), "hwy_step_kernel");
 }
 
 int hwy_step_info_size(void) { return (int)sizeof(hwy_step_info); }
 
-static int check_info(const hwy_step_info* info, const char* who) {
-  if (!info) return fail(HWY_EINVAL, "%s: info is NULL", who);
-  if (info->ep_stats && !info->acc)
+// the info variants' and (where info is given) the final variants' rule on the info pointers
+static int check_ep_stats(const hwy_step_info* info, const char* who) {
+  if (info && info->ep_stats && !info->acc)
     return fail(HWY_EINVAL, "%s: ep_stats needs acc (the episode's running sums)", who);
   return HWY_OK;
+}
+
+static int check_info(const hwy_step_info* info, const char* who) {
+  if (!info) return fail(HWY_EINVAL, "%s: info is NULL", who);
+  return check_ep_stats(info, who);
 }
 
 int hwy_step_with_info(hwy_handle* h, const float* actions, float* obs, float* reward,
                        uint8_t* terminated, uint8_t* truncated, float* ep_return,
                        int32_t* ep_length, const hwy_step_info* info, void* stream) {
   if (!h) return fail(HWY_EINVAL, "handle is NULL");
-  if (!actions || !obs || !reward || !terminated || !truncated)
-    return fail(HWY_EINVAL,
-                "hwy_step_with_info: actions/obs/reward/terminated/truncated must be non-NULL");
+  const hwy_step_io io = {actions, obs, reward, terminated, truncated, ep_return, ep_length};
+  if (int rc = check_step_io("hwy_step_with_info", io)) return rc;
   if (int rc = check_info(info, "hwy_step_with_info")) return rc;
   if (int rc = check_pe(h, "hwy_step_with_info")) return rc;
-  StepParams p = params_of(h);
-  p.actions = actions;
-  p.obs = obs;
-  p.reward = reward;
-  p.term = terminated;
-  p.trunc = truncated;
-  p.ep_ret = ep_return;
-  p.ep_len = ep_length;
-  if (hwy_launch_step_info(&p, info, (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_step_info_kernel");
-  return HWY_OK;
+  const StepParams p = step_params(h, io);
+  return launched(hwy_launch_step_info(&p, info, (hipStream_t)stream), "hwy_step_info_kernel");
 }
 
 int hwy_cut_episodes(hwy_handle* h, float* obs, float* ep_return, int32_t* ep_length,
@@ -313,9 +338,7 @@ int hwy_cut_episodes(hwy_handle* h, float* obs, float* ep_return, int32_t* ep_le
   p.obs = obs;
   p.ep_ret = ep_return;
   p.ep_len = ep_length;
-  if (hwy_launch_cut(&p, cut, (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_cut_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_cut(&p, cut, (hipStream_t)stream), "hwy_cut_kernel");
 }
 
 int64_t hwy_step_group_table_bytes(int n) {
@@ -326,36 +349,21 @@ int hwy_step_group_prepare(hwy_handle* const* handles, const hwy_step_io* io, in
                            hwy_step_group_plan* plan, void* stream) {
   if (!handles || !io || n < 1 || !table || !plan)
     return fail(HWY_EINVAL, "hwy_step_group_prepare: handles/io/table/plan NULL or n < 1");
-  StepParams* tab = new StepParams[n];
+  std::vector<StepParams> tab(n);
   int blocks = 0, dev = -1;
   int64_t total = 0;
   for (int i = 0; i < n; ++i) {
     hwy_handle* h = handles[i];
     const hwy_step_io& a = io[i];
-    if (!h || !a.actions || !a.obs || !a.reward || !a.terminated || !a.truncated) {
-      delete[] tab;
+    if (!h || !step_io_ok(a))
       return fail(HWY_EINVAL, "hwy_step_group_prepare: handle %d or its actions/obs/reward/"
                               "terminated/truncated is NULL", i);
-    }
-    if (dev >= 0 && h->device != dev) {
-      delete[] tab;
+    if (dev >= 0 && h->device != dev)
       return fail(HWY_EINVAL, "hwy_step_group_prepare: handles on devices %d and %d", dev,
                   h->device);
-    }
     dev = h->device;
-    if (int rc = check_pe(h, "hwy_step_group_prepare")) {
-      delete[] tab;
-      return rc;
-    }
-    StepParams p = params_of(h);
-    p.actions = a.actions;
-    p.obs = a.obs;
-    p.reward = a.reward;
-    p.term = a.terminated;
-    p.trunc = a.truncated;
-    p.ep_ret = a.ep_return;
-    p.ep_len = a.ep_length;
-    tab[i] = p;
+    if (int rc = check_pe(h, "hwy_step_group_prepare")) return rc;
+    tab[i] = step_params(h, a);
     const int b = hwy_step_blocks(h->cfg.num_envs);
     blocks = b > blocks ? b : blocks;
     total += h->cfg.num_envs;
@@ -363,9 +371,9 @@ int hwy_step_group_prepare(hwy_handle* const* handles, const hwy_step_io* io, in
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipStreamSynchronize(s);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(table, tab, (size_t)n * sizeof(StepParams), hipMemcpyHostToDevice, s);
+    e = hipMemcpyAsync(table, tab.data(), (size_t)n * sizeof(StepParams), hipMemcpyHostToDevice,
+                       s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  delete[] tab;
   if (e != hipSuccess) return hip_fail(e, "hwy_step_group_prepare");
   plan->n = n;
   plan->blocks = blocks;
@@ -376,10 +384,9 @@ int hwy_step_group_prepare(hwy_handle* const* handles, const hwy_step_io* io, in
 int hwy_step_group(const hwy_step_group_plan* plan, const void* table, void* stream) {
   if (!plan || !table || plan->n < 1 || plan->blocks < 1)
     return fail(HWY_EINVAL, "hwy_step_group: empty plan or NULL table");
-  if (hwy_launch_step_group((const StepParams*)table, plan->n, plan->blocks, plan->big,
-                            (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_step_grp_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_step_group((const StepParams*)table, plan->n, plan->blocks,
+                                        plan->big, (hipStream_t)stream),
+                  "hwy_step_grp_kernel");
 }
 
 int64_t hwy_step_group_info_table_bytes(int n) {
@@ -394,22 +401,18 @@ int hwy_step_group_info_prepare(hwy_handle* const* handles, const hwy_step_io* i
   for (int i = 0; i < n; ++i)
     if (int rc = check_info(info + i, "hwy_step_group_info_prepare")) return rc;
   if (int rc = hwy_step_group_prepare(handles, io, n, table, plan, stream)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t e =
-      hipMemcpyAsync(info_table, info, (size_t)n * sizeof(InfoParams), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return hip_fail(e, "hwy_step_group_info_prepare");
-  return HWY_OK;
+  return upload_table(info_table, info, (size_t)n * sizeof(InfoParams), stream,
+                      "hwy_step_group_info_prepare");
 }
 
 int hwy_step_group_info(const hwy_step_group_plan* plan, const void* table, const void* info_table,
                         void* stream) {
   if (!plan || !table || !info_table || plan->n < 1 || plan->blocks < 1)
     return fail(HWY_EINVAL, "hwy_step_group_info: empty plan or NULL table");
-  if (hwy_launch_step_group_info((const StepParams*)table, (const InfoParams*)info_table, plan->n,
-                                 plan->blocks, plan->big, (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_step_grp_info_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_step_group_info((const StepParams*)table,
+                                             (const InfoParams*)info_table, plan->n,
+                                             plan->blocks, plan->big, (hipStream_t)stream),
+                  "hwy_step_grp_info_kernel");
 }
 
 // hwy_step_with_final / hwy_step_group_final_prepare: every refusal before any device call
@@ -417,9 +420,7 @@ static int check_final(const hwy_step_info* info, const float* final_obs, const 
                        const char* who) {
   if (!final_obs) return fail(HWY_EINVAL, "%s: final_obs is NULL", who);
   if (final_obs == obs) return fail(HWY_EINVAL, "%s: final_obs must not be the obs buffer", who);
-  if (info && info->ep_stats && !info->acc)
-    return fail(HWY_EINVAL, "%s: ep_stats needs acc (the episode's running sums)", who);
-  return HWY_OK;
+  return check_ep_stats(info, who);
 }
 
 int hwy_step_with_final(hwy_handle* h, const float* actions, float* obs, float* reward,
@@ -427,26 +428,16 @@ int hwy_step_with_final(hwy_handle* h, const float* actions, float* obs, float* 
                         int32_t* ep_length, const hwy_step_info* info, float* final_obs,
                         void* stream) {
   if (!h) return fail(HWY_EINVAL, "handle is NULL");
-  if (!actions || !obs || !reward || !terminated || !truncated)
-    return fail(HWY_EINVAL,
-                "hwy_step_with_final: actions/obs/reward/terminated/truncated must be non-NULL");
+  const hwy_step_io io = {actions, obs, reward, terminated, truncated, ep_return, ep_length};
+  if (int rc = check_step_io("hwy_step_with_final", io)) return rc;
   if (int rc = check_final(info, final_obs, obs, "hwy_step_with_final")) return rc;
   if (int rc = check_pe(h, "hwy_step_with_final")) return rc;
-  StepParams p = params_of(h);
-  p.actions = actions;
-  p.obs = obs;
-  p.reward = reward;
-  p.term = terminated;
-  p.trunc = truncated;
-  p.ep_ret = ep_return;
-  p.ep_len = ep_length;
+  const StepParams p = step_params(h, io);
   FinalParams f;
   memset(&f, 0, sizeof(f));
   if (info) f.info = *info;
   f.final_obs = final_obs;
-  if (hwy_launch_step_final(&p, &f, (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_step_final_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_step_final(&p, &f, (hipStream_t)stream), "hwy_step_final_kernel");
 }
 
 int64_t hwy_step_group_final_table_bytes(int n) {
@@ -464,45 +455,37 @@ int hwy_step_group_final_prepare(hwy_handle* const* handles, const hwy_step_io* 
     if (int rc = check_final(info ? info + i : nullptr, final_obs[i], io[i].obs,
                              "hwy_step_group_final_prepare"))
       return rc;
-  FinalParams* ftab = new FinalParams[n];
-  memset(ftab, 0, (size_t)n * sizeof(FinalParams));
+  std::vector<FinalParams> ftab(n);  // value-initialised: zero bytes in the padding too
   for (int i = 0; i < n; ++i) {
     if (info) ftab[i].info = info[i];
     ftab[i].final_obs = final_obs[i];
   }
-  int rc = hwy_step_group_prepare(handles, io, n, table, plan, stream);
-  if (rc == HWY_OK) {
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(final_table, ftab, (size_t)n * sizeof(FinalParams),
-                                  hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) rc = hip_fail(e, "hwy_step_group_final_prepare");
-  }
-  delete[] ftab;
-  return rc;
+  if (int rc = hwy_step_group_prepare(handles, io, n, table, plan, stream)) return rc;
+  return upload_table(final_table, ftab.data(), (size_t)n * sizeof(FinalParams), stream,
+                      "hwy_step_group_final_prepare");
 }
 
 int hwy_step_group_final(const hwy_step_group_plan* plan, const void* table,
                          const void* final_table, void* stream) {
   if (!plan || !table || !final_table || plan->n < 1 || plan->blocks < 1)
     return fail(HWY_EINVAL, "hwy_step_group_final: empty plan or NULL table");
-  if (hwy_launch_step_group_final((const StepParams*)table, (const FinalParams*)final_table,
-                                  plan->n, plan->blocks, plan->big, (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_step_grp_final_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_step_group_final((const StepParams*)table,
+                                              (const FinalParams*)final_table, plan->n,
+                                              plan->blocks, plan->big, (hipStream_t)stream),
+                  "hwy_step_grp_final_kernel");
 }
 
 int hwy_export_state(hwy_handle* h, uint32_t* dst, void* stream) {
   if (!h || !dst) return fail(HWY_EINVAL, "handle/dst is NULL");
-  size_t bytes = (size_t)HWY_NFIELDS * h->cfg.num_envs * HWY_MAX_VEHICLES * sizeof(uint32_t);
-  hipError_t e = hipMemcpyAsync(dst, h->state, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  hipError_t e =
+      hipMemcpyAsync(dst, h->state, state_bytes(h), hipMemcpyDeviceToDevice, (hipStream_t)stream);
   return e == hipSuccess ? HWY_OK : hip_fail(e, "hwy_export_state");
 }
 
 int hwy_import_state(hwy_handle* h, const uint32_t* src, void* stream) {
   if (!h || !src) return fail(HWY_EINVAL, "handle/src is NULL");
-  size_t bytes = (size_t)HWY_NFIELDS * h->cfg.num_envs * HWY_MAX_VEHICLES * sizeof(uint32_t);
-  hipError_t e = hipMemcpyAsync(h->state, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  hipError_t e =
+      hipMemcpyAsync(h->state, src, state_bytes(h), hipMemcpyDeviceToDevice, (hipStream_t)stream);
   return e == hipSuccess ? HWY_OK : hip_fail(e, "hwy_import_state");
 }
 
@@ -519,7 +502,7 @@ static int64_t render_bytes(const hwy_render_args* a) {
   if (a->n < 1 || a->n > (1 << 22))
     return fail(HWY_EINVAL, "hwy_render: n must be in [1, 2^22], got %d", a->n);
   const float inf = __builtin_inff();
-  if (!(a->scaling > 0.0f && a->scaling < inf))
+  if (!finite_pos(a->scaling))
     return fail(HWY_EINVAL, "hwy_render: scaling must be finite and > 0");
   for (int i = 0; i < 2; ++i)
     if (!(a->centering[i] > -inf && a->centering[i] < inf))
@@ -542,18 +525,22 @@ int hwy_render(hwy_handle* h, const hwy_render_args* a, void* stream) {
   p.state = h->state;
   p.num_envs = h->cfg.num_envs;
   p.lanes_count = h->cfg.lanes_count;
-  if (hwy_launch_render(&p, (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_render_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_render(&p, (hipStream_t)stream), "hwy_render_kernel");
 }
 
 int hwy_observe_args_size(void) { return (int)sizeof(hwy_observe_args); }
 
+// hwy_observe_args' and hwy_sense_args' row order
+static int check_order(const char* who, int order) {
+  if (order != -1 && order != HWY_ORDER_SORTED && order != HWY_ORDER_SHUFFLED)
+    return fail(HWY_EINVAL, "%s: order must be -1 (the handle's), sorted or shuffled, got %d", who,
+                order);
+  return HWY_OK;
+}
+
 int hwy_observe_check(const hwy_observe_args* a) {
   if (!a) return fail(HWY_EINVAL, "hwy_observe: args is NULL");
-  if (a->order != -1 && a->order != HWY_ORDER_SORTED && a->order != HWY_ORDER_SHUFFLED)
-    return fail(HWY_EINVAL, "hwy_observe: order must be -1 (the handle's), sorted or shuffled, "
-                            "got %d", a->order);
+  if (int rc = check_order("hwy_observe", a->order)) return rc;
   if (!a->obs && !a->row_vehicle && !a->veh_values)
     return fail(HWY_EINVAL, "hwy_observe: obs, row_vehicle and veh_values are all NULL");
   if ((a->row_values != nullptr) != (a->veh_values != nullptr))
@@ -573,9 +560,7 @@ int hwy_observe(hwy_handle* h, const hwy_observe_args* a, void* stream) {
   p.row_vehicle = a->row_vehicle;
   p.row_values = a->row_values;
   p.veh_values = a->veh_values;
-  if (hwy_launch_observe(&p, (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_observe_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_observe(&p, (hipStream_t)stream), "hwy_observe_kernel");
 }
 
 int hwy_traffic_args_size(void) { return (int)sizeof(hwy_traffic_args); }
@@ -590,11 +575,10 @@ int hwy_traffic_check(const hwy_traffic_args* a) {
   for (int k = 0; k < 3; ++k)
     if (a->restart[k] && !a->acc)
       return fail(HWY_EINVAL, "hwy_traffic: restart[%d] needs acc", k);
-  const float inf = __builtin_inff();
   const float vals[4] = {a->ttc_thresh, a->thw_thresh, a->risk_horizon, a->near_range};
   const char* names[4] = {"ttc_thresh", "thw_thresh", "risk_horizon", "near_range"};
   for (int i = 0; i < 4; ++i)
-    if (!(vals[i] > 0.0f && vals[i] < inf))
+    if (!finite_pos(vals[i]))
       return fail(HWY_EINVAL, "hwy_traffic: %s must be finite and > 0, got %g", names[i],
                   (double)vals[i]);
   return HWY_OK;
@@ -607,18 +591,14 @@ int hwy_traffic(hwy_handle* h, const hwy_traffic_args* a, void* stream) {
   p.a = *a;
   p.state = h->state;
   p.cfg = h->cfg;
-  if (hwy_launch_traffic(&p, (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_traffic_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_traffic(&p, (hipStream_t)stream), "hwy_traffic_kernel");
 }
 
 int hwy_sense_args_size(void) { return (int)sizeof(hwy_sense_args); }
 
 int hwy_sense_check(const hwy_sense_args* a) {
   if (!a) return fail(HWY_EINVAL, "hwy_sense: args is NULL");
-  if (a->order != -1 && a->order != HWY_ORDER_SORTED && a->order != HWY_ORDER_SHUFFLED)
-    return fail(HWY_EINVAL, "hwy_sense: order must be -1 (the handle's), sorted or shuffled, "
-                            "got %d", a->order);
+  if (int rc = check_order("hwy_sense", a->order)) return rc;
   const float inf = __builtin_inff();
   if (!(a->range_m > 0.0f))  // +inf passes, a NaN does not
     return fail(HWY_EINVAL, "hwy_sense: range_m must be > 0 (+inf: no range limit), got %g",
@@ -652,9 +632,7 @@ int hwy_sense(hwy_handle* h, const hwy_sense_args* a, void* stream) {
   // 4 m over the 2.7 m half diagonal, and 1e-4 of the range over what binary32 rounds of it
   const float far = (a->range_m + 4.0f) * 1.0001f;
   p.cull2 = far * far;
-  if (hwy_launch_sense(&p, (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_sense_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_sense(&p, (hipStream_t)stream), "hwy_sense_kernel");
 }
 
 int hwy_obs_pe(const float* obs_in, float* obs_out, int E, int N, int F, int kind, int d,
@@ -672,10 +650,9 @@ int hwy_obs_pe(const float* obs_in, float* obs_out, int E, int N, int F, int kin
   if (ego_idx < 0 || ego_idx >= N) return fail(HWY_EINVAL, "ego_idx %d out of range", ego_idx);
   if (kind != HWY_PE_NONE && !table && !(kind == HWY_PE_ROPE && d == 0))
     return fail(HWY_EINVAL, "pe table is NULL");
-  if (hwy_launch_obs_pe(obs_in, obs_out, E, N, F, kind, d, ego_idx, max_dist, table, dist_override,
-                        (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_obs_pe_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_obs_pe(obs_in, obs_out, E, N, F, kind, d, ego_idx, max_dist, table,
+                                    dist_override, (hipStream_t)stream),
+                  "hwy_obs_pe_kernel");
 }
 
 int hwy_gae(const float* rewards, const uint8_t* dones, const float* values,
@@ -683,10 +660,9 @@ int hwy_gae(const float* rewards, const uint8_t* dones, const float* values,
             float* returns, void* stream) {
   if (T < 0 || E < 0) return fail(HWY_EINVAL, "hwy_gae: bad shape T=%d E=%d", T, E);
   if (T == 0 || E == 0) return HWY_OK;
-  if (hwy_launch_gae(rewards, dones, values, last_values, gamma, lam, T, E, advantages, returns,
-                     (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_gae_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_gae(rewards, dones, values, last_values, gamma, lam, T, E,
+                                 advantages, returns, (hipStream_t)stream),
+                  "hwy_gae_kernel");
 }
 
 int hwy_gae_boot(const float* rewards, const uint8_t* terminated, const uint8_t* truncated,
@@ -695,17 +671,15 @@ int hwy_gae_boot(const float* rewards, const uint8_t* terminated, const uint8_t*
                  void* stream) {
   if (T < 0 || E < 0) return fail(HWY_EINVAL, "hwy_gae_boot: bad shape T=%d E=%d", T, E);
   if (T == 0 || E == 0) return HWY_OK;
-  if (hwy_launch_gae_boot(rewards, terminated, truncated, values, last_values, boot_values, gamma,
-                          lam, T, E, advantages, returns, (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_gae_boot_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_gae_boot(rewards, terminated, truncated, values, last_values,
+                                      boot_values, gamma, lam, T, E, advantages, returns,
+                                      (hipStream_t)stream),
+                  "hwy_gae_boot_kernel");
 }
 
 int hwy_math_selftest(int op, const float* in, const float* in2, float* out, int n, void* stream) {
   if (op < 0 || op > 16 || n < 0) return fail(HWY_EINVAL, "bad selftest op %d", op);
-  if (hwy_launch_math(op, in, in2, out, n, (hipStream_t)stream))
-    return hip_fail(hipGetLastError(), "hwy_math_kernel");
-  return HWY_OK;
+  return launched(hwy_launch_math(op, in, in2, out, n, (hipStream_t)stream), "hwy_math_kernel");
 }
 
 }  // extern "C"

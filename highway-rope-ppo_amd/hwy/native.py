@@ -46,6 +46,58 @@ def build(jobs: int = 4) -> str:
     return LIB_PATH
 
 
+def _signatures() -> dict:
+    """include/hwy.h as ctypes: name -> argtypes, or (argtypes, restype) where the function does
+    not return an int."""
+    vp, i32, i64, f32, f64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float,
+                              ctypes.c_double)
+    P = ctypes.POINTER
+    plan, info = P(HwyStepGroupPlan), P(HwyStepInfo)
+    return {
+        "hwy_abi_version": [],
+        "hwy_last_error": ([], ctypes.c_char_p),
+        "hwy_create": [P(HwyConfig), i32, P(vp)],
+        "hwy_destroy": ([vp], None),
+        "hwy_obs_features": [vp],
+        "hwy_set_pe_table": [vp, vp, i32],
+        "hwy_set_seed_schedule": [vp, i64, ctypes.c_int32, i64],
+        "hwy_set_seed_groups": [vp, vp, i32, i32],
+        "hwy_reset": [vp] * 5,
+        "hwy_step": [vp] * 9,
+        "hwy_cut_episodes": [vp] * 6,
+        "hwy_step_group_table_bytes": ([i32], i64),
+        "hwy_step_group_prepare": [vp, vp, i32, vp, plan, vp],
+        "hwy_step_group": [plan, vp, vp],
+        "hwy_step_info_size": [],
+        "hwy_step_with_info": [vp] * 8 + [info, vp],
+        "hwy_step_group_info_table_bytes": ([i32], i64),
+        "hwy_step_group_info_prepare": [vp, vp, vp, i32, vp, vp, plan, vp],
+        "hwy_step_group_info": [plan, vp, vp, vp],
+        "hwy_step_with_final": [vp] * 8 + [info, vp, vp],
+        "hwy_step_group_final_table_bytes": ([i32], i64),
+        "hwy_step_group_final_prepare": [vp, vp, vp, vp, i32, vp, vp, plan, vp],
+        "hwy_step_group_final": [plan, vp, vp, vp],
+        "hwy_gae": [vp, vp, vp, vp, f64, f64, i32, i32, vp, vp, vp],
+        "hwy_gae_boot": [vp] * 6 + [f64, f64, i32, i32, vp, vp, vp],
+        "hwy_render_args_size": [],
+        "hwy_render_frame_bytes": ([P(RenderArgs)], i64),
+        "hwy_render": [vp, P(RenderArgs), vp],
+        "hwy_observe_args_size": [],
+        "hwy_observe_check": [P(ObserveArgs)],
+        "hwy_observe": [vp, P(ObserveArgs), vp],
+        "hwy_traffic_args_size": [],
+        "hwy_traffic_check": [P(TrafficArgs)],
+        "hwy_traffic": [vp, P(TrafficArgs), vp],
+        "hwy_sense_args_size": [],
+        "hwy_sense_check": [P(SenseArgs)],
+        "hwy_sense": [vp, P(SenseArgs), vp],
+        "hwy_export_state": [vp, vp, vp],
+        "hwy_import_state": [vp, vp, vp],
+        "hwy_obs_pe": [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp],
+        "hwy_math_selftest": [i32, vp, vp, vp, i32, vp],
+    }
+
+
 def lib():
     """The loaded libhwy.so (raises HwyNativeError when it is missing)."""
     global _lib
@@ -62,77 +114,16 @@ def lib():
         L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as e:  # pragma: no cover - depends on the box
         raise HwyNativeError(f"cannot load {LIB_PATH}: {e}") from e
-    vp, i32, f32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double
-    cfgp = ctypes.POINTER(HwyConfig)
-    L.hwy_abi_version.restype = i32
-    L.hwy_last_error.restype = ctypes.c_char_p
-    L.hwy_create.argtypes = [cfgp, i32, ctypes.POINTER(vp)]
-    L.hwy_destroy.argtypes = [vp]
-    L.hwy_destroy.restype = None
-    L.hwy_obs_features.argtypes = [vp]
-    L.hwy_set_pe_table.argtypes = [vp, vp, i32]
-    L.hwy_set_seed_schedule.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64]
-    L.hwy_reset.argtypes = [vp, vp, vp, vp, vp]
-    L.hwy_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.hwy_cut_episodes.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.hwy_step_info_size.restype = i32
-    L.hwy_step_with_info.argtypes = [vp] * 8 + [ctypes.POINTER(HwyStepInfo), vp]
-    L.hwy_step_group_info_table_bytes.argtypes = [i32]
-    L.hwy_step_group_info_table_bytes.restype = ctypes.c_int64
-    L.hwy_step_group_info_prepare.argtypes = [vp, vp, vp, i32, vp, vp,
-                                              ctypes.POINTER(HwyStepGroupPlan), vp]
-    L.hwy_step_group_info.argtypes = [ctypes.POINTER(HwyStepGroupPlan), vp, vp, vp]
-    L.hwy_step_with_final.argtypes = [vp] * 8 + [ctypes.POINTER(HwyStepInfo), vp, vp]
-    L.hwy_step_group_final_table_bytes.argtypes = [i32]
-    L.hwy_step_group_final_table_bytes.restype = ctypes.c_int64
-    L.hwy_step_group_final_prepare.argtypes = [vp, vp, vp, vp, i32, vp, vp,
-                                               ctypes.POINTER(HwyStepGroupPlan), vp]
-    L.hwy_step_group_final.argtypes = [ctypes.POINTER(HwyStepGroupPlan), vp, vp, vp]
-    L.hwy_gae_boot.argtypes = [vp, vp, vp, vp, vp, vp, f64, f64, i32, i32, vp, vp, vp]
-    L.hwy_render_args_size.restype = i32
-    L.hwy_render_frame_bytes.argtypes = [ctypes.POINTER(RenderArgs)]
-    L.hwy_render_frame_bytes.restype = ctypes.c_int64
-    L.hwy_render.argtypes = [vp, ctypes.POINTER(RenderArgs), vp]
-    L.hwy_observe_args_size.restype = i32
-    L.hwy_observe_check.argtypes = [ctypes.POINTER(ObserveArgs)]
-    L.hwy_observe.argtypes = [vp, ctypes.POINTER(ObserveArgs), vp]
-    L.hwy_traffic_args_size.restype = i32
-    L.hwy_traffic_check.argtypes = [ctypes.POINTER(TrafficArgs)]
-    L.hwy_traffic.argtypes = [vp, ctypes.POINTER(TrafficArgs), vp]
-    L.hwy_sense_args_size.restype = i32
-    L.hwy_sense_check.argtypes = [ctypes.POINTER(SenseArgs)]
-    L.hwy_sense.argtypes = [vp, ctypes.POINTER(SenseArgs), vp]
-    L.hwy_export_state.argtypes = [vp, vp, vp]
-    L.hwy_import_state.argtypes = [vp, vp, vp]
-    L.hwy_obs_pe.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp]
-    L.hwy_gae.argtypes = [vp, vp, vp, vp, f64, f64, i32, i32, vp, vp, vp]
-    L.hwy_math_selftest.argtypes = [i32, vp, vp, vp, i32, vp]
-    L.hwy_set_seed_groups.argtypes = [vp, vp, i32, i32]
-    L.hwy_step_group_table_bytes.argtypes = [i32]
-    L.hwy_step_group_table_bytes.restype = ctypes.c_int64
-    L.hwy_step_group_prepare.argtypes = [vp, vp, i32, vp, ctypes.POINTER(HwyStepGroupPlan), vp]
-    L.hwy_step_group.argtypes = [ctypes.POINTER(HwyStepGroupPlan), vp, vp]
-    for name in ("hwy_create", "hwy_obs_features", "hwy_set_pe_table", "hwy_set_seed_schedule",
-                 "hwy_set_seed_groups", "hwy_reset", "hwy_step", "hwy_cut_episodes",
-                 "hwy_step_group_prepare",
-                 "hwy_step_group", "hwy_step_with_info", "hwy_step_group_info_prepare",
-                 "hwy_step_group_info", "hwy_step_with_final", "hwy_step_group_final_prepare",
-                 "hwy_step_group_final", "hwy_gae_boot", "hwy_render",
-                 "hwy_observe_check", "hwy_observe", "hwy_traffic_check", "hwy_traffic",
-                 "hwy_sense_check", "hwy_sense",
-                 "hwy_export_state", "hwy_import_state", "hwy_obs_pe", "hwy_gae",
-                 "hwy_math_selftest"):
-        getattr(L, name).restype = i32
-    if L.hwy_step_info_size() != ctypes.sizeof(HwyStepInfo):
-        raise HwyNativeError("libhwy.so's hwy_step_info differs from the python mirror; rebuild")
-    if L.hwy_render_args_size() != ctypes.sizeof(RenderArgs):
-        raise HwyNativeError("libhwy.so's hwy_render_args differs from the python mirror; rebuild")
-    if L.hwy_observe_args_size() != ctypes.sizeof(ObserveArgs):
-        raise HwyNativeError("libhwy.so's hwy_observe_args differs from the python mirror; rebuild")
-    if L.hwy_traffic_args_size() != ctypes.sizeof(TrafficArgs):
-        raise HwyNativeError("libhwy.so's hwy_traffic_args differs from the python mirror; rebuild")
-    if L.hwy_sense_args_size() != ctypes.sizeof(SenseArgs):
-        raise HwyNativeError("libhwy.so's hwy_sense_args differs from the python mirror; rebuild")
+    for name, sig in _signatures().items():
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, ctypes.c_int)
+    for size, mirror, cname in (("hwy_step_info_size", HwyStepInfo, "hwy_step_info"),
+                                ("hwy_render_args_size", RenderArgs, "hwy_render_args"),
+                                ("hwy_observe_args_size", ObserveArgs, "hwy_observe_args"),
+                                ("hwy_traffic_args_size", TrafficArgs, "hwy_traffic_args"),
+                                ("hwy_sense_args_size", SenseArgs, "hwy_sense_args")):
+        if getattr(L, size)() != ctypes.sizeof(mirror):
+            raise HwyNativeError(f"libhwy.so's {cname} differs from the python mirror; rebuild")
     if L.hwy_abi_version() != HWY_ABI_VERSION:
         raise HwyNativeError(
             f"libhwy.so ABI {L.hwy_abi_version()} != python ABI {HWY_ABI_VERSION}; rebuild"

@@ -34,7 +34,7 @@ from __future__ import annotations
 
 import ctypes
 import copy
-from typing import Any, Dict, Optional
+from typing import Any, Callable, Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -76,6 +76,18 @@ def _check_final_obs(env, t: torch.Tensor) -> None:
                          f"(E x N x F_out), got {tuple(t.shape)} {t.dtype} on {t.device}")
 
 
+def _dev_tensor(name: str, t, dtype, n: int, what: str, device) -> int:
+    """The device pointer of ``t``, a contiguous ``dtype`` tensor of ``n`` elements (``what``: their
+    layout, for the message) on ``device``; anything else is a ValueError."""
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
+            and t.numel() == n and t.device == torch.device(device)):
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements "
+                         f"({what}) on {device}, got "
+                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} "
+                         f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
+    return t.data_ptr()
+
+
 def observe_args(num_envs: int, rows: int, fout: int, device, order=None, *, obs=None,
                  row_vehicle=None, row_values=None, veh_values=None) -> _abi.ObserveArgs:
     """hwy_observe_args for an env of ``num_envs`` x ``rows`` x ``fout`` on ``device`` from
@@ -88,15 +100,8 @@ def observe_args(num_envs: int, rows: int, fout: int, device, order=None, *, obs
             ("row_values", row_values, torch.float32, E * N, "E x N"),
             ("veh_values", veh_values, torch.float32, E * HWY_MAX_VEHICLES, "E x 64"))
     for name, t, dtype, n, what in spec:
-        if t is None:
-            continue
-        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
-                and t.numel() == n and t.device == torch.device(device)):
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements "
-                             f"({what}) on {device}, got "
-                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} "
-                             f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
-        setattr(a, name, t.data_ptr())
+        if t is not None:
+            setattr(a, name, _dev_tensor(name, t, dtype, n, what, device))
     if obs is None and row_vehicle is None and veh_values is None:
         raise ValueError("observe_into needs at least one of obs, row_vehicle and veh_values")
     if (row_values is None) != (veh_values is None):
@@ -130,15 +135,6 @@ def traffic_args(num_envs: int, device, *, restart=(), ttc_thresh=None, thw_thre
     a = _abi.TrafficArgs()
     E = int(num_envs)
 
-    def dev_tensor(name, t, dtype, n, what):
-        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
-                and t.numel() == n and t.device == torch.device(device)):
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements "
-                             f"({what}) on {device}, got "
-                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} "
-                             f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
-        return t.data_ptr()
-
     for name in TRAFFIC_OUTPUTS:
         t = outputs.get(name)
         if t is None:
@@ -149,7 +145,7 @@ def traffic_args(num_envs: int, device, *, restart=(), ttc_thresh=None, thw_thre
         else:
             width = _abi.HWY_TRAFFIC_NEGO if name == "ego" else _abi.HWY_TRAFFIC_NACC
             dtype, n, what = torch.float32, E * width, f"E x {width}"
-        setattr(a, name, dev_tensor(name, t, dtype, n, what))
+        setattr(a, name, _dev_tensor(name, t, dtype, n, what, device))
     if all(outputs.get(n) is None for n in TRAFFIC_OUTPUTS if n != "ep_stats"):
         raise ValueError("traffic_into needs at least one output besides ep_stats")
     masks = [m for m in (restart or ()) if m is not None]
@@ -161,7 +157,7 @@ def traffic_args(num_envs: int, device, *, restart=(), ttc_thresh=None, thw_thre
     if masks and not has_acc:
         raise ValueError("restart masks need acc")
     for k, m in enumerate(masks):
-        a.restart[k] = dev_tensor(f"restart[{k}]", m, torch.uint8, E, "E")
+        a.restart[k] = _dev_tensor(f"restart[{k}]", m, torch.uint8, E, "E", device)
     given = {"ttc_thresh": ttc_thresh, "thw_thresh": thw_thresh, "risk_horizon": risk_horizon,
              "near_range": near_range}
     for name, default in _abi.TRAFFIC_DEFAULTS.items():
@@ -186,15 +182,8 @@ def sense_args(num_envs: int, rows: int, fout: int, device, sensor, order=None, 
             ("hidden", hidden, torch.float32, E * HWY_MAX_VEHICLES, "E x 64"),
             ("counts", counts, torch.int32, E * 4, "E x 4"))
     for name, t, dtype, n, what in spec:
-        if t is None:
-            continue
-        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
-                and t.numel() == n and t.device == torch.device(device)):
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements "
-                             f"({what}) on {device}, got "
-                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} "
-                             f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
-        setattr(a, name, t.data_ptr())
+        if t is not None:
+            setattr(a, name, _dev_tensor(name, t, dtype, n, what, device))
     if all(t is None for _, t, _, _, _ in spec):
         raise ValueError("sense_into needs at least one of obs, row_vehicle, visible, hidden and "
                          "counts")
@@ -351,41 +340,24 @@ class HighwayVecEnv:
             a = torch.as_tensor(a, device=self.device, dtype=torch.float32).contiguous()
         if a.numel() != 2 * self.num_envs:
             raise ValueError(f"actions must have {self.num_envs}x2 elements, got {tuple(a.shape)}")
-        if self.final_obs_buf is not None:
-            return self._step_final(a)
-        if self.info_buf is not None:
-            return self._step_info(a)
-        check(lib().hwy_step(self._handle, ptr(a), ptr(self.obs_buf), ptr(self.reward_buf),
-                             ptr(self.term_buf), ptr(self.trunc_buf), ptr(self.ep_ret_buf),
-                             ptr(self.ep_len_buf), stream_ptr()), "hwy_step")
+        self.step_into(a, self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf,
+                       self.ep_ret_buf, self.ep_len_buf, info=self.info_buf,
+                       final_obs=self.final_obs_buf)
         self._keep = a
+        return self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf, self._info_dict()
+
+    def _info_dict(self) -> Dict[str, Any]:
+        """step()'s info from whichever of the env's own buffers exist."""
         info = {"episode_return": self.ep_ret_buf, "episode_length": self.ep_len_buf}
-        return self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf, info
-
-    def _step_info(self, a: torch.Tensor):
+        if self.final_obs_buf is not None:
+            info["final_observation"] = self.final_obs_buf
+            info["_final_observation"] = (self.term_buf | self.trunc_buf).bool()
         b = self.info_buf
-        self.step_into(a, self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf,
-                       self.ep_ret_buf, self.ep_len_buf, info=b)
-        self._keep = a
-        info = {"episode_return": self.ep_ret_buf, "episode_length": self.ep_len_buf,
-                "speed": b["speed"], "crashed": b["crashed"], "lane": b["lane"],
-                "rewards": {k: b["rewards"][:, i] for i, k in enumerate(REWARD_KEYS)},
-                "episode_stats": b["ep_stats"]}
-        return self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf, info
-
-    def _step_final(self, a: torch.Tensor):
-        b = self.info_buf
-        self.step_into(a, self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf,
-                       self.ep_ret_buf, self.ep_len_buf, info=b, final_obs=self.final_obs_buf)
-        self._keep = a
-        info = {"episode_return": self.ep_ret_buf, "episode_length": self.ep_len_buf,
-                "final_observation": self.final_obs_buf,
-                "_final_observation": (self.term_buf | self.trunc_buf).bool()}
         if b is not None:
             info.update({"speed": b["speed"], "crashed": b["crashed"], "lane": b["lane"],
                          "rewards": {k: b["rewards"][:, i] for i, k in enumerate(REWARD_KEYS)},
                          "episode_stats": b["ep_stats"]})
-        return self.obs_buf, self.reward_buf, self.term_buf, self.trunc_buf, info
+        return info
 
     def step_into(self, actions: torch.Tensor, obs: torch.Tensor, reward: torch.Tensor,
                   terminated: torch.Tensor, truncated: torch.Tensor,
@@ -401,24 +373,16 @@ class HighwayVecEnv:
         the other envs are not written); combines with ``info``."""
         if final_obs is not None:
             _check_final_obs(self, final_obs)
-            si = None if info is None else HwyStepInfo(*_info_ptrs(info))
-            check(lib().hwy_step_with_final(self._handle, ptr(actions), ptr(obs), ptr(reward),
-                                            ptr(terminated), ptr(truncated), ptr(ep_return),
-                                            ptr(ep_length),
-                                            None if si is None else ctypes.byref(si),
-                                            ptr(final_obs), stream_ptr()),
-                  "hwy_step_with_final")
-            return
-        if info is not None:
-            si = HwyStepInfo(*_info_ptrs(info))
-            check(lib().hwy_step_with_info(self._handle, ptr(actions), ptr(obs), ptr(reward),
-                                           ptr(terminated), ptr(truncated), ptr(ep_return),
-                                           ptr(ep_length), ctypes.byref(si), stream_ptr()),
-                  "hwy_step_with_info")
-            return
-        check(lib().hwy_step(self._handle, ptr(actions), ptr(obs), ptr(reward), ptr(terminated),
-                             ptr(truncated), ptr(ep_return), ptr(ep_length), stream_ptr()),
-              "hwy_step")
+        si = None if info is None else ctypes.byref(HwyStepInfo(*_info_ptrs(info)))
+        if final_obs is not None:
+            name, more = "hwy_step_with_final", (si, ptr(final_obs))
+        elif info is not None:
+            name, more = "hwy_step_with_info", (si,)
+        else:
+            name, more = "hwy_step", ()
+        check(getattr(lib(), name)(self._handle, ptr(actions), ptr(obs), ptr(reward),
+                                   ptr(terminated), ptr(truncated), ptr(ep_return),
+                                   ptr(ep_length), *more, stream_ptr()), name)
 
     def cut_episodes(self, obs: torch.Tensor, ep_return: Optional[torch.Tensor] = None,
                      ep_length: Optional[torch.Tensor] = None,
@@ -678,13 +642,41 @@ class HighwayVecEnv:
         return self
 
 
+def _info_array(iptrs, n: int):
+    """hwy_step_info[n] from _info_ptrs' tuples (None: the caller wants no info)."""
+    return None if iptrs is None else (HwyStepInfo * n)(*[HwyStepInfo(*p) for p in iptrs])
+
+
+class _GroupVariant(NamedTuple):
+    """One variant of the grouped step: its entry points, the size function of its second device
+    table (None: it has none) and its prepare's arrays between ``io`` and ``n``."""
+    prepare: str
+    launch: str
+    table_bytes: Optional[str]
+    arrays: Callable
+
+
+_GROUP_VARIANTS = {
+    "plain": _GroupVariant("hwy_step_group_prepare", "hwy_step_group", None,
+                           lambda iptrs, fptrs, n: ()),
+    "info": _GroupVariant("hwy_step_group_info_prepare", "hwy_step_group_info",
+                          "hwy_step_group_info_table_bytes",
+                          lambda iptrs, fptrs, n: (_info_array(iptrs, n),)),
+    "final": _GroupVariant("hwy_step_group_final_prepare", "hwy_step_group_final",
+                           "hwy_step_group_final_table_bytes",
+                           lambda iptrs, fptrs, n: (_info_array(iptrs, n),
+                                                    (ctypes.c_void_p * n)(*fptrs))),
+}
+
+
 class GroupEnvStep:
     """HighwayVecEnv.step_into for several handles in ONE launch (hwy_step_group): the cells of a
     sweep batch (ppo/group.py GroupBatch), whose handles differ in observation width and fused
     wrapper.  Each env computes exactly what its own handle's step computes.  The launch
-    parameters live in a device table per (handle configurations, buffers) key, prepared on first
-    use -- outside any graph capture, as GroupBatch's eager first rollout at a key does -- so the
-    launch itself is graph-capturable."""
+    parameters live in device tables per (variant, handle configurations, buffers) key, prepared on
+    first use -- outside any graph capture, as GroupBatch's eager first rollout at a key does --
+    so the launch itself is graph-capturable.  The variants (plain, info, final) differ only in
+    their _GROUP_VARIANTS record."""
 
     def __init__(self, envs):
         self.envs = [e.unwrapped if hasattr(e, "unwrapped") else e for e in envs]
@@ -694,59 +686,6 @@ class GroupEnvStep:
         self._nb = int(lib().hwy_step_group_table_bytes(self.n))
         self._tables: Dict[Any, Any] = {}
 
-    def _launch_info(self, ptrs, infos) -> None:
-        """launch() through hwy_step_group_info: a second device table holds the info pointers."""
-        iptrs = tuple(_info_ptrs(i) for i in infos)
-        key = (tuple((e._handle.value, e.launch_version) for e in self.envs), ptrs, iptrs)
-        hit = self._tables.get(key)
-        if hit is None:
-            arr = (HwyStepIO * self.n)(*[HwyStepIO(*p) for p in ptrs])
-            iarr = (HwyStepInfo * self.n)(*[HwyStepInfo(*p) for p in iptrs])
-            hs = (ctypes.c_void_p * self.n)(*[e._handle.value for e in self.envs])
-            dev = self.envs[0].device
-            t = torch.empty(self._nb, dtype=torch.uint8, device=dev)
-            it = torch.empty(int(lib().hwy_step_group_info_table_bytes(self.n)), dtype=torch.uint8,
-                             device=dev)
-            plan = HwyStepGroupPlan()
-            check(lib().hwy_step_group_info_prepare(hs, arr, iarr, self.n, t.data_ptr(),
-                                                    it.data_ptr(), ctypes.byref(plan),
-                                                    stream_ptr()), "hwy_step_group_info_prepare")
-            hit = (t, plan, it)
-            self._tables[key] = hit
-        check(lib().hwy_step_group_info(ctypes.byref(hit[1]), hit[0].data_ptr(),
-                                        hit[2].data_ptr(), stream_ptr()), "hwy_step_group_info")
-
-    def _launch_final(self, ptrs, infos, final_obs) -> None:
-        """launch() through hwy_step_group_final: a second device table holds the (optional) info
-        pointers and the terminal-observation buffers."""
-        if len(final_obs) != self.n or (infos is not None and len(infos) != self.n):
-            raise ValueError("one final_obs buffer (and one step info dict) per handle")
-        for e, f in zip(self.envs, final_obs):
-            _check_final_obs(e, f)
-        iptrs = None if infos is None else tuple(_info_ptrs(i) for i in infos)
-        fptrs = tuple(ptr(f) for f in final_obs)
-        key = (tuple((e._handle.value, e.launch_version) for e in self.envs), ptrs, iptrs, fptrs,
-               "final")
-        hit = self._tables.get(key)
-        if hit is None:
-            arr = (HwyStepIO * self.n)(*[HwyStepIO(*p) for p in ptrs])
-            iarr = (None if iptrs is None
-                    else (HwyStepInfo * self.n)(*[HwyStepInfo(*p) for p in iptrs]))
-            farr = (ctypes.c_void_p * self.n)(*fptrs)
-            hs = (ctypes.c_void_p * self.n)(*[e._handle.value for e in self.envs])
-            dev = self.envs[0].device
-            t = torch.empty(self._nb, dtype=torch.uint8, device=dev)
-            ft = torch.empty(int(lib().hwy_step_group_final_table_bytes(self.n)),
-                             dtype=torch.uint8, device=dev)
-            plan = HwyStepGroupPlan()
-            check(lib().hwy_step_group_final_prepare(hs, arr, iarr, farr, self.n, t.data_ptr(),
-                                                     ft.data_ptr(), ctypes.byref(plan),
-                                                     stream_ptr()), "hwy_step_group_final_prepare")
-            hit = (t, plan, ft)
-            self._tables[key] = hit
-        check(lib().hwy_step_group_final(ctypes.byref(hit[1]), hit[0].data_ptr(),
-                                         hit[2].data_ptr(), stream_ptr()), "hwy_step_group_final")
-
     def launch(self, ios, infos=None, final_obs=None) -> None:
         """ios[i] = (actions, obs, reward, terminated, truncated, ep_return, ep_length) of env i,
         as step_into takes them (the last two may be None).  ``infos[i]``: env i's step info
@@ -755,25 +694,38 @@ class GroupEnvStep:
         step_into's ``final_obs`` (the launch is then the final variant, hwy_step_group_final,
         with the info outputs too when ``infos`` is given)."""
         ptrs = tuple(tuple(ptr(x) for x in io) for io in ios)
+        iptrs = fptrs = None
         if final_obs is not None:
-            return self._launch_final(ptrs, infos, final_obs)
+            if len(final_obs) != self.n or (infos is not None and len(infos) != self.n):
+                raise ValueError("one final_obs buffer (and one step info dict) per handle")
+            for e, f in zip(self.envs, final_obs):
+                _check_final_obs(e, f)
+            fptrs = tuple(ptr(f) for f in final_obs)
+        elif infos is not None and len(infos) != self.n:
+            raise ValueError("one step info dict per handle")
         if infos is not None:
-            if len(infos) != self.n:
-                raise ValueError("one step info dict per handle")
-            return self._launch_info(ptrs, infos)
-        key = (tuple((e._handle.value, e.launch_version) for e in self.envs), ptrs)
+            iptrs = tuple(_info_ptrs(i) for i in infos)
+        name = "final" if fptrs is not None else "plain" if iptrs is None else "info"
+        v = _GROUP_VARIANTS[name]
+        key = (name, tuple((e._handle.value, e.launch_version) for e in self.envs), ptrs, iptrs,
+               fptrs)
         hit = self._tables.get(key)
         if hit is None:
-            arr = (HwyStepIO * self.n)()
-            for i, p in enumerate(ptrs):
-                arr[i] = HwyStepIO(*p)
-            hs = (ctypes.c_void_p * self.n)(*[e._handle.value for e in self.envs])
-            dev = self.envs[0].device
-            t = torch.empty(self._nb, dtype=torch.uint8, device=dev)
-            plan = HwyStepGroupPlan()
-            check(lib().hwy_step_group_prepare(hs, arr, self.n, t.data_ptr(), ctypes.byref(plan),
-                                               stream_ptr()), "hwy_step_group_prepare")
-            hit = (t, plan)
-            self._tables[key] = hit
-        check(lib().hwy_step_group(ctypes.byref(hit[1]), hit[0].data_ptr(), stream_ptr()),
-              "hwy_step_group")
+            hit = self._tables[key] = self._prepare(v, ptrs, iptrs, fptrs)
+        check(hit[0](*hit[1], stream_ptr()), v.launch)
+
+    def _prepare(self, v, ptrs, iptrs, fptrs) -> tuple:
+        """A cache entry: variant ``v``'s device tables filled for these buffers, as (the launch
+        entry point, its arguments before the stream, what they point into)."""
+        n, dev = self.n, self.envs[0].device
+        hs = (ctypes.c_void_p * n)(*[e._handle.value for e in self.envs])
+        arr = (HwyStepIO * n)(*[HwyStepIO(*p) for p in ptrs])
+        tables = [torch.empty(self._nb, dtype=torch.uint8, device=dev)]
+        if v.table_bytes is not None:
+            tables.append(torch.empty(int(getattr(lib(), v.table_bytes)(n)), dtype=torch.uint8,
+                                      device=dev))
+        plan = HwyStepGroupPlan()
+        tptrs = tuple(t.data_ptr() for t in tables)
+        check(getattr(lib(), v.prepare)(hs, arr, *v.arrays(iptrs, fptrs, n), n, *tptrs,
+                                        ctypes.byref(plan), stream_ptr()), v.prepare)
+        return getattr(lib(), v.launch), (ctypes.byref(plan),) + tptrs, (plan, tables)

@@ -134,10 +134,7 @@ class ExperimentGroup:
                 buf.ep_length[t])
 
     def env_step(self, t: int) -> None:
-        if self.episode_stats:
-            self.env.step_into(*self.env_io(t), info=self.buf.step_info(t))
-        else:
-            self.env.step_into(*self.env_io(t))
+        self.env.step_into(*self.env_io(t), info=self.buf.step_info(t))
 
     def env_traffic(self, t: int) -> None:
         """safety_stats: hwy_traffic on the states step t left (LockstepRollout._steps: on the
@@ -480,11 +477,10 @@ class GroupBatch:
         t1 = self.T if t1 is None else t1
         for t in range(t0, t1):
             self.act.launch(self._rows(t), tiles)
-            if self.envstep is not None and self.episode_stats:
+            if self.envstep is not None:
                 self.envstep.launch([g.env_io(t) for g in self.groups],
-                                    infos=[g.buf.step_info(t) for g in self.groups])
-            elif self.envstep is not None:
-                self.envstep.launch([g.env_io(t) for g in self.groups])
+                                    infos=([g.buf.step_info(t) for g in self.groups]
+                                           if self.episode_stats else None))
             else:
                 self.groups[0].env_step(t)
             for g in self.groups:

@@ -194,25 +194,17 @@ class LockstepRollout:
                              noise=buf.noise[t])
             io = (buf.actions[t], buf.states[t + 1].view(E, *obs_shape), buf.rewards[t],
                   buf.terminated[t], buf.truncated[t], buf.ep_return[t], buf.ep_length[t])
-            if self.truncation == "bootstrap":
-                info = buf.step_info(t) if self.episode_stats else None
-                if self._envstep is not None:
-                    self._envstep.launch([io], infos=None if info is None else [info],
-                                         final_obs=[buf.final_obs])
-                else:
-                    env.step_into(*io, info=info, final_obs=buf.final_obs)
+            boot = self.truncation == "bootstrap"
+            info = buf.step_info(t) if self.episode_stats else None
+            final_obs = buf.final_obs if boot else None
+            if self._envstep is not None:
+                self._envstep.launch([io], infos=None if info is None else [info],
+                                     final_obs=None if final_obs is None else [final_obs])
+            else:
+                env.step_into(*io, info=info, final_obs=final_obs)
+            if boot:
                 ag.value_masked(buf.final_obs, buf.truncated[t], buf.terminated[t],
                                 out=buf.boot_values[t])
-            elif self.episode_stats:
-                info = buf.step_info(t)
-                if self._envstep is not None:
-                    self._envstep.launch([io], infos=[info])
-                else:
-                    env.step_into(*io, info=info)
-            elif self._envstep is not None:
-                self._envstep.launch([io])
-            else:
-                env.step_into(*io)
             if self.sensor is not None:
                 env.sense_into(self.sensor, obs=buf.states[t + 1])
             if self.safety_stats and not (self.episode_schedule == "reference" and t == buf.T - 1):
