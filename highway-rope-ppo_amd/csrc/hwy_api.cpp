@@ -635,6 +635,62 @@ int hwy_sense(hwy_handle* h, const hwy_sense_args* a, void* stream) {
   return launched(hwy_launch_sense(&p, (hipStream_t)stream), "hwy_sense_kernel");
 }
 
+int hwy_lookahead_args_size(void) { return (int)sizeof(hwy_lookahead_args); }
+
+int hwy_lookahead_check(const hwy_lookahead_args* a) {
+  if (!a) return fail(HWY_EINVAL, "hwy_lookahead: args is NULL");
+  if (a->k < 1 || a->k > HWY_LOOKAHEAD_MAX_K)
+    return fail(HWY_EINVAL, "hwy_lookahead: k must lie in 1..%d, got %d", HWY_LOOKAHEAD_MAX_K, a->k);
+  if (a->horizon < 1 || a->horizon > HWY_LOOKAHEAD_MAX_H)
+    return fail(HWY_EINVAL, "hwy_lookahead: horizon must lie in 1..%d, got %d",
+                HWY_LOOKAHEAD_MAX_H, a->horizon);
+  if (!(a->gamma >= 0.0f && a->gamma <= 1.0f))  // a NaN fails both
+    return fail(HWY_EINVAL, "hwy_lookahead: gamma must be finite and lie in [0, 1], got %g",
+                (double)a->gamma);
+  if (!a->actions) return fail(HWY_EINVAL, "hwy_lookahead: actions is NULL");
+  if (!a->steps && !a->terminated && !a->truncated && !a->rewards && !a->ret && !a->ego_final &&
+      !a->obs && !a->chosen && !a->chosen_action)
+    return fail(HWY_EINVAL, "hwy_lookahead: no output given");
+  if ((a->lazy || a->chosen) && !(a->steps && a->terminated))
+    return fail(HWY_EINVAL, "hwy_lookahead: lazy and chosen need steps and terminated");
+  if (a->chosen_action && !a->chosen)
+    return fail(HWY_EINVAL, "hwy_lookahead: chosen_action needs chosen");
+  return HWY_OK;
+}
+
+int hwy_lookahead(hwy_handle* h, const hwy_lookahead_args* a, void* stream) {
+  if (!h) return fail(HWY_EINVAL, "hwy_lookahead: handle is NULL");
+  if (int rc = hwy_lookahead_check(a)) return rc;
+  if ((int64_t)h->cfg.num_envs * a->k > HWY_LOOKAHEAD_MAX_BRANCHES)
+    return fail(HWY_EINVAL, "hwy_lookahead: num_envs * k must be <= %d, got %d * %d",
+                HWY_LOOKAHEAD_MAX_BRANCHES, h->cfg.num_envs, a->k);
+  if (a->obs)
+    if (int rc = check_pe(h, "hwy_lookahead")) return rc;
+  LookaheadParams p;
+  memset(&p, 0, sizeof(p));
+  p.p = params_of(h);
+  p.a = *a;
+  hipStream_t s = (hipStream_t)stream;
+  const int E = h->cfg.num_envs;
+  if (a->lazy && a->k > 1) {
+    // candidate 0 of every env, then the rest behind it on the stream, each wave gated by its
+    // env's terminated[e][0]
+    p.k0 = 0, p.nk = 1, p.gate = 0;
+    if (hwy_launch_lookahead(&p, hwy_step_big(E), s))
+      return hip_fail(hipGetLastError(), "hwy_lookahead_kernel");
+    p.k0 = 1, p.nk = a->k - 1, p.gate = 1;
+    if (hwy_launch_lookahead(&p, hwy_step_big((int64_t)E * p.nk), s))
+      return hip_fail(hipGetLastError(), "hwy_lookahead_kernel");
+  } else {
+    p.k0 = 0, p.nk = a->k, p.gate = 0;
+    if (hwy_launch_lookahead(&p, hwy_step_big((int64_t)E * p.nk), s))
+      return hip_fail(hipGetLastError(), "hwy_lookahead_kernel");
+  }
+  if (a->chosen && hwy_launch_lookahead_choice(&p, s))
+    return hip_fail(hipGetLastError(), "hwy_lookahead_choice_kernel");
+  return HWY_OK;
+}
+
 int hwy_obs_pe(const float* obs_in, float* obs_out, int E, int N, int F, int kind, int d,
                int ego_idx, float max_dist, const float* table, const float* dist_override,
                void* stream) {

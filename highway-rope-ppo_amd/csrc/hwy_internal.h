@@ -73,7 +73,19 @@ struct SenseParams {
   float cull2;  // ((a.range_m + 4) * 1.0001)^2: a body farther from the ego blocks nothing in range
 };
 
+// hwy_lookahead's launch parameters (the lookahead unit of hwy_kernels.hip): p the handle's own
+// (its state is only read), a the checked arguments; the launch runs candidates k0 .. k0 + nk - 1
+// of every env, and with gate != 0 only those of envs whose terminated[e][0] is set
+struct LookaheadParams {
+  StepParams p;
+  hwy_lookahead_args a;
+  int k0, nk, gate;
+};
+
 extern "C" {
+// big: the register budget, hwy_step_big(waves of the launch)
+int hwy_launch_lookahead(const LookaheadParams* p, int big, hipStream_t s);
+int hwy_launch_lookahead_choice(const LookaheadParams* p, hipStream_t s);
 int hwy_launch_sense(const SenseParams* p, hipStream_t s);
 int hwy_launch_traffic(const TrafficParams* p, hipStream_t s);
 int hwy_launch_observe(const ObserveParams* p, hipStream_t s);

@@ -1953,6 +1953,234 @@ extern "C" int hwy_launch_sense(const SenseParams* p, hipStream_t s) {
   hipLaunchKernelGGL(hwy_sense_kernel, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#elif defined(HWY_LOOKAHEAD_TU)
+// hwy_lookahead's kernels, likewise a unit of their own (-DHWY_LOOKAHEAD_TU -> hwy_lookahead.o):
+// K what-if rollouts per env from the stored state, through the step's own load_veh, road_order,
+// frame_wave and observe_wave.  One wave per (env, candidate), lane = vehicle, four waves per
+// workgroup as the step.  A branch is what hwy_step does on an autoreset-off handle, H times or
+// until the first done step, with the state kept in registers: between two steps the vehicles go
+// through the image of store_veh / load_veh (the words a step stores and the next one loads), so
+// every step starts from exactly what a stored state would have given it.  Nothing is written
+// but the outputs; store_veh is never called.  `done` is wave-uniform: the early exit needs no
+// barrier, and every cross-lane operation runs with all 64 lanes active.
+
+// the "not run" values of branch b (lazy: its env's candidate 0 did not terminate)
+__device__ __forceinline__ void lookahead_not_run(const hwy_lookahead_args& A, int lane, size_t b,
+                                                  int H, int nobs) {
+  if (lane == 0) {
+    if (A.steps) A.steps[b] = 0;
+    if (A.terminated) A.terminated[b] = 0;
+    if (A.truncated) A.truncated[b] = 0;
+    if (A.ret) A.ret[b] = 0.0f;
+  }
+  if (A.rewards && lane < H) A.rewards[b * H + lane] = 0.0f;  // H <= 64
+  if (A.ego_final && lane < 4) A.ego_final[b * 4 + lane] = 0.0f;
+  if (A.obs)
+    for (int i = lane; i < nobs; i += WAVE) A.obs[b * nobs + i] = 0.0f;
+}
+
+// W: waves per SIMD the registers are sized for, as the step's kernels and picked as they are (4,
+// or HWY_STEP_BIG_W above 32 waves per CU: at 16,384 / 24,576 waves the 6-wave build takes 857 /
+// 1,608 us against the 4-wave build's 917 / 1,776, profiles/r20/lookahead).  This launch runs
+// candidates k0 .. k0 + nk - 1 of every env; gate: a wave first reads terminated[e][0] (written by
+// an earlier launch on the stream) and writes the "not run" values when it is 0.
+template <int W>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
+hwy_lookahead_kernel(LookaheadParams P) {
+  __shared__ int lds_vor[ENVS_PER_BLOCK][WAVE];
+  __shared__ int lds_inv[ENVS_PER_BLOCK][WAVE];
+  __shared__ CollLds lds_coll[ENVS_PER_BLOCK];
+  const hwy_config& C = P.p.cfg;
+  const hwy_lookahead_args& A = P.a;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int w = threadIdx.x / WAVE;
+  const int wi = blockIdx.x * ENVS_PER_BLOCK + w;  // < E * K <= 2^22
+  if (wi >= C.num_envs * P.nk) return;             // whole wave
+  const int e = wi / P.nk;
+  const int k = P.k0 + (wi - e * P.nk);
+  const int K = A.k, H = A.horizon;
+  const size_t b = (size_t)e * K + k;
+  const int V = C.vehicles_count + 1;
+  const int nobs = C.obs_vehicles * P.p.fout;
+  if (P.gate && A.terminated[(size_t)e * K] == 0) {  // wave-uniform
+    lookahead_not_run(A, lane, b, H, nobs);
+    return;
+  }
+  const size_t fstride = (size_t)C.num_envs * WAVE;
+  const uint32_t idx = (uint32_t)e * WAVE + lane;  // < 2^32: hwy_create bounds num_envs
+  const uint32_t* st = P.p.state;
+
+  SecProf sp;
+  SEC_START(sp);
+  Veh v;
+  int order_pos;
+  load_veh(st, fstride, idx, lane, V, v, order_pos);
+  const uint32_t ew = (st + HWY_F_ENV * fstride)[idx];
+  int step = rdli((int)ew, HWY_E_STEP);
+  const uint64_t seed = (uint64_t)(uint32_t)rdli((int)ew, HWY_E_SEED_LO) |
+                        ((uint64_t)(uint32_t)rdli((int)ew, HWY_E_SEED_HI) << 32);
+  if (lane == 0) {
+    v.aacc = hm_bits2f((uint32_t)rdli((int)ew, HWY_E_EGO_ACC));
+    v.asteer = hm_bits2f((uint32_t)rdli((int)ew, HWY_E_EGO_STEER));
+  }
+  const float dt = 1.0f / (float)C.sim_freq;
+  const int frames = C.sim_freq / C.policy_freq;
+  const float* act = A.actions + (A.hold ? b * 2 : b * (size_t)H * 2);
+
+  RoadOrder ro;
+  ro.rk = order_pos;
+  float cos_h = 1.0f, sin_h = 0.0f;
+  float ret = 0.0f, g = 1.0f;
+  int terminated = 0, truncated = 0, n = 0;
+  for (int h = 0; h < H; ++h) {
+    if (h > 0) {
+      // what store_veh writes and load_veh reads back: a slot past V holds zero words, the
+      // impact of a vehicle without the impact flag is zero, only the ego's action persists
+      const bool live = lane < V;
+      v.x = live ? v.x : 0.0f;
+      v.y = live ? v.y : 0.0f;
+      v.h = live ? v.h : 0.0f;
+      v.spd = live ? v.spd : 0.0f;
+      v.tsp = live ? v.tsp : 0.0f;
+      v.dlt = live ? v.dlt : 0.0f;
+      v.tmr = live ? v.tmr : 0.0f;
+      v.ix = (live && v.imp) ? v.ix : 0.0f;
+      v.iy = (live && v.imp) ? v.iy : 0.0f;
+      v.ln = live ? v.ln : 0;
+      v.tl = live ? v.tl : 0;
+      v.crashed = live && v.crashed;
+      v.imp = live && v.imp;
+      v.present = live && v.present;
+      if (lane != 0) {
+        v.aacc = 0.0f;
+        v.asteer = 0.0f;
+      }
+    }
+    const float a0 = act[A.hold ? 0 : 2 * h], a1 = act[A.hold ? 1 : 2 * h + 1];
+    // the road order kept from the previous step, validated as step_body does
+    ro.rk = lane < V ? ro.rk : V + (WAVE - 1 - lane);
+    ro.ord = __builtin_amdgcn_ds_permute(ro.rk << 2, lane);
+    ro.valid = true;
+    const uint64_t pres = ballot(v.present);
+    road_order(lane, v, pres, ro);
+    hm_sincosf(v.h, &sin_h, &cos_h);
+    if (frames > 0 && lane == 0) {  // ContinuousAction.act (first frame)
+      v.aacc = hm_lmap(hm_clipf(a0, -1.0f, 1.0f), -1.0f, 1.0f, -5.0f, 5.0f);
+      v.asteer = hm_lmap(hm_clipf(a1, -1.0f, 1.0f), -1.0f, 1.0f, -HM_PIO4_F, HM_PIO4_F);
+    }
+    const float tan_ego = rdlf(lane == 0 ? hm_tanf_sc(v.asteer) : 0.0f, 0);
+    for (int frame = 0; frame < frames; ++frame) {  // the step's priority ladder
+      const int f15 = 15 * frame;
+      if (f15 < 6 * frames) __builtin_amdgcn_s_setprio(3);
+      else if (f15 < 10 * frames) __builtin_amdgcn_s_setprio(2);
+      else if (f15 < 13 * frames) __builtin_amdgcn_s_setprio(1);
+      else __builtin_amdgcn_s_setprio(0);
+      frame_wave(C, lane, v, dt, tan_ego, ro, cos_h, sin_h, lds_coll[w], sp, pres);
+    }
+    __builtin_amdgcn_s_setprio(0);
+    step += 1;
+
+    // HighwayEnv._reward / _is_terminated / _is_truncated on the ego: step_body's expressions
+    float rew = 0.0f;
+    terminated = 0;
+    if (lane == 0) {
+      const float forward_speed = v.spd * cos_h;
+      const float scaled_speed = hm_lmap(forward_speed, C.reward_speed_range[0],
+                                         C.reward_speed_range[1], 0.0f, 1.0f);
+      const float collision = v.crashed ? 1.0f : 0.0f;
+      const int nl = C.lanes_count - 1;
+      const float right_lane = (float)v.ln / (float)(nl > 1 ? nl : 1);
+      const float high_speed = hm_clipf(scaled_speed, 0.0f, 1.0f);
+      const bool on_road = on_lane_m(v.x, v.y, v.ln, 0.0f);
+      const float on_road_f = on_road ? 1.0f : 0.0f;
+      rew = 0.0f;
+      rew = rew + C.collision_reward * collision;
+      rew = rew + C.right_lane_reward * right_lane;
+      rew = rew + C.high_speed_reward * high_speed;
+      rew = rew + C.on_road_reward * on_road_f;
+      if (C.normalize_reward)
+        rew = hm_lmap(rew, C.collision_reward, C.high_speed_reward + C.right_lane_reward, 0.0f, 1.0f);
+      rew = rew * on_road_f;
+      terminated = v.crashed || (C.offroad_terminal && !on_road);
+    }
+    rew = rdlf(rew, 0);
+    terminated = rdli(terminated, 0);
+    truncated = step >= C.max_steps;
+    const float gr = g * rew;  // rounded before the sum (no contraction in this unit)
+    ret = ret + gr;
+    g = g * A.gamma;
+    if (A.rewards && lane == 0) A.rewards[b * H + h] = rew;
+    n = h + 1;
+    if (terminated || truncated) break;  // wave-uniform
+  }
+  if (A.rewards && lane >= n && lane < H) A.rewards[b * H + lane] = 0.0f;
+  if (lane == 0) {
+    if (A.steps) A.steps[b] = n;
+    if (A.terminated) A.terminated[b] = (uint8_t)terminated;
+    if (A.truncated) A.truncated[b] = (uint8_t)truncated;
+    if (A.ret) A.ret[b] = ret;
+    if (A.ego_final) {
+      float* o = A.ego_final + b * 4;
+      o[0] = v.x;
+      o[1] = v.y;
+      o[2] = v.h;
+      o[3] = v.spd;
+    }
+  }
+  if (A.obs)  // wave-uniform; the collision pass's scratch is free after the frames
+    observe_wave(C, lane, v, cos_h, sin_h, step, seed, group_pe_table(P.p, e), A.obs + b * nobs,
+                 P.p.fout, lds_vor[w], lds_inv[w], lds_coll[w].imx);
+}
+
+// the shield's choice, one thread per env: the least k with terminated 0; if there is none the k
+// with the most steps, the least such k on ties.  Under lazy a skipped candidate holds steps 0
+// and terminated 0 only when candidate 0 is safe, which is then chosen first anyway.
+__global__ void __launch_bounds__(256) hwy_lookahead_choice_kernel(LookaheadParams P) {
+  const hwy_lookahead_args& A = P.a;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= P.p.cfg.num_envs) return;
+  const int K = A.k;
+  const size_t b0 = (size_t)e * K;
+  int best = -1, best_steps = -1, pick = -1;
+  for (int k = 0; k < K; ++k) {
+    if (A.terminated[b0 + k] == 0) {
+      pick = k;
+      break;
+    }
+    const int s = A.steps[b0 + k];
+    if (s > best_steps) {
+      best_steps = s;
+      best = k;
+    }
+  }
+  if (pick < 0) pick = best;
+  A.chosen[e] = pick;
+  if (A.chosen_action) {
+    const uint32_t* src = (const uint32_t*)A.actions +
+                          (A.hold ? (b0 + pick) * 2 : (b0 + pick) * (size_t)A.horizon * 2);
+    uint32_t* dst = (uint32_t*)A.chosen_action + (size_t)e * 2;
+    dst[0] = src[0];
+    dst[1] = src[1];
+  }
+}
+
+extern "C" int hwy_launch_lookahead(const LookaheadParams* p, int big, hipStream_t s) {
+  const long waves = (long)p->p.cfg.num_envs * p->nk;
+  const int blocks = (int)((waves + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK);
+  if (big)
+    hipLaunchKernelGGL(hwy_lookahead_kernel<HWY_STEP_BIG_W>, dim3(blocks),
+                       dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p);
+  else
+    hipLaunchKernelGGL(hwy_lookahead_kernel<4>, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s,
+                       *p);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int hwy_launch_lookahead_choice(const LookaheadParams* p, hipStream_t s) {
+  const int blocks = (p->p.cfg.num_envs + 255) / 256;
+  hipLaunchKernelGGL(hwy_lookahead_choice_kernel, dim3(blocks), dim3(256), 0, s, *p);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 #else  // the main unit, to the end of the file
 template <int W>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
@@ -2192,4 +2420,5 @@ extern "C" int hwy_debug_sections(unsigned long long* out, int reset) {
   return 0;
 }
 #endif
-#endif  // HWY_CUT_TU / HWY_INFO_TU / HWY_FINAL_TU / HWY_OBSERVE_TU / HWY_TRAFFIC_TU / HWY_SENSE_TU
+#endif  // HWY_CUT_TU / HWY_INFO_TU / HWY_FINAL_TU / HWY_OBSERVE_TU / HWY_TRAFFIC_TU / HWY_SENSE_TU /
+        // HWY_LOOKAHEAD_TU

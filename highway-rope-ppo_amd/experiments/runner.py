@@ -33,7 +33,11 @@ that sensor perceives; the training is likewise unchanged, and the grouped launc
 ``sensor`` (one such dict: the run *trains* under it -- every state the policy acts on is sensed,
 its own evaluations use the same sensor, the metrics carry it as ``sensor``; launch() on the
 vectorised loop only, not over a process group, not with truncation "bootstrap" or the reference
-schedule, refused by the grouped launches).
+schedule, refused by the grouped launches) and ``shield`` / ``eval_shields`` (a hwy.Shield's
+dict, fields ``horizon``, ``fallbacks``, ``lazy``, and {name: such a dict or None}: the run trains
+with the action shield inside its rollout, ``shield_rate`` per update and ``shield`` in the
+metrics, and evaluate(num_episodes=10, shield=...) at the final weights goes in as
+``shield_rewards[name]``; the same restrictions as ``sensor``, and not together with it).
 
 Launched under torchrun (WORLD_SIZE > 1) one experiment spans the ranks, one GPU each: the
 runner joins the process group (RCCL, or ``HWY_DIST_BACKEND``), gives rank r the envs
@@ -183,6 +187,12 @@ class ExperimentRunner:
                         if group is not None:
                             raise ValueError("extra['sensor'] does not run over a process group")
                         stats_kw["sensor"] = exp.extra["sensor"]
+                    if exp.extra.get("eval_shields"):
+                        stats_kw["eval_shields"] = dict(exp.extra["eval_shields"])
+                    if exp.extra.get("shield") is not None:
+                        if group is not None:
+                            raise ValueError("extra['shield'] does not run over a process group")
+                        stats_kw["shield"] = exp.extra["shield"]
                     if group is not None:
                         e = int(overrides.get("num_envs", 1))
                         if e <= 1:
@@ -282,6 +292,14 @@ class ExperimentRunner:
                                      f"use launch()")
                 if e.extra.get("sensor") is not None:  # any sensor, the null one ({}) too
                     raise ValueError(f"launch_group / launch_batch: extra['sensor'] is not "
+                                     f"supported by the grouped launches (experiment {e.name}); "
+                                     f"use launch()")
+                if e.extra.get("eval_shields"):
+                    raise ValueError(f"launch_group / launch_batch: extra['eval_shields'] is not "
+                                     f"supported by the grouped launches (experiment {e.name}); "
+                                     f"use launch()")
+                if e.extra.get("shield") is not None:  # any shield, the default one ({}) too
+                    raise ValueError(f"launch_group / launch_batch: extra['shield'] is not "
                                      f"supported by the grouped launches (experiment {e.name}); "
                                      f"use launch()")
 

@@ -17,6 +17,7 @@ from ._abi import (  # noqa: F401
     PE_ROPE,
     HwyConfig,
     SensorModel,
+    Shield,
     config_from_dict,
 )
 from .native import HwyNativeError, build  # noqa: F401

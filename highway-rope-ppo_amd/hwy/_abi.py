@@ -234,6 +234,102 @@ class SensorModel:
         return a
 
 
+class LookaheadArgs(ctypes.Structure):
+    """hwy_lookahead_args (include/hwy.h): one hwy_lookahead call's candidates and outputs."""
+    _fields_ = [
+        ("k", ctypes.c_int32),
+        ("horizon", ctypes.c_int32),
+        ("hold", ctypes.c_int32),
+        ("lazy", ctypes.c_int32),
+        ("gamma", ctypes.c_float),
+        ("actions", ctypes.c_void_p),
+        ("steps", ctypes.c_void_p),
+        ("terminated", ctypes.c_void_p),
+        ("truncated", ctypes.c_void_p),
+        ("rewards", ctypes.c_void_p),
+        ("ret", ctypes.c_void_p),
+        ("ego_final", ctypes.c_void_p),
+        ("obs", ctypes.c_void_p),
+        ("chosen", ctypes.c_void_p),
+        ("chosen_action", ctypes.c_void_p),
+    ]
+
+
+LOOKAHEAD_OUTPUTS = ("steps", "terminated", "truncated", "rewards", "ret", "ego_final", "obs",
+                     "chosen", "chosen_action")
+LOOKAHEAD_MAX_K = 64
+LOOKAHEAD_MAX_H = 64
+LOOKAHEAD_MAX_BRANCHES = 1 << 22
+
+
+class Shield:
+    """The action shield on top of hwy_lookahead (include/hwy.h), an immutable, hashable value.
+
+    The policy's action, held for ``horizon`` policy steps, is candidate 0; the ``fallbacks``
+    (pairs of raw actions, each held likewise) are candidates 1, 2, ...  The env executes the
+    first candidate that does not terminate within the horizon, or, if all do, the one that
+    survives longest.  ``lazy``: the fallbacks are rolled out only for envs whose candidate 0
+    terminates (the choice is the same either way)."""
+
+    __slots__ = ("horizon", "fallbacks", "lazy")
+
+    def __init__(self, horizon: int = 3, fallbacks=((-1.0, 0.0), (0.0, 0.0), (1.0, 0.0)),
+                 lazy: bool = True):
+        try:
+            hz = int(horizon)
+            fb = tuple((float(a), float(b)) for a, b in fallbacks)
+        except (TypeError, ValueError):
+            raise ValueError(f"bad shield fields: horizon={horizon!r} "
+                             f"fallbacks={fallbacks!r}") from None
+        if hz != horizon or not 1 <= hz <= LOOKAHEAD_MAX_H:
+            raise ValueError(f"horizon must be an integer in 1..{LOOKAHEAD_MAX_H}, got {horizon!r}")
+        if not 1 <= len(fb) <= LOOKAHEAD_MAX_K - 1:
+            raise ValueError(f"a shield takes 1..{LOOKAHEAD_MAX_K - 1} fallbacks, got {len(fb)}")
+        if not all(math.isfinite(x) for pair in fb for x in pair):
+            raise ValueError(f"fallback actions must be finite, got {fallbacks!r}")
+        object.__setattr__(self, "horizon", hz)
+        object.__setattr__(self, "fallbacks", fb)
+        object.__setattr__(self, "lazy", bool(lazy))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Shield is immutable")
+
+    def _key(self):
+        return (self.horizon, self.fallbacks, self.lazy)
+
+    def __eq__(self, other):
+        return isinstance(other, Shield) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"Shield(horizon={self.horizon}, fallbacks={self.fallbacks}, lazy={self.lazy})"
+
+    @property
+    def k(self) -> int:
+        """Candidates per env: the policy's action and the fallbacks."""
+        return 1 + len(self.fallbacks)
+
+    def to_dict(self) -> Dict[str, Any]:
+        """JSON-ready (the metrics file)."""
+        return {"horizon": self.horizon, "fallbacks": [list(p) for p in self.fallbacks],
+                "lazy": self.lazy}
+
+    @classmethod
+    def from_dict(cls, d) -> "Shield":
+        """A Shield from ``to_dict``'s form (missing keys: the defaults), or ``d`` itself when it
+        already is one; unknown keys are a ValueError."""
+        if isinstance(d, cls):
+            return d
+        if not isinstance(d, dict):
+            raise ValueError(f"a shield is a Shield or a dict of its fields, got {d!r}")
+        unknown = set(d) - set(cls.__slots__)
+        if unknown:
+            raise ValueError(f"unknown shield keys {sorted(unknown)}; known: {list(cls.__slots__)}")
+        return cls(**d)
+
+
 # the view hwy_render draws by default: upstream's AbstractEnv.default_config screen_width,
 # screen_height, scaling and centering_position [highway-env 1.10.1]
 RENDER_DEFAULTS = {"screen_width": 600, "screen_height": 150, "scaling": 5.5,

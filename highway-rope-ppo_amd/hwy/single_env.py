@@ -112,5 +112,16 @@ class HighwayEnv(Env):
         its dict), an [N, F_out] float32 numpy array."""
         return self._vec.sense(sensor)[0].cpu().numpy()
 
+    def lookahead(self, actions, gamma: float = 1.0, obs: bool = False):
+        """What-if rollouts from the current state (HighwayVecEnv.lookahead): ``actions`` is a
+        [K, H, 2] array of K action sequences; returns a dict of numpy arrays, ``steps``,
+        ``terminated``, ``truncated``, ``ret`` [K], ``rewards`` [K, H], ``ego_final`` [K, 4] and,
+        with ``obs``, ``obs`` [K, N, F_out].  The env itself does not move."""
+        a = np.asarray(actions, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 2:
+            raise ValueError(f"actions must be [K, H, 2], got {a.shape}")
+        out = self._vec.lookahead(a[None], gamma=gamma, obs=obs)
+        return {k: t[0].cpu().numpy() for k, t in out.items()}
+
     def close(self):
         self._vec.close()

@@ -190,6 +190,70 @@ def sense_args(num_envs: int, rows: int, fout: int, device, sensor, order=None, 
     return a
 
 
+def lookahead_args(num_envs: int, rows: int, fout: int, device, actions, horizon: int, *,
+                   hold: bool = False, lazy: bool = False, gamma: float = 1.0, steps=None,
+                   terminated=None, truncated=None, rewards=None, ret=None, ego_final=None,
+                   obs=None, chosen=None, chosen_action=None) -> _abi.LookaheadArgs:
+    """hwy_lookahead_args for an env of ``num_envs`` x ``rows`` x ``fout`` on ``device`` from
+    caller-owned tensors, every refusal a ValueError (no device call, no library call).  K is read
+    off ``actions``: [E, K, 2] with ``hold``, else [E, K, H, 2]."""
+    E, N = int(num_envs), int(rows)
+    try:
+        H = int(horizon)
+        g = float(gamma)
+    except (TypeError, ValueError):
+        raise ValueError(f"bad horizon {horizon!r} or gamma {gamma!r}") from None
+    if H != horizon or not 1 <= H <= _abi.LOOKAHEAD_MAX_H:
+        raise ValueError(f"horizon must be an integer in 1..{_abi.LOOKAHEAD_MAX_H}, "
+                         f"got {horizon!r}")
+    if not 0.0 <= g <= 1.0:  # a NaN fails
+        raise ValueError(f"gamma must be finite and lie in [0, 1], got {gamma!r}")
+    dev = torch.device(device)
+    want = (E, -1, 2) if hold else (E, -1, H, 2)
+    if not (isinstance(actions, torch.Tensor) and actions.dtype == torch.float32
+            and actions.is_contiguous() and actions.device == dev
+            and actions.dim() == len(want) and actions.shape[1] >= 1
+            and all(w in (-1, int(n)) for w, n in zip(want, actions.shape))):
+        raise ValueError(f"actions must be a contiguous float32 tensor "
+                         f"{'[E, K, 2]' if hold else '[E, K, H, 2]'} (E {E}, H {H}) on {dev}, got "
+                         f"{tuple(actions.shape) if hasattr(actions, 'shape') else type(actions)} "
+                         f"{getattr(actions, 'dtype', None)} on {getattr(actions, 'device', None)}")
+    K = int(actions.shape[1])
+    if K > _abi.LOOKAHEAD_MAX_K or E * K > _abi.LOOKAHEAD_MAX_BRANCHES:
+        raise ValueError(f"K must lie in 1..{_abi.LOOKAHEAD_MAX_K} and E * K be at most "
+                         f"{_abi.LOOKAHEAD_MAX_BRANCHES}, got K {K}, E {E}")
+    a = _abi.LookaheadArgs()
+    a.k, a.horizon, a.hold, a.lazy, a.gamma = K, H, int(bool(hold)), int(bool(lazy)), g
+    a.actions = actions.data_ptr()
+    spec = (("steps", steps, torch.int32, E * K, "E x K"),
+            ("terminated", terminated, torch.uint8, E * K, "E x K"),
+            ("truncated", truncated, torch.uint8, E * K, "E x K"),
+            ("rewards", rewards, torch.float32, E * K * H, "E x K x H"),
+            ("ret", ret, torch.float32, E * K, "E x K"),
+            ("ego_final", ego_final, torch.float32, E * K * 4, "E x K x 4"),
+            ("obs", obs, torch.float32, E * K * N * int(fout), "E x K x N x F_out"),
+            ("chosen", chosen, torch.int32, E, "E"),
+            ("chosen_action", chosen_action, torch.float32, E * 2, "E x 2"))
+    for name, t, dtype, n, what in spec:
+        if t is None:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
+                and t.numel() == n and t.device == dev):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements "
+                             f"({what}) on {dev}, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} "
+                             f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
+        setattr(a, name, t.data_ptr())
+    if all(t is None for _, t, _, _, _ in spec):
+        raise ValueError("lookahead_into needs at least one output: "
+                         + ", ".join(_abi.LOOKAHEAD_OUTPUTS))
+    if (lazy or chosen is not None) and (steps is None or terminated is None):
+        raise ValueError("lazy and chosen need the steps and terminated outputs")
+    if chosen_action is not None and chosen is None:
+        raise ValueError("chosen_action needs chosen")
+    return a
+
+
 class HighwayVecEnv:
     """E lockstep highway-v0 envs with state resident in HBM (one wavefront per env)."""
 
@@ -625,6 +689,96 @@ class HighwayVecEnv:
                               device=self.device)
         self.sense_into(sensor, hidden=out)
         return out.view(self.num_envs, HWY_MAX_VEHICLES)
+
+    def lookahead_into(self, actions: torch.Tensor, horizon: int, *, hold: bool = False,
+                       lazy: bool = False, gamma: float = 1.0, **outputs) -> None:
+        """What-if rollouts of the envs' current states into caller-owned device tensors
+        (hwy_lookahead, include/hwy.h: no synchronisation, no allocation, graph-capturable; the
+        env's own state is not written).  ``actions``: float32 [E, K, H, 2], or [E, K, 2] with
+        ``hold`` (each held for all ``horizon`` steps).  Branch (e, k) is what ``horizon``
+        autoreset-off steps of a copy of env e give, stopped at the first done step.
+        ``outputs`` (any subset, at least one): ``steps`` [E, K] int32, ``terminated`` /
+        ``truncated`` [E, K] uint8, ``rewards`` [E, K, H], ``ret`` [E, K] (discounted by
+        ``gamma``), ``ego_final`` [E, K, 4], ``obs`` [E, K, N, F_out] float32, and the shield's
+        ``chosen`` [E] int32 / ``chosen_action`` [E, 2] float32.  ``lazy``: candidates k >= 1 run
+        only for envs whose candidate 0 terminated (the others hold steps 0 and zeros)."""
+        unknown = set(outputs) - set(_abi.LOOKAHEAD_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown lookahead outputs {sorted(unknown)}; known: "
+                             f"{list(_abi.LOOKAHEAD_OUTPUTS)}")
+        a = lookahead_args(self.num_envs, self.obs_rows, self.obs_features, self.device, actions,
+                           horizon, hold=hold, lazy=lazy, gamma=gamma, **outputs)
+        check(lib().hwy_lookahead(self._handle, ctypes.byref(a), stream_ptr()), "hwy_lookahead")
+        self._keep_lookahead = (actions, outputs)
+
+    def lookahead(self, actions, horizon: Optional[int] = None, gamma: float = 1.0,
+                  obs: bool = False) -> Dict[str, torch.Tensor]:
+        """What-if rollouts of the current states as a dict of new tensors (lookahead_into's
+        outputs but the shield's; ``obs`` only when asked for).  ``actions``: [E, K, H, 2], or
+        [E, K, 2] together with ``horizon`` (each action held for that many steps)."""
+        a = torch.as_tensor(actions, device=self.device, dtype=torch.float32).contiguous()
+        if a.dim() not in (3, 4) or a.shape[0] != self.num_envs:
+            raise ValueError(f"actions must be [E, K, H, 2] or [E, K, 2] with E = {self.num_envs}, "
+                             f"got {tuple(a.shape)}")
+        hold = a.dim() == 3
+        if hold and horizon is None:
+            raise ValueError("actions [E, K, 2] are held for `horizon` steps: give horizon")
+        H = int(a.shape[2]) if not hold else horizon
+        if not hold and horizon is not None and int(horizon) != H:
+            raise ValueError(f"horizon {horizon} differs from the actions' {H} steps")
+        E, K, kw = self.num_envs, int(a.shape[1]), dict(device=self.device)
+        out = {"steps": torch.empty(E, K, dtype=torch.int32, **kw),
+               "terminated": torch.empty(E, K, dtype=torch.uint8, **kw),
+               "truncated": torch.empty(E, K, dtype=torch.uint8, **kw),
+               "rewards": torch.empty(E, K, max(int(H), 1), dtype=torch.float32, **kw),
+               "ret": torch.empty(E, K, dtype=torch.float32, **kw),
+               "ego_final": torch.empty(E, K, 4, dtype=torch.float32, **kw)}
+        if obs:
+            out["obs"] = torch.empty(E, K, self.obs_rows, self.obs_features, dtype=torch.float32,
+                                     **kw)
+        self.lookahead_into(a, H, hold=hold, gamma=gamma, **out)
+        return out
+
+    def shield_into(self, shield, actions: torch.Tensor, out_actions: torch.Tensor, *,
+                    chosen: Optional[torch.Tensor] = None,
+                    scratch: Optional[Dict[str, torch.Tensor]] = None) -> None:
+        """The action the env should execute instead of ``actions`` [E, 2] under ``shield`` (a
+        hwy.Shield or its dict), into ``out_actions`` [E, 2]: one copy into the preallocated
+        candidate tensor and one hwy_lookahead call (hold mode, chosen / chosen_action), no
+        synchronisation, graph-capturable.  Candidate 0 is the given action, the rest the
+        shield's fallbacks, each held for the shield's horizon.  ``chosen`` [E] int32 receives
+        the candidate picked (0: the policy's action stands).  ``scratch``: caller-owned
+        ``cand`` [E, K, 2] float32, ``steps`` [E, K] int32, ``terminated`` [E, K] uint8 and
+        ``chosen`` [E] int32 (default: the env's own, allocated once per shield)."""
+        sh = _abi.Shield.from_dict(shield)
+        E, K = self.num_envs, sh.k
+        if not (isinstance(actions, torch.Tensor) and actions.dtype == torch.float32
+                and actions.numel() == 2 * E and actions.device == self.device):
+            raise ValueError(f"actions must be a float32 tensor of {E} x 2 elements on "
+                             f"{self.device}")
+        sc = scratch if scratch is not None else self._shield_scratch(sh)
+        cand = sc["cand"]
+        cand[:, 0, :].copy_(actions.view(E, 2))
+        if chosen is None:
+            chosen = sc["chosen"]
+        self.lookahead_into(cand, sh.horizon, hold=True, lazy=sh.lazy, steps=sc["steps"],
+                            terminated=sc["terminated"], chosen=chosen,
+                            chosen_action=out_actions)
+
+    def _shield_scratch(self, sh) -> Dict[str, torch.Tensor]:
+        """The env's own candidate tensor (fallbacks filled in) and steps / terminated / chosen
+        scratch for ``sh``, allocated on first use."""
+        cache = self.__dict__.setdefault("_shield_cache", {})
+        sc = cache.get(sh)
+        if sc is None:
+            E, K, kw = self.num_envs, sh.k, dict(device=self.device)
+            cand = torch.zeros(E, K, 2, dtype=torch.float32, **kw)
+            cand[:, 1:, :] = torch.tensor(sh.fallbacks, dtype=torch.float32, **kw)
+            sc = cache[sh] = {"cand": cand,
+                              "steps": torch.zeros(E, K, dtype=torch.int32, **kw),
+                              "terminated": torch.zeros(E, K, dtype=torch.uint8, **kw),
+                              "chosen": torch.zeros(E, dtype=torch.int32, **kw)}
+        return sc
 
     def close(self) -> None:
         if self._handle:

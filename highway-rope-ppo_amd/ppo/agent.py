@@ -180,11 +180,16 @@ class RolloutBuffer:
     ego's time-to-collision, headway, gap and distance where an episode finished -- on the
     reference schedule row T - 1 also holds the rows of the episodes the cut ended -- 0
     elsewhere) and ``traffic_acc`` [E, 8] (the running reduction of the current episodes, carried
-    from rollout to rollout); the rollout then issues one hwy_traffic launch per env step."""
+    from rollout to rollout); the rollout then issues one hwy_traffic launch per env step.
+
+    ``shield``: also ``exec_actions`` [T, E, A] (the actions the env executed: the policy's where
+    the shield let it stand, a fallback's elsewhere) and ``chosen`` [T, E] int32 (the candidate the
+    shield picked, 0: the policy's own); ``actions``, ``pre_tanh``, ``log_probs`` and ``values``
+    stay the policy's (LockstepRollout(shield=...))."""
 
     def __init__(self, T: int, E: int, state_dim: int, action_dim: int, device: torch.device,
                  episode_stats: bool = False, truncation_bootstrap: bool = False,
-                 safety_stats: bool = False):
+                 safety_stats: bool = False, shield: bool = False):
         kw = dict(device=device, dtype=torch.float32)
         self.T, self.E, self.state_dim = T, E, state_dim
         self.states = torch.zeros(T + 1, E, state_dim, **kw)  # row T = bootstrap obs
@@ -215,6 +220,10 @@ class RolloutBuffer:
 
             self.traffic_stats = torch.zeros(T, E, HWY_TRAFFIC_NACC, **kw)
             self.traffic_acc = torch.zeros(E, HWY_TRAFFIC_NACC, **kw)
+        self.exec_actions = self.chosen = None
+        if shield:
+            self.exec_actions = torch.zeros(T, E, action_dim, **kw)
+            self.chosen = torch.zeros(T, E, device=device, dtype=torch.int32)
 
     @property
     def n(self) -> int:

@@ -42,6 +42,14 @@ perceives them.  One hwy_sense launch after every env step, inside the captured 
 reset states the caller left overwrites ``buf.states[0]``; the env step itself is unchanged.  Not
 with ``truncation="bootstrap"`` (``final_obs`` would not be sensed) and not on the reference
 schedule (the cut's first observations would not be).
+
+``shield=`` (a hwy.Shield or its dict): the shield is part of the environment.  After the policy
+acted, one hwy_lookahead call (``env.shield_into``) inside the captured graph rolls the policy's
+action and the shield's fallbacks out from the env's state and writes the action the env executes
+to ``buf.exec_actions[t]`` and the candidate picked to ``buf.chosen[t]``; the env step takes
+``exec_actions[t]``.  ``buf.actions``, ``pre_tanh``, ``log_probs`` and ``values`` stay the
+policy's own, so PPO's stored data is untouched.  Not together with ``sensor``, not with
+``truncation="bootstrap"`` and not on the reference schedule (none of these is tested).
 """
 
 from __future__ import annotations
@@ -87,6 +95,25 @@ def check_sensor(sensor, truncation: str = "terminal", episode_schedule: str = "
     return sensor
 
 
+def check_shield(shield, truncation: str = "terminal", episode_schedule: str = "lockstep",
+                 sensor=None):
+    """``shield`` as a hwy.Shield (None: none), refusing what a shielded rollout does not do."""
+    if shield is None:
+        return None
+    from hwy._abi import Shield
+
+    shield = Shield.from_dict(shield)
+    if sensor is not None:
+        raise ValueError("shield does not go with sensor: the combination is not tested")
+    if truncation == "bootstrap":
+        raise ValueError('shield does not go with truncation="bootstrap": the combination is '
+                         "not tested")
+    if episode_schedule == "reference":
+        raise ValueError('shield does not go with episode_schedule="reference": the combination '
+                         "is not tested")
+    return shield
+
+
 def rollout_chunks(T: int, episode_schedule: str):
     """The (t0, t1) step ranges a rollout of T steps is issued (and captured) in: the whole
     rollout, or, for a long reference-schedule rollout, chunks of REFERENCE_GRAPH_CHUNK steps."""
@@ -118,12 +145,21 @@ def traffic_after_step(env, buf, t: int, cut=None) -> None:
 class LockstepRollout:
     def __init__(self, agent, env, buf, use_graph: bool = True,
                  episode_schedule: str = "lockstep", episode_stats: bool = False,
-                 truncation: str = "terminal", safety_stats: bool = False, sensor=None):
+                 truncation: str = "terminal", safety_stats: bool = False, sensor=None,
+                 shield=None):
         self.agent = agent
         self.env = env.unwrapped if hasattr(env, "unwrapped") else env
         self.buf = buf
         # one hwy_sense launch per env step (and one now, on the reset states the caller left)
         self.sensor = check_sensor(sensor, truncation, episode_schedule)
+        # one hwy_lookahead call per env step, between acting and stepping
+        self.shield = check_shield(shield, truncation, episode_schedule, sensor)
+        if self.shield is not None:
+            if not hasattr(self.env, "shield_into"):
+                raise ValueError("shield needs a vector env (HighwayVecEnv)")
+            if getattr(buf, "exec_actions", None) is None:
+                raise ValueError("shield needs a RolloutBuffer built with shield=True")
+            self.env._shield_scratch(self.shield)  # allocated here, not inside a capture
         # the steps as hwy_step_with_info, the episodes' sums going to buf.ep_stats / buf.acc
         # (after a reference-schedule cut, buf.acc's rows of the cut envs hold their partial sums)
         self.episode_stats = bool(episode_stats)
@@ -181,6 +217,8 @@ class LockstepRollout:
             key += (buf.traffic_stats.data_ptr(), buf.traffic_acc.data_ptr())
         if self.sensor is not None:
             key += (self.sensor,)
+        if self.shield is not None:
+            key += (self.shield, buf.exec_actions.data_ptr(), buf.chosen.data_ptr())
         return key
 
     def _steps(self, t0: int = 0, t1: Optional[int] = None) -> None:
@@ -192,7 +230,11 @@ class LockstepRollout:
             ag.select_action(buf.states[t], out=(buf.actions[t], buf.pre_tanh[t],
                                                  buf.log_probs[t], buf.values[t]),
                              noise=buf.noise[t])
-            io = (buf.actions[t], buf.states[t + 1].view(E, *obs_shape), buf.rewards[t],
+            executed = buf.actions[t]
+            if self.shield is not None:
+                executed = buf.exec_actions[t]
+                env.shield_into(self.shield, buf.actions[t], executed, chosen=buf.chosen[t])
+            io = (executed, buf.states[t + 1].view(E, *obs_shape), buf.rewards[t],
                   buf.terminated[t], buf.truncated[t], buf.ep_return[t], buf.ep_length[t])
             boot = self.truncation == "bootstrap"
             info = buf.step_info(t) if self.episode_stats else None

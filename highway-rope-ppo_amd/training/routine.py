@@ -63,6 +63,13 @@ occlusion, a sensing range, missed detections, position and speed noise); ``eval
 ({name: sensor}) books each at the final weights as ``sensor_rewards``.  ``sensor`` trains under
 one: the rollout senses every state the policy acts on (ppo/rollout.py), the run's own
 evaluations use the same sensor and the metrics carry it as ``sensor``.
+``evaluate(..., shield=S)`` (a hwy.Shield or its dict) runs them with the shield picking what the
+env executes (HighwayVecEnv.shield_into: the policy's action unless it ends in a crash within the
+shield's horizon, then the first fallback that does not); ``eval_shields`` ({name: shield or
+None}) books each at the final weights as ``shield_rewards``.  ``shield`` trains with one inside
+the rollout (ppo/rollout.py): every update's metrics carry ``shield_rate``, the summary its last
+value, the run's own evaluations use the shield and the metrics carry it as ``shield``.
+``shield_profile`` counts, on unshielded episodes, the crashes a shield could still have avoided.
 """
 
 from __future__ import annotations
@@ -89,12 +96,25 @@ def _flat_dim(env) -> int:
 
 # ---------------------------------------------------------------------------------- evaluation
 def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order=None,
-             sensor=None):
+             sensor=None, shield=None, tape=None):
     """Mean return of deterministic episodes seeded exp_seed + 1000 + k.  ``order`` ("sorted" or
     "shuffled"; vector envs only): the same episodes with the policy acting on the states
     re-observed under that row order (HighwayVecEnv.observe) instead of the step's own rows.
     ``sensor`` (a hwy.SensorModel or its dict; vector envs only): the policy acts on the states as
-    that sensor perceives them (HighwayVecEnv.sense), under ``order`` when that is given too."""
+    that sensor perceives them (HighwayVecEnv.sense), under ``order`` when that is given too.
+    ``shield`` (a hwy.Shield or its dict; vector envs only, not with ``sensor`` or ``order``): the
+    policy acts, the shield picks what the env executes (HighwayVecEnv.shield_into) and the return
+    is the executed episode's.  ``tape`` (with ``shield``): a list that receives, per step, the
+    exported state before it, the policy's actions, the executed actions and the shield's choice
+    as host arrays (tests); a taped evaluation is always run."""
+    if shield is not None:
+        if not _is_vector(env):
+            raise ValueError("evaluate(shield=...) needs a HighwayVecEnv (num_envs > 1, or "
+                             "make_env's vector_env key for one env)")
+        if sensor is not None or order is not None:
+            raise ValueError("evaluate(shield=...) does not go with sensor or order: the "
+                             "combination is not tested")
+        return _evaluate_vector_shield(env, agent, num_episodes, exp_seed, shield, tape)
     if sensor is not None:
         if not _is_vector(env):
             raise ValueError("evaluate(sensor=...) needs a HighwayVecEnv (num_envs > 1, or "
@@ -199,7 +219,26 @@ def _evaluate_vector_sensor(env, agent, num_episodes, exp_seed, sensor, order):
     return r
 
 
-def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None):
+def _evaluate_vector_shield(env, agent, num_episodes, exp_seed, shield, tape=None):
+    """_evaluate_vector for evaluate(shield=...), with a memo of its own keyed by the shield (the
+    other memos are neither read nor written); a taped run bypasses it."""
+    from hwy._abi import Shield
+
+    shield = Shield.from_dict(shield)
+    key = _eval_key(agent, num_episodes, exp_seed) + (shield,)
+    memo = getattr(env.unwrapped, "_eval_shield_memo", None)
+    if memo is None:
+        memo = env.unwrapped._eval_shield_memo = {}
+    hit = memo.get(shield)
+    if tape is None and hit is not None and hit[0] == key and key[0] is not None:
+        return hit[1]
+    r = _run_eval_vector(env, agent, num_episodes, exp_seed, shield=shield, tape=tape)
+    memo[shield] = (key, r)
+    return r
+
+
+def _eval_env(env, num_episodes):
+    """evaluate()'s num_episodes-wide env of ``env``, made once and kept on it"""
     cache = getattr(env.unwrapped, "_eval_envs", None)
     if cache is None:
         cache = {}
@@ -207,18 +246,97 @@ def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None
     ev = cache.get(num_episodes)
     if ev is None:
         ev = cache[num_episodes] = _eval_env_like(env, num_episodes)
+    return ev
+
+
+def shield_profile(env, agent, shield, num_episodes=10, exp_seed: int = 0, tape=None):
+    """What ``shield`` would have done on evaluate()'s episodes, which run *unshielded*: the
+    look-ahead (every candidate, HighwayVecEnv.lookahead_into in hold mode) is called on every
+    state an episode acts on and never overrides.  Returns a dict: ``episodes``; ``crashes``, the
+    episodes that ended terminated; ``avoidable``, the crashed episodes in whose last acted-on
+    state some fallback was safe; ``states``, the states acted on; ``would_override``, those of
+    them where the shield would have replaced the policy's action (its candidate 0 terminates
+    within the horizon); ``mean_steps0``, the mean steps candidate 0 survives over those states;
+    ``reward``, evaluate()'s mean return.  ``tape``: as in evaluate(shield=...), the executed
+    actions being the policy's."""
+    from hwy._abi import Shield
+
+    if not _is_vector(env):
+        raise ValueError("shield_profile needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                         "vector_env key for one env)")
+    shield = Shield.from_dict(shield)
+    n = int(num_episodes)
+    ev = _eval_env(env, n)
+    dev = ev.device
+    K = shield.k
+    cand = torch.zeros(n, K, 2, dtype=torch.float32, device=dev)
+    cand[:, 1:, :] = torch.tensor(shield.fallbacks, dtype=torch.float32, device=dev)
+    steps = torch.zeros(n, K, dtype=torch.int32, device=dev)
+    term = torch.zeros(n, K, dtype=torch.uint8, device=dev)
+    chosen = torch.zeros(n, dtype=torch.int32, device=dev)
+    seeds = torch.arange(n, device=dev, dtype=torch.int64) + (exp_seed + 1000)
+    obs, _ = ev.reset(seeds=seeds)
+    alive = torch.ones(n, dtype=torch.bool, device=dev)
+    total = torch.zeros(n, dtype=torch.float64, device=dev)
+    count = torch.zeros(5, dtype=torch.int64, device=dev)  # crashes, avoidable, states, overrides, steps0
+    for k in range(ev.max_episode_steps + 1):
+        a, _, _, _ = agent.select_action(obs.reshape(n, -1), deterministic=True)
+        a = a.contiguous()
+        cand[:, 0, :].copy_(a.view(n, 2))
+        ev.lookahead_into(cand, shield.horizon, hold=True, steps=steps, terminated=term,
+                          chosen=chosen)
+        if tape is not None:
+            tape.append(dict(state=ev.export_state().cpu().numpy(), actions=a.cpu().numpy().copy(),
+                             executed=a.cpu().numpy().copy(), chosen=chosen.cpu().numpy().copy(),
+                             steps=steps.cpu().numpy().copy(),
+                             terminated=term.cpu().numpy().copy(), alive=alive.cpu().numpy().copy()))
+        fallback_safe = (term[:, 1:] == 0).any(dim=1)
+        obs, r, te, tr, _ = ev.step(a)
+        total += torch.where(alive, r.double(), torch.zeros_like(total))
+        crashed = alive & te.bool()
+        count[0] += crashed.sum()
+        count[1] += (crashed & fallback_safe).sum()
+        count[2] += alive.sum()
+        count[3] += (alive & (chosen != 0)).sum()
+        count[4] += torch.where(alive, steps[:, 0].long(), torch.zeros_like(steps[:, 0].long())).sum()
+        alive &= ~(te.bool() | tr.bool())
+        if k % 8 == 7 and not bool(alive.any()):
+            break
+    c = [int(x) for x in count.cpu().tolist()]
+    return {"episodes": n, "crashes": c[0], "avoidable": c[1], "states": c[2],
+            "would_override": c[3], "mean_steps0": c[4] / max(c[2], 1),
+            "reward": float(total.mean().item())}
+
+
+def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None, shield=None,
+                     tape=None):
+    ev = _eval_env(env, num_episodes)
     dev = ev.device
     seeds = torch.arange(num_episodes, device=dev, dtype=torch.int64) + (exp_seed + 1000)
     obs, _ = ev.reset(seeds=seeds)
     alive = torch.ones(num_episodes, dtype=torch.bool, device=dev)
     total = torch.zeros(num_episodes, dtype=torch.float64, device=dev)
     seen = None  # order / sensor given: the states as observed under it, in a buffer of its own
+    executed = chosen = None  # shield given: the executed actions and the shield's choice
     for k in range(ev.max_episode_steps + 1):
         if sensor is not None:
             obs = seen = ev.sense(sensor, order=order, out=seen)
         elif order is not None:
             obs = seen = ev.observe(order=order, out=seen)
         a, _, _, _ = agent.select_action(obs.reshape(num_episodes, -1), deterministic=True)
+        if shield is not None:  # the shield picks what the env executes
+            policy_a = a.contiguous()
+            if executed is None:
+                executed = torch.zeros(num_episodes, 2, dtype=torch.float32, device=dev)
+                chosen = torch.zeros(num_episodes, dtype=torch.int32, device=dev)
+            ev.shield_into(shield, policy_a, executed, chosen=chosen)
+            if tape is not None:
+                tape.append(dict(state=ev.export_state().cpu().numpy(),
+                                 actions=policy_a.cpu().numpy().copy(),
+                                 executed=executed.cpu().numpy().copy(),
+                                 chosen=chosen.cpu().numpy().copy(),
+                                 alive=alive.cpu().numpy().copy()))
+            a = executed
         obs, r, te, tr, _ = ev.step(a.contiguous())
         total += torch.where(alive, r.double(), torch.zeros_like(total))
         alive &= ~(te.bool() | tr.bool())
@@ -787,6 +905,9 @@ def _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_hist
     for k in CONTROL_KEYS:  # runs with a KL target / an lr schedule only
         if k in metrics_history:
             head, tail = f"{head},{k}", f"{tail},{metrics_history[k]}"
+    if "shield" in metrics_history:  # shielded runs only: the last update's share of overrides
+        ups = [u["shield_rate"] for u in metrics_history["policy_updates"] if "shield_rate" in u]
+        head, tail = f"{head},shield_rate", f"{tail},{(ups[-1] if ups else 0.0):.4f}"
     with open(csv_path, "w") as f:
         f.write(f"experiment,final_reward,max_reward,steps,best_model,plot{head}\n")
         f.write(f"{experiment_name},{avg_rewards[-1]:.4f},{max(avg_rewards):.4f},{total_steps},"
@@ -847,9 +968,10 @@ class _EvalTracker:
     """Eval / moving-average / checkpoint bookkeeping of routine.py:172-222."""
 
     def __init__(self, env, agent, exp_seed, target_reward, checkpoint_dir, experiment_name,
-                 metrics_history, logger, exp_prefix, start_time, sensor=None):
+                 metrics_history, logger, exp_prefix, start_time, sensor=None, shield=None):
         self.env, self.agent, self.exp_seed = env, agent, exp_seed
         self.sensor = sensor  # the sensor the run trains under: its own evaluations use it too
+        self.shield = shield  # likewise the shield (never both)
         self.target_reward = target_reward
         self.checkpoint_dir, self.name = checkpoint_dir, experiment_name
         self.mh, self.logger, self.prefix, self.t0 = metrics_history, logger, exp_prefix, start_time
@@ -860,7 +982,8 @@ class _EvalTracker:
     def initial(self, r=None):
         if r is None:
             r = evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed,
-                         **({} if self.sensor is None else {"sensor": self.sensor}))
+                         **({} if self.sensor is None else {"sensor": self.sensor}),
+                         **({} if self.shield is None else {"shield": self.shield}))
         self.rewards.append(r)
         self.avg_rewards.append(r)
         self.mh["eval_rewards"].append(r)
@@ -874,7 +997,8 @@ class _EvalTracker:
         self.logger.info(f"{self.prefix} Evaluating at episode {episode_num}...")
         if r is None:
             r = evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed,
-                         **({} if self.sensor is None else {"sensor": self.sensor}))
+                         **({} if self.sensor is None else {"sensor": self.sensor}),
+                         **({} if self.shield is None else {"shield": self.shield}))
         self.rewards.append(r)
         self.eval_episodes.append(episode_num)
         elapsed = time.time() - self.t0
@@ -902,8 +1026,9 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
                                exp_seed: int = 0, logger=None, episode_schedule="lockstep",
                                episode_stats: bool = False, truncation: str = "terminal",
                                attribution: bool = False, eval_orders=None,
-                               safety_stats: bool = False, sensor=None, eval_sensors=None):
-    from ppo.rollout import check_episode_schedule, check_sensor, check_truncation
+                               safety_stats: bool = False, sensor=None, eval_sensors=None,
+                               shield=None, eval_shields=None):
+    from ppo.rollout import check_episode_schedule, check_sensor, check_shield, check_truncation
 
     if attribution and not _is_vector(env):
         raise ValueError("attribution needs a HighwayVecEnv (num_envs > 1, or make_env's "
@@ -925,6 +1050,19 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
                              "vector_env key for one env)")
         if getattr(agent, "_dist", None) is not None:
             raise ValueError("sensor does not run over a process group")
+
+    eval_shields = check_eval_shields(eval_shields)
+    if eval_shields and not _is_vector(env):
+        raise ValueError("eval_shields needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                         "vector_env key for one env)")
+    shield = check_shield(shield, check_truncation(truncation),
+                          check_episode_schedule(episode_schedule), sensor)
+    if shield is not None:
+        if not _is_vector(env):
+            raise ValueError("shield needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                             "vector_env key for one env)")
+        if getattr(agent, "_dist", None) is not None:
+            raise ValueError("shield does not run over a process group")
 
     if check_truncation(truncation) == "bootstrap":
         if not _is_vector(env):
@@ -982,13 +1120,16 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         metrics_history["truncation"] = truncation
     if sensor is not None:
         metrics_history["sensor"] = sensor.to_dict()
+    if shield is not None:
+        metrics_history["shield"] = shield.to_dict()
     _book_controls(metrics_history, agent)
     start_time = time.time()
     artifacts_dir = ensure_artifacts_dir()
     checkpoint_dir = os.path.join(artifacts_dir, "checkpoints")
     os.makedirs(checkpoint_dir, exist_ok=True)
     tracker = _EvalTracker(env, agent, exp_seed, target_reward, checkpoint_dir, experiment_name,
-                           metrics_history, logger, exp_prefix, start_time, sensor=sensor)
+                           metrics_history, logger, exp_prefix, start_time, sensor=sensor,
+                           shield=shield)
     rank, _ = _rank_world(getattr(agent, "_dist", None))
     if rank == 0:
         logger.info(f"{exp_prefix} Performing initial evaluation...")
@@ -1005,6 +1146,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         sched_kw["safety_stats"] = True
     if sensor is not None:
         sched_kw["sensor"] = sensor
+    if shield is not None:
+        sched_kw["shield"] = shield
     episode_rewards, training_episodes, total_steps = loop(
         env, agent, max_episodes, log_interval, eval_interval, steps_per_update, exp_seed, logger,
         exp_prefix, metrics_history, tracker, start_time, **sched_kw)
@@ -1021,6 +1164,11 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         metrics_history["sensor_rewards"] = {
             name: evaluate(env, agent, num_episodes=10, exp_seed=exp_seed, sensor=s)
             for name, s in eval_sensors.items()}
+    if eval_shields:  # likewise, under each shield (None: unshielded)
+        metrics_history["shield_rewards"] = {
+            name: evaluate(env, agent, num_episodes=10, exp_seed=exp_seed,
+                           **({} if s is None else {"shield": s}))
+            for name, s in eval_shields.items()}
     _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_history,
                     training_episodes, episode_rewards, tracker.eval_episodes, tracker.rewards,
                     tracker.avg_rewards, target_reward, total_steps, logger, exp_prefix)
@@ -1047,6 +1195,18 @@ def check_eval_sensors(eval_sensors) -> dict:
     if not isinstance(eval_sensors, dict) or not all(isinstance(n, str) for n in eval_sensors):
         raise ValueError(f"eval_sensors must be a dict of names to sensors, got {eval_sensors!r}")
     return {name: SensorModel.from_dict(s) for name, s in eval_sensors.items()}
+
+
+def check_eval_shields(eval_shields) -> dict:
+    """``eval_shields`` as {name: hwy.Shield or None} (None or empty: none) from a dict of names
+    to shields, their dicts or None (the unshielded evaluation); ValueError otherwise."""
+    from hwy._abi import Shield
+
+    if eval_shields is None:
+        return {}
+    if not isinstance(eval_shields, dict) or not all(isinstance(n, str) for n in eval_shields):
+        raise ValueError(f"eval_shields must be a dict of names to shields, got {eval_shields!r}")
+    return {name: None if s is None else Shield.from_dict(s) for name, s in eval_shields.items()}
 
 
 def _log_episode(logger, prefix, episode_num, ep_reward, episode_rewards, log_interval,
@@ -1102,8 +1262,15 @@ def _train_single(env, agent, max_episodes, log_interval, eval_interval, steps_p
 
 def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_per_update,
                   exp_seed, logger, prefix, mh, tracker, start_time, episode_schedule="lockstep",
-                  episode_stats=False, truncation="terminal", safety_stats=False, sensor=None):
+                  episode_stats=False, truncation="terminal", safety_stats=False, sensor=None,
+                  shield=None):
     """E lockstep envs, device rollout of T steps, batched PPO update.
+
+    shield: after the policy acted, the rollout's shield (one hwy_lookahead call per step,
+    ppo/rollout.py) picks the action the env executes; PPO's stored actions, log-probs and values
+    stay the policy's.  Every update's metrics carry ``shield_rate``, the share of the rollout's
+    steps the shield overrode.  Not over a process group, not with a sensor, truncation
+    "bootstrap" or the reference schedule.
 
     sensor: the rollout senses the reset states and the state every env step leaves into the
     rows the policy acts on (one hwy_sense launch each, ppo/rollout.py); not over a process
@@ -1140,6 +1307,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
         raise ValueError("safety_stats does not run over a process group")
     if sensor is not None and group is not None:
         raise ValueError("sensor does not run over a process group")
+    if shield is not None and group is not None:
+        raise ValueError("shield does not run over a process group")
     base = env.unwrapped
     E = base.num_envs
     sd = _flat_dim(env)
@@ -1147,7 +1316,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
     stats_kw = {"episode_stats": True} if episode_stats else {}
     safety_kw = {"safety_stats": True} if safety_stats else {}
     buf = RolloutBuffer(T, E, sd, 2, base.device, **stats_kw, **safety_kw,
-                        **({"truncation_bootstrap": True} if bootstrap else {}))
+                        **({"truncation_bootstrap": True} if bootstrap else {}),
+                        **({"shield": True} if shield is not None else {}))
     base.set_seed_schedule(exp_seed)
     obs, _ = env.reset()
     buf.states[0].copy_(obs.reshape(E, sd))
@@ -1156,7 +1326,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
                            **({"episode_schedule": episode_schedule} if reference else {}),
                            **stats_kw, **safety_kw,
                            **({"truncation": truncation} if bootstrap else {}),
-                           **({"sensor": sensor} if sensor is not None else {}))
+                           **({"sensor": sensor} if sensor is not None else {}),
+                           **({"shield": shield} if shield is not None else {}))
     episode_rewards, training_episodes = [], []
     total_steps = episode_num = 0
     while episode_num < max_episodes:
@@ -1195,6 +1366,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
                 tracker.on_episode(episode_num)
         if reference:
             upd = agent.update_rollout(buf, agent.value(buf.states[T]))
+        if shield is not None:  # the share of this rollout's steps the shield overrode
+            upd = dict(upd, shield_rate=float((buf.chosen != 0).float().mean().item()))
         mh["policy_updates"].append({"episode": episode_num, "steps": T * E * world,
                                      "time": time.time() - t_update, **upd})
         roll.start_next()

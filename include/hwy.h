@@ -48,6 +48,7 @@
  *                                on the ego perceives (range, line of sight, dropout, noise)
  *   hwy_traffic               <- env.unwrapped.road.neighbour_vehicles(v) for every vehicle, and the
  *                                gap / time-to-collision / headway a driving study derives from it
+ *   hwy_lookahead             <- copy.deepcopy(env) then env.step(a), repeated, for K action sequences
  *
  * Conventions
  *   - Plain pointers and sizes only; device pointers are HIP device pointers (e.g. torch
@@ -612,6 +613,74 @@ int hwy_sense_args_size(void);
  * pure, no device call. */
 int hwy_sense_check(const hwy_sense_args* a);
 int hwy_sense(hwy_handle* h, const hwy_sense_args* a, void* stream);
+
+/* ---- What-if rollouts of the stored states, and an action shield.
+ *
+ * hwy_lookahead runs K branches per env.  Branch (e, k) starts from env e's state words as they
+ * stand and runs exactly what hwy_step runs on a handle with autoreset 0, up to `horizon` times:
+ * the ego action of step h is mapped as ContinuousAction.act is (the step's own clip applies),
+ * sim_freq / policy_freq frames follow, the step word goes up by 1, reward and terminated are the
+ * step's expressions and truncated = step >= max_steps.  The branch ends after the first step with
+ * terminated | truncated, or after `horizon` steps.  Nothing is ever reset, whatever the handle's
+ * autoreset, and the handle's state is not written.  The frames draw no random numbers (Philox
+ * enters only at reset and in the shuffled row order), so a branch is the future itself, bit for
+ * bit: what `horizon` hwy_step calls on an autoreset-off handle holding a copy of the state
+ * (hwy_export_state / hwy_import_state) return.
+ *
+ *   actions: hold != 0: [E][K][2], each held for all steps; else [E][K][H][2].
+ *   steps [E][K] i32: the policy steps run, 1..H (0: not run, see lazy).
+ *   terminated, truncated [E][K] u8: of the last step run.
+ *   rewards [E][K][H] f32: the step's reward; +0.0 past `steps`.
+ *   ret [E][K] f32, all in binary32: ret = 0, g = 1; per step run ret = ret + g * r, then
+ *     g = g * gamma, each product rounded before the sum.  With gamma 1 this is the step's own
+ *     running return.
+ *   ego_final [E][K][4] f32: the ego's x, y, heading, speed after the last step run.
+ *   obs [E][K][N][F_out] f32: what that autoreset-off hwy_step would have written on the
+ *     branch's last step: under the branch's step count and the env's seed words (the shuffled
+ *     order needs both), with the fused wrapper, and under hwy_set_seed_groups with the RankPE
+ *     table of env e's group (indexed by the env, not by the branch).
+ *   lazy != 0: candidates k >= 1 of an env run only if its candidate 0 terminated (two launches
+ *     inside the call: k = 0, then k >= 1 reading terminated[e][0] behind it on the stream).  A
+ *     branch that is skipped is written steps 0, flags 0 and +0.0 everywhere else.
+ *   chosen [E] i32, chosen_action [E][2] f32 (one further small launch, integer logic only):
+ *     candidate k is safe iff terminated[e][k] == 0 (a truncation or a full horizon is safe).
+ *     chosen[e] is the least safe k; if none is safe, the k with the greatest steps[e][k], the
+ *     least such k on ties.  Under lazy a safe candidate 0 is chosen without looking further.
+ *     chosen_action[e] is the chosen candidate's first-step action, bits copied.
+ *
+ * No entry of a given output is left unwritten.  All outputs are device pointers and nullable,
+ * but at least one must be given.  hwy_lookahead is asynchronous, allocates nothing, is
+ * hipGraph-capturable and writes nothing but its outputs.  It returns HWY_EINVAL before any
+ * device call for a NULL handle or NULL args, k or horizon outside 1..64, E * K above 2^22, a
+ * gamma that is not finite or lies outside [0, 1], NULL actions, no output at all, lazy or chosen
+ * without steps and terminated, chosen_action without chosen, and obs on a handle whose per-group
+ * PE tables are without meaning (hwy_set_seed_groups).  On non-finite state words the values are
+ * not specified; the kernel terminates and stays inside its outputs. */
+#define HWY_LOOKAHEAD_MAX_K 64
+#define HWY_LOOKAHEAD_MAX_H 64
+#define HWY_LOOKAHEAD_MAX_BRANCHES (1 << 22)
+typedef struct hwy_lookahead_args {
+  int32_t k, horizon;     /* K candidates per env 1..64; H policy steps 1..64; E*K <= 2^22 */
+  int32_t hold;           /* != 0: actions is [E][K][2], each held for all H steps; else [E][K][H][2] */
+  int32_t lazy;           /* != 0: candidates k >= 1 of an env run only if its candidate 0 terminated */
+  float gamma;            /* finite, 0 <= gamma <= 1 */
+  const float* actions;   /* device, as `hold` says; the step's own clip applies */
+  int32_t* steps;         /* [E][K]    policy steps run, 1..H (0: not run) */
+  uint8_t* terminated;    /* [E][K]    of the last step run */
+  uint8_t* truncated;     /* [E][K]    of the last step run */
+  float* rewards;         /* [E][K][H] the step's reward; +0.0 past `steps` */
+  float* ret;             /* [E][K]    see above */
+  float* ego_final;       /* [E][K][4] the ego's x, y, heading, speed after the last step run */
+  float* obs;             /* [E][K][N][F_out] the observation after the last step run */
+  int32_t* chosen;        /* [E]       the shield's choice */
+  float* chosen_action;   /* [E][2] */
+} hwy_lookahead_args;
+/* sizeof(hwy_lookahead_args) as compiled into the library (binding layout check). */
+int hwy_lookahead_args_size(void);
+/* HWY_OK, or HWY_EINVAL for arguments hwy_lookahead refuses (every check that needs no handle);
+ * pure, no device call. */
+int hwy_lookahead_check(const hwy_lookahead_args* a);
+int hwy_lookahead(hwy_handle* h, const hwy_lookahead_args* a, void* stream);
 
 /* Stand-alone observation wrapper on [E,N,F] f32 -> [E,N,F_out] f32 (foreign envs).
  *   kind = enum hwy_pe_kind, d = appended width (rank/dist) or rotate_dim (rope),
