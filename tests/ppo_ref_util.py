@@ -1,7 +1,8 @@
 """Reference helpers of the fused PPO parity tests: agents and inputs, the float64 autograd
 reference taking the fused step's own ReLU decisions, the gradient criterion (_check_grads), and
 the CPU-drawn edge cases shared by test_ppo_edge_inputs.py (input conditions, no GPU) and
-test_ppo_edges_gpu.py (the kernels against float64)."""
+test_ppo_edges_gpu.py (the kernels against float64), and the general path's cases with their
+split-K plans (test_ppo_general_inputs.py, test_ppo_general_gpu.py)."""
 
 import copy
 
@@ -190,10 +191,14 @@ GRAD_CASES = (
     # B edges: below / at / past one 16-row tile and one 64-row chunk; 130 = two 65-row slices
     (60, 256, 1, 0, 0, 0), (60, 256, 15, 1, 1, 0), (60, 256, 16, 2, 2, 0), (60, 256, 17, 0, 1, 0),
     (60, 256, 63, 1, 2, 0), (60, 256, 65, 2, 0, 0), (60, 256, 130, 0, 1, 5),
-    # the general path: scalar gemm64 (S % 4 != 0) and gemm64v past the fused bound (S > 256)
-    (75, 128, 50, 1, 0, 0), (75, 320, 40, 1, 0, 0), (30, 64, 17, 2, 1, 0), (260, 256, 72, 0, 2, 0),
-    (300, 512, 130, 1, 1, 0),
+    # the general path through scalar gemm64 (S % 4 != 0); GENERAL_CASES below holds the rest
+    (75, 128, 50, 1, 0, 0), (75, 320, 40, 1, 0, 0), (30, 64, 17, 2, 1, 0),
+    # wide fused states (256 < S <= 1,024, S % 4 == 0): the row kernels' chunked first layer
+    (260, 256, 72, 0, 2, 0), (300, 512, 130, 1, 1, 0),
 )
+# the GRAD_CASES shapes labelled general above: exactly these have no tile image
+# (FusedPPO._tile_off is None), which test_edge_gradient_matches_autograd asserts
+GRAD_GENERAL_SHAPES = frozenset({(75, 128, 50), (75, 320, 40), (30, 64, 17)})
 _BY_SHAPE = {c[:3]: c for c in GRAD_CASES}
 # the exact checks (zero signal, dead units) and the in-kernel gradient norm run at these
 EXACT_CASES = tuple(_BY_SHAPE[k] for k in ((60, 320, 40), (200, 448, 72), (60, 256, 40),
@@ -204,6 +209,72 @@ NORM_CASES = tuple(_BY_SHAPE[k] for k in [(60, H, 40) for H in WIDTHS]
 # two-deep ring widths with a padded W1 image over more than one workgroup's rows
 ACT_CASES = tuple((S, H, B) for H in WIDTHS for S in (4, 60, 256) for B in (1, 17)) + (
     (200, 320, 100), (200, 448, 100))
+
+
+# ------------------------------------------------------------------ the general path
+# Shapes outside the fused bound (S % 4 != 0 or S > 1,024): 11 gemm64 / gemm64v launches, ppo_head,
+# split-K slabs, ppo_reduce and the flat ppo_adam (test_ppo_general_inputs.py: the conditions on
+# the inputs and what each row reaches, without a GPU; test_ppo_general_gpu.py: the kernels).
+# Same row format as GRAD_CASES; the seeds are the smallest at which the inputs meet every
+# condition of test_ppo_general_inputs.py.  These have up to 1,000 rows, so they stay out of
+# GRAD_CASES (16-row tiles at every CU count hold only up to 130).
+GENERAL_CASES = (
+    # ---- dW1 and the first layer through scalar gemm64 (S % 4 != 0)
+    (1, 64, 17, 0, 1, 0),        # a single k in the first layer; dW1 has one column
+    (33, 128, 40, 1, 2, 2),      # one live k in the second 32-deep K-step of the first layer
+    (63, 192, 72, 2, 0, 0),      # dW1's 64-column tile, one column short of full
+    (65, 256, 130, 0, 2, 0),     # dW1's second column tile holds one column
+    (130, 320, 72, 1, 1, 1),     # S % 4 == 2, three column tiles of dW1
+    (25, 64, 1000, 2, 1, 0),     # 32 slabs of 32 rows, the last holding 8: ppo_reduce sums 32
+    (258, 512, 300, 1, 0, 0),    # dW1: scalar chunks of 64 (prefetch taken); vector 160 and 96
+    (75, 512, 300, 0, 0, 0),     # the same plan at the five-feature width
+    (130, 512, 1000, 2, 2, 1),   # chunks above 64 rows on all three weight gradients
+    # ---- gemm64v with K = S / N = S and gathered operand rows (S > 1,024, S % 4 == 0)
+    (1028, 64, 17, 2, 0, 0),     # 16 K-tiles and one float4; one partial chunk of 17 rows
+    (1028, 256, 72, 1, 0, 0),    # ... and 16 whole column tiles of dW1 plus 4 columns
+    (1088, 128, 130, 0, 1, 0),   # whole K-tiles and whole column tiles only
+    (1100, 512, 130, 1, 2, 0),   # S % 64 == 12; dW1 in one chunk of 160 rows
+    (1028, 512, 300, 2, 1, 0),   # dW1 in one chunk of 320 rows: five gathered K-tiles, prefetched
+    (1028, 384, 520, 0, 2, 0),   # odd H / 64; chunks of 192 / 96 / 288 rows
+)
+_GENERAL_BY_SHAPE = {c[:3]: c for c in GENERAL_CASES}
+# the exact checks (zero signal, dead units): every split-K GEMM with more than one K-tile per
+# chunk, scalar and vector dW1
+GENERAL_EXACT_CASES = tuple(_GENERAL_BY_SHAPE[k] for k in ((258, 512, 300), (1028, 256, 72)))
+# the in-kernel norm: every row whose float64 gradient norm is above 0.5, so that max_grad_norm
+# 0.5 clips (the others: 0.24 - 0.50); ppo_reduce's norm partials at nred up to 5,287
+GENERAL_NORM_CASES = tuple(_GENERAL_BY_SHAPE[k] for k in (
+    (1, 64, 17), (33, 128, 40), (63, 192, 72), (130, 320, 72), (258, 512, 300), (1028, 64, 17),
+    (1028, 256, 72), (1088, 128, 130), (1100, 512, 130), (1028, 512, 300)))
+
+K_STEP, V_K = 32, 64  # K-tile depth of gemm64 (kKStep) and of gemm64v (kVK)
+
+
+def split_for(tiles, K):
+    """csrc/ppo_kernels.hip split_for: workgroups along K for `tiles` output tiles."""
+    return min(max(1, 256 // max(tiles, 1)), -(-K // K_STEP))
+
+
+def chunk_for(K, split):
+    """csrc/ppo_kernels.hip chunk_for: rows per split-K chunk, whole 32-deep K-steps."""
+    return -(-(-(-K // split)) // K_STEP) * K_STEP
+
+
+def general_plan(S, H, B):
+    """carve()'s split-K plan of the general path's three weight-gradient GEMMs (K = B):
+    'ac' d[Wa1;Wc1] (2H x H), '2' dW2 (H x H), '1' dW1 (H x S).  Per GEMM: `slabs`, `kchunk`,
+    `lens` (rows of each chunk), `vector` (launch_gemm takes gemm64v: M and N multiples of 4,
+    which the H x H ones always are and dW1 is when S % 4 == 0) and `ktile`, that kernel's
+    K-tile."""
+    t = lambda n: -(-n // 64)  # noqa: E731
+    out = {}
+    for name, tiles, vec in (("ac", t(2 * H) * t(H), True), ("2", t(H) * t(H), True),
+                             ("1", t(H) * t(S), S % 4 == 0)):
+        c = chunk_for(B, split_for(tiles, B))
+        s = -(-B // c)
+        out[name] = dict(slabs=s, kchunk=c, lens=[min(c, B - z * c) for z in range(s)],
+                         vector=vec, ktile=V_K if vec else K_STEP)
+    return out
 
 
 def case_id(c):

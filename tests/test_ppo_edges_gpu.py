@@ -1,8 +1,10 @@
 """The solo fused PPO step and the acting kernels (csrc/ppo_kernels.hip, ppo_rows_body.inc)
 against float64 autograd / the float64 model where the grouped and mixed-width tests only assert
 bit equality with the solo call: hidden widths 320 and 448 (TW 5 / 7, the two-deep weight ring),
-S and B edges, the general path, inputs on which 20-80 % of the rows are clipped, non-default
-log_std and coefficients, and the clip coefficient from the in-kernel gradient norm.  The inputs
+S and B edges, wide fused states (S 260 / 300: 256 < S <= 1,024), the general path's scalar GEMMs
+at S 75 / 30 (test_ppo_general_gpu.py covers that path), inputs on which 20-80 % of the rows are
+clipped, non-default log_std and coefficients, and the clip coefficient from the in-kernel
+gradient norm.  The inputs
 are drawn on the CPU (ppo_ref_util.edge_case); test_ppo_edge_inputs.py checks, without a GPU,
 that they are well conditioned.  Every test prints its measured figures (pytest -s)."""
 
@@ -14,9 +16,9 @@ import torch
 from hwy.native import check, lib, stream_ptr
 from hwy.ppo_native import (_PARAM_ORDER, FusedPPO, PpoActArgs, PpoArgs, PpoDims, _bind, act_tiles,
                             flat_params, fused_act)
-from ppo_ref_util import (ACT_CASES, EXACT_CASES, GRAD_CASES, NORM_CASES, U32, _check_grads,
-                          _fused_relu_masks, _grad64, _torch_grad, act64, act_case, case_id,
-                          case_kwargs, dead_columns, edge_case)
+from ppo_ref_util import (ACT_CASES, EXACT_CASES, GRAD_CASES, GRAD_GENERAL_SHAPES, NORM_CASES, U32,
+                          _check_grads, _fused_relu_masks, _grad64, _torch_grad, act64, act_case,
+                          case_id, case_kwargs, dead_columns, edge_case)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -64,6 +66,8 @@ def test_edge_gradient_matches_autograd(c):
     S, H, B = c[:3]
     a, b, s, z, lp, adv, ret, idx = edge_case(S, H, B, **case_kwargs(c))
     F = FusedPPO(b, B, 1, use_graphs=False)
+    # the cases labelled general, and only those, have no tile image: the label names the path
+    assert (F._tile_off is None) == (c[:3] in GRAD_GENERAL_SHAPES)
     _fused_step(F, F._args(s, z, lp, adv, ret, idx.data_ptr()))
     worst = _parity(F, a, b, s, z, lp, adv, ret, idx)
     print(f"\nEDGE grad {case_id(c)} fused error / gradient scale {worst:.3e}"
