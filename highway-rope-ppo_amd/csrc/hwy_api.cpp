@@ -563,6 +563,65 @@ int hwy_observe(hwy_handle* h, const hwy_observe_args* a, void* stream) {
   return launched(hwy_launch_observe(&p, (hipStream_t)stream), "hwy_observe_kernel");
 }
 
+int hwy_grid_args_size(void) { return (int)sizeof(hwy_grid_args); }
+
+static bool finite_f(float x) { return x > -__builtin_inff() && x < __builtin_inff(); }
+
+int hwy_grid_check(const hwy_grid_args* a) {
+  if (!a) return fail(HWY_EINVAL, "hwy_grid: args is NULL");
+  if (!a->grid && !a->cell_vehicle && !a->veh_cell && !a->counts)
+    return fail(HWY_EINVAL, "hwy_grid: no output given (grid, cell_vehicle, veh_cell and counts "
+                            "are all NULL)");
+  if (a->nx < 1 || a->ny < 1 || a->nx > HWY_GRID_MAX_CELLS || a->ny > HWY_GRID_MAX_CELLS ||
+      a->nx * a->ny > HWY_GRID_MAX_CELLS)
+    return fail(HWY_EINVAL, "hwy_grid: nx and ny must be >= 1 with nx * ny <= %d, got %d x %d",
+                HWY_GRID_MAX_CELLS, a->nx, a->ny);
+  if (!finite_f(a->x0) || !finite_f(a->y0))
+    return fail(HWY_EINVAL, "hwy_grid: x0 and y0 must be finite, got %g, %g", (double)a->x0,
+                (double)a->y0);
+  if (!finite_pos(a->step_x) || !finite_pos(a->step_y))
+    return fail(HWY_EINVAL, "hwy_grid: step_x and step_y must be finite and > 0, got %g, %g",
+                (double)a->step_x, (double)a->step_y);
+  if (a->n_layers < 1 || a->n_layers > HWY_GRID_MAX_LAYERS)
+    return fail(HWY_EINVAL, "hwy_grid: n_layers must lie in 1..%d, got %d", HWY_GRID_MAX_LAYERS,
+                a->n_layers);
+  for (int l = 0; l < a->n_layers; ++l) {
+    if (a->layer_ids[l] < 0 || a->layer_ids[l] > HWY_GRID_ON_ROAD)
+      return fail(HWY_EINVAL, "hwy_grid: layer_ids[%d] must lie in 0..%d, got %d", l,
+                  HWY_GRID_ON_ROAD, a->layer_ids[l]);
+    for (int m = 0; m < l; ++m)
+      if (a->layer_ids[m] == a->layer_ids[l])
+        return fail(HWY_EINVAL, "hwy_grid: layer id %d is given twice (layers %d and %d)",
+                    a->layer_ids[l], m, l);
+    if (a->has_range[l] && (!finite_f(a->range[l][0]) || !finite_f(a->range[l][1]) ||
+                            a->range[l][0] == a->range[l][1]))
+      return fail(HWY_EINVAL, "hwy_grid: range[%d] must be finite with lo != hi, got [%g, %g]", l,
+                  (double)a->range[l][0], (double)a->range[l][1]);
+  }
+  const int cells = a->n_layers * a->nx * a->ny + (a->ego_tail ? 1 : 0);
+  if (a->row_stride < cells || a->row_stride > HWY_GRID_MAX_STRIDE)
+    return fail(HWY_EINVAL, "hwy_grid: row_stride must hold the %d layers of %d x %d%s and be <= "
+                            "%d, got %d", a->n_layers, a->nx, a->ny,
+                a->ego_tail ? " and the ego tail" : "", HWY_GRID_MAX_STRIDE, a->row_stride);
+  return HWY_OK;
+}
+
+int hwy_grid(hwy_handle* h, const hwy_grid_args* a, void* stream) {
+  if (!h) return fail(HWY_EINVAL, "hwy_grid: handle is NULL");
+  if (int rc = hwy_grid_check(a)) return rc;
+  GridParams p;
+  memset(&p, 0, sizeof(p));
+  p.a = *a;
+  p.state = h->state;
+  p.cfg = h->cfg;
+  const int width = a->n_layers * a->nx * a->ny + (a->ego_tail ? h->cfg.n_features : 0);
+  if (a->row_stride < width)
+    return fail(HWY_EINVAL, "hwy_grid: row_stride %d is below the width %d (%d layers of %d x %d "
+                            "and an ego tail of %d)", a->row_stride, width, a->n_layers, a->nx,
+                a->ny, h->cfg.n_features);
+  return launched(hwy_launch_grid(&p, (hipStream_t)stream), "hwy_grid_kernel");
+}
+
 int hwy_traffic_args_size(void) { return (int)sizeof(hwy_traffic_args); }
 
 int hwy_traffic_check(const hwy_traffic_args* a) {

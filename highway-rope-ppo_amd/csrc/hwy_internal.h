@@ -82,7 +82,16 @@ struct LookaheadParams {
   int k0, nk, gate;
 };
 
+// hwy_grid's launch parameters (the grid unit of hwy_kernels.hip): the checked arguments, the
+// handle's state and its config (V, lanes_count and the ego tail's features and ranges)
+struct GridParams {
+  hwy_grid_args a;
+  const uint32_t* state;  // [HWY_NFIELDS][E][64]
+  hwy_config cfg;
+};
+
 extern "C" {
+int hwy_launch_grid(const GridParams* p, hipStream_t s);
 // big: the register budget, hwy_step_big(waves of the launch)
 int hwy_launch_lookahead(const LookaheadParams* p, int big, hipStream_t s);
 int hwy_launch_lookahead_choice(const LookaheadParams* p, hipStream_t s);

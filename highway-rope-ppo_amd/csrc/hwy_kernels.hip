@@ -2181,6 +2181,159 @@ extern "C" int hwy_launch_lookahead_choice(const LookaheadParams* p, hipStream_t
   hipLaunchKernelGGL(hwy_lookahead_choice_kernel, dim3(blocks), dim3(256), 0, s, *p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#elif defined(HWY_GRID_TU)
+// hwy_grid's kernel, likewise a unit of its own (-DHWY_GRID_TU -> hwy_grid.o): the occupancy grid
+// of include/hwy.h.  One wave per env, lane = vehicle, as the step; it loads the five fields the
+// observation reads (x, y, heading, speed, flags), 1,280 B per env, and writes nothing but the
+// outputs it was given.  The owner of every cell lives in per-wave LDS (nx * ny words, dynamic):
+// filled with the sentinel WAVE, then taken with an LDS integer minimum on the vehicle index.
+// Each lane lays its own per-layer values out in lds_val; an output element reads its value
+// through its cell's owner, and consecutive lanes store consecutive floats of the row.  Every
+// cross-lane read runs with all 64 lanes active; an LDS index is the lane, a bounded loop index
+// or a cell index that passed the inside test.
+__global__ void __launch_bounds__(256) hwy_grid_kernel(GridParams P) {
+  extern __shared__ int lds_own_all[];  // [ENVS_PER_BLOCK][nx * ny]
+  __shared__ float lds_val[ENVS_PER_BLOCK][HWY_GRID_MAX_LAYERS][WAVE];
+  __shared__ float lds_tail[ENVS_PER_BLOCK][HWY_MAX_FEATURES];
+  const hwy_config& C = P.cfg;
+  const hwy_grid_args& A = P.a;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int w = threadIdx.x / WAVE;
+  const int e = blockIdx.x * ENVS_PER_BLOCK + w;
+  if (e >= C.num_envs) return;  // whole wave
+  const int V = C.vehicles_count + 1;
+  const int F = C.n_features;
+  const int ncells = A.nx * A.ny;  // <= HWY_GRID_MAX_CELLS
+  int* own = lds_own_all + w * ncells;
+  const size_t fstride = (size_t)C.num_envs * WAVE;
+  const uint32_t idx = (uint32_t)e * WAVE + lane;  // < 2^32: hwy_create bounds num_envs
+  const uint32_t* st = P.state;
+  const float x = hm_bits2f((st + HWY_F_X * fstride)[idx]);
+  const float y = hm_bits2f((st + HWY_F_Y * fstride)[idx]);
+  const float h = hm_bits2f((st + HWY_F_HEADING * fstride)[idx]);
+  const float spd = hm_bits2f((st + HWY_F_SPEED * fstride)[idx]);
+  const uint32_t fl = (st + HWY_F_FLAGS * fstride)[idx];
+  const bool present = ((fl & HWY_FLAG_PRESENT) != 0u) && lane < V;  // load_veh's rule
+  float cos_h, sin_h;
+  hm_sincosf(h, &sin_h, &cos_h);
+  const float ex = rdlf(x, 0), ey = rdlf(y, 0), eh = rdlf(h, 0), espd = rdlf(spd, 0);
+  const float ec = rdlf(cos_h, 0), es = rdlf(sin_h, 0);
+
+  // ---- the cell of this lane's vehicle
+  const float dx = x - ex, dy = y - ey;
+  float u = dx, ww = dy;
+  if (A.align) {
+    u = dx * ec + dy * es;
+    ww = dy * ec - dx * es;
+  }
+  const float qx = (u - A.x0) / A.step_x, qy = (ww - A.y0) / A.step_y;
+  // in float, before any conversion: a NaN or an infinity fails a comparison and is never an index
+  const bool inside =
+      present && qx >= 0.0f && qx < (float)A.nx && qy >= 0.0f && qy < (float)A.ny;
+  int cell = 0;
+  if (inside) cell = (int)hm_floorf(qx) * A.ny + (int)hm_floorf(qy);  // in 0..ncells-1
+
+  // ---- the owners: the least inside vehicle index per cell
+  for (int c = lane; c < ncells; c += WAVE) own[c] = WAVE;
+  wave_lds_sync();
+  if (inside) atomicMin(&own[cell], lane);
+
+  // ---- this vehicle's value per layer, and the ego tail (lane f holds feature f)
+#pragma unroll
+  for (int l = 0; l < HWY_GRID_MAX_LAYERS; ++l)
+    if (l < A.n_layers) {
+      const int fid = A.layer_ids[l];
+      float val = 0.0f;  // the on_road layer reads nothing from here
+      if (fid != HWY_GRID_ON_ROAD) {
+        val = feature_value(fid, x, y, spd, h, cos_h, sin_h);
+        if (is_relative_feature(fid)) val = val - feature_value(fid, ex, ey, espd, eh, ec, es);
+        if (A.has_range[l]) {
+          val = hm_lmap(val, A.range[l][0], A.range[l][1], -1.0f, 1.0f);
+          if (A.clip) val = hm_clipf(val, -1.0f, 1.0f);
+        }
+      }
+      lds_val[w][l][lane] = val;
+    }
+  float tv = 0.0f;
+  if (A.ego_tail) {
+#pragma unroll
+    for (int f = 0; f < HWY_MAX_FEATURES; ++f)
+      if (f < F) {
+        float val = feature_value(C.feature_ids[f], ex, ey, espd, eh, ec, es);
+        if (C.normalize && C.has_range[f]) {
+          val = hm_lmap(val, C.features_range[f][0], C.features_range[f][1], -1.0f, 1.0f);
+          if (C.clip) val = hm_clipf(val, -1.0f, 1.0f);
+        }
+        tv = lane == f ? val : tv;
+      }
+  }
+  if (lane < HWY_MAX_FEATURES) lds_tail[w][lane] = tv;
+  wave_lds_sync();
+
+  // ---- the row: the layers, the ego tail, the padding
+  if (A.grid) {
+    float* row = A.grid + (size_t)e * A.row_stride;
+#pragma unroll
+    for (int l = 0; l < HWY_GRID_MAX_LAYERS; ++l)
+      if (l < A.n_layers) {
+        float* lay = row + l * ncells;
+        if (A.layer_ids[l] == HWY_GRID_ON_ROAD) {
+          const float y_hi = (float)(4 * C.lanes_count - 2);
+          for (int c = lane; c < ncells; c += WAVE) {
+            const int i = c / A.ny, j = c - i * A.ny;
+            const float gx = A.x0 + ((float)i + 0.5f) * A.step_x;
+            const float gy = A.y0 + ((float)j + 0.5f) * A.step_y;
+            float rx = gx, ry = gy;
+            if (A.align) {
+              rx = gx * ec - gy * es;
+              ry = gx * es + gy * ec;
+            }
+            const float X = ex + rx, Y = ey + ry;
+            const bool on = 0.0f <= X && X <= ROAD_LENGTH && -2.0f <= Y && Y < y_hi;
+            lay[c] = on ? 1.0f : 0.0f;
+          }
+        } else {
+          for (int c = lane; c < ncells; c += WAVE) {
+            const int o = own[c];
+            const float val = lds_val[w][l][o < WAVE ? o : 0];
+            lay[c] = o < WAVE ? val : 0.0f;
+          }
+        }
+      }
+    const int base = A.n_layers * ncells;
+    for (int k = base + lane; k < A.row_stride; k += WAVE) {
+      const int f = k - base;
+      const float val = lds_tail[w][f < HWY_MAX_FEATURES ? f : 0];
+      row[k] = (A.ego_tail && f < F) ? val : 0.0f;
+    }
+  }
+  if (A.cell_vehicle)
+    for (int c = lane; c < ncells; c += WAVE) {
+      const int o = own[c];
+      A.cell_vehicle[(size_t)e * ncells + c] = o < WAVE ? o : -1;
+    }
+  if (A.veh_cell) A.veh_cell[idx] = inside ? cell : -1;
+  if (A.counts) {
+    const bool other = present && lane >= 1;
+    bool lost = false;
+    if (inside) lost = own[cell] != lane;
+    const uint64_t otherm = ballot(other);
+    const uint64_t inm = ballot(other && inside);
+    const uint64_t lostm = ballot(other && lost);
+    int cv = __popcll(otherm);
+    cv = lane == 1 ? __popcll(inm) : cv;
+    cv = lane == 2 ? __popcll(lostm) : cv;
+    cv = lane == 3 ? __popcll(otherm & ~inm) : cv;
+    if (lane < 4) A.counts[(size_t)e * 4 + lane] = cv;
+  }
+}
+
+extern "C" int hwy_launch_grid(const GridParams* p, hipStream_t s) {
+  const int blocks = (p->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  const size_t lds = (size_t)ENVS_PER_BLOCK * p->a.nx * p->a.ny * sizeof(int);
+  hipLaunchKernelGGL(hwy_grid_kernel, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), lds, s, *p);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 #else  // the main unit, to the end of the file
 template <int W>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
@@ -2421,4 +2574,4 @@ extern "C" int hwy_debug_sections(unsigned long long* out, int reset) {
 }
 #endif
 #endif  // HWY_CUT_TU / HWY_INFO_TU / HWY_FINAL_TU / HWY_OBSERVE_TU / HWY_TRAFFIC_TU / HWY_SENSE_TU /
-        // HWY_LOOKAHEAD_TU
+        // HWY_LOOKAHEAD_TU / HWY_GRID_TU

@@ -37,7 +37,12 @@ schedule, refused by the grouped launches) and ``shield`` / ``eval_shields`` (a 
 dict, fields ``horizon``, ``fallbacks``, ``lazy``, and {name: such a dict or None}: the run trains
 with the action shield inside its rollout, ``shield_rate`` per update and ``shield`` in the
 metrics, and evaluate(num_episodes=10, shield=...) at the final weights goes in as
-``shield_rewards[name]``; the same restrictions as ``sensor``, and not together with it).
+``shield_rewards[name]``; the same restrictions as ``sensor``, and not together with it) and
+``grid`` (a hwy.GridSpec, its dict, or True for the default: the run trains on an occupancy grid of
+the env states instead of the Kinematics rows -- hwy_grid inside the rollout, ``state_dim`` the
+spec's stride, the run's own evaluations on the same grid, ``grid`` in the metrics; launch() on the
+vectorised loop only, not over a process group, not with ``sensor``, ``shield``, truncation
+"bootstrap" or the reference schedule, refused by the grouped launches).
 
 Launched under torchrun (WORLD_SIZE > 1) one experiment spans the ranks, one GPU each: the
 runner joins the process group (RCCL, or ``HWY_DIST_BACKEND``), gives rank r the envs
@@ -193,6 +198,13 @@ class ExperimentRunner:
                         if group is not None:
                             raise ValueError("extra['shield'] does not run over a process group")
                         stats_kw["shield"] = exp.extra["shield"]
+                    grid = None
+                    if exp.extra.get("grid") not in (None, False):
+                        from hwy._abi import GridSpec
+
+                        if group is not None:
+                            raise ValueError("extra['grid'] does not run over a process group")
+                        grid = stats_kw["grid"] = GridSpec.from_dict(exp.extra["grid"])
                     if group is not None:
                         e = int(overrides.get("num_envs", 1))
                         if e <= 1:
@@ -205,6 +217,11 @@ class ExperimentRunner:
                     if not isinstance(env.observation_space, spaces.Box):
                         raise TypeError(f"Unsupported observation space: {type(env.observation_space)}")
                     state_dim = int(np.prod(env.observation_space.shape))
+                    if grid is not None:  # the policy's input is the grid row, not the rows
+                        if not hasattr(env.unwrapped, "grid_into"):
+                            raise ValueError("extra['grid'] needs the vectorised loop "
+                                             "(extra['num_envs'] > 1)")
+                        state_dim = grid.stride(int(env.unwrapped.hwy_config.n_features))
                     action_dim = env.action_space.shape[0]
                     logger.info(f"[{exp.name}] state_dim={state_dim}, action_dim={action_dim}")
                     # every rank seeds the global RNGs with exp.seed (the RankPE table and the
@@ -292,6 +309,10 @@ class ExperimentRunner:
                                      f"use launch()")
                 if e.extra.get("sensor") is not None:  # any sensor, the null one ({}) too
                     raise ValueError(f"launch_group / launch_batch: extra['sensor'] is not "
+                                     f"supported by the grouped launches (experiment {e.name}); "
+                                     f"use launch()")
+                if e.extra.get("grid") not in (None, False):  # any grid, the default one too
+                    raise ValueError(f"launch_group / launch_batch: extra['grid'] is not "
                                      f"supported by the grouped launches (experiment {e.name}); "
                                      f"use launch()")
                 if e.extra.get("eval_shields"):

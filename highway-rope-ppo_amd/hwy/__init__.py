@@ -15,6 +15,7 @@ from ._abi import (  # noqa: F401
     PE_NONE,
     PE_RANK,
     PE_ROPE,
+    GridSpec,
     HwyConfig,
     SensorModel,
     Shield,

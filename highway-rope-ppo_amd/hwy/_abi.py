@@ -234,6 +234,216 @@ class SensorModel:
         return a
 
 
+class GridArgs(ctypes.Structure):
+    """hwy_grid_args (include/hwy.h): one hwy_grid launch's geometry, layers and outputs."""
+    _fields_ = [
+        ("nx", ctypes.c_int32),
+        ("ny", ctypes.c_int32),
+        ("x0", ctypes.c_float),
+        ("y0", ctypes.c_float),
+        ("step_x", ctypes.c_float),
+        ("step_y", ctypes.c_float),
+        ("align", ctypes.c_int32),
+        ("n_layers", ctypes.c_int32),
+        ("layer_ids", ctypes.c_int32 * 8),
+        ("has_range", ctypes.c_int32 * 8),
+        ("range", (ctypes.c_float * 2) * 8),
+        ("clip", ctypes.c_int32),
+        ("ego_tail", ctypes.c_int32),
+        ("row_stride", ctypes.c_int32),
+        ("grid", ctypes.c_void_p),
+        ("cell_vehicle", ctypes.c_void_p),
+        ("veh_cell", ctypes.c_void_p),
+        ("counts", ctypes.c_void_p),
+    ]
+
+
+GRID_OUTPUTS = ("grid", "cell_vehicle", "veh_cell", "counts")
+GRID_ON_ROAD = 8
+GRID_MAX_LAYERS = 8
+GRID_MAX_CELLS = 1024
+GRID_MAX_STRIDE = 4096
+GRID_LAYERS = dict(FEATURES, on_road=GRID_ON_ROAD)
+(GCOUNT_PRESENT, GCOUNT_INSIDE, GCOUNT_LOST, GCOUNT_OUTSIDE) = range(4)
+
+
+class GridSpec:
+    """The occupancy grid of hwy_grid (include/hwy.h), an immutable, hashable value.
+
+    ``layers``: names out of FEATURES and "on_road", distinct; ``nx`` x ``ny`` cells of
+    ``step_x`` x ``step_y`` metres whose cell 0 has its lower edge at (``x0``, ``y0``) from the
+    ego; ``ranges``: {layer: (lo, hi)} mapped to [-1, 1]; ``clip``: clip the ranged layers;
+    ``align``: the ego's axes instead of the road's; ``ego_tail``: append the ego's own
+    Kinematics row; ``pad_to``: the row stride is the width rounded up to a multiple of it.  The
+    defaults are upstream's OccupancyGrid features over the road ahead: presence, vx and vy on
+    24 x 5 cells of 5 m x 4 m from 32.5 m behind to 87.5 m ahead and 10 m to either side.
+    Everything hwy_grid_check refuses is a ValueError here."""
+
+    __slots__ = ("layers", "nx", "ny", "x0", "y0", "step_x", "step_y", "ranges", "clip", "align",
+                 "ego_tail", "pad_to")
+
+    def __init__(self, layers=("presence", "vx", "vy"), nx: int = 24, ny: int = 5,
+                 x0: float = -32.5, y0: float = -10.0, step_x: float = 5.0, step_y: float = 4.0,
+                 ranges=None, clip: bool = True, align: bool = False, ego_tail: bool = True,
+                 pad_to: int = 4):
+        if ranges is None:  # upstream's, of the layers asked for
+            ranges = {k: (-2 * MAX_SPEED, 2 * MAX_SPEED) for k in ("vx", "vy")
+                      if not isinstance(layers, str) and k in layers}
+        try:
+            lay = tuple(str(n) for n in layers)
+            gx, gy, pad = int(nx), int(ny), int(pad_to)
+            geo = tuple(float(v) for v in (x0, y0, step_x, step_y))
+            items = ranges.items() if isinstance(ranges, dict) else ranges
+            rng = tuple(sorted((str(k), (float(lo), float(hi))) for k, (lo, hi) in items))
+        except (TypeError, ValueError):
+            raise ValueError(f"bad grid fields: layers={layers!r} nx={nx!r} ny={ny!r} x0={x0!r} "
+                             f"y0={y0!r} step_x={step_x!r} step_y={step_y!r} ranges={ranges!r} "
+                             f"pad_to={pad_to!r}") from None
+        if isinstance(layers, str) or not 1 <= len(lay) <= GRID_MAX_LAYERS:
+            raise ValueError(f"a grid takes 1..{GRID_MAX_LAYERS} layers, got {layers!r}")
+        for n in lay:
+            if n not in GRID_LAYERS:
+                raise ValueError(f"unknown grid layer {n!r}; known: {list(GRID_LAYERS)}")
+        if len(set(lay)) != len(lay):
+            raise ValueError(f"a grid layer is given twice: {list(lay)}")
+        if gx != nx or gy != ny or gx < 1 or gy < 1 or gx * gy > GRID_MAX_CELLS:
+            raise ValueError(f"nx and ny must be integers >= 1 with nx * ny <= {GRID_MAX_CELLS}, "
+                             f"got {nx!r} x {ny!r}")
+        if not (math.isfinite(geo[0]) and math.isfinite(geo[1])):
+            raise ValueError(f"x0 and y0 must be finite, got {x0!r}, {y0!r}")
+        if not all(math.isfinite(s) and s > 0.0 for s in geo[2:]):
+            raise ValueError(f"step_x and step_y must be finite and > 0, got {step_x!r}, {step_y!r}")
+        for k, (lo, hi) in rng:
+            if k not in lay or k == "on_road":
+                raise ValueError(f"a range for {k!r}: not a vehicle layer of this grid {list(lay)}")
+            if not (math.isfinite(lo) and math.isfinite(hi)) or lo == hi:
+                raise ValueError(f"range of {k!r} must be finite with lo != hi, got {(lo, hi)!r}")
+        if len(set(k for k, _ in rng)) != len(rng):
+            raise ValueError(f"a range is given twice: {[k for k, _ in rng]}")
+        if pad != pad_to or pad < 1:
+            raise ValueError(f"pad_to must be an integer >= 1, got {pad_to!r}")
+        for name, v in (("layers", lay), ("nx", gx), ("ny", gy), ("x0", geo[0]), ("y0", geo[1]),
+                        ("step_x", geo[2]), ("step_y", geo[3]), ("ranges", rng),
+                        ("clip", bool(clip)), ("align", bool(align)),
+                        ("ego_tail", bool(ego_tail)), ("pad_to", pad)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("GridSpec is immutable")
+
+    def _key(self):
+        return tuple(getattr(self, n) for n in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, GridSpec) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "GridSpec(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+
+    @property
+    def shape(self):
+        """(C, W, H) of the layers: layer, cell along x, cell along y."""
+        return (len(self.layers), self.nx, self.ny)
+
+    def width(self, n_features: int) -> int:
+        """Floats of a row that carry something: the layers and, with ``ego_tail``, the F values
+        of the ego's Kinematics row."""
+        return len(self.layers) * self.nx * self.ny + (int(n_features) if self.ego_tail else 0)
+
+    def stride(self, n_features: int) -> int:
+        """Floats per env: ``width`` rounded up to a multiple of ``pad_to``."""
+        w = self.width(n_features)
+        s = -(-w // self.pad_to) * self.pad_to
+        if s > GRID_MAX_STRIDE:
+            raise ValueError(f"a grid row of {s} floats is above hwy_grid's {GRID_MAX_STRIDE}")
+        return s
+
+    def to_dict(self) -> Dict[str, Any]:
+        """JSON-ready (the metrics file)."""
+        d = {n: getattr(self, n) for n in self.__slots__}
+        d["layers"] = list(self.layers)
+        d["ranges"] = {k: [lo, hi] for k, (lo, hi) in self.ranges}
+        return d
+
+    @classmethod
+    def from_dict(cls, d) -> "GridSpec":
+        """A GridSpec from ``to_dict``'s form (missing keys: the defaults), ``d`` itself when it
+        already is one, the default for True; unknown keys are a ValueError."""
+        if isinstance(d, cls):
+            return d
+        if d is True:
+            return cls()
+        if not isinstance(d, dict):
+            raise ValueError(f"a grid is a GridSpec, True or a dict of its fields, got {d!r}")
+        unknown = set(d) - set(cls.__slots__)
+        if unknown:
+            raise ValueError(f"unknown grid keys {sorted(unknown)}; known: {list(cls.__slots__)}")
+        return cls(**d)
+
+    @classmethod
+    def from_observation_config(cls, obs: Dict[str, Any], *, ego_tail: bool = True,
+                                pad_to: int = 4) -> "GridSpec":
+        """A GridSpec from the keys of upstream's OccupancyGrid observation config: ``features``
+        (with "on_road"), ``grid_size`` [[x lo, x hi], [y lo, y hi]], ``grid_step`` [sx, sy],
+        ``features_range``, ``align_to_vehicle_axes`` and ``clip``, each defaulting as upstream's
+        does; the cell counts are floor((hi - lo) / step) in float64, as upstream takes them.
+        ``absolute`` and ``as_image`` are refused, and so is any other key but ``type``."""
+        if not isinstance(obs, dict):
+            raise ValueError(f"an observation config is a dict, got {obs!r}")
+        known = ("type", "features", "grid_size", "grid_step", "features_range",
+                 "align_to_vehicle_axes", "clip", "absolute", "as_image")
+        unknown = set(obs) - set(known)
+        if unknown:
+            raise ValueError(f"unknown OccupancyGrid keys {sorted(unknown)}; known: {list(known)}")
+        if obs.get("type", "OccupancyGrid") != "OccupancyGrid":
+            raise ValueError(f"not an OccupancyGrid observation config: type {obs.get('type')!r}")
+        if obs.get("absolute"):
+            raise ValueError("an absolute OccupancyGrid is not built: the grid is ego-centred")
+        if obs.get("as_image"):
+            raise ValueError("as_image is not built: the grid is float32")
+        feats = list(obs.get("features") or ["presence", "vx", "vy"])
+        size = obs.get("grid_size") or [[-27.5, 27.5], [-27.5, 27.5]]
+        step = obs.get("grid_step") or [5, 5]
+        try:
+            (xlo, xhi), (ylo, yhi) = ((float(a), float(b)) for a, b in size)
+            sx, sy = (float(s) for s in step)
+        except (TypeError, ValueError):
+            raise ValueError(f"bad grid_size {size!r} or grid_step {step!r}") from None
+        if not (sx > 0.0 and sy > 0.0 and math.isfinite(sx) and math.isfinite(sy)):
+            raise ValueError(f"grid_step must be finite and > 0, got {step!r}")
+        if not all(math.isfinite(v) for v in (xlo, xhi, ylo, yhi)):
+            raise ValueError(f"grid_size must be finite, got {size!r}")
+        franges = obs.get("features_range")
+        if franges is None:  # upstream's defaults, of the layers asked for
+            franges = {"vx": [-2 * MAX_SPEED, 2 * MAX_SPEED], "vy": [-2 * MAX_SPEED, 2 * MAX_SPEED]}
+        ranges = {k: v for k, v in dict(franges).items() if k in feats and k != "on_road"}
+        return cls(layers=feats, nx=int(math.floor((xhi - xlo) / sx)),
+                   ny=int(math.floor((yhi - ylo) / sy)), x0=xlo, y0=ylo, step_x=sx, step_y=sy,
+                   ranges=ranges, clip=bool(obs.get("clip", True)),
+                   align=bool(obs.get("align_to_vehicle_axes", False)), ego_tail=ego_tail,
+                   pad_to=pad_to)
+
+    def fill(self, a: GridArgs, n_features: int) -> GridArgs:
+        """Write the grid's fields into hwy_grid_args ``a`` for a handle of ``n_features``."""
+        a.nx, a.ny = self.nx, self.ny
+        a.x0, a.y0, a.step_x, a.step_y = self.x0, self.y0, self.step_x, self.step_y
+        a.align = int(self.align)
+        a.n_layers = len(self.layers)
+        rng = dict(self.ranges)
+        for i, name in enumerate(self.layers):
+            a.layer_ids[i] = GRID_LAYERS[name]
+            if name in rng:
+                a.has_range[i] = 1
+                a.range[i][0], a.range[i][1] = rng[name]
+        a.clip = int(self.clip)
+        a.ego_tail = int(self.ego_tail)
+        a.row_stride = self.stride(n_features)
+        return a
+
+
 class LookaheadArgs(ctypes.Structure):
     """hwy_lookahead_args (include/hwy.h): one hwy_lookahead call's candidates and outputs."""
     _fields_ = [

@@ -13,8 +13,8 @@ import os
 import subprocess
 from typing import Optional
 
-from ._abi import (HWY_ABI_VERSION, HwyConfig, HwyStepInfo, LookaheadArgs, ObserveArgs, RenderArgs,
-                   SenseArgs, TrafficArgs)
+from ._abi import (HWY_ABI_VERSION, GridArgs, HwyConfig, HwyStepInfo, LookaheadArgs, ObserveArgs,
+                   RenderArgs, SenseArgs, TrafficArgs)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhwy.so")
@@ -94,6 +94,9 @@ def _signatures() -> dict:
         "hwy_lookahead_args_size": [],
         "hwy_lookahead_check": [P(LookaheadArgs)],
         "hwy_lookahead": [vp, P(LookaheadArgs), vp],
+        "hwy_grid_args_size": [],
+        "hwy_grid_check": [P(GridArgs)],
+        "hwy_grid": [vp, P(GridArgs), vp],
         "hwy_export_state": [vp, vp, vp],
         "hwy_import_state": [vp, vp, vp],
         "hwy_obs_pe": [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp],
@@ -126,7 +129,8 @@ def lib():
                                 ("hwy_traffic_args_size", TrafficArgs, "hwy_traffic_args"),
                                 ("hwy_sense_args_size", SenseArgs, "hwy_sense_args"),
                                 ("hwy_lookahead_args_size", LookaheadArgs,
-                                 "hwy_lookahead_args")):
+                                 "hwy_lookahead_args"),
+                                ("hwy_grid_args_size", GridArgs, "hwy_grid_args")):
         if getattr(L, size)() != ctypes.sizeof(mirror):
             raise HwyNativeError(f"libhwy.so's {cname} differs from the python mirror; rebuild")
     if L.hwy_abi_version() != HWY_ABI_VERSION:

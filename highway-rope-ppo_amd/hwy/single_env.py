@@ -112,6 +112,11 @@ class HighwayEnv(Env):
         its dict), an [N, F_out] float32 numpy array."""
         return self._vec.sense(sensor)[0].cpu().numpy()
 
+    def grid(self, spec):
+        """The current occupancy grid row (HighwayVecEnv.grid: a hwy.GridSpec, its dict, or True
+        for the default), a float32 vector of spec.stride(F)."""
+        return self._vec.grid(spec)[0].cpu().numpy()
+
     def lookahead(self, actions, gamma: float = 1.0, obs: bool = False):
         """What-if rollouts from the current state (HighwayVecEnv.lookahead): ``actions`` is a
         [K, H, 2] array of K action sequences; returns a dict of numpy arrays, ``steps``,

@@ -190,6 +190,27 @@ def sense_args(num_envs: int, rows: int, fout: int, device, sensor, order=None, 
     return a
 
 
+def grid_args(num_envs: int, n_features: int, device, spec, *, out=None, cell_vehicle=None,
+              veh_cell=None, counts=None) -> _abi.GridArgs:
+    """hwy_grid_args for ``num_envs`` envs of ``n_features`` Kinematics features on ``device`` from
+    a GridSpec (its dict, or True for the default) and caller-owned tensors, every refusal a
+    ValueError (no device call, no library call)."""
+    g = _abi.GridSpec.from_dict(spec)
+    a = g.fill(_abi.GridArgs(), n_features)
+    E, cells = int(num_envs), g.nx * g.ny
+    outs = (("grid", out, torch.float32, E * a.row_stride, f"E x {a.row_stride}", "out"),
+            ("cell_vehicle", cell_vehicle, torch.int32, E * cells, f"E x {g.nx} x {g.ny}",
+             "cell_vehicle"),
+            ("veh_cell", veh_cell, torch.int32, E * HWY_MAX_VEHICLES, "E x 64", "veh_cell"),
+            ("counts", counts, torch.int32, E * 4, "E x 4", "counts"))
+    for field, t, dtype, n, what, name in outs:
+        if t is not None:
+            setattr(a, field, _dev_tensor(name, t, dtype, n, what, device))
+    if all(t is None for _, t, _, _, _, _ in outs):
+        raise ValueError("grid_into needs at least one of out, cell_vehicle, veh_cell and counts")
+    return a
+
+
 def lookahead_args(num_envs: int, rows: int, fout: int, device, actions, horizon: int, *,
                    hold: bool = False, lazy: bool = False, gamma: float = 1.0, steps=None,
                    terminated=None, truncated=None, rewards=None, ret=None, ego_final=None,
@@ -689,6 +710,41 @@ class HighwayVecEnv:
                               device=self.device)
         self.sense_into(sensor, hidden=out)
         return out.view(self.num_envs, HWY_MAX_VEHICLES)
+
+    def grid_into(self, spec, *, out: Optional[torch.Tensor] = None,
+                  cell_vehicle: Optional[torch.Tensor] = None,
+                  veh_cell: Optional[torch.Tensor] = None,
+                  counts: Optional[torch.Tensor] = None) -> None:
+        """The occupancy grid of the envs' current states (``spec``: a GridSpec, its dict, or
+        True for the default) into caller-owned device tensors (hwy_grid, include/hwy.h: one
+        launch, no synchronisation, graph-capturable).  ``out`` [E, spec.stride(F)] float32: per
+        env the layers [C][nx][ny], the ego's own Kinematics row with ``ego_tail``, zero padding;
+        ``cell_vehicle`` [E, nx, ny] int32: the vehicle that won each cell, -1 for none;
+        ``veh_cell`` [E, 64] int32: each vehicle's flat cell, -1 outside the grid or absent;
+        ``counts`` [E, 4] int32: other vehicles present, inside, inside but without their cell,
+        outside."""
+        a = grid_args(self.num_envs, int(self._cfg.n_features), self.device, spec, out=out,
+                      cell_vehicle=cell_vehicle, veh_cell=veh_cell, counts=counts)
+        check(lib().hwy_grid(self._handle, ctypes.byref(a), stream_ptr()), "hwy_grid")
+        self._keep_grid = (out, cell_vehicle, veh_cell, counts)
+
+    def grid(self, spec, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The current occupancy grid [E, spec.stride(F)] (grid_into's ``out``): the observation
+        a grid-trained policy acts on."""
+        g = _abi.GridSpec.from_dict(spec)
+        stride = g.stride(int(self._cfg.n_features))
+        if out is None:
+            out = torch.empty(self.num_envs, stride, dtype=torch.float32, device=self.device)
+        self.grid_into(g, out=out)
+        return out.view(self.num_envs, stride)
+
+    def grid_cells(self, spec) -> torch.Tensor:
+        """[E, nx, ny] int32: the vehicle that won each cell of the current grid, -1 for none
+        (grid_into's ``cell_vehicle``)."""
+        g = _abi.GridSpec.from_dict(spec)
+        out = torch.empty(self.num_envs, g.nx, g.ny, dtype=torch.int32, device=self.device)
+        self.grid_into(g, cell_vehicle=out)
+        return out
 
     def lookahead_into(self, actions: torch.Tensor, horizon: int, *, hold: bool = False,
                        lazy: bool = False, gamma: float = 1.0, **outputs) -> None:

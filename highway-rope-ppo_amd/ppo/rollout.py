@@ -50,6 +50,14 @@ to ``buf.exec_actions[t]`` and the candidate picked to ``buf.chosen[t]``; the en
 ``exec_actions[t]``.  ``buf.actions``, ``pre_tanh``, ``log_probs`` and ``values`` stay the
 policy's own, so PPO's stored data is untouched.  Not together with ``sensor``, not with
 ``truncation="bootstrap"`` and not on the reference schedule (none of these is tested).
+
+``grid=`` (a hwy.GridSpec, its dict, or True for the default): the policy acts on an occupancy
+grid of the env states instead of the Kinematics rows.  Each env step writes its Kinematics
+observation into the env's own observation buffer, and one hwy_grid launch after it, inside the
+captured graph, writes ``buf.states[t + 1]``; one more on the reset states the caller left writes
+``buf.states[0]``.  ``buf.states`` is ``spec.stride(F)`` wide.  Not with
+``truncation="bootstrap"`` (``final_obs`` would stay a Kinematics row), not on the reference
+schedule (the cut's first observations would), and not with ``sensor`` or ``shield``.
 """
 
 from __future__ import annotations
@@ -114,6 +122,28 @@ def check_shield(shield, truncation: str = "terminal", episode_schedule: str = "
     return shield
 
 
+def check_grid(grid, truncation: str = "terminal", episode_schedule: str = "lockstep", sensor=None,
+               shield=None):
+    """``grid`` as a hwy.GridSpec (None: none), refusing what a grid rollout does not do."""
+    if grid is None:
+        return None
+    from hwy._abi import GridSpec
+
+    grid = GridSpec.from_dict(grid)
+    if truncation == "bootstrap":
+        raise ValueError('grid does not go with truncation="bootstrap": the terminal '
+                         "observations (final_obs) would be Kinematics rows, not grids")
+    if episode_schedule == "reference":
+        raise ValueError('grid does not go with episode_schedule="reference": the first '
+                         "observations after the cut would be Kinematics rows, not grids")
+    if sensor is not None:
+        raise ValueError("grid does not go with sensor: a grid of the perceived vehicles is not "
+                         "built")
+    if shield is not None:
+        raise ValueError("grid does not go with shield: the combination is not tested")
+    return grid
+
+
 def rollout_chunks(T: int, episode_schedule: str):
     """The (t0, t1) step ranges a rollout of T steps is issued (and captured) in: the whole
     rollout, or, for a long reference-schedule rollout, chunks of REFERENCE_GRAPH_CHUNK steps."""
@@ -146,7 +176,7 @@ class LockstepRollout:
     def __init__(self, agent, env, buf, use_graph: bool = True,
                  episode_schedule: str = "lockstep", episode_stats: bool = False,
                  truncation: str = "terminal", safety_stats: bool = False, sensor=None,
-                 shield=None):
+                 shield=None, grid=None):
         self.agent = agent
         self.env = env.unwrapped if hasattr(env, "unwrapped") else env
         self.buf = buf
@@ -154,6 +184,15 @@ class LockstepRollout:
         self.sensor = check_sensor(sensor, truncation, episode_schedule)
         # one hwy_lookahead call per env step, between acting and stepping
         self.shield = check_shield(shield, truncation, episode_schedule, sensor)
+        # one hwy_grid launch per env step (and one now, on the reset states the caller left)
+        self.grid = check_grid(grid, truncation, episode_schedule, sensor, shield)
+        if self.grid is not None:
+            if not hasattr(self.env, "grid_into"):
+                raise ValueError("grid needs a vector env (HighwayVecEnv)")
+            stride = self.grid.stride(int(self.env.hwy_config.n_features))
+            if buf.states.shape[-1] != stride:
+                raise ValueError(f"grid needs a RolloutBuffer of state width {stride} "
+                                 f"(GridSpec.stride), got {buf.states.shape[-1]}")
         if self.shield is not None:
             if not hasattr(self.env, "shield_into"):
                 raise ValueError("shield needs a vector env (HighwayVecEnv)")
@@ -194,6 +233,8 @@ class LockstepRollout:
             traffic_after_reset(self.env, buf)
         if self.sensor is not None:
             self.env.sense_into(self.sensor, obs=buf.states[0])
+        if self.grid is not None:
+            self.env.grid_into(self.grid, out=buf.states[0])
 
     def _launch_key(self):
         from hwy.ppo_native import act_tiles, flat_params
@@ -217,6 +258,8 @@ class LockstepRollout:
             key += (buf.traffic_stats.data_ptr(), buf.traffic_acc.data_ptr())
         if self.sensor is not None:
             key += (self.sensor,)
+        if self.grid is not None:
+            key += (self.grid, env.obs_buf.data_ptr())
         if self.shield is not None:
             key += (self.shield, buf.exec_actions.data_ptr(), buf.chosen.data_ptr())
         return key
@@ -234,7 +277,10 @@ class LockstepRollout:
             if self.shield is not None:
                 executed = buf.exec_actions[t]
                 env.shield_into(self.shield, buf.actions[t], executed, chosen=buf.chosen[t])
-            io = (executed, buf.states[t + 1].view(E, *obs_shape), buf.rewards[t],
+            # under a grid the step's Kinematics rows stay in the env's own buffer
+            next_obs = (env.obs_buf if self.grid is not None
+                        else buf.states[t + 1].view(E, *obs_shape))
+            io = (executed, next_obs, buf.rewards[t],
                   buf.terminated[t], buf.truncated[t], buf.ep_return[t], buf.ep_length[t])
             boot = self.truncation == "bootstrap"
             info = buf.step_info(t) if self.episode_stats else None
@@ -249,6 +295,8 @@ class LockstepRollout:
                                 out=buf.boot_values[t])
             if self.sensor is not None:
                 env.sense_into(self.sensor, obs=buf.states[t + 1])
+            if self.grid is not None:
+                env.grid_into(self.grid, out=buf.states[t + 1])
             if self.safety_stats and not (self.episode_schedule == "reference" and t == buf.T - 1):
                 traffic_after_step(env, buf, t)
         if t1 < buf.T:

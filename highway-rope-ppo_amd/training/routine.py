@@ -70,6 +70,11 @@ None}) books each at the final weights as ``shield_rewards``.  ``shield`` trains
 the rollout (ppo/rollout.py): every update's metrics carry ``shield_rate``, the summary its last
 value, the run's own evaluations use the shield and the metrics carry it as ``shield``.
 ``shield_profile`` counts, on unshielded episodes, the crashes a shield could still have avoided.
+``evaluate(..., grid=G)`` (a hwy.GridSpec, its dict, or True for the default) runs them with the
+policy acting on the occupancy grid of the states (HighwayVecEnv.grid: an observation without a
+row order); ``grid`` trains on one: the rollout writes every state the policy acts on with one
+hwy_grid launch (ppo/rollout.py), the policy's input is ``G.stride(F)`` wide, the run's own
+evaluations act on the same grid and the metrics carry it as ``grid``.
 """
 
 from __future__ import annotations
@@ -96,7 +101,7 @@ def _flat_dim(env) -> int:
 
 # ---------------------------------------------------------------------------------- evaluation
 def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order=None,
-             sensor=None, shield=None, tape=None):
+             sensor=None, shield=None, tape=None, grid=None):
     """Mean return of deterministic episodes seeded exp_seed + 1000 + k.  ``order`` ("sorted" or
     "shuffled"; vector envs only): the same episodes with the policy acting on the states
     re-observed under that row order (HighwayVecEnv.observe) instead of the step's own rows.
@@ -106,7 +111,19 @@ def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order
     policy acts, the shield picks what the env executes (HighwayVecEnv.shield_into) and the return
     is the executed episode's.  ``tape`` (with ``shield``): a list that receives, per step, the
     exported state before it, the policy's actions, the executed actions and the shield's choice
-    as host arrays (tests); a taped evaluation is always run."""
+    as host arrays (tests); a taped evaluation is always run.
+    ``grid`` (a hwy.GridSpec, its dict, or True for the default; not with ``order``, ``sensor`` or
+    ``shield``): the policy acts on the occupancy grid of the states (HighwayVecEnv.grid; on the
+    one-env facade HighwayEnv.grid per step)."""
+    if grid is not None:
+        from hwy._abi import GridSpec
+
+        grid = GridSpec.from_dict(grid)
+        if order is not None or sensor is not None or shield is not None:
+            raise ValueError("evaluate(grid=...) does not go with order, sensor or shield: a grid "
+                             "has no row order, and the other combinations are not built")
+        if _is_vector(env):
+            return _evaluate_vector_grid(env, agent, num_episodes, exp_seed, grid)
     if shield is not None:
         if not _is_vector(env):
             raise ValueError("evaluate(shield=...) needs a HighwayVecEnv (num_envs > 1, or "
@@ -130,13 +147,13 @@ def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order
     totals = []
     for ep in range(num_episodes):
         state, _ = env.reset(seed=exp_seed + 1000 + ep)
-        flat = state.reshape(-1)
+        flat = state.reshape(-1) if grid is None else env.unwrapped.grid(grid)
         done, ep_reward = False, 0.0
         while not done:
             action, _, _, _ = agent.select_action(flat, deterministic=True)
             nxt, reward, terminated, truncated, _ = env.step(action)
             done = terminated or truncated
-            flat = nxt.reshape(-1)
+            flat = nxt.reshape(-1) if grid is None else env.unwrapped.grid(grid)
             ep_reward += reward
         totals.append(ep_reward)
     return float(np.mean(totals))
@@ -216,6 +233,21 @@ def _evaluate_vector_sensor(env, agent, num_episodes, exp_seed, sensor, order):
         return hit[1]
     r = _run_eval_vector(env, agent, num_episodes, exp_seed, order=order, sensor=sensor)
     memo[(sensor, order)] = (key, r)
+    return r
+
+
+def _evaluate_vector_grid(env, agent, num_episodes, exp_seed, grid):
+    """_evaluate_vector for evaluate(grid=...), with a memo of its own keyed by the spec (the
+    other memos are neither read nor written)."""
+    key = _eval_key(agent, num_episodes, exp_seed) + (grid,)
+    memo = getattr(env.unwrapped, "_eval_grid_memo", None)
+    if memo is None:
+        memo = env.unwrapped._eval_grid_memo = {}
+    hit = memo.get(grid)
+    if hit is not None and hit[0] == key and key[0] is not None:
+        return hit[1]
+    r = _run_eval_vector(env, agent, num_episodes, exp_seed, grid=grid)
+    memo[grid] = (key, r)
     return r
 
 
@@ -309,7 +341,7 @@ def shield_profile(env, agent, shield, num_episodes=10, exp_seed: int = 0, tape=
 
 
 def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None, shield=None,
-                     tape=None):
+                     tape=None, grid=None):
     ev = _eval_env(env, num_episodes)
     dev = ev.device
     seeds = torch.arange(num_episodes, device=dev, dtype=torch.int64) + (exp_seed + 1000)
@@ -319,7 +351,9 @@ def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None
     seen = None  # order / sensor given: the states as observed under it, in a buffer of its own
     executed = chosen = None  # shield given: the executed actions and the shield's choice
     for k in range(ev.max_episode_steps + 1):
-        if sensor is not None:
+        if grid is not None:
+            obs = seen = ev.grid(grid, out=seen)
+        elif sensor is not None:
             obs = seen = ev.sense(sensor, order=order, out=seen)
         elif order is not None:
             obs = seen = ev.observe(order=order, out=seen)
@@ -387,7 +421,7 @@ VISUALIZE_TINTS = ("ttc", "hidden")
 
 
 def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, out_dir=None,
-                    attribution=None, tape=None, tint=None, sensor=None):
+                    attribution=None, tape=None, tint=None, sensor=None, grid=None):
     """Deterministic episodes of a trained agent, seeded exp_seed + 2000 + ep, on a fresh env of
     ``env``'s config and fused wrapper (reference training/routine.py:32-58, which opens a
     render_mode="human" window; there is no display here).  All ``num_episodes`` run as one
@@ -402,7 +436,10 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
     frame's state (HighwayVecEnv.traffic_into's ``risk``), or "hidden" to tint the vehicles
     ``sensor`` does not see at the frame's state (HighwayVecEnv.sense_into's ``hidden``); not
     together with ``attribution``.  ``sensor`` (a hwy.SensorModel or its dict): the policy acts on
-    what that sensor perceives, as in evaluate(sensor=...); "hidden" needs it.
+    what that sensor perceives, as in evaluate(sensor=...); "hidden" needs it.  ``grid`` (a
+    hwy.GridSpec, its dict, or True for the default): the policy acts on the occupancy grid of the
+    states, as in evaluate(grid=...); not with ``sensor`` or ``attribution`` (whose overlay is per
+    Kinematics row).
     ``tape``: a list that receives, per grabbed step, (observation, exported state, the episodes
     still recording) as clones (tests)."""
     from hwy.vec_env import HighwayVecEnv
@@ -420,6 +457,12 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
         sensor = SensorModel.from_dict(sensor)
     elif tint == "hidden":
         raise ValueError('tint="hidden" needs a sensor')
+    if grid is not None:
+        from hwy._abi import GridSpec
+
+        grid = GridSpec.from_dict(grid)
+        if sensor is not None or attribution is not None:
+            raise ValueError("visualize_agent(grid=...) does not go with sensor or attribution")
 
     if logger is None:
         logger = logging.getLogger(__name__)
@@ -438,6 +481,8 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
         obs, _ = ev.reset(seeds=seeds)
         if sensor is not None:
             obs = ev.sense(sensor)
+        if grid is not None:
+            obs = ev.grid(grid)
         alive = torch.ones(n, dtype=torch.bool, device=dev)
         total = torch.zeros(n, dtype=torch.float64, device=dev)
         frames = [[] for _ in range(n)]
@@ -467,6 +512,8 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
             obs, r, te, tr, _ = ev.step(a.contiguous())
             if sensor is not None:
                 obs = ev.sense(sensor)
+            if grid is not None:
+                obs = ev.grid(grid)
             total += torch.where(alive, r.double(), torch.zeros_like(total))
             if out_dir is not None:
                 grab()  # the frame after this step, for the episodes that took it
@@ -968,8 +1015,10 @@ class _EvalTracker:
     """Eval / moving-average / checkpoint bookkeeping of routine.py:172-222."""
 
     def __init__(self, env, agent, exp_seed, target_reward, checkpoint_dir, experiment_name,
-                 metrics_history, logger, exp_prefix, start_time, sensor=None, shield=None):
+                 metrics_history, logger, exp_prefix, start_time, sensor=None, shield=None,
+                 grid=None):
         self.env, self.agent, self.exp_seed = env, agent, exp_seed
+        self.grid = grid  # the grid the run trains on: its own evaluations act on it too
         self.sensor = sensor  # the sensor the run trains under: its own evaluations use it too
         self.shield = shield  # likewise the shield (never both)
         self.target_reward = target_reward
@@ -983,7 +1032,8 @@ class _EvalTracker:
         if r is None:
             r = evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed,
                          **({} if self.sensor is None else {"sensor": self.sensor}),
-                         **({} if self.shield is None else {"shield": self.shield}))
+                         **({} if self.shield is None else {"shield": self.shield}),
+                         **({} if self.grid is None else {"grid": self.grid}))
         self.rewards.append(r)
         self.avg_rewards.append(r)
         self.mh["eval_rewards"].append(r)
@@ -998,7 +1048,8 @@ class _EvalTracker:
         if r is None:
             r = evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed,
                          **({} if self.sensor is None else {"sensor": self.sensor}),
-                         **({} if self.shield is None else {"shield": self.shield}))
+                         **({} if self.shield is None else {"shield": self.shield}),
+                         **({} if self.grid is None else {"grid": self.grid}))
         self.rewards.append(r)
         self.eval_episodes.append(episode_num)
         elapsed = time.time() - self.t0
@@ -1027,8 +1078,9 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
                                episode_stats: bool = False, truncation: str = "terminal",
                                attribution: bool = False, eval_orders=None,
                                safety_stats: bool = False, sensor=None, eval_sensors=None,
-                               shield=None, eval_shields=None):
-    from ppo.rollout import check_episode_schedule, check_sensor, check_shield, check_truncation
+                               shield=None, eval_shields=None, grid=None):
+    from ppo.rollout import (check_episode_schedule, check_grid, check_sensor, check_shield,
+                             check_truncation)
 
     if attribution and not _is_vector(env):
         raise ValueError("attribution needs a HighwayVecEnv (num_envs > 1, or make_env's "
@@ -1063,6 +1115,18 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
                              "vector_env key for one env)")
         if getattr(agent, "_dist", None) is not None:
             raise ValueError("shield does not run over a process group")
+
+    grid = check_grid(grid, check_truncation(truncation), check_episode_schedule(episode_schedule),
+                      sensor, shield)
+    if grid is not None:
+        if not _is_vector(env):
+            raise ValueError("grid needs a HighwayVecEnv (num_envs > 1, or make_env's "
+                             "vector_env key for one env)")
+        if getattr(agent, "_dist", None) is not None:
+            raise ValueError("grid does not run over a process group")
+        if attribution or eval_orders or eval_sensors or eval_shields:
+            raise ValueError("grid does not go with attribution, eval_orders, eval_sensors or "
+                             "eval_shields: they evaluate the policy on Kinematics rows")
 
     if check_truncation(truncation) == "bootstrap":
         if not _is_vector(env):
@@ -1122,6 +1186,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         metrics_history["sensor"] = sensor.to_dict()
     if shield is not None:
         metrics_history["shield"] = shield.to_dict()
+    if grid is not None:
+        metrics_history["grid"] = grid.to_dict()
     _book_controls(metrics_history, agent)
     start_time = time.time()
     artifacts_dir = ensure_artifacts_dir()
@@ -1129,7 +1195,7 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
     os.makedirs(checkpoint_dir, exist_ok=True)
     tracker = _EvalTracker(env, agent, exp_seed, target_reward, checkpoint_dir, experiment_name,
                            metrics_history, logger, exp_prefix, start_time, sensor=sensor,
-                           shield=shield)
+                           shield=shield, grid=grid)
     rank, _ = _rank_world(getattr(agent, "_dist", None))
     if rank == 0:
         logger.info(f"{exp_prefix} Performing initial evaluation...")
@@ -1148,6 +1214,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
         sched_kw["sensor"] = sensor
     if shield is not None:
         sched_kw["shield"] = shield
+    if grid is not None:
+        sched_kw["grid"] = grid
     episode_rewards, training_episodes, total_steps = loop(
         env, agent, max_episodes, log_interval, eval_interval, steps_per_update, exp_seed, logger,
         exp_prefix, metrics_history, tracker, start_time, **sched_kw)
@@ -1263,8 +1331,13 @@ def _train_single(env, agent, max_episodes, log_interval, eval_interval, steps_p
 def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_per_update,
                   exp_seed, logger, prefix, mh, tracker, start_time, episode_schedule="lockstep",
                   episode_stats=False, truncation="terminal", safety_stats=False, sensor=None,
-                  shield=None):
+                  shield=None, grid=None):
     """E lockstep envs, device rollout of T steps, batched PPO update.
+
+    grid: the policy acts on the occupancy grid of the env states: the rollout buffer's states are
+    ``grid.stride(F)`` wide, the rollout writes them with one hwy_grid launch on the reset states
+    and one after every env step (ppo/rollout.py); not over a process group, not with a sensor, a
+    shield, truncation "bootstrap" or the reference schedule.
 
     shield: after the policy acted, the rollout's shield (one hwy_lookahead call per step,
     ppo/rollout.py) picks the action the env executes; PPO's stored actions, log-probs and values
@@ -1309,9 +1382,11 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
         raise ValueError("sensor does not run over a process group")
     if shield is not None and group is not None:
         raise ValueError("shield does not run over a process group")
+    if grid is not None and group is not None:
+        raise ValueError("grid does not run over a process group")
     base = env.unwrapped
     E = base.num_envs
-    sd = _flat_dim(env)
+    sd = _flat_dim(env) if grid is None else grid.stride(int(base.hwy_config.n_features))
     T = max(1, math.ceil(steps_per_update / E))
     stats_kw = {"episode_stats": True} if episode_stats else {}
     safety_kw = {"safety_stats": True} if safety_stats else {}
@@ -1320,14 +1395,16 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
                         **({"shield": True} if shield is not None else {}))
     base.set_seed_schedule(exp_seed)
     obs, _ = env.reset()
-    buf.states[0].copy_(obs.reshape(E, sd))
+    if grid is None:  # under a grid the rollout writes states[0] itself, from the reset states
+        buf.states[0].copy_(obs.reshape(E, sd))
     reference = episode_schedule == "reference"
     roll = LockstepRollout(agent, base, buf, use_graph=getattr(agent, "use_graphs", True),
                            **({"episode_schedule": episode_schedule} if reference else {}),
                            **stats_kw, **safety_kw,
                            **({"truncation": truncation} if bootstrap else {}),
                            **({"sensor": sensor} if sensor is not None else {}),
-                           **({"shield": shield} if shield is not None else {}))
+                           **({"shield": shield} if shield is not None else {}),
+                           **({"grid": grid} if grid is not None else {}))
     episode_rewards, training_episodes = [], []
     total_steps = episode_num = 0
     while episode_num < max_episodes:

@@ -6,6 +6,7 @@
     python visualize.py --model <checkpoint> --attribution value     # what the critic looks at
     python visualize.py --model <checkpoint> --tint ttc              # who is about to be hit
     python visualize.py --model <checkpoint> --tint hidden --sensor '{"los": true, "range": 80}'
+    python visualize.py --model <checkpoint> --grid true              # a grid-trained checkpoint
 
 For every checkpoint the network's dimensions are read from the saved weights
 (``shared.0.weight`` is [hidden_dim, state_dim], ``actor_mean.2.weight`` [action_dim,
@@ -22,7 +23,9 @@ vehicle map; training.routine.attribution_shade); ``--tint ttc`` tints them by t
 time-to-collision risk instead (hwy_traffic's ``risk``: 1 - ttc / 4 s below 4 s), and the two
 exclude each other.  ``--sensor JSON`` (hwy.SensorModel's fields) lets the policy act on what that
 sensor perceives (hwy_sense), and ``--tint hidden`` with it tints the vehicles the sensor does not
-see.  There is no live window and no MP4: neither a display nor an encoder is a
+see.  ``--grid JSON`` (hwy.GridSpec's fields, or ``true`` for the default) lets a checkpoint
+trained on the occupancy grid (hwy_grid) drive the episodes: its input width is checked against
+the spec's stride.  There is no live window and no MP4: neither a display nor an encoder is a
 dependency.
 """
 
@@ -98,17 +101,25 @@ def load_agent(path: str, device=None):
 
 def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=None,
            attribution: Optional[str] = None, tint: Optional[str] = None,
-           sensor=None) -> List[float]:
+           sensor=None, grid=None) -> List[float]:
     """Record ``episodes`` episodes of one checkpoint into out_dir/<checkpoint stem>/; returns
     their rewards.  ``attribution`` ("acceleration", "steering" or "value"): tint every vehicle by
     the policy's input-gradient mass on the row that shows it (visualize_agent).  ``tint``
     ("ttc"): tint them by their time-to-collision risk instead; not together with it.  ``sensor``
     (a hwy.SensorModel or its dict): the policy acts on what it perceives, and ``tint`` "hidden"
-    tints the vehicles it does not see."""
+    tints the vehicles it does not see.  ``grid`` (a hwy.GridSpec, its dict, or True): the policy
+    acts on the occupancy grid of the states, as a grid-trained checkpoint expects; not with
+    ``sensor`` or ``attribution``."""
     if tint is not None and attribution is not None:
         raise ValueError("tint and attribution both shade the vehicles: give one of them")
     if tint == "hidden" and sensor is None:
         raise ValueError('tint "hidden" needs a sensor')
+    if grid is not None:
+        from hwy._abi import GridSpec
+
+        grid = GridSpec.from_dict(grid)
+        if sensor is not None or attribution is not None:
+            raise ValueError("grid does not go with sensor or attribution")
     from config.base_config import HIGHWAY_CONFIG
     from experiments.wrappers import make_env
     from training.routine import visualize_agent
@@ -119,6 +130,8 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
                    env_overrides={"vector_env": True, "device": agent.device})
     try:
         have = int(env.observation_space.shape[0] * env.observation_space.shape[1])
+        if grid is not None:
+            have = grid.stride(int(env.unwrapped.hwy_config.n_features))
         want = infer_dims(agent.actor_critic.state_dict())[0]
         if have != want:
             raise ValueError(f"{os.path.basename(path)}: the checkpoint takes {want} inputs, the "
@@ -126,7 +139,8 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
         dest = os.path.join(out_dir, os.path.splitext(os.path.basename(path))[0])
         rewards = visualize_agent(env, agent, num_episodes=episodes, exp_seed=seed, out_dir=dest,
                                   attribution=attribution, **({"tint": tint} if tint else {}),
-                                  **({"sensor": sensor} if sensor is not None else {}))
+                                  **({"sensor": sensor} if sensor is not None else {}),
+                                  **({"grid": grid} if grid is not None else {}))
     finally:
         env.close()
     for ep, r in enumerate(rewards):
@@ -159,6 +173,9 @@ def main(argv=None) -> int:
     p.add_argument("--sensor", default=None, metavar="JSON",
                    help='the policy acts through this sensor, e.g. \'{"los": true, "range": 80, '
                         '"dropout": 0.1, "noise": [0.5, 0.2, 0.5]}\'')
+    p.add_argument("--grid", default=None, metavar="JSON",
+                   help="the policy acts on this occupancy grid (a grid-trained checkpoint), e.g. "
+                        '\'{"nx": 24, "ny": 5, "align": true}\', or true for the default grid')
     args = p.parse_args(argv)
     if args.tint and args.attribution:
         p.error("--tint and --attribution both shade the vehicles: give one of them")
@@ -174,10 +191,23 @@ def main(argv=None) -> int:
             p.error(f"--sensor: {e}")
     if args.tint == "hidden" and sensor is None:
         p.error("--tint hidden needs --sensor")
+    grid = None
+    if args.grid is not None:
+        import json
+
+        from hwy._abi import GridSpec
+
+        try:
+            grid = GridSpec.from_dict(json.loads(args.grid))
+        except ValueError as e:
+            p.error(f"--grid: {e}")
+        if sensor is not None or args.attribution:
+            p.error("--grid does not go with --sensor or --attribution")
     models = [args.model] if args.model else list(models_from_file(args.models_file))
     for m in models:
         record(m, args.out, episodes=args.episodes, seed=args.seed, attribution=args.attribution,
-               tint=args.tint, **({"sensor": sensor} if sensor is not None else {}))
+               tint=args.tint, **({"sensor": sensor} if sensor is not None else {}),
+               **({"grid": grid} if grid is not None else {}))
     return 0
 
 

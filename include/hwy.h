@@ -49,6 +49,8 @@
  *   hwy_traffic               <- env.unwrapped.road.neighbour_vehicles(v) for every vehicle, and the
  *                                gap / time-to-collision / headway a driving study derives from it
  *   hwy_lookahead             <- copy.deepcopy(env) then env.step(a), repeated, for K action sequences
+ *   hwy_grid                  <- OccupancyGridObservation.observe() [highway-env 1.10.1] of a
+ *                                Kinematics env's road (this project's own rule, not upstream's bits)
  *
  * Conventions
  *   - Plain pointers and sizes only; device pointers are HIP device pointers (e.g. torch
@@ -681,6 +683,93 @@ int hwy_lookahead_args_size(void);
  * pure, no device call. */
 int hwy_lookahead_check(const hwy_lookahead_args* a);
 int hwy_lookahead(hwy_handle* h, const hwy_lookahead_args* a, void* stream);
+
+/* ---- An occupancy grid of the env states: an observation without a row order.
+ *
+ * hwy_grid writes, for all E envs and from the state words as they stand, an ego-centred grid:
+ * each vehicle goes into the cell its position falls in, so the result does not depend on any
+ * ordering of the vehicles.  highway-env's OccupancyGridObservation is the model for the defaults
+ * (the Python layer's), for the layout [C][W][H] (layer, cell along x, cell along y), for "the
+ * lower vehicle index wins a cell" and for "empty cells are 0"; the rule itself is this project's
+ * own, stated here, and is not pinned against upstream.  The grid observes a Kinematics env, as
+ * hwy_sense does; "type": "OccupancyGrid" in an env config stays refused.
+ *
+ * All arithmetic is binary32 without contraction, each product rounded before the sum it
+ * enters; a comparison with a NaN is false.  The ego is vehicle 0 at (xe, ye) with heading h_ego,
+ * V = vehicles_count + 1, F the handle's n_features.
+ *
+ * Cell of vehicle k, 0 <= k < V, carrying HWY_FLAG_PRESENT (a flag word in a lane >= V means
+ * nothing, as in the step):
+ *   dx = x_k - xe, dy = y_k - ye
+ *   align != 0: (s, c) = hm_sincosf(h_ego), u = dx*c + dy*s, w = dy*c - dx*s; else u = dx, w = dy
+ *   qx = (u - x0) / step_x, qy = (w - y0) / step_y
+ *   inside iff qx >= 0 && qx < nx && qy >= 0 && qy < ny, tested in float before any conversion:
+ *     -0.0 is inside cell 0, an edge shared by two cells belongs to the upper one,
+ *     x0 + nx*step_x is outside, and a non-finite position is outside and never becomes an index
+ *   i = (int)floorf(qx), j = (int)floorf(qy), the flat cell is i*ny + j
+ * Winner: the present, inside vehicle of least index wins its cell.  The ego is vehicle 0, so it
+ * wins its own cell whenever it is inside the grid.  A crashed vehicle is drawn like any other.
+ *
+ *   grid [E][row_stride] f32: per env, n_layers layers of [nx][ny], then the ego tail, then
+ *     padding.
+ *     Vehicle layer l (layer_ids[l] an enum hwy_feature) in a won cell: the winner's feature value
+ *       (the Kinematics observation's: vx = speed * cos h, ... with hm_sincosf of its heading); for
+ *       x, y, vx and vy minus the ego's value of the same feature (the expression of the
+ *       observation's relative rows, applied to the ego too, whose entries are therefore +0.0);
+ *       then, where has_range[l], hm_lmap(., range[l][0], range[l][1], -1, 1) and, where clip,
+ *       hm_clipf(., -1, 1).  Every other cell of the layer is +0.0.
+ *     HWY_GRID_ON_ROAD layer: 1.0 where the cell's centre is on the road surface by hwy_render's
+ *       layer-2 rule, else +0.0; vehicles do not touch it.  The centre is
+ *       (gx, gy) = (x0 + ((float)i + 0.5f)*step_x, y0 + ((float)j + 0.5f)*step_y) in the grid's
+ *       frame; under align (rx, ry) = (gx*c - gy*s, gx*s + gy*c), else (gx, gy); X = xe + rx,
+ *       Y = ye + ry; on the road iff 0 <= X <= 10000 and -2 <= Y < 4*lanes_count - 2.
+ *     Ego tail (ego_tail != 0): the F values of the handle's own Kinematics row 0 before any
+ *       wrapper -- the ego's absolute feature values with the handle's normalize, has_range,
+ *       features_range and clip as the observation applies them; on a handle without a wrapper,
+ *       bit for bit, hwy_observe's row 0.
+ *     Entries from the width n_layers*nx*ny + (ego_tail ? F : 0) up to row_stride are +0.0.
+ *   cell_vehicle [E][nx][ny] i32: the winner of each cell, -1 for none.
+ *   veh_cell [E][64] i32: the flat cell of each vehicle whether it won or not; -1 when it is
+ *     outside the grid, absent, or k >= V.
+ *   counts [E][4] i32, of the other vehicles (1 <= k < V): present; inside; inside but lost their
+ *     cell; outside.  The second and the fourth add up to the first.
+ *
+ * No entry of a given output is left unwritten and nothing past E*row_stride floats of grid is
+ * touched.  All outputs are device pointers and nullable, but at least one must be given.
+ * hwy_grid is asynchronous, allocates nothing, is hipGraph-capturable, reads the state and writes
+ * nothing but the outputs it was given.  It returns HWY_EINVAL before any device call for a NULL
+ * handle or NULL args, no output at all, nx or ny below 1 or nx*ny above 1024, an x0 or y0 that
+ * is not finite, a step that is not finite and > 0, n_layers outside 1..8, a layer id outside
+ * 0..8 or given twice, a range (of a layer with has_range) with lo == hi or a bound that is not
+ * finite, and a row_stride below the width or above 4096. */
+#define HWY_GRID_ON_ROAD 8
+#define HWY_GRID_MAX_LAYERS 8
+#define HWY_GRID_MAX_CELLS 1024
+#define HWY_GRID_MAX_STRIDE 4096
+typedef struct hwy_grid_args {
+  int32_t nx, ny;          /* cells along x and y, each >= 1, nx*ny <= 1024 */
+  float x0, y0;            /* m, finite: the lower edge of cell 0, relative to the ego */
+  float step_x, step_y;    /* m, finite and > 0 */
+  int32_t align;           /* != 0: the ego's axes instead of the road's */
+  int32_t n_layers;        /* 1..8 */
+  int32_t layer_ids[HWY_GRID_MAX_LAYERS];  /* enum hwy_feature or HWY_GRID_ON_ROAD, distinct */
+  int32_t has_range[HWY_GRID_MAX_LAYERS];  /* layer has a range */
+  float range[HWY_GRID_MAX_LAYERS][2];     /* [lo, hi] per layer, finite, lo != hi */
+  int32_t clip;            /* != 0: clip ranged layers to [-1, 1] */
+  int32_t ego_tail;        /* != 0: append the ego's own Kinematics row */
+  int32_t row_stride;      /* floats per env in grid: width..4096 */
+  float* grid;             /* device [E][row_stride], nullable */
+  int32_t* cell_vehicle;   /* device [E][nx][ny], nullable */
+  int32_t* veh_cell;       /* device [E][64], nullable */
+  int32_t* counts;         /* device [E][4], nullable */
+} hwy_grid_args;
+/* sizeof(hwy_grid_args) as compiled into the library (binding layout check). */
+int hwy_grid_args_size(void);
+/* HWY_OK, or HWY_EINVAL for arguments hwy_grid refuses (every check that needs no handle: of
+ * row_stride, that it holds the layers, one more float with ego_tail, and is at most 4096; the
+ * handle's F enters in hwy_grid); pure, no device call. */
+int hwy_grid_check(const hwy_grid_args* a);
+int hwy_grid(hwy_handle* h, const hwy_grid_args* a, void* stream);
 
 /* Stand-alone observation wrapper on [E,N,F] f32 -> [E,N,F_out] f32 (foreign envs).
  *   kind = enum hwy_pe_kind, d = appended width (rank/dist) or rotate_dim (rope),

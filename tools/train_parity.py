@@ -72,6 +72,9 @@ def main():
     p.add_argument("--order", choices=["sorted", "shuffled"], default=None,
                    help="observation order set explicitly, as bench.py does (default: make_env's own)")
     p.add_argument("--d-embed", type=int, default=4, help="PE d_embed / rotate_dim")
+    p.add_argument("--grid", default=None, metavar="JSON",
+                   help="train on this occupancy grid (extra['grid']: hwy.GridSpec's fields, or "
+                        "true for the default)")
     args = p.parse_args()
 
     out = os.path.abspath(args.out)
@@ -99,7 +102,8 @@ def main():
                 + (f"_obs{args.obs_vehicles}" if args.obs_vehicles else "")
                 + (f"_{args.order}" if args.order else "")
                 + f"_seed{seed}" + (f"_envs{args.num_envs}" if args.num_envs > 1 else "")
-                + (f"_T{args.rollout}_mb{args.minibatches}" if args.rollout else ""))
+                + (f"_T{args.rollout}_mb{args.minibatches}" if args.rollout else "")
+                + ("_grid" if args.grid else ""))
         hp = ConditionHP(lr=args.lr, clip_eps=0.2, epochs=args.epochs, batch_size=64,
                          hidden_dim=args.hidden, d_embed=d_embed)
         hp.entropy_coef = 0.005
@@ -110,6 +114,8 @@ def main():
             extra["num_envs"] = args.num_envs
         if args.minibatches:
             extra["num_minibatches"] = args.minibatches
+        if args.grid:
+            extra["grid"] = json.loads(args.grid)
         exp = Experiment(name=name, condition=cond, hp=hp, seed=seed,
                          max_episodes=args.episodes, target_reward=130.0, extra=extra,
                          env_config_overrides={"observation": obs_over} if obs_over else {})
@@ -128,7 +134,7 @@ def main():
                "minibatches": args.minibatches, "eval_interval": args.eval_interval,
                "lr": args.lr, "epochs": args.epochs, "hidden_dim": args.hidden,
                "obs_vehicles": args.obs_vehicles or 15, "order": args.order or "make_env default",
-               "d_embed": d_embed,
+               "d_embed": d_embed, "grid": res.get("metrics_history", {}).get("grid"),
                "device": torch.cuda.get_device_name(0) if torch.cuda.is_available() else "cpu"}
         if res["status"] == "COMPLETED":
             avg = res["avg_rewards"]
