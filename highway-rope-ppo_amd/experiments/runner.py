@@ -2,47 +2,23 @@
 
 Same launch sequence and status dict: acquire device -> seed -> logger -> make_env ->
 ``env.to(device)`` when the wrapper has it -> state/action dims -> PPOAgent ->
-train_with_experiment_name -> {"status": "COMPLETED"|"FAILED", ...}.  Experiment.extra may carry
-``num_envs`` (lockstep envs, > 1 selects the vectorised loop), ``num_minibatches`` and
-``episode_schedule`` ("lockstep", the default, or "reference": episodes cut at the update
-boundary and evaluations ahead of the update, training/routine.py; with it ``num_envs`` 1 runs
-the vectorised loop on a one-env HighwayVecEnv, which is the reference's own episode stream)
-and ``episode_stats`` (True: per-episode lengths, crashes, mean speeds and lane changes in the
-metrics and a crash rate in the summary, training/routine.py; vectorised loop only) and
-``safety_stats`` (True: one hwy_traffic launch per env step books every episode's least
-time-to-collision, headway, gap and distance and its shares of critical and tailgating states in
-the metrics, and a near-miss rate in the summary, training/routine.py; vectorised loop only, not
-over a process group; training, rewards and weights are bit for bit those without it) and
-``truncation`` ("terminal", the default and the reference's behaviour, or "bootstrap": GAE takes
-V(final observation) at a time limit, ppo/rollout.py; launch() on the vectorised loop only --
-a process group, launch_group and launch_batch refuse it) and ``attribution`` (True: after
-training, training/routine.py's attribution() at the final weights on the evaluations' seeds goes
-into the metrics JSON as ``attribution`` -- mean |input gradient| of acceleration, steering and
-value per observed row, per distance rank and per feature column, with the share on the embedding
-columns and on the ego row; training, rewards and weights are bit for bit those without it;
-launch() on the vectorised loop only -- launch_group and launch_batch refuse it) and
-``eval_orders`` (a list of "sorted" / "shuffled": after training, evaluate(num_episodes=10,
-order=name) at the final weights goes into the metrics JSON as ``order_rewards[name]`` -- the
-evaluation's episodes with the policy acting on the same worlds observed under that row order,
-whatever order it trained on; it draws no random number, so everything else is bit for bit the
-run without it; launch() on the vectorised loop only, refused by the grouped launches likewise)
-and ``eval_sensors`` ({name: sensor dict}, hwy.SensorModel's fields ``los``, ``range``,
-``dropout``, ``noise``, ``salt``: after training, evaluate(num_episodes=10, sensor=...) at the
-final weights goes into the metrics JSON as ``sensor_rewards[name]`` -- the policy acting on what
-that sensor perceives; the training is likewise unchanged, and the grouped launches refuse it) and
-``sensor`` (one such dict: the run *trains* under it -- every state the policy acts on is sensed,
-its own evaluations use the same sensor, the metrics carry it as ``sensor``; launch() on the
-vectorised loop only, not over a process group, not with truncation "bootstrap" or the reference
-schedule, refused by the grouped launches) and ``shield`` / ``eval_shields`` (a hwy.Shield's
-dict, fields ``horizon``, ``fallbacks``, ``lazy``, and {name: such a dict or None}: the run trains
-with the action shield inside its rollout, ``shield_rate`` per update and ``shield`` in the
-metrics, and evaluate(num_episodes=10, shield=...) at the final weights goes in as
-``shield_rewards[name]``; the same restrictions as ``sensor``, and not together with it) and
-``grid`` (a hwy.GridSpec, its dict, or True for the default: the run trains on an occupancy grid of
-the env states instead of the Kinematics rows -- hwy_grid inside the rollout, ``state_dim`` the
-spec's stride, the run's own evaluations on the same grid, ``grid`` in the metrics; launch() on the
-vectorised loop only, not over a process group, not with ``sensor``, ``shield``, truncation
-"bootstrap" or the reference schedule, refused by the grouped launches).
+train_with_experiment_name -> {"status": "COMPLETED"|"FAILED", ...}.
+
+Experiment.extra carries the run's options.  ``num_envs`` (lockstep envs, > 1 selects the
+vectorised loop), ``num_minibatches``, ``log_interval`` and ``eval_interval`` are read here.  The
+run options proper are ppo/options.py's table, which says for each one when it counts as given,
+whether it needs the vectorised loop, whether a process group, launch_group and launch_batch
+take it, and which others it excludes; launch() passes the given ones on to the routine, which
+documents what they do (training/routine.py, ppo/rollout.py):
+  * ``episode_schedule`` "reference" (with it ``num_envs`` 1 runs the vectorised loop on a one-env
+    HighwayVecEnv, which is the reference's own episode stream), ``episode_stats``,
+    ``safety_stats``, ``truncation`` "bootstrap": how the rollout runs and what it books;
+  * ``sensor``, ``shield``, ``grid`` (hwy.SensorModel's / hwy.Shield's / hwy.GridSpec's dict, or
+    True for the default grid): what the policy acts on, or through, while it trains; under a grid
+    ``state_dim`` is the spec's stride;
+  * ``attribution``, ``eval_orders``, ``eval_sensors``, ``eval_shields``: evaluations at the
+    final weights that go into the metrics JSON and leave the training bit for bit what it was;
+  * ``target_kl``, ``lr_anneal_updates``: PPOAgent's KL target and lr schedule.
 
 Launched under torchrun (WORLD_SIZE > 1) one experiment spans the ranks, one GPU each: the
 runner joins the process group (RCCL, or ``HWY_DIST_BACKEND``), gives rank r the envs
@@ -64,6 +40,7 @@ import numpy as np
 import torch
 
 from hwy.gym import spaces
+from ppo import options
 from ppo.agent import PPOAgent
 from training.routine import train_with_experiment_name
 from utils.logging_utils import setup_experiment_logger
@@ -127,8 +104,8 @@ class ExperimentRunner:
                       process_group=None, seed=None):
         extra = extra or {}
         # the KL target and the lr schedule (PPOAgent): passed only where a cell sets them
-        control = {k: extra[k] for k in ("target_kl", "lr_anneal_updates")
-                   if extra.get(k) is not None}
+        control = options.given(**{o.name: extra.get(o.name) for o in options.OPTIONS
+                                   if o.on_agent})
         return PPOAgent(state_dim=state_dim, action_dim=action_dim, lr=hp.lr, gamma=hp.gamma,
                         lam=hp.lam, eps_clip=hp.clip_eps, value_coef=hp.value_coef,
                         entropy_coef=hp.entropy_coef, max_grad_norm=hp.max_grad_norm,
@@ -164,47 +141,22 @@ class ExperimentRunner:
                         overrides.setdefault("num_envs", exp.extra["num_envs"])
                     if device.type == "cuda":
                         overrides.setdefault("device", device)
-                    schedule = exp.extra.get("episode_schedule", "lockstep")
-                    if schedule == "reference":
+                    # the options of exp.extra that are given (ppo/options.py), each passed on
+                    # as it is -- the routine normalises them -- but for the grid, whose spec
+                    # sets the policy's input width here
+                    run_kw = {}
+                    for opt in options.extra_given(exp.extra, options.LAUNCH_ORDER):
+                        if opt.on_agent:  # _create_agent's
+                            continue
+                        if group is not None and opt.group == "launch":
+                            raise ValueError(f"{options.extra_label(opt)} does not run over a "
+                                             f"process group")
+                        run_kw[opt.name] = exp.extra[opt.name]
+                    if run_kw.get("episode_schedule") == "reference":
                         overrides.setdefault("vector_env", True)
-                    stats_kw = ({"episode_stats": True} if exp.extra.get("episode_stats")
-                                else {})
-                    from ppo.rollout import check_truncation
-
-                    truncation = check_truncation(exp.extra.get("truncation", "terminal"))
-                    if truncation != "terminal":
-                        if group is not None:
-                            raise ValueError("extra['truncation']='bootstrap' does not run over "
-                                             "a process group")
-                        stats_kw["truncation"] = truncation
-                    if exp.extra.get("safety_stats"):
-                        if group is not None:
-                            raise ValueError("extra['safety_stats'] does not run over a process "
-                                             "group")
-                        stats_kw["safety_stats"] = True
-                    if exp.extra.get("attribution"):
-                        stats_kw["attribution"] = True
-                    if exp.extra.get("eval_orders"):
-                        stats_kw["eval_orders"] = list(exp.extra["eval_orders"])
-                    if exp.extra.get("eval_sensors"):
-                        stats_kw["eval_sensors"] = dict(exp.extra["eval_sensors"])
-                    if exp.extra.get("sensor") is not None:
-                        if group is not None:
-                            raise ValueError("extra['sensor'] does not run over a process group")
-                        stats_kw["sensor"] = exp.extra["sensor"]
-                    if exp.extra.get("eval_shields"):
-                        stats_kw["eval_shields"] = dict(exp.extra["eval_shields"])
-                    if exp.extra.get("shield") is not None:
-                        if group is not None:
-                            raise ValueError("extra['shield'] does not run over a process group")
-                        stats_kw["shield"] = exp.extra["shield"]
                     grid = None
-                    if exp.extra.get("grid") not in (None, False):
-                        from hwy._abi import GridSpec
-
-                        if group is not None:
-                            raise ValueError("extra['grid'] does not run over a process group")
-                        grid = stats_kw["grid"] = GridSpec.from_dict(exp.extra["grid"])
+                    if "grid" in run_kw:
+                        grid = run_kw["grid"] = options.BY_NAME["grid"].normalise(run_kw["grid"])
                     if group is not None:
                         e = int(overrides.get("num_envs", 1))
                         if e <= 1:
@@ -236,9 +188,7 @@ class ExperimentRunner:
                         log_interval=exp.extra.get("log_interval", 20),
                         eval_interval=exp.extra.get("eval_interval", 50),
                         steps_per_update=exp.hp.steps_per_update, experiment_name=exp.name,
-                        exp_seed=exp.seed, logger=logger,
-                        **({} if schedule == "lockstep" else {"episode_schedule": schedule}),
-                        **stats_kw)
+                        exp_seed=exp.seed, logger=logger, **run_kw)
                     results.update(status="COMPLETED", rewards=rewards, avg_rewards=avg_rewards,
                                    metrics_history=metrics)
                 except Exception as e:
@@ -286,46 +236,17 @@ class ExperimentRunner:
         import math
 
         from ppo.agent import PPOAgent
-        from ppo.rollout import check_episode_schedule, check_truncation
 
         for exps in cells:
             for e in exps:
-                if check_truncation(e.extra.get("truncation", "terminal")) != "terminal":
-                    raise ValueError(f"launch_group / launch_batch: extra['truncation']="
-                                     f"{e.extra['truncation']!r} is not supported by the grouped "
-                                     f"launches (experiment {e.name}); use launch()")
-
-                if e.extra.get("attribution"):
-                    raise ValueError(f"launch_group / launch_batch: extra['attribution'] is not "
-                                     f"supported by the grouped launches (experiment {e.name}); "
-                                     f"use launch()")
-                if e.extra.get("eval_orders"):
-                    raise ValueError(f"launch_group / launch_batch: extra['eval_orders'] is not "
-                                     f"supported by the grouped launches (experiment {e.name}); "
-                                     f"use launch()")
-                if e.extra.get("eval_sensors"):
-                    raise ValueError(f"launch_group / launch_batch: extra['eval_sensors'] is not "
-                                     f"supported by the grouped launches (experiment {e.name}); "
-                                     f"use launch()")
-                if e.extra.get("sensor") is not None:  # any sensor, the null one ({}) too
-                    raise ValueError(f"launch_group / launch_batch: extra['sensor'] is not "
-                                     f"supported by the grouped launches (experiment {e.name}); "
-                                     f"use launch()")
-                if e.extra.get("grid") not in (None, False):  # any grid, the default one too
-                    raise ValueError(f"launch_group / launch_batch: extra['grid'] is not "
-                                     f"supported by the grouped launches (experiment {e.name}); "
-                                     f"use launch()")
-                if e.extra.get("eval_shields"):
-                    raise ValueError(f"launch_group / launch_batch: extra['eval_shields'] is not "
-                                     f"supported by the grouped launches (experiment {e.name}); "
-                                     f"use launch()")
-                if e.extra.get("shield") is not None:  # any shield, the default one ({}) too
-                    raise ValueError(f"launch_group / launch_batch: extra['shield'] is not "
-                                     f"supported by the grouped launches (experiment {e.name}); "
-                                     f"use launch()")
+                for opt in options.extra_given(e.extra, options.GROUPED_ORDER):
+                    if not opt.grouped:
+                        raise ValueError(f"launch_group / launch_batch: "
+                                         f"{options.extra_label(opt)} is not supported by the "
+                                         f"grouped launches (experiment {e.name}); use launch()")
 
         def episode_schedule(e):
-            return check_episode_schedule(e.extra.get("episode_schedule", "lockstep"))
+            return options.extra_value(e.extra, "episode_schedule")
 
         for exps in cells:
             key = {(e.condition, repr(e.hp), repr(sorted(e.extra.items())),
@@ -336,12 +257,9 @@ class ExperimentRunner:
                     and episode_schedule(exps[0]) != "reference"):
                 raise ValueError("launch_group needs extra['num_envs'] > 1 (the vectorised loop)")
         first = [c[0] for c in cells]
-        if len({episode_schedule(e) for e in first}) != 1:
-            raise ValueError("launch_batch: the cells must share extra['episode_schedule']")
-        if len({bool(e.extra.get("episode_stats", False)) for e in first}) != 1:
-            raise ValueError("launch_batch: the cells must share extra['episode_stats']")
-        if len({bool(e.extra.get("safety_stats", False)) for e in first}) != 1:
-            raise ValueError("launch_batch: the cells must share extra['safety_stats']")
+        for name in options.GROUPED_SHARED:  # what selects the launches the cells share
+            if len({options.extra_value(e.extra, name) for e in first}) != 1:
+                raise ValueError(f"launch_batch: the cells must share extra[{name!r}]")
 
         def shared(e):
             return (int(e.extra.get("num_envs", 1)), e.hp.steps_per_update, e.max_episodes,
@@ -396,13 +314,9 @@ class ExperimentRunner:
         t0 = time.time()
         self.check_batch(cells, own_schedules=True)
         first = [c[0] for c in cells]
-        schedule = first[0].extra.get("episode_schedule", "lockstep")
-        # the default schedule passes no keyword: that path is the one without the feature
-        sched_kw = {} if schedule == "lockstep" else {"episode_schedule": schedule}
-        if first[0].extra.get("episode_stats"):
-            sched_kw["episode_stats"] = True
-        if first[0].extra.get("safety_stats"):
-            sched_kw["safety_stats"] = True
+        # a default passes no keyword: that path is the one without the feature
+        sched_kw = {o.name: options.extra_value(first[0].extra, o.name)
+                    for o in options.extra_given(first[0].extra, options.GROUPED_SHARED)}
         results = [[{"experiment_name": e.name, "status": "FAILED"} for e in exps]
                    for exps in cells]
         loggers = []

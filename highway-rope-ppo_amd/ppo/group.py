@@ -35,6 +35,7 @@ from utils.graphs import capture as graph_capture
 from utils.graphs import run_or_replay as _graph_run
 from utils.graphs import run_or_replay_chunks as _graph_run_chunks
 
+from . import options
 from .agent import RolloutBuffer
 from .rollout import (alloc_cut_buffers, check_episode_schedule, rollout_chunks,
                       traffic_after_reset, traffic_after_step)
@@ -79,9 +80,8 @@ class ExperimentGroup:
                                                   for t in rank_tables]))
         N, Fo = self.env.obs_rows, self.env.obs_features
         self.sd = N * Fo
-        self.buf = RolloutBuffer(self.T, self.G * self.E, self.sd, 2, self.dev,
-                                 **({"episode_stats": True} if self.episode_stats else {}),
-                                 **({"safety_stats": True} if self.safety_stats else {}))
+        self.buf = RolloutBuffer(self.T, self.G * self.E, self.sd, 2, self.dev, **options.given(
+            episode_stats=self.episode_stats, safety_stats=self.safety_stats))
         self.use_graphs = bool(use_graphs)
         self.act = GroupAct(self.agents, self.E)
         GE = self.G * self.E
@@ -558,10 +558,8 @@ def build_group(condition, base_config, seeds: Sequence[int], envs_per_experimen
     rank = env.unwrapped.hwy_config.pe_kind == PE_RANK and tables[0] is not None
     grp = ExperimentGroup(agents, env, seeds, E, rollout_len, use_graphs=use_graphs,
                           rank_tables=tables if rank else None,
-                          **({} if episode_schedule == "lockstep"
-                             else {"episode_schedule": episode_schedule}),
-                          **({"episode_stats": True} if episode_stats else {}),
-                          **({"safety_stats": True} if safety_stats else {}))
+                          **options.given(episode_schedule=episode_schedule,
+                                          episode_stats=episode_stats, safety_stats=safety_stats))
     grp.solo_envs = solos
     grp.group_env = env
     return grp

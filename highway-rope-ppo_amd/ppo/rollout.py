@@ -39,25 +39,22 @@ restarted is not counted twice.
 ``sensor=`` (a hwy.SensorModel or its dict): the policy acts on the states as that sensor
 perceives them.  One hwy_sense launch after every env step, inside the captured graph, overwrites
 ``buf.states[t + 1]`` with the sensed observation of the state the step left, and one on the
-reset states the caller left overwrites ``buf.states[0]``; the env step itself is unchanged.  Not
-with ``truncation="bootstrap"`` (``final_obs`` would not be sensed) and not on the reference
-schedule (the cut's first observations would not be).
+reset states the caller left overwrites ``buf.states[0]``; the env step itself is unchanged.
 
 ``shield=`` (a hwy.Shield or its dict): the shield is part of the environment.  After the policy
 acted, one hwy_lookahead call (``env.shield_into``) inside the captured graph rolls the policy's
 action and the shield's fallbacks out from the env's state and writes the action the env executes
 to ``buf.exec_actions[t]`` and the candidate picked to ``buf.chosen[t]``; the env step takes
 ``exec_actions[t]``.  ``buf.actions``, ``pre_tanh``, ``log_probs`` and ``values`` stay the
-policy's own, so PPO's stored data is untouched.  Not together with ``sensor``, not with
-``truncation="bootstrap"`` and not on the reference schedule (none of these is tested).
+policy's own, so PPO's stored data is untouched.
 
 ``grid=`` (a hwy.GridSpec, its dict, or True for the default): the policy acts on an occupancy
 grid of the env states instead of the Kinematics rows.  Each env step writes its Kinematics
 observation into the env's own observation buffer, and one hwy_grid launch after it, inside the
 captured graph, writes ``buf.states[t + 1]``; one more on the reset states the caller left writes
-``buf.states[0]``.  ``buf.states`` is ``spec.stride(F)`` wide.  Not with
-``truncation="bootstrap"`` (``final_obs`` would stay a Kinematics row), not on the reference
-schedule (the cut's first observations would), and not with ``sensor`` or ``shield``.
+``buf.states[0]``.  ``buf.states`` is ``spec.stride(F)`` wide.
+
+Which of these options exclude each other, and why, is ppo/options.py's table.
 """
 
 from __future__ import annotations
@@ -68,80 +65,34 @@ import torch
 
 from utils.graphs import run_or_replay, run_or_replay_chunks
 
-EPISODE_SCHEDULES = ("lockstep", "reference")
-TRUNCATIONS = ("terminal", "bootstrap")
+from . import options
+from .options import EPISODE_SCHEDULES, TRUNCATIONS  # noqa: F401  (this module's names too)
+
 # steps per captured graph of a reference-schedule rollout (2 launches per step)
 REFERENCE_GRAPH_CHUNK = 256
 
-
-def check_episode_schedule(episode_schedule: str) -> str:
-    if episode_schedule not in EPISODE_SCHEDULES:
-        raise ValueError(f"episode_schedule must be one of {EPISODE_SCHEDULES}, "
-                         f"got {episode_schedule!r}")
-    return episode_schedule
-
-
-def check_truncation(truncation: str) -> str:
-    if truncation not in TRUNCATIONS:
-        raise ValueError(f"truncation must be one of {TRUNCATIONS}, got {truncation!r}")
-    return truncation
+check_episode_schedule = options.BY_NAME["episode_schedule"].normalise
+check_truncation = options.BY_NAME["truncation"].normalise
 
 
 def check_sensor(sensor, truncation: str = "terminal", episode_schedule: str = "lockstep"):
     """``sensor`` as a hwy.SensorModel (None: none), refusing what a sensed rollout does not do."""
-    if sensor is None:
-        return None
-    from hwy._abi import SensorModel
-
-    sensor = SensorModel.from_dict(sensor)
-    if truncation == "bootstrap":
-        raise ValueError('sensor does not go with truncation="bootstrap": the terminal '
-                         "observations (final_obs) would not be sensed")
-    if episode_schedule == "reference":
-        raise ValueError('sensor does not go with episode_schedule="reference": the first '
-                         "observations after the cut would not be sensed")
-    return sensor
+    return options.checked("sensor", sensor, truncation=truncation,
+                           episode_schedule=episode_schedule)
 
 
 def check_shield(shield, truncation: str = "terminal", episode_schedule: str = "lockstep",
                  sensor=None):
     """``shield`` as a hwy.Shield (None: none), refusing what a shielded rollout does not do."""
-    if shield is None:
-        return None
-    from hwy._abi import Shield
-
-    shield = Shield.from_dict(shield)
-    if sensor is not None:
-        raise ValueError("shield does not go with sensor: the combination is not tested")
-    if truncation == "bootstrap":
-        raise ValueError('shield does not go with truncation="bootstrap": the combination is '
-                         "not tested")
-    if episode_schedule == "reference":
-        raise ValueError('shield does not go with episode_schedule="reference": the combination '
-                         "is not tested")
-    return shield
+    return options.checked("shield", shield, truncation=truncation,
+                           episode_schedule=episode_schedule, sensor=sensor)
 
 
 def check_grid(grid, truncation: str = "terminal", episode_schedule: str = "lockstep", sensor=None,
                shield=None):
     """``grid`` as a hwy.GridSpec (None: none), refusing what a grid rollout does not do."""
-    if grid is None:
-        return None
-    from hwy._abi import GridSpec
-
-    grid = GridSpec.from_dict(grid)
-    if truncation == "bootstrap":
-        raise ValueError('grid does not go with truncation="bootstrap": the terminal '
-                         "observations (final_obs) would be Kinematics rows, not grids")
-    if episode_schedule == "reference":
-        raise ValueError('grid does not go with episode_schedule="reference": the first '
-                         "observations after the cut would be Kinematics rows, not grids")
-    if sensor is not None:
-        raise ValueError("grid does not go with sensor: a grid of the perceived vehicles is not "
-                         "built")
-    if shield is not None:
-        raise ValueError("grid does not go with shield: the combination is not tested")
-    return grid
+    return options.checked("grid", grid, truncation=truncation, episode_schedule=episode_schedule,
+                           sensor=sensor, shield=shield)
 
 
 def rollout_chunks(T: int, episode_schedule: str):

@@ -18,63 +18,55 @@ Two loops behind it:
     ``agent.update_rollout``.  Episode bookkeeping (logging / eval every ``eval_interval``
     completed episodes, best / solved checkpoints, moving average over the last 10 evals) follows
     the reference, with completed episodes counted in env order within each step.
-``episode_schedule="reference"`` (vectorised loop, train_group, train_batch) runs the reference's
-own schedule (:121-243): after each rollout every running episode is cut (hwy_cut_episodes,
-ppo/rollout.py), booked with its partial return after the rollout's finished episodes and
-bootstrapped with V of its last state; the next rollout starts the schedule's next episodes; and
-the evaluation points that stream crosses are evaluated before the update, on the weights that
-collected it (:173-175).  With one env and T = ``steps_per_update`` that is the reference's
-episode stream, seeds exp_seed + episode_num.  The default, "lockstep", is the loop above.
-``episode_stats=True`` (vectorised loop, train_group, train_batch) steps the envs with
-hwy_step_with_info and books, per episode and in the order of ``episode_rewards`` (cut episodes
-included), ``episode_lengths``, ``episode_crashed``, ``episode_mean_speed`` (sum of the ego's speed
-over the episode's steps / its length) and ``episode_lane_changes`` into metrics_history, and a
-``crash_rate`` column (over the last 100 episodes) into the summary.  The training itself is
-unchanged, bit for bit.
-``safety_stats=True`` (vectorised loop, train_group, train_batch; not over a process group) issues
-one hwy_traffic launch per env step (ppo/rollout.py) and books, per episode and in the order of
-``episode_rewards`` (cut episodes included), ``episode_min_ttc``, ``episode_min_headway``,
-``episode_min_gap``, ``episode_min_distance`` (the least time-to-collision, time headway,
-bumper-to-bumper gap to the front vehicle and centre distance to any vehicle over the states the
-policy acted on; +inf, written to the JSON as null, where the episode never had a front
-vehicle), ``episode_ttc_critical_share`` and ``episode_tailgating_share`` (the share of those
-states with ttc < 2 s and headway < 1 s), and a ``near_miss_rate`` column (the share of the last
-100 episodes whose least ttc was below 2 s) into the summary.  The training itself is unchanged,
-bit for bit.  ``safety_profile`` measures the same over evaluate()'s episodes.
+Which option needs the vectorised loop, which a process group or the grouped launches refuse and
+which exclude each other is ppo/options.py's table; train_with_experiment_name refuses from it in
+one pass before anything runs.  What the options do:
+``episode_schedule="reference"`` runs the reference's own schedule (:121-243): after each rollout
+every running episode is cut (hwy_cut_episodes, ppo/rollout.py), booked with its partial return
+after the rollout's finished episodes and bootstrapped with V of its last state; the next rollout
+starts the schedule's next episodes; and the evaluation points that stream crosses are evaluated
+before the update, on the weights that collected it (:173-175).  With one env and T =
+``steps_per_update`` that is the reference's episode stream, seeds exp_seed + episode_num.  The
+default, "lockstep", is the loop above.
+``episode_stats=True`` steps the envs with hwy_step_with_info and books, per episode and in the
+order of ``episode_rewards`` (cut episodes included), ``episode_lengths``, ``episode_crashed``,
+``episode_mean_speed`` (sum of the ego's speed over the episode's steps / its length) and
+``episode_lane_changes`` into metrics_history, and a ``crash_rate`` column (over the last 100
+episodes) into the summary.  The training itself is unchanged, bit for bit.
+``safety_stats=True`` issues one hwy_traffic launch per env step (ppo/rollout.py) and books, per
+episode likewise, ``episode_min_ttc``, ``episode_min_headway``, ``episode_min_gap``,
+``episode_min_distance`` (the least time-to-collision, time headway, bumper-to-bumper gap to the
+front vehicle and centre distance to any vehicle over the states the policy acted on; +inf,
+written to the JSON as null, where the episode never had a front vehicle),
+``episode_ttc_critical_share`` and ``episode_tailgating_share`` (the share of those states with
+ttc < 2 s and headway < 1 s), and a ``near_miss_rate`` column (the share of the last 100 episodes
+whose least ttc was below 2 s) into the summary.  The training itself is unchanged, bit for bit.
+``safety_profile`` measures the same over evaluate()'s episodes.
 ``evaluate`` runs ``num_episodes`` deterministic episodes seeded exp_seed + 1000 + k (:14-29),
-as one batched env for the vectorised path.
-``attribution`` runs the same episodes and reports what the policy looks at: the mean |input
-gradient| of acceleration, steering and value per observed row, per distance rank and per feature
-column (PPOAgent.input_gradients at every step).  ``attribution=True`` books it, at the final
-weights on the evaluations' seeds, as ``attribution`` in the metrics; it runs after training and
-draws no random number, so the training is unchanged, bit for bit.
+as one batched env for the vectorised path; ``safety_profile``, ``shield_profile`` and
+``attribution`` run the same episodes through the same loop (_run_episodes).
+``attribution`` reports what the policy looks at: the mean |input gradient| of acceleration,
+steering and value per observed row, per distance rank and per feature column
+(PPOAgent.input_gradients at every step).  ``attribution=True`` books it, at the final weights on
+the evaluations' seeds, as ``attribution`` in the metrics; it runs after training and draws no
+random number, so the training is unchanged, bit for bit.
 ``visualize_agent`` (:32-58) runs deterministic episodes seeded exp_seed + 2000 + k and, with
 ``out_dir``, records their frames (HighwayVecEnv.render, one launch per step); there is no window.
 ``attribution="value"`` (or another of ATTRIBUTION_OUTPUTS) tints every vehicle of every frame by
 the policy's input-gradient mass on the observation row that shows it (``attribution_shade``).
 ``tint="ttc"`` tints them by hwy_traffic's ``risk`` instead (1 - ttc / 4 s below 4 s, else 0),
 ``tint="hidden"`` with ``sensor=`` the vehicles that sensor does not see (hwy_sense's ``hidden``).
-``evaluate(..., order="sorted" | "shuffled")`` runs the evaluation's episodes with the policy acting
-on the same worlds observed under that row order (HighwayVecEnv.observe), whatever the env's own
-order is; ``eval_orders`` books both at the final weights as ``order_rewards`` in the metrics.
-``evaluate(..., sensor=S)`` (a hwy.SensorModel or its dict; it combines with ``order``) runs them
-with the policy acting on what that sensor perceives (HighwayVecEnv.sense: line-of-sight
-occlusion, a sensing range, missed detections, position and speed noise); ``eval_sensors``
-({name: sensor}) books each at the final weights as ``sensor_rewards``.  ``sensor`` trains under
-one: the rollout senses every state the policy acts on (ppo/rollout.py), the run's own
-evaluations use the same sensor and the metrics carry it as ``sensor``.
-``evaluate(..., shield=S)`` (a hwy.Shield or its dict) runs them with the shield picking what the
-env executes (HighwayVecEnv.shield_into: the policy's action unless it ends in a crash within the
-shield's horizon, then the first fallback that does not); ``eval_shields`` ({name: shield or
-None}) books each at the final weights as ``shield_rewards``.  ``shield`` trains with one inside
-the rollout (ppo/rollout.py): every update's metrics carry ``shield_rate``, the summary its last
-value, the run's own evaluations use the shield and the metrics carry it as ``shield``.
-``shield_profile`` counts, on unshielded episodes, the crashes a shield could still have avoided.
-``evaluate(..., grid=G)`` (a hwy.GridSpec, its dict, or True for the default) runs them with the
-policy acting on the occupancy grid of the states (HighwayVecEnv.grid: an observation without a
-row order); ``grid`` trains on one: the rollout writes every state the policy acts on with one
-hwy_grid launch (ppo/rollout.py), the policy's input is ``G.stride(F)`` wide, the run's own
-evaluations act on the same grid and the metrics carry it as ``grid``.
+``evaluate(..., order= | sensor= | shield= | grid=)`` runs the evaluation's episodes with the
+policy acting on the same worlds observed under that row order (HighwayVecEnv.observe), as that
+sensor perceives them (HighwayVecEnv.sense; it combines with ``order``), with that shield picking
+what the env executes (HighwayVecEnv.shield_into), or on the occupancy grid of the states
+(HighwayVecEnv.grid); ``eval_orders``, ``eval_sensors`` and ``eval_shields`` book such evaluations
+at the final weights as ``order_rewards``, ``sensor_rewards`` and ``shield_rewards``.
+``sensor`` / ``shield`` / ``grid`` train under one: the rollout applies it at every step
+(ppo/rollout.py), the run's own evaluations use the same one and the metrics carry it under its
+name; a shielded run's updates also carry ``shield_rate`` and the summary its last value, and
+under a grid the policy's input is ``G.stride(F)`` wide.  ``shield_profile`` counts, on unshielded
+episodes, the crashes a shield could still have avoided.
 """
 
 from __future__ import annotations
@@ -88,7 +80,12 @@ import time
 import numpy as np
 import torch
 
+from ppo import options
+from ppo.options import (SAFETY_KEYS, STATS_KEYS, check_eval_orders,  # noqa: F401
+                         check_eval_sensors, check_eval_shields)
 from utils.logging_utils import ensure_artifacts_dir, setup_experiment_logger
+
+CONTROL_KEYS = tuple(o.name for o in options.OPTIONS if o.on_agent)
 
 
 def _is_vector(env) -> bool:
@@ -115,35 +112,33 @@ def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order
     ``grid`` (a hwy.GridSpec, its dict, or True for the default; not with ``order``, ``sensor`` or
     ``shield``): the policy acts on the occupancy grid of the states (HighwayVecEnv.grid; on the
     one-env facade HighwayEnv.grid per step)."""
-    if grid is not None:
-        from hwy._abi import GridSpec
+    from hwy._abi import observe_order
 
-        grid = GridSpec.from_dict(grid)
+    vector = _is_vector(env)
+    grid = options.BY_NAME["grid"].normalise(grid)
+    if grid is not None:
         if order is not None or sensor is not None or shield is not None:
             raise ValueError("evaluate(grid=...) does not go with order, sensor or shield: a grid "
                              "has no row order, and the other combinations are not built")
-        if _is_vector(env):
-            return _evaluate_vector_grid(env, agent, num_episodes, exp_seed, grid)
-    if shield is not None:
-        if not _is_vector(env):
-            raise ValueError("evaluate(shield=...) needs a HighwayVecEnv (num_envs > 1, or "
+    else:
+        # the view the policy acts through is named after the first of these that is given
+        view = next((n for n, v in (("shield", shield), ("sensor", sensor), ("order", order))
+                     if v is not None), None)
+        if view is not None and not vector:
+            raise ValueError(f"evaluate({view}=...) needs a HighwayVecEnv (num_envs > 1, or "
                              "make_env's vector_env key for one env)")
-        if sensor is not None or order is not None:
-            raise ValueError("evaluate(shield=...) does not go with sensor or order: the "
-                             "combination is not tested")
-        return _evaluate_vector_shield(env, agent, num_episodes, exp_seed, shield, tape)
-    if sensor is not None:
-        if not _is_vector(env):
-            raise ValueError("evaluate(sensor=...) needs a HighwayVecEnv (num_envs > 1, or "
-                             "make_env's vector_env key for one env)")
-        return _evaluate_vector_sensor(env, agent, num_episodes, exp_seed, sensor, order)
-    if order is not None:
-        if not _is_vector(env):
-            raise ValueError("evaluate(order=...) needs a HighwayVecEnv (num_envs > 1, or "
-                             "make_env's vector_env key for one env)")
-        return _evaluate_vector_order(env, agent, num_episodes, exp_seed, order)
-    if _is_vector(env):
-        return _evaluate_vector(env, agent, num_episodes, exp_seed)
+        if shield is not None:
+            if sensor is not None or order is not None:
+                raise ValueError("evaluate(shield=...) does not go with sensor or order: the "
+                                 "combination is not tested")
+            shield = options.BY_NAME["shield"].normalise(shield)
+        elif view is not None:
+            sensor = options.BY_NAME["sensor"].normalise(sensor)
+            observe_order(order)  # ValueError for anything but None / "sorted" / "shuffled"
+    if vector:
+        return _evaluate_vector(env, agent, num_episodes, exp_seed, **options.given(
+            order=order, sensor=sensor, shield=shield, grid=grid,
+            tape=None if shield is None else tape))
     totals = []
     for ep in range(num_episodes):
         state, _ = env.reset(seed=exp_seed + 1000 + ep)
@@ -171,6 +166,20 @@ def _eval_env_like(env, num_episodes: int):
     return ev
 
 
+def _cached_env(env, attr: str, num_episodes: int, make=None):
+    """The num_episodes-wide env of ``env``, made once (``make``, default _eval_env_like) and kept
+    on it in the dict ``attr``: ``_eval_envs`` (evaluate), ``_attr_envs``, ``_safety_envs``."""
+    base = env.unwrapped
+    cache = getattr(base, attr, None)
+    if cache is None:
+        cache = {}
+        setattr(base, attr, cache)
+    ev = cache.get(num_episodes)
+    if ev is None:
+        ev = cache[num_episodes] = (make or _eval_env_like)(env, num_episodes)
+    return ev
+
+
 def _eval_key(agent, num_episodes, exp_seed):
     """Identity of a deterministic evaluation: the same weights (no update since, no torch-side
     parameter write) on the same seeds give the same return, bit for bit."""
@@ -184,101 +193,80 @@ def _eval_key(agent, num_episodes, exp_seed):
     return (getattr(agent, "updates", None), params, flat_v, num_episodes, exp_seed, writes)
 
 
-def _evaluate_vector(env, agent, num_episodes, exp_seed):
-    # With thousands of lockstep envs many eval points (every eval_interval completed episodes)
-    # fall between two updates; the evaluation is deterministic, so a repeat at unchanged
-    # weights reuses the last result instead of re-running the episodes.
+def _evaluate_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None, shield=None,
+                     grid=None, tape=None):
+    """_run_eval_vector behind a memo.  With thousands of lockstep envs many eval points (every
+    eval_interval completed episodes) fall between two updates; the evaluation is deterministic,
+    so a repeat at unchanged weights reuses the last result instead of re-running the episodes.
+    Each variant has a memo of its own on the env and neither reads nor writes another's: the
+    plain one is the pair ``_eval_memo``; the others are dicts of such pairs, ``_eval_grid_memo``
+    by spec, ``_eval_shield_memo`` by shield, ``_eval_sensor_memo`` by (sensor, order) and
+    ``_eval_order_memo`` by order, one entry per value ever evaluated on this env, never dropped
+    (a handful for eval_sensors; a caller sweeping many may clear the dict).  A taped run
+    bypasses the memo."""
+    base = env.unwrapped
     key = _eval_key(agent, num_episodes, exp_seed)
-    memo = getattr(env.unwrapped, "_eval_memo", None)
-    if memo is not None and memo[0] == key and key[0] is not None:
-        return memo[1]
-    r = _run_eval_vector(env, agent, num_episodes, exp_seed)
-    env.unwrapped._eval_memo = (key, r)
-    return r
-
-
-def _evaluate_vector_order(env, agent, num_episodes, exp_seed, order):
-    """_evaluate_vector for evaluate(order=...), with a memo of its own keyed by the order too
-    (the order=None memo is neither read nor written)."""
-    from hwy._abi import observe_order
-
-    observe_order(order)  # ValueError for anything but None / "sorted" / "shuffled"
-    key = _eval_key(agent, num_episodes, exp_seed) + (order,)
-    memo = getattr(env.unwrapped, "_eval_order_memo", None)
-    if memo is None:
-        memo = env.unwrapped._eval_order_memo = {}
-    hit = memo.get(order)
-    if hit is not None and hit[0] == key and key[0] is not None:
-        return hit[1]
-    r = _run_eval_vector(env, agent, num_episodes, exp_seed, order=order)
-    memo[order] = (key, r)
-    return r
-
-
-def _evaluate_vector_sensor(env, agent, num_episodes, exp_seed, sensor, order):
-    """_evaluate_vector for evaluate(sensor=...), with a memo of its own keyed by the sensor and
-    the order too (the plain memo and the order memo are neither read nor written)."""
-    from hwy._abi import SensorModel, observe_order
-
-    sensor = SensorModel.from_dict(sensor)
-    observe_order(order)
-    key = _eval_key(agent, num_episodes, exp_seed) + (sensor, order)
-    # one (key, value) pair per (sensor, order) ever evaluated on this env, never dropped: a
-    # handful for eval_sensors; a caller sweeping many sensors may clear env._eval_sensor_memo
-    memo = getattr(env.unwrapped, "_eval_sensor_memo", None)
-    if memo is None:
-        memo = env.unwrapped._eval_sensor_memo = {}
-    hit = memo.get((sensor, order))
-    if hit is not None and hit[0] == key and key[0] is not None:
-        return hit[1]
-    r = _run_eval_vector(env, agent, num_episodes, exp_seed, order=order, sensor=sensor)
-    memo[(sensor, order)] = (key, r)
-    return r
-
-
-def _evaluate_vector_grid(env, agent, num_episodes, exp_seed, grid):
-    """_evaluate_vector for evaluate(grid=...), with a memo of its own keyed by the spec (the
-    other memos are neither read nor written)."""
-    key = _eval_key(agent, num_episodes, exp_seed) + (grid,)
-    memo = getattr(env.unwrapped, "_eval_grid_memo", None)
-    if memo is None:
-        memo = env.unwrapped._eval_grid_memo = {}
-    hit = memo.get(grid)
-    if hit is not None and hit[0] == key and key[0] is not None:
-        return hit[1]
-    r = _run_eval_vector(env, agent, num_episodes, exp_seed, grid=grid)
-    memo[grid] = (key, r)
-    return r
-
-
-def _evaluate_vector_shield(env, agent, num_episodes, exp_seed, shield, tape=None):
-    """_evaluate_vector for evaluate(shield=...), with a memo of its own keyed by the shield (the
-    other memos are neither read nor written); a taped run bypasses it."""
-    from hwy._abi import Shield
-
-    shield = Shield.from_dict(shield)
-    key = _eval_key(agent, num_episodes, exp_seed) + (shield,)
-    memo = getattr(env.unwrapped, "_eval_shield_memo", None)
-    if memo is None:
-        memo = env.unwrapped._eval_shield_memo = {}
-    hit = memo.get(shield)
+    if grid is not None:
+        attr, slot = "_eval_grid_memo", (grid,)
+    elif shield is not None:
+        attr, slot = "_eval_shield_memo", (shield,)
+    elif sensor is not None:
+        attr, slot = "_eval_sensor_memo", (sensor, order)
+    elif order is not None:
+        attr, slot = "_eval_order_memo", (order,)
+    else:
+        attr, slot = "_eval_memo", None
+    memo = getattr(base, attr, None)
+    if slot is None:
+        hit = memo
+    else:
+        key += slot
+        slot = slot[0] if len(slot) == 1 else slot
+        if memo is None:
+            memo = {}
+            setattr(base, attr, memo)
+        hit = memo.get(slot)
     if tape is None and hit is not None and hit[0] == key and key[0] is not None:
         return hit[1]
-    r = _run_eval_vector(env, agent, num_episodes, exp_seed, shield=shield, tape=tape)
-    memo[shield] = (key, r)
+    r = _run_eval_vector(env, agent, num_episodes, exp_seed, **options.given(
+        order=order, sensor=sensor, shield=shield, tape=tape, grid=grid))
+    if slot is None:
+        base._eval_memo = (key, r)
+    else:
+        memo[slot] = (key, r)
     return r
 
 
-def _eval_env(env, num_episodes):
-    """evaluate()'s num_episodes-wide env of ``env``, made once and kept on it"""
-    cache = getattr(env.unwrapped, "_eval_envs", None)
-    if cache is None:
-        cache = {}
-        env.unwrapped._eval_envs = cache
-    ev = cache.get(num_episodes)
-    if ev is None:
-        ev = cache[num_episodes] = _eval_env_like(env, num_episodes)
-    return ev
+def _run_episodes(ev, first_seed: int, act, after_step=None):
+    """One deterministic episode per env of ``ev`` (no autoreset), seeded first_seed + k, all in
+    lockstep: ``act(obs, alive)`` gets the current observation and the mask of the episodes still
+    running and returns the actions the env executes; ``after_step(alive, terminated, truncated)``,
+    if given, sees each step's flags with the mask as it was when the step was taken.  Returns the
+    episodes' returns [n] (float64, on the device), summed under the mask."""
+    n, dev = ev.num_envs, ev.device
+    seeds = torch.arange(n, device=dev, dtype=torch.int64) + first_seed
+    obs, _ = ev.reset(seeds=seeds)
+    alive = torch.ones(n, dtype=torch.bool, device=dev)
+    total = torch.zeros(n, dtype=torch.float64, device=dev)
+    for k in range(ev.max_episode_steps + 1):
+        obs, r, te, tr, _ = ev.step(act(obs, alive).contiguous())
+        total += torch.where(alive, r.double(), torch.zeros_like(total))
+        if after_step is not None:
+            after_step(alive, te, tr)
+        alive &= ~(te.bool() | tr.bool())
+        # the host learns "all done" every 8 steps (one sync instead of eight): the steps after
+        # every episode ended add nothing to total (alive is all False), so the result is the same
+        if k % 8 == 7 and not bool(alive.any()):
+            break
+    return total
+
+
+def _shield_tape(tape, ev, alive, actions, executed, chosen, **more) -> None:
+    """One step of evaluate(shield=...)'s / shield_profile's ``tape``, as host arrays."""
+    if tape is not None:
+        host = dict(actions=actions, executed=executed, chosen=chosen, **more, alive=alive)
+        tape.append(dict(state=ev.export_state().cpu().numpy(),
+                         **{k: v.cpu().numpy().copy() for k, v in host.items()}))
 
 
 def shield_profile(env, agent, shield, num_episodes=10, exp_seed: int = 0, tape=None):
@@ -291,14 +279,12 @@ def shield_profile(env, agent, shield, num_episodes=10, exp_seed: int = 0, tape=
     within the horizon); ``mean_steps0``, the mean steps candidate 0 survives over those states;
     ``reward``, evaluate()'s mean return.  ``tape``: as in evaluate(shield=...), the executed
     actions being the policy's."""
-    from hwy._abi import Shield
-
     if not _is_vector(env):
         raise ValueError("shield_profile needs a HighwayVecEnv (num_envs > 1, or make_env's "
                          "vector_env key for one env)")
-    shield = Shield.from_dict(shield)
+    shield = options.BY_NAME["shield"].normalise(shield)
     n = int(num_episodes)
-    ev = _eval_env(env, n)
+    ev = _cached_env(env, "_eval_envs", n)
     dev = ev.device
     K = shield.k
     cand = torch.zeros(n, K, 2, dtype=torch.float32, device=dev)
@@ -306,34 +292,26 @@ def shield_profile(env, agent, shield, num_episodes=10, exp_seed: int = 0, tape=
     steps = torch.zeros(n, K, dtype=torch.int32, device=dev)
     term = torch.zeros(n, K, dtype=torch.uint8, device=dev)
     chosen = torch.zeros(n, dtype=torch.int32, device=dev)
-    seeds = torch.arange(n, device=dev, dtype=torch.int64) + (exp_seed + 1000)
-    obs, _ = ev.reset(seeds=seeds)
-    alive = torch.ones(n, dtype=torch.bool, device=dev)
-    total = torch.zeros(n, dtype=torch.float64, device=dev)
     count = torch.zeros(5, dtype=torch.int64, device=dev)  # crashes, avoidable, states, overrides, steps0
-    for k in range(ev.max_episode_steps + 1):
+
+    def act(obs, alive):
         a, _, _, _ = agent.select_action(obs.reshape(n, -1), deterministic=True)
         a = a.contiguous()
         cand[:, 0, :].copy_(a.view(n, 2))
         ev.lookahead_into(cand, shield.horizon, hold=True, steps=steps, terminated=term,
                           chosen=chosen)
-        if tape is not None:
-            tape.append(dict(state=ev.export_state().cpu().numpy(), actions=a.cpu().numpy().copy(),
-                             executed=a.cpu().numpy().copy(), chosen=chosen.cpu().numpy().copy(),
-                             steps=steps.cpu().numpy().copy(),
-                             terminated=term.cpu().numpy().copy(), alive=alive.cpu().numpy().copy()))
-        fallback_safe = (term[:, 1:] == 0).any(dim=1)
-        obs, r, te, tr, _ = ev.step(a)
-        total += torch.where(alive, r.double(), torch.zeros_like(total))
+        _shield_tape(tape, ev, alive, a, a, chosen, steps=steps, terminated=term)
+        return a
+
+    def after_step(alive, te, tr):
         crashed = alive & te.bool()
         count[0] += crashed.sum()
-        count[1] += (crashed & fallback_safe).sum()
+        count[1] += (crashed & (term[:, 1:] == 0).any(dim=1)).sum()  # some fallback was safe
         count[2] += alive.sum()
         count[3] += (alive & (chosen != 0)).sum()
         count[4] += torch.where(alive, steps[:, 0].long(), torch.zeros_like(steps[:, 0].long())).sum()
-        alive &= ~(te.bool() | tr.bool())
-        if k % 8 == 7 and not bool(alive.any()):
-            break
+
+    total = _run_episodes(ev, exp_seed + 1000, act, after_step)
     c = [int(x) for x in count.cpu().tolist()]
     return {"episodes": n, "crashes": c[0], "avoidable": c[1], "states": c[2],
             "would_override": c[3], "mean_steps0": c[4] / max(c[2], 1),
@@ -342,15 +320,15 @@ def shield_profile(env, agent, shield, num_episodes=10, exp_seed: int = 0, tape=
 
 def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None, shield=None,
                      tape=None, grid=None):
-    ev = _eval_env(env, num_episodes)
+    ev = _cached_env(env, "_eval_envs", num_episodes)
     dev = ev.device
-    seeds = torch.arange(num_episodes, device=dev, dtype=torch.int64) + (exp_seed + 1000)
-    obs, _ = ev.reset(seeds=seeds)
-    alive = torch.ones(num_episodes, dtype=torch.bool, device=dev)
-    total = torch.zeros(num_episodes, dtype=torch.float64, device=dev)
-    seen = None  # order / sensor given: the states as observed under it, in a buffer of its own
-    executed = chosen = None  # shield given: the executed actions and the shield's choice
-    for k in range(ev.max_episode_steps + 1):
+    seen = None  # grid / sensor / order given: the states as observed under it, in its own buffer
+    if shield is not None:  # the executed actions and the shield's choice
+        executed = torch.zeros(num_episodes, 2, dtype=torch.float32, device=dev)
+        chosen = torch.zeros(num_episodes, dtype=torch.int32, device=dev)
+
+    def act(obs, alive):
+        nonlocal seen
         if grid is not None:
             obs = seen = ev.grid(grid, out=seen)
         elif sensor is not None:
@@ -358,27 +336,14 @@ def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None
         elif order is not None:
             obs = seen = ev.observe(order=order, out=seen)
         a, _, _, _ = agent.select_action(obs.reshape(num_episodes, -1), deterministic=True)
-        if shield is not None:  # the shield picks what the env executes
-            policy_a = a.contiguous()
-            if executed is None:
-                executed = torch.zeros(num_episodes, 2, dtype=torch.float32, device=dev)
-                chosen = torch.zeros(num_episodes, dtype=torch.int32, device=dev)
-            ev.shield_into(shield, policy_a, executed, chosen=chosen)
-            if tape is not None:
-                tape.append(dict(state=ev.export_state().cpu().numpy(),
-                                 actions=policy_a.cpu().numpy().copy(),
-                                 executed=executed.cpu().numpy().copy(),
-                                 chosen=chosen.cpu().numpy().copy(),
-                                 alive=alive.cpu().numpy().copy()))
-            a = executed
-        obs, r, te, tr, _ = ev.step(a.contiguous())
-        total += torch.where(alive, r.double(), torch.zeros_like(total))
-        alive &= ~(te.bool() | tr.bool())
-        # the host learns "all done" every 8 steps (one sync instead of eight): the steps after
-        # every episode ended add nothing to total (alive is all False), so the result is the same
-        if k % 8 == 7 and not bool(alive.any()):
-            break
-    return float(total.mean().item())
+        if shield is None:
+            return a
+        policy_a = a.contiguous()  # the shield picks what the env executes
+        ev.shield_into(shield, policy_a, executed, chosen=chosen)
+        _shield_tape(tape, ev, alive, policy_a, executed, chosen)
+        return executed
+
+    return float(_run_episodes(ev, exp_seed + 1000, act).mean().item())
 
 
 # ---------------------------------------------------------------------------------- visualisation
@@ -442,8 +407,6 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
     Kinematics row).
     ``tape``: a list that receives, per grabbed step, (observation, exported state, the episodes
     still recording) as clones (tests)."""
-    from hwy.vec_env import HighwayVecEnv
-
     if attribution is not None and attribution not in ATTRIBUTION_OUTPUTS:
         raise ValueError(f"attribution must be None or one of {ATTRIBUTION_OUTPUTS}, got "
                          f"{attribution!r}")
@@ -451,18 +414,12 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
         raise ValueError(f"tint must be None or one of {VISUALIZE_TINTS}, got {tint!r}")
     if tint is not None and attribution is not None:
         raise ValueError("tint and attribution both shade the vehicles: give one of them")
-    if sensor is not None:
-        from hwy._abi import SensorModel
-
-        sensor = SensorModel.from_dict(sensor)
-    elif tint == "hidden":
+    sensor = options.BY_NAME["sensor"].normalise(sensor)
+    if sensor is None and tint == "hidden":
         raise ValueError('tint="hidden" needs a sensor')
-    if grid is not None:
-        from hwy._abi import GridSpec
-
-        grid = GridSpec.from_dict(grid)
-        if sensor is not None or attribution is not None:
-            raise ValueError("visualize_agent(grid=...) does not go with sensor or attribution")
+    grid = options.BY_NAME["grid"].normalise(grid)
+    if grid is not None and (sensor is not None or attribution is not None):
+        raise ValueError("visualize_agent(grid=...) does not go with sensor or attribution")
 
     if logger is None:
         logger = logging.getLogger(__name__)
@@ -470,11 +427,7 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
     n = int(num_episodes)
     if n < 1:
         return []
-    base = _vec_base(env)
-    cfg = base.hwy_config
-    ev = HighwayVecEnv(base.config, num_envs=n, device=base.device, autoreset=False,
-                       pe_kind=cfg.pe_kind, d_embed=cfg.d_embed, ego_idx=cfg.ego_idx,
-                       pe_max_dist=cfg.pe_max_dist, pe_table=base._pe_table)
+    ev = _eval_env_like(_vec_base(env), n)
     try:
         dev = ev.device
         seeds = torch.arange(n, device=dev, dtype=torch.int64) + (exp_seed + 2000)
@@ -665,24 +618,16 @@ def attribution(env, agent, num_episodes=10, exp_seed: int = 0, tape=None):
                          "vector_env key for one env)")
     base = env.unwrapped
     cfg = base.hwy_config
-    cache = getattr(base, "_attr_envs", None)
-    if cache is None:
-        cache = base._attr_envs = {}
-    ev = cache.get(num_episodes)
-    if ev is None:
-        ev = cache[num_episodes] = _attribution_env_like(env, num_episodes)
-    dev = ev.device
+    ev = _cached_env(env, "_attr_envs", num_episodes, _attribution_env_like)
     wrap = _obs_wrapper_of(env)
     from hwy._abi import _OBS_DEFAULTS
 
     features = (base.config.get("observation") or {}).get("features") or _OBS_DEFAULTS["features"]
     F = ev.obs_features
-    seeds = torch.arange(num_episodes, device=dev, dtype=torch.int64) + (exp_seed + 1000)
-    base_obs, _ = ev.reset(seeds=seeds)
-    alive = torch.ones(num_episodes, dtype=torch.bool, device=dev)
-    total = torch.zeros(num_episodes, dtype=torch.float64, device=dev)
     sums = None
-    for k in range(ev.max_episode_steps + 1):
+
+    def act(base_obs, alive):
+        nonlocal sums
         obs = wrap(base_obs).reshape(num_episodes, -1)
         g = agent.input_gradients(obs)
         grads = torch.stack([g[n] for n in ATTRIBUTION_OUTPUTS])
@@ -691,12 +636,9 @@ def attribution(env, agent, num_episodes=10, exp_seed: int = 0, tape=None):
             absolute=bool(cfg.absolute)))
         if tape is not None:
             tape.append((base_obs.clone(), obs.clone(), alive.clone()))
-        a, _, _, _ = agent.select_action(obs, deterministic=True)
-        base_obs, r, te, tr, _ = ev.step(a.contiguous())
-        total += torch.where(alive, r.double(), torch.zeros_like(total))
-        alive &= ~(te.bool() | tr.bool())
-        if k % 8 == 7 and not bool(alive.any()):  # as _run_eval_vector: later steps add nothing
-            break
+        return agent.select_action(obs, deterministic=True)[0]
+
+    total = _run_episodes(ev, exp_seed + 1000, act)
     out = attribution_stats(sums, F, int(cfg.ego_idx))
     out["mean_reward"] = float(total.mean().item())
     return out
@@ -706,10 +648,6 @@ _attribution = attribution  # train_with_experiment_name's keyword shadows the n
 
 
 # ---------------------------------------------------------------------------------- safety
-SAFETY_KEYS = ("episode_min_ttc", "episode_min_headway", "episode_min_gap", "episode_min_distance",
-               "episode_ttc_critical_share", "episode_tailgating_share")
-
-
 def safety_row(row) -> tuple:
     """One episode's SAFETY_KEYS values from its hwy_traffic reduction row [8] (float32): the
     four minima as they are, the two counts over the states counted (0 of 0 states: 0)."""
@@ -776,30 +714,18 @@ def safety_profile(env, agent, num_episodes=10, exp_seed: int = 0):
                          "vector_env key for one env)")
     from hwy._abi import HWY_TRAFFIC_NACC, TACC_N
 
-    base = env.unwrapped
-    cache = getattr(base, "_safety_envs", None)
-    if cache is None:
-        cache = base._safety_envs = {}
-    ev = cache.get(num_episodes)
-    if ev is None:
-        ev = cache[num_episodes] = _eval_env_like(env, num_episodes)
-    dev = ev.device
-    seeds = torch.arange(num_episodes, device=dev, dtype=torch.int64) + (exp_seed + 1000)
-    obs, _ = ev.reset(seeds=seeds)
-    alive = torch.ones(num_episodes, dtype=torch.bool, device=dev)
-    total = torch.zeros(num_episodes, dtype=torch.float64, device=dev)
-    acc = torch.zeros(num_episodes, HWY_TRAFFIC_NACC, dtype=torch.float32, device=dev)
+    ev = _cached_env(env, "_safety_envs", num_episodes)
+    acc = torch.zeros(num_episodes, HWY_TRAFFIC_NACC, dtype=torch.float32, device=ev.device)
     rows = torch.zeros_like(acc)
-    for k in range(ev.max_episode_steps + 1):
+
+    def act(obs, alive):
+        nonlocal rows
         # the state the policy is about to act on; a finished episode's row stays as it ended
         ev.traffic_into(acc=acc)
         rows = torch.where(alive[:, None], acc, rows)
-        a, _, _, _ = agent.select_action(obs.reshape(num_episodes, -1), deterministic=True)
-        obs, r, te, tr, _ = ev.step(a.contiguous())
-        total += torch.where(alive, r.double(), torch.zeros_like(total))
-        alive &= ~(te.bool() | tr.bool())
-        if k % 8 == 7 and not bool(alive.any()):  # as _run_eval_vector: later steps add nothing
-            break
+        return agent.select_action(obs.reshape(num_episodes, -1), deterministic=True)[0]
+
+    total = _run_episodes(ev, exp_seed + 1000, act)
     host = rows.cpu().numpy()
     names = [k[len("episode_"):] for k in SAFETY_KEYS]
     per = {n: [] for n in names}
@@ -860,18 +786,10 @@ def _run_eval_group(items, num_episodes):
     from hwy.ppo_native import GroupAct
     from hwy.vec_env import GroupEnvStep
 
-    evs, rows = [], []
+    rows = []
     n, k = num_episodes, len(items)
     agents = [a for _, a, _ in items]
-    for env, agent, seed in items:
-        cache = getattr(env.unwrapped, "_eval_envs", None)
-        if cache is None:
-            cache = {}
-            env.unwrapped._eval_envs = cache
-        ev = cache.get(n)
-        if ev is None:
-            ev = cache[n] = _eval_env_like(env, n)
-        evs.append(ev)
+    evs = [_cached_env(env, "_eval_envs", n) for env, _, _ in items]
     dev = evs[0].device
     act = GroupAct(agents, n)
     tiles = act.tiles()
@@ -962,21 +880,6 @@ def _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_hist
     logger.info(f"{exp_prefix} Summary CSV saved to {csv_path}")
 
 
-CONTROL_KEYS = ("target_kl", "lr_anneal_updates")
-
-
-def _book_controls(mh, agent) -> None:
-    """The agent's KL target and lr schedule into the metrics, where set (the default's metrics
-    stay what they were, as with truncation)."""
-    for k in CONTROL_KEYS:
-        v = getattr(agent, k, None)
-        if v is not None:
-            mh[k] = v
-
-
-STATS_KEYS = ("episode_lengths", "episode_crashed", "episode_mean_speed", "episode_lane_changes")
-
-
 def crash_rate(crashed, last: int = 100) -> float:
     """Share of the last ``last`` booked episodes that ended in a crash (0 with none booked)."""
     tail = list(crashed)[-last:]
@@ -1028,12 +931,13 @@ class _EvalTracker:
         self.best = -float("inf")
         self.solved = False
 
+    def _evaluate(self):
+        return evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed,
+                        **options.given(sensor=self.sensor, shield=self.shield, grid=self.grid))
+
     def initial(self, r=None):
         if r is None:
-            r = evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed,
-                         **({} if self.sensor is None else {"sensor": self.sensor}),
-                         **({} if self.shield is None else {"shield": self.shield}),
-                         **({} if self.grid is None else {"grid": self.grid}))
+            r = self._evaluate()
         self.rewards.append(r)
         self.avg_rewards.append(r)
         self.mh["eval_rewards"].append(r)
@@ -1046,10 +950,7 @@ class _EvalTracker:
         """r: the evaluation's result when the caller ran it (evaluate_many), else evaluated here."""
         self.logger.info(f"{self.prefix} Evaluating at episode {episode_num}...")
         if r is None:
-            r = evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed,
-                         **({} if self.sensor is None else {"sensor": self.sensor}),
-                         **({} if self.shield is None else {"shield": self.shield}),
-                         **({} if self.grid is None else {"grid": self.grid}))
+            r = self._evaluate()
         self.rewards.append(r)
         self.eval_episodes.append(episode_num)
         elapsed = time.time() - self.t0
@@ -1079,202 +980,87 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
                                attribution: bool = False, eval_orders=None,
                                safety_stats: bool = False, sensor=None, eval_sensors=None,
                                shield=None, eval_shields=None, grid=None):
-    from ppo.rollout import (check_episode_schedule, check_grid, check_sensor, check_shield,
-                             check_truncation)
-
-    if attribution and not _is_vector(env):
-        raise ValueError("attribution needs a HighwayVecEnv (num_envs > 1, or make_env's "
-                         "vector_env key for one env)")
-    eval_orders = check_eval_orders(eval_orders)
-    if eval_orders and not _is_vector(env):
-        raise ValueError("eval_orders needs a HighwayVecEnv (num_envs > 1, or make_env's "
-                         "vector_env key for one env)")
-
-    eval_sensors = check_eval_sensors(eval_sensors)
-    if eval_sensors and not _is_vector(env):
-        raise ValueError("eval_sensors needs a HighwayVecEnv (num_envs > 1, or make_env's "
-                         "vector_env key for one env)")
-    sensor = check_sensor(sensor, check_truncation(truncation),
-                          check_episode_schedule(episode_schedule))
-    if sensor is not None:
-        if not _is_vector(env):
-            raise ValueError("sensor needs a HighwayVecEnv (num_envs > 1, or make_env's "
-                             "vector_env key for one env)")
-        if getattr(agent, "_dist", None) is not None:
-            raise ValueError("sensor does not run over a process group")
-
-    eval_shields = check_eval_shields(eval_shields)
-    if eval_shields and not _is_vector(env):
-        raise ValueError("eval_shields needs a HighwayVecEnv (num_envs > 1, or make_env's "
-                         "vector_env key for one env)")
-    shield = check_shield(shield, check_truncation(truncation),
-                          check_episode_schedule(episode_schedule), sensor)
-    if shield is not None:
-        if not _is_vector(env):
-            raise ValueError("shield needs a HighwayVecEnv (num_envs > 1, or make_env's "
-                             "vector_env key for one env)")
-        if getattr(agent, "_dist", None) is not None:
-            raise ValueError("shield does not run over a process group")
-
-    grid = check_grid(grid, check_truncation(truncation), check_episode_schedule(episode_schedule),
-                      sensor, shield)
-    if grid is not None:
-        if not _is_vector(env):
-            raise ValueError("grid needs a HighwayVecEnv (num_envs > 1, or make_env's "
-                             "vector_env key for one env)")
-        if getattr(agent, "_dist", None) is not None:
-            raise ValueError("grid does not run over a process group")
-        if attribution or eval_orders or eval_sensors or eval_shields:
-            raise ValueError("grid does not go with attribution, eval_orders, eval_sensors or "
-                             "eval_shields: they evaluate the policy on Kinematics rows")
-
-    if check_truncation(truncation) == "bootstrap":
-        if not _is_vector(env):
-            raise ValueError("truncation='bootstrap' needs a HighwayVecEnv (num_envs > 1, or "
-                             "make_env's vector_env key for one env); the one-env reference loop "
-                             "books a time limit as terminal")
-        if getattr(agent, "_dist", None) is not None:
-            raise ValueError("truncation='bootstrap' does not run over a process group")
-
-    if episode_stats:
-        if not _is_vector(env):
-            raise ValueError("episode_stats needs a HighwayVecEnv (num_envs > 1, or make_env's "
-                             "vector_env key for one env)")
-        if getattr(agent, "_dist", None) is not None:
-            raise ValueError("episode_stats does not run over a process group")
-
-    if safety_stats:
-        if not _is_vector(env):
-            raise ValueError("safety_stats needs a HighwayVecEnv (num_envs > 1, or make_env's "
-                             "vector_env key for one env)")
-        if getattr(agent, "_dist", None) is not None:
-            raise ValueError("safety_stats does not run over a process group")
-
-    for k in CONTROL_KEYS:
-        if getattr(agent, k, None) is not None and not _is_vector(env):
-            raise ValueError(f"{k} needs a HighwayVecEnv (num_envs > 1, or make_env's vector_env "
-                             "key for one env); the one-env reference loop does not take it")
-
-    if check_episode_schedule(episode_schedule) == "reference":
-        if getattr(agent, "_dist", None) is not None:
-            raise ValueError("episode_schedule='reference' does not run over a process group")
-        if not _is_vector(env):
-            raise ValueError("episode_schedule='reference' needs a HighwayVecEnv (make_env's "
-                             "vector_env key for one env); the one-env facade already runs the "
-                             "reference loop")
+    group = getattr(agent, "_dist", None)
+    # every option normalised, and every refusal (ppo/options.py's table, in its ROUTINE_ORDER)
+    opts = options.check_run(
+        dict(episode_schedule=episode_schedule, episode_stats=episode_stats,
+             truncation=truncation, attribution=attribution, eval_orders=eval_orders,
+             safety_stats=safety_stats, sensor=sensor, eval_sensors=eval_sensors, shield=shield,
+             eval_shields=eval_shields, grid=grid, **_controls_of(agent)),
+        lambda: _is_vector(env), group is not None)
     if logger is None:
         logger = setup_experiment_logger(experiment_name)
     exp_prefix = f"[{experiment_name}]" if experiment_name else ""
     logger.info(f"{exp_prefix} Starting training for experiment: {experiment_name}")
-    metrics_history = {
-        "experiment_name": experiment_name,
-        "episode_rewards": [],
-        "eval_rewards": [],
-        "avg_eval_rewards": [],
-        "policy_updates": [],
-        "episode_numbers": [],
-        "eval_episode_numbers": [],
-        "timestamps": [],
-    }
-    if episode_stats:
-        metrics_history.update({k: [] for k in STATS_KEYS})
-    if safety_stats:
-        metrics_history.update({k: [] for k in SAFETY_KEYS})
-    if truncation != "terminal":  # the default's metrics stay what they were
-        metrics_history["truncation"] = truncation
-    if sensor is not None:
-        metrics_history["sensor"] = sensor.to_dict()
-    if shield is not None:
-        metrics_history["shield"] = shield.to_dict()
-    if grid is not None:
-        metrics_history["grid"] = grid.to_dict()
-    _book_controls(metrics_history, agent)
+    metrics_history = _new_metrics(experiment_name, opts)
     start_time = time.time()
     artifacts_dir = ensure_artifacts_dir()
     checkpoint_dir = os.path.join(artifacts_dir, "checkpoints")
     os.makedirs(checkpoint_dir, exist_ok=True)
     tracker = _EvalTracker(env, agent, exp_seed, target_reward, checkpoint_dir, experiment_name,
-                           metrics_history, logger, exp_prefix, start_time, sensor=sensor,
-                           shield=shield, grid=grid)
-    rank, _ = _rank_world(getattr(agent, "_dist", None))
+                           metrics_history, logger, exp_prefix, start_time, sensor=opts["sensor"],
+                           shield=opts["shield"], grid=opts["grid"])
+    rank, _ = _rank_world(group)
     if rank == 0:
         logger.info(f"{exp_prefix} Performing initial evaluation...")
         tracker.initial()
-    if not _is_vector(env) and getattr(agent, "_dist", None) is not None:
+    if not _is_vector(env) and group is not None:
         raise ValueError("a process group needs the vectorised env (num_envs > 1)")
     loop = _train_vector if _is_vector(env) else _train_single
-    sched_kw = {} if episode_schedule == "lockstep" else {"episode_schedule": episode_schedule}
-    if episode_stats:
-        sched_kw["episode_stats"] = True
-    if truncation != "terminal":
-        sched_kw["truncation"] = truncation
-    if safety_stats:
-        sched_kw["safety_stats"] = True
-    if sensor is not None:
-        sched_kw["sensor"] = sensor
-    if shield is not None:
-        sched_kw["shield"] = shield
-    if grid is not None:
-        sched_kw["grid"] = grid
+    # the default passes no keyword: that path is the one without the feature
+    loop_kw = options.given(**{o.name: opts[o.name] for o in options.OPTIONS if o.rollout})
     episode_rewards, training_episodes, total_steps = loop(
         env, agent, max_episodes, log_interval, eval_interval, steps_per_update, exp_seed, logger,
-        exp_prefix, metrics_history, tracker, start_time, **sched_kw)
+        exp_prefix, metrics_history, tracker, start_time, **loop_kw)
     if rank != 0:
         return tracker.rewards, tracker.avg_rewards, metrics_history
-    if attribution:  # after training, at the final weights, on the evaluations' seeds
+    if opts["attribution"]:  # after training, at the final weights, on the evaluations' seeds
         metrics_history["attribution"] = _attribution(env, agent, num_episodes=5,
                                                       exp_seed=exp_seed)
-    if eval_orders:  # likewise: the final weights under each row order, evaluate()'s episodes
-        metrics_history["order_rewards"] = {
-            name: evaluate(env, agent, num_episodes=10, exp_seed=exp_seed, order=name)
-            for name in eval_orders}
-    if eval_sensors:  # likewise, under each sensor
-        metrics_history["sensor_rewards"] = {
-            name: evaluate(env, agent, num_episodes=10, exp_seed=exp_seed, sensor=s)
-            for name, s in eval_sensors.items()}
-    if eval_shields:  # likewise, under each shield (None: unshielded)
-        metrics_history["shield_rewards"] = {
-            name: evaluate(env, agent, num_episodes=10, exp_seed=exp_seed,
-                           **({} if s is None else {"shield": s}))
-            for name, s in eval_shields.items()}
+    # likewise: the final weights under each row order, sensor and shield (None: unshielded),
+    # over evaluate()'s episodes
+    for key, view, variants in (("order_rewards", "order", {n: n for n in opts["eval_orders"]}),
+                                ("sensor_rewards", "sensor", opts["eval_sensors"]),
+                                ("shield_rewards", "shield", opts["eval_shields"])):
+        if variants:
+            metrics_history[key] = {
+                name: evaluate(env, agent, num_episodes=10, exp_seed=exp_seed,
+                               **({} if v is None else {view: v}))
+                for name, v in variants.items()}
     _save_artifacts(artifacts_dir, checkpoint_dir, experiment_name, metrics_history,
                     training_episodes, episode_rewards, tracker.eval_episodes, tracker.rewards,
                     tracker.avg_rewards, target_reward, total_steps, logger, exp_prefix)
     return tracker.rewards, tracker.avg_rewards, metrics_history
 
 
-def check_eval_orders(eval_orders) -> list:
-    """``eval_orders`` as a list of row-order names (None or empty: none), each "sorted" or
-    "shuffled" and none twice; ValueError otherwise."""
-    names = [] if eval_orders is None else list(eval_orders)
-    if any(n not in ("sorted", "shuffled") for n in names) or len(set(names)) != len(names):
-        raise ValueError(f"eval_orders must list 'sorted' and / or 'shuffled' once each, got "
-                         f"{eval_orders!r}")
-    return names
+def _controls_of(agent) -> dict:
+    """The agent's KL target and lr schedule (None: not set), by option name."""
+    return {k: getattr(agent, k, None) for k in CONTROL_KEYS}
 
 
-def check_eval_sensors(eval_sensors) -> dict:
-    """``eval_sensors`` as {name: hwy.SensorModel} (None or empty: none) from a dict of names to
-    sensors or their dicts; ValueError otherwise."""
-    from hwy._abi import SensorModel
-
-    if eval_sensors is None:
-        return {}
-    if not isinstance(eval_sensors, dict) or not all(isinstance(n, str) for n in eval_sensors):
-        raise ValueError(f"eval_sensors must be a dict of names to sensors, got {eval_sensors!r}")
-    return {name: SensorModel.from_dict(s) for name, s in eval_sensors.items()}
+def _new_metrics(experiment_name, values) -> dict:
+    """metrics_history as a run starts it: the reference's keys, then what the given options of
+    ``values`` (by name) add -- the default's metrics stay what they were."""
+    return {"experiment_name": experiment_name, "episode_rewards": [], "eval_rewards": [],
+            "avg_eval_rewards": [], "policy_updates": [], "episode_numbers": [],
+            "eval_episode_numbers": [], "timestamps": [], **options.initial_metrics(values)}
 
 
-def check_eval_shields(eval_shields) -> dict:
-    """``eval_shields`` as {name: hwy.Shield or None} (None or empty: none) from a dict of names
-    to shields, their dicts or None (the unshielded evaluation); ValueError otherwise."""
-    from hwy._abi import Shield
-
-    if eval_shields is None:
-        return {}
-    if not isinstance(eval_shields, dict) or not all(isinstance(n, str) for n in eval_shields):
-        raise ValueError(f"eval_shields must be a dict of names to shields, got {eval_shields!r}")
-    return {name: None if s is None else Shield.from_dict(s) for name, s in eval_shields.items()}
+def _book_episode(mh, episode_rewards, training_episodes, episode_num, ret, i, stats, safety,
+                  logger, prefix, log_interval, total_steps, start_time) -> None:
+    """One finished (or cut) episode into a run's records: its return and number, its row ``i``
+    of the rollout's _stats_stream ``stats`` and _safety_stream ``safety`` (None: the run does
+    not book them), and the log line."""
+    episode_rewards.append(ret)
+    training_episodes.append(episode_num)
+    mh["episode_rewards"].append(ret)
+    mh["episode_numbers"].append(episode_num)
+    if stats is not None:
+        _book_stats(mh, *stats, i)
+    if safety is not None:
+        _book_safety(mh, safety, i)
+    _log_episode(logger, prefix, episode_num, ret, episode_rewards, log_interval, total_steps,
+                 start_time)
 
 
 def _log_episode(logger, prefix, episode_num, ep_reward, episode_rewards, log_interval,
@@ -1336,26 +1122,22 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
 
     grid: the policy acts on the occupancy grid of the env states: the rollout buffer's states are
     ``grid.stride(F)`` wide, the rollout writes them with one hwy_grid launch on the reset states
-    and one after every env step (ppo/rollout.py); not over a process group, not with a sensor, a
-    shield, truncation "bootstrap" or the reference schedule.
+    and one after every env step (ppo/rollout.py).
 
     shield: after the policy acted, the rollout's shield (one hwy_lookahead call per step,
     ppo/rollout.py) picks the action the env executes; PPO's stored actions, log-probs and values
     stay the policy's.  Every update's metrics carry ``shield_rate``, the share of the rollout's
-    steps the shield overrode.  Not over a process group, not with a sensor, truncation
-    "bootstrap" or the reference schedule.
+    steps the shield overrode.
 
     sensor: the rollout senses the reset states and the state every env step leaves into the
-    rows the policy acts on (one hwy_sense launch each, ppo/rollout.py); not over a process
-    group, not with truncation "bootstrap" or the reference schedule.
+    rows the policy acts on (one hwy_sense launch each, ppo/rollout.py).
 
     safety_stats: the rollout issues one hwy_traffic launch per env step and every booked
-    episode's reduction row goes to mh's SAFETY_KEYS lists (read before the next rollout); not
-    over a process group.
+    episode's reduction row goes to mh's SAFETY_KEYS lists (read before the next rollout).
 
     truncation "bootstrap": the rollout also stores V(final observation) of the truncated rows
     (ppo/rollout.py) and the update's GAE bootstraps them (hwy_gae_boot) instead of booking a
-    time limit as terminal; not over a process group.
+    time limit as terminal.
 
     episode_stats: the rollout steps with hwy_step_with_info and every booked episode's
     statistics go to mh's STATS_KEYS lists (read before the update and the next rollout).
@@ -1367,54 +1149,42 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
     With a process group on the agent (one rank per GPU, envs env_offset = rank*E of world*E),
     every rank steps its own E envs and joins the update's collectives; the episode stream is
     gathered so all ranks count the same episodes and stop after the same update, and rank 0
-    alone evaluates and writes artifacts."""
+    alone evaluates and writes artifacts.  What the caller has already refused (a process group
+    or another option an option does not go with) is ppo/options.py's table."""
     from ppo.agent import RolloutBuffer
     from ppo.rollout import LockstepRollout
 
     group = getattr(agent, "_dist", None)
     rank, world = _rank_world(group)
     bootstrap = truncation == "bootstrap"
-    if bootstrap and group is not None:
-        raise ValueError("truncation='bootstrap' does not run over a process group")
-    if safety_stats and group is not None:
-        raise ValueError("safety_stats does not run over a process group")
-    if sensor is not None and group is not None:
-        raise ValueError("sensor does not run over a process group")
-    if shield is not None and group is not None:
-        raise ValueError("shield does not run over a process group")
-    if grid is not None and group is not None:
-        raise ValueError("grid does not run over a process group")
+    reference = episode_schedule == "reference"
     base = env.unwrapped
     E = base.num_envs
     sd = _flat_dim(env) if grid is None else grid.stride(int(base.hwy_config.n_features))
     T = max(1, math.ceil(steps_per_update / E))
-    stats_kw = {"episode_stats": True} if episode_stats else {}
-    safety_kw = {"safety_stats": True} if safety_stats else {}
-    buf = RolloutBuffer(T, E, sd, 2, base.device, **stats_kw, **safety_kw,
-                        **({"truncation_bootstrap": True} if bootstrap else {}),
-                        **({"shield": True} if shield is not None else {}))
+    buf = RolloutBuffer(T, E, sd, 2, base.device, **options.given(
+        episode_stats=episode_stats, safety_stats=safety_stats, truncation_bootstrap=bootstrap,
+        shield=None if shield is None else True))
     base.set_seed_schedule(exp_seed)
     obs, _ = env.reset()
     if grid is None:  # under a grid the rollout writes states[0] itself, from the reset states
         buf.states[0].copy_(obs.reshape(E, sd))
-    reference = episode_schedule == "reference"
     roll = LockstepRollout(agent, base, buf, use_graph=getattr(agent, "use_graphs", True),
-                           **({"episode_schedule": episode_schedule} if reference else {}),
-                           **stats_kw, **safety_kw,
-                           **({"truncation": truncation} if bootstrap else {}),
-                           **({"sensor": sensor} if sensor is not None else {}),
-                           **({"shield": shield} if shield is not None else {}),
-                           **({"grid": grid} if grid is not None else {}))
+                           **options.given(episode_schedule=episode_schedule,
+                                           episode_stats=episode_stats, safety_stats=safety_stats,
+                                           truncation=truncation, sensor=sensor, shield=shield,
+                                           grid=grid))
     episode_rewards, training_episodes = [], []
     total_steps = episode_num = 0
     while episode_num < max_episodes:
         t_update = time.time()
         roll.run()
         total_steps += T * E * world
+        stats = safety = None
         if episode_stats:
-            cut_kw = ({"cut": roll.cut, "cut_length": roll.cut_length, "acc": buf.acc}
-                      if reference else {})
-            sums, lens = _stats_stream(buf.dones, buf.ep_length, buf.ep_stats, **cut_kw)
+            stats = _stats_stream(buf.dones, buf.ep_length, buf.ep_stats, **(
+                {"cut": roll.cut, "cut_length": roll.cut_length, "acc": buf.acc}
+                if reference else {}))
         if safety_stats:
             safety = _safety_stream(buf.dones, buf.traffic_stats, roll.cut if reference else None)
         if reference:  # the stream's evaluations run below, ahead of the update (:173-175)
@@ -1428,17 +1198,8 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
             if episode_num >= max_episodes:
                 break
             episode_num += 1
-            r = float(r)
-            episode_rewards.append(r)
-            training_episodes.append(episode_num)
-            mh["episode_rewards"].append(r)
-            mh["episode_numbers"].append(episode_num)
-            if episode_stats:
-                _book_stats(mh, sums, lens, i)
-            if safety_stats:
-                _book_safety(mh, safety, i)
-            _log_episode(logger, prefix, episode_num, r, episode_rewards, log_interval,
-                         total_steps, start_time)
+            _book_episode(mh, episode_rewards, training_episodes, episode_num, float(r), i, stats,
+                          safety, logger, prefix, log_interval, total_steps, start_time)
             if episode_num % eval_interval == 0 and rank == 0:
                 tracker.on_episode(episode_num)
         if reference:
@@ -1467,8 +1228,7 @@ def train_group(group, experiment_names, exp_seeds, max_episodes=500, target_rew
                        target_reward=target_reward, log_interval=log_interval,
                        eval_interval=eval_interval, loggers=loggers,
                        episode_schedule=episode_schedule,
-                       **({"episode_stats": True} if episode_stats else {}),
-                       **({"safety_stats": True} if safety_stats else {}))
+                       **options.given(episode_stats=episode_stats, safety_stats=safety_stats))
 
 
 def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, target_reward=0.0,
@@ -1485,8 +1245,6 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
     per-episode statistics are booked beside its returns, as _train_vector books them.
     safety_stats (likewise): each experiment's hwy_traffic reduction rows, from its own slice of
     its group's traffic_stats."""
-    from ppo.rollout import check_episode_schedule
-
     if any(bool(getattr(g, "safety_stats", False)) != bool(safety_stats) for g in groups):
         raise ValueError(f"train_batch: every group must be built with safety_stats="
                          f"{bool(safety_stats)}")
@@ -1498,7 +1256,7 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
         raise ValueError(f"train_batch: every group must be built with episode_stats="
                          f"{bool(episode_stats)}")
 
-    reference = check_episode_schedule(episode_schedule) == "reference"
+    reference = options.BY_NAME["episode_schedule"].normalise(episode_schedule) == "reference"
     if any(getattr(g, "episode_schedule", "lockstep") != episode_schedule for g in groups):
         raise ValueError(f"train_batch: every group must be built with episode_schedule="
                          f"{episode_schedule!r}")
@@ -1519,14 +1277,8 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
         prefix = f"[{name}]" if name else ""
         logger.info(f"{prefix} Starting training for experiment: {name} (group of {grp.G}, "
                     f"batch of {len(members)})")
-        mh = {"experiment_name": name, "episode_rewards": [], "eval_rewards": [],
-              "avg_eval_rewards": [], "policy_updates": [], "episode_numbers": [],
-              "eval_episode_numbers": [], "timestamps": []}
-        if episode_stats:
-            mh.update({k: [] for k in STATS_KEYS})
-        if safety_stats:
-            mh.update({k: [] for k in SAFETY_KEYS})
-        _book_controls(mh, grp.agents[j])
+        mh = _new_metrics(name, dict(episode_stats=episode_stats, safety_stats=safety_stats,
+                                     **_controls_of(grp.agents[j])))
         tracker = _EvalTracker(grp.solo_envs[j], grp.agents[j], int(exp_seeds[k]),
                                target_reward, checkpoint_dir, name, mh, logger, prefix, start_time)
         logger.info(f"{prefix} Performing initial evaluation...")
@@ -1557,11 +1309,12 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
                                          grp.cut[sl], grp.cut_return[sl])
             else:
                 stream = _episode_ends(grp.buf.dones[:, sl], grp.buf.ep_return[:, sl])
+            stats = safety = None
             if episode_stats:
                 cut_kw = ({"cut": grp.cut[sl], "cut_length": grp.cut_length[sl],
                            "acc": grp.buf.acc[sl]} if reference else {})
-                sums, lens = _stats_stream(grp.buf.dones[:, sl], grp.buf.ep_length[:, sl],
-                                           grp.buf.ep_stats[:, sl], **cut_kw)
+                stats = _stats_stream(grp.buf.dones[:, sl], grp.buf.ep_length[:, sl],
+                                      grp.buf.ep_stats[:, sl], **cut_kw)
             if safety_stats:
                 safety = _safety_stream(grp.buf.dones[:, sl], grp.buf.traffic_stats[:, sl],
                                         grp.cut[sl] if reference else None)
@@ -1569,17 +1322,9 @@ def train_batch(stepper, groups, experiment_names, exp_seeds, max_episodes=500, 
                 if r["episode_num"] >= max_episodes:
                     break
                 r["episode_num"] += 1
-                ret = float(ret)
-                r["episode_rewards"].append(ret)
-                r["training_episodes"].append(r["episode_num"])
-                r["mh"]["episode_rewards"].append(ret)
-                r["mh"]["episode_numbers"].append(r["episode_num"])
-                if episode_stats:
-                    _book_stats(r["mh"], sums, lens, i)
-                if safety_stats:
-                    _book_safety(r["mh"], safety, i)
-                _log_episode(r["logger"], r["prefix"], r["episode_num"], ret, r["episode_rewards"],
-                             log_interval, r["total_steps"], start_time)
+                _book_episode(r["mh"], r["episode_rewards"], r["training_episodes"],
+                              r["episode_num"], float(ret), i, stats, safety, r["logger"],
+                              r["prefix"], log_interval, r["total_steps"], start_time)
                 if r["episode_num"] % eval_interval == 0:
                     r["pending"].append(r["episode_num"])
             if reference:

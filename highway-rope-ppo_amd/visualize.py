@@ -42,6 +42,7 @@ if _HERE not in sys.path:
     sys.path.insert(0, _HERE)
 
 from experiments.config import Condition  # noqa: E402
+from ppo.options import given  # noqa: E402
 
 CHECKPOINT_RE = re.compile(r"^ppo_highway_(?:best|solved)_(?P<exp>.+)\.pth$")
 # longest prefix first: every positional-embedding condition's name begins with "shuffled"
@@ -138,9 +139,8 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
                              f"{cond.name} env (d_embed={d_embed}) gives {have}")
         dest = os.path.join(out_dir, os.path.splitext(os.path.basename(path))[0])
         rewards = visualize_agent(env, agent, num_episodes=episodes, exp_seed=seed, out_dir=dest,
-                                  attribution=attribution, **({"tint": tint} if tint else {}),
-                                  **({"sensor": sensor} if sensor is not None else {}),
-                                  **({"grid": grid} if grid is not None else {}))
+                                  attribution=attribution,
+                                  **given(tint=tint or None, sensor=sensor, grid=grid))
     finally:
         env.close()
     for ep, r in enumerate(rewards):
@@ -206,8 +206,7 @@ def main(argv=None) -> int:
     models = [args.model] if args.model else list(models_from_file(args.models_file))
     for m in models:
         record(m, args.out, episodes=args.episodes, seed=args.seed, attribution=args.attribution,
-               tint=args.tint, **({"sensor": sensor} if sensor is not None else {}),
-               **({"grid": grid} if grid is not None else {}))
+               tint=args.tint, **given(sensor=sensor, grid=grid))
     return 0
 
 
