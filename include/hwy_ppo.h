@@ -28,6 +28,23 @@
  * Adam step; call hwy_ppo_sync_params once before the first hwy_ppo_forward_backward on a
  * workspace, and again whenever params were written by anything other than hwy_ppo_optimizer
  * (a checkpoint load, a torch optimizer step, a broadcast).
+ *
+ * Memory contract.  The workspace is hwy_ppo_workspace_bytes(dims) bytes of device memory
+ * and may contain ARBITRARY bytes before the first hwy_ppo_sync_params: no call
+ * needs it zeroed, and none reads a word of it that the same call sequence has not written.  The
+ * only state it carries from one call to the next is the weight tile image (the last
+ * workspace bytes from hwy_ppo_tile_image_offset on; none on the general path) and, from a
+ * hwy_ppo_forward_backward to the hwy_ppo_optimizer of the same step with grads_modified == 0, the
+ * gradient-norm partials: every other byte may be overwritten between steps, and with
+ * grads_modified == 1 between the two calls of a step as well.  hwy_ppo_forward_backward writes
+ * the whole flat gradient (what grads held before does not matter) and one metrics row.  No call
+ * writes outside the buffers it is given, each taken at exactly the size this header states
+ * (states [n, S] with n > B rows, idx [B], the outputs of hwy_ppo_act [B] rows, the device tables
+ * and the control block exactly their *_bytes), and none writes a buffer declared const here or
+ * an output it was not asked for.  tests/test_ppo_memory_gpu.py runs the step, acting, grouped,
+ * mixed, scheduled and control calls under these conditions: between guard words, on a workspace
+ * poisoned with NaNs and with FLT_MAX, bit for bit against a zeroed one
+ * (tests/test_input_grad_gpu.py guards hwy_ppo_input_grad).
  */
 #ifndef HWY_PPO_H_
 #define HWY_PPO_H_
@@ -66,7 +83,8 @@ typedef struct hwy_ppo_args {
   float* adam_v;
   int32_t* counters;      /* [0] Adam step t, [1] metrics row */
   float* metrics;         /* [rows, 6]: policy, value, entropy, loss, clip count, kl */
-  void* workspace;        /* hwy_ppo_workspace_bytes(dims) bytes, owned by these calls */
+  void* workspace;        /* hwy_ppo_workspace_bytes(dims) bytes, owned by these calls; arbitrary
+                             contents before hwy_ppo_sync_params (memory contract, above) */
   /* hyper-parameters (PPOAgent defaults: eps_clip .2, value_coef .5, entropy_coef .005) */
   float eps_clip, value_coef, entropy_coef, max_grad_norm;
   float lr, beta1, beta2, adam_eps;

@@ -2,7 +2,9 @@
 reference taking the fused step's own ReLU decisions, the gradient criterion (_check_grads), and
 the CPU-drawn edge cases shared by test_ppo_edge_inputs.py (input conditions, no GPU) and
 test_ppo_edges_gpu.py (the kernels against float64), and the general path's cases with their
-split-K plans (test_ppo_general_inputs.py, test_ppo_general_gpu.py)."""
+split-K plans (test_ppo_general_inputs.py, test_ppo_general_gpu.py), and the host plan of the
+fused path restated with the shapes of the memory tests (test_ppo_memory_inputs.py,
+test_ppo_memory_gpu.py)."""
 
 import copy
 
@@ -275,6 +277,200 @@ def general_plan(S, H, B):
         out[name] = dict(slabs=s, kchunk=c, lens=[min(c, B - z * c) for z in range(s)],
                          vector=vec, ktile=V_K if vec else K_STEP)
     return out
+
+
+# ------------------------------------------------------------------ the host plan, restated
+# What csrc/ppo_kernels.hip decides on the host for a shape and a chip (rows_tile, fused_ok,
+# rows_blocks, tile_geom, carve with its balanced weight-gradient partition, hwy_ppo_act's kernel
+# choice), restated for the memory tests: test_ppo_memory_inputs.py checks without a GPU that
+# MEMORY_* below reach every addressing path at the full MI355X (256 CUs, 8 XCDs) and that
+# workspace_sizes adds up to hwy_ppo_workspace_bytes; test_ppo_memory_gpu.py asserts the same
+# with the device's own CU count.
+MAX_ROW_S, MAX_FUSED_S = 256, 1024   # kMaxRowS, kMaxFusedS
+WG_TM, WG_TN = 128, 64               # ppo_wgrad's output tile
+WG_PART = WG_TM * WG_TN + WG_TM      # kWgPart: floats per partial tile (+ bias sums)
+HEAD_ROWS, RED_THREADS = 16, 256     # kHeadRows, kRedThreads
+FULL_CHIP = (256, 8)                 # CUs, XCDs of an unpartitioned MI355X
+
+
+def fused_ok(S, H):
+    return S % 4 == 0 and S <= MAX_FUSED_S and H % 64 == 0 and 64 <= H <= 512
+
+
+def rows_tile(B, H, S, cus):
+    """Minibatch rows per ppo_rows workgroup."""
+    if H > 256 or S > MAX_ROW_S:
+        return 16
+    if H == 256 and B >= 64 * cus:
+        return 64
+    return 32 if B >= 32 * cus else 16
+
+
+def row_waves(H):
+    """Waves of the row and act kernels: 8 when H / 64 is even, else 4."""
+    return 8 if (H // 64) % 2 == 0 else 4
+
+
+def ring_depth(H):
+    return 4 if H // row_waves(H) // 16 <= 4 else 2
+
+
+def rows_blocks(S, H):
+    """(sb, hb): 16-deep k blocks of W1's image and of an H x H image, whole ring groups."""
+    D = ring_depth(H)
+    return -(-(-(-S // 16)) // D) * D, -(-(H // 16) // D) * D
+
+
+def tile_image_floats(S, H):
+    """TileGeom.total: W1's forward image and six H x H images in 1-KB blocks."""
+    sb, hb = rows_blocks(S, H)
+    g = H // 16
+    return g * sb * 256 + 6 * g * hb * 256
+
+
+def ppo_numel(S, H):
+    return H * S + H + 3 * (H * H + H) + 2 * H + 2 + 2 + H + 1
+
+
+def wgrad_plan(S, H, B, cus, xcds, fill=1.5):
+    """carve()'s ppo_wgrad partition: tiles, row slices per tile (split) and whether the
+    balanced partition (two partial-tile slots) is on."""
+    import math
+
+    tmh, tnh = -(-H // WG_TM), -(-H // WG_TN)
+    tac, t2, t1 = -(-2 * H // WG_TM) * tnh, tmh * tnh, tmh * -(-S // WG_TN)
+    ntile, nh = tac + t2 + t1, (3 * H + 9 + 63) // 64
+
+    def plan(sp):
+        P, nck = cus // sp, (-(-B // sp) + 63) // 64
+        q = dict(split=sp, bal=0, wm=0, tpe=0, cost=nck)
+        if ntile >= 16 and P - ntile >= 2 and nck >= 16:
+            E = P - ntile
+            tpe = -(-ntile // E)
+            m = math.ceil(tpe * (nck + fill) / (1.0 + tpe))
+            if m < nck:
+                q.update(bal=1, wm=m, tpe=tpe, cost=m)
+        return q
+
+    cap = max(1, min(xcds, 8, cus // ntile, (B + 63) // 64))
+    best = plan(1)
+    for sp in range(cap, 0, -1):
+        if xcds % sp == 0:
+            best = plan(sp)
+            break
+    for sp in range(2, min(8, max(1, (B + 63) // 64)) + 1):
+        if xcds % sp == 0:
+            continue
+        q = plan(sp)
+        if q["bal"] and q["cost"] < 0.85 * best["cost"] and (not best["bal"] or q["cost"] < best["cost"]):
+            best = q
+    best.update(ntile=ntile, nh=nh, nslot=2 if best["bal"] else 1,
+                grid=best["split"] * (cus // best["split"]) if best["bal"]
+                else ntile * best["split"] + nh)
+    return best
+
+
+WORK_REGIONS = ("h1", "h2", "ac", "dac", "dh2", "dh1", "head_part", "slab_ac", "bias_ac", "slab_2",
+                "bias_2", "slab_1", "bias_1", "norm_part", "wg_slab", "xg", "wtile")
+
+
+def workspace_sizes(S, H, B, cus=FULL_CHIP[0], xcds=FULL_CHIP[1]):
+    """carve()'s 17 sub-buffers in floats, in WORK_REGIONS order, before the rounding of each to
+    64 floats.  All of them are float arrays (struct Work): the workspace holds no address."""
+    fused = fused_ok(S, H)
+    g = general_plan(S, H, B)
+    sa, s2, s1 = (0, 0, 0) if fused else (g["ac"]["slabs"], g["2"]["slabs"], g["1"]["slabs"])
+    nhead, HP = -(-B // HEAD_ROWS), 3 * H + 16
+    nred = -(-ppo_numel(S, H) // RED_THREADS)
+    w = wgrad_plan(S, H, B, cus, xcds)
+    n1 = -(-B // rows_tile(B, H, S, cus))
+    nred2 = w["nh"] + w["ntile"] * (WG_TM * WG_TN // 1024)
+    return [B * H, B * H, 2 * B * H, 2 * B * H, B * H, B * H,
+            (max(nhead, n1) if fused else nhead) * HP,
+            sa * 2 * H * H, sa * 2 * H, s2 * H * H, s2 * H, s1 * H * S, s1 * H,
+            max(nred, nred2) if fused else nred,
+            w["ntile"] * w["split"] * w["nslot"] * WG_PART if fused else 0,
+            B * S if fused else 0, tile_image_floats(S, H) if fused else 0]
+
+
+def workspace_floats(S, H, B, cus=FULL_CHIP[0], xcds=FULL_CHIP[1]):
+    return sum(-(-n // 64) * 64 for n in workspace_sizes(S, H, B, cus, xcds))
+
+
+def act_kernel(S, H, B, tiles, cus):
+    """The kernel hwy_ppo_act / hwy_ppo_value_masked launch: (body, rows per workgroup)."""
+    if tiles and H == 256:
+        return ("ppo_act_c", 32 if S <= MAX_ROW_S and B >= 64 * cus else 16)
+    return ("ppo_act_tiles" if tiles else "ppo_act_params", 16)
+
+
+def memory_paths(S, H, B, cus=FULL_CHIP[0], xcds=FULL_CHIP[1]):
+    """The addressing paths the minibatch step of (S, H, B) takes on a chip, as tags."""
+    if not fused_ok(S, H):
+        g = general_plan(S, H, B)
+        t = {"general", "adam-flat", "gemm-vector" if g["1"]["vector"] else "gemm-scalar"}
+        if any(p["slabs"] > 1 for p in g.values()):
+            t.add("split-k")
+        if any(p["lens"][-1] != p["kchunk"] for p in g.values()):
+            t.add("ragged-slab")
+        return t
+    rt, w = rows_tile(B, H, S, cus), wgrad_plan(S, H, B, cus, xcds)
+    sb, _ = rows_blocks(S, H)
+    t = {f"rows{rt}", f"waves{row_waves(H)}", f"ring{ring_depth(H)}", "adam-tiles"}
+    if S > MAX_ROW_S:
+        t.add("wide")
+    if S == MAX_FUSED_S and H == 512:
+        t.add("widest")
+    if B % rt:
+        t.add("ragged-tile")
+    if B % 64:
+        t.add("ragged-chunk")
+    if S % 16:
+        t.add("w1-pad-columns")
+    if 16 * sb - S >= 16:
+        t.add("w1-pad-block")
+    if w["split"] > 1:
+        t.add("slices")
+    if w["bal"]:
+        t.add("balanced")
+    return t
+
+
+# (B, S, H) of the memory tests: the smallest shapes reaching each path, with the tags each must
+# carry (test_ppo_memory_inputs.py).  The two large ones depend on the chip's CU count.
+MEMORY_FUSED = (
+    ((1, 4, 64), {"rows16", "waves4", "ragged-tile", "w1-pad-columns"}),
+    ((17, 60, 64), {"rows16", "ragged-tile", "ragged-chunk"}),
+    ((100, 60, 128), {"rows16", "waves8", "ragged-tile", "ragged-chunk", "slices"}),
+    ((129, 200, 320), {"ring2", "w1-pad-block", "waves4", "slices"}),
+    ((65, 120, 192), {"waves4", "ring4", "ragged-chunk"}),
+    ((48, 60, 448), {"waves4", "ring2"}),
+    ((72, 260, 256), {"wide", "rows16", "waves8"}),
+    ((64, 1024, 512), {"wide", "widest", "ring4", "waves8"}),
+)
+MEMORY_GENERAL = (
+    ((33, 30, 64), {"general", "gemm-scalar", "split-k", "ragged-slab", "adam-flat"}),
+    ((64, 75, 128), {"general", "gemm-scalar", "split-k"}),
+    ((16, 1028, 64), {"general", "gemm-vector", "adam-flat"}),
+)
+
+
+def memory_large(cus):
+    """The 32-row tiles and the 64-row tiles with the balanced partition: B just past each
+    threshold, ragged in its last tile."""
+    return (((32 * cus + 5, 60, 128), {"rows32", "ragged-tile", "slices"}),
+            ((64 * cus + 37, 60, 256), {"rows64", "ragged-tile", "balanced", "slices"}))
+
+
+# acting (B, S, H): the step's fused shapes, and ppo_act_c at a ragged B in both tile heights
+def memory_act(cus):
+    return tuple(c for c, _ in MEMORY_FUSED) + ((1000, 120, 256), (64 * cus + 5, 60, 256))
+
+
+MEMORY_PATHS = frozenset({
+    "rows16", "rows32", "rows64", "waves4", "waves8", "ring2", "ring4", "wide", "widest",
+    "ragged-tile", "ragged-chunk", "w1-pad-columns", "w1-pad-block", "slices", "balanced",
+    "adam-tiles", "general", "gemm-scalar", "gemm-vector", "split-k", "ragged-slab", "adam-flat"})
 
 
 def case_id(c):
