@@ -622,6 +622,59 @@ int hwy_grid(hwy_handle* h, const hwy_grid_args* a, void* stream) {
   return launched(hwy_launch_grid(&p, (hipStream_t)stream), "hwy_grid_kernel");
 }
 
+int hwy_lidar_args_size(void) { return (int)sizeof(hwy_lidar_args); }
+
+int hwy_lidar_check(const hwy_lidar_args* a) {
+  if (!a) return fail(HWY_EINVAL, "hwy_lidar: args is NULL");
+  if (!a->obs && !a->hit_vehicle && !a->seen && !a->counts)
+    return fail(HWY_EINVAL, "hwy_lidar: no output given (obs, hit_vehicle, seen and counts are "
+                            "all NULL)");
+  if (a->cells < 1 || a->cells > HWY_LIDAR_MAX_CELLS)
+    return fail(HWY_EINVAL, "hwy_lidar: cells must lie in 1..%d, got %d", HWY_LIDAR_MAX_CELLS,
+                a->cells);
+  if (a->sub < 1 || a->sub > HWY_LIDAR_MAX_SUB)
+    return fail(HWY_EINVAL, "hwy_lidar: sub must lie in 1..%d, got %d", HWY_LIDAR_MAX_SUB, a->sub);
+  if (a->cells * a->sub > HWY_LIDAR_MAX_RAYS)
+    return fail(HWY_EINVAL, "hwy_lidar: cells * sub must be <= %d, got %d x %d",
+                HWY_LIDAR_MAX_RAYS, a->cells, a->sub);
+  if (!finite_pos(a->range_m) || !finite_pos(a->speed_scale))
+    return fail(HWY_EINVAL, "hwy_lidar: range_m and speed_scale must be finite and > 0, got %g, %g",
+                (double)a->range_m, (double)a->speed_scale);
+  if (!(a->p_drop >= 0.0f && a->p_drop <= 1.0f))
+    return fail(HWY_EINVAL, "hwy_lidar: p_drop must lie in [0, 1], got %g", (double)a->p_drop);
+  if (!(a->sigma_r >= 0.0f && a->sigma_r < __builtin_inff()))
+    return fail(HWY_EINVAL, "hwy_lidar: sigma_r must be finite and >= 0, got %g",
+                (double)a->sigma_r);
+  if (a->salt < 0 || a->salt > 65535)
+    return fail(HWY_EINVAL, "hwy_lidar: salt must lie in 0..65535, got %d", a->salt);
+  const int width = 2 * a->cells + (a->ego_tail ? 1 : 0);
+  if (a->row_stride < width || a->row_stride > HWY_LIDAR_MAX_STRIDE)
+    return fail(HWY_EINVAL, "hwy_lidar: row_stride must hold the %d cells%s and be <= %d, got %d",
+                a->cells, a->ego_tail ? " and the ego tail" : "", HWY_LIDAR_MAX_STRIDE,
+                a->row_stride);
+  return HWY_OK;
+}
+
+int hwy_lidar(hwy_handle* h, const hwy_lidar_args* a, void* stream) {
+  if (!h) return fail(HWY_EINVAL, "hwy_lidar: handle is NULL");
+  if (int rc = hwy_lidar_check(a)) return rc;
+  LidarParams p;
+  memset(&p, 0, sizeof(p));
+  p.a = *a;
+  p.state = h->state;
+  p.cfg = h->cfg;
+  p.dth = (float)(6.283185307179586 / (double)(a->cells * a->sub));
+  p.salt_word = HWY_LIDAR_SALT + (uint32_t)a->salt;
+  // 4 m over the 2.7 m half diagonal, and 1e-4 of the range over what binary32 rounds of it
+  const float far = (a->range_m + 4.0f) * 1.0001f;
+  p.cull2 = far * far;  // +inf for a range near FLT_MAX: nothing is culled
+  const int width = 2 * a->cells + (a->ego_tail ? h->cfg.n_features : 0);
+  if (a->row_stride < width)
+    return fail(HWY_EINVAL, "hwy_lidar: row_stride %d is below the width %d (%d cells and an ego "
+                            "tail of %d)", a->row_stride, width, a->cells, h->cfg.n_features);
+  return launched(hwy_launch_lidar(&p, (hipStream_t)stream), "hwy_lidar_kernel");
+}
+
 int hwy_traffic_args_size(void) { return (int)sizeof(hwy_traffic_args); }
 
 int hwy_traffic_check(const hwy_traffic_args* a) {

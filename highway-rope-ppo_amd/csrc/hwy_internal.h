@@ -90,8 +90,22 @@ struct GridParams {
   hwy_config cfg;
 };
 
+// hwy_lidar's launch parameters (the lidar unit of hwy_kernels.hip): the checked arguments, the
+// handle's state and its config, dth = (float)(2 pi / (cells * sub)), salt_word =
+// HWY_LIDAR_SALT + a.salt and cull2 = ((range_m + 4) * 1.0001)^2, the squared centre distance
+// beyond which no ray can count a hit on a body
+struct LidarParams {
+  hwy_lidar_args a;
+  const uint32_t* state;  // [HWY_NFIELDS][E][64]
+  hwy_config cfg;
+  float dth;
+  uint32_t salt_word;
+  float cull2;
+};
+
 extern "C" {
 int hwy_launch_grid(const GridParams* p, hipStream_t s);
+int hwy_launch_lidar(const LidarParams* p, hipStream_t s);
 // big: the register budget, hwy_step_big(waves of the launch)
 int hwy_launch_lookahead(const LookaheadParams* p, int big, hipStream_t s);
 int hwy_launch_lookahead_choice(const LookaheadParams* p, hipStream_t s);

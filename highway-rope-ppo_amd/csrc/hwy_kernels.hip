@@ -2334,6 +2334,192 @@ extern "C" int hwy_launch_grid(const GridParams* p, hipStream_t s) {
   hipLaunchKernelGGL(hwy_grid_kernel, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), lds, s, *p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#elif defined(HWY_LIDAR_TU)
+// hwy_lidar's kernel, likewise a unit of its own (-DHWY_LIDAR_TU -> hwy_lidar.o): the ray-cast
+// range observation of include/hwy.h.  One wave per env.  Lanes first act as vehicles: each loads
+// the five fields the rule reads and the env words (1,536 B per env), runs hm_sincosf once and
+// lays the ego's centre in its own frame (ou, ow), its axes and its velocity out in per-wave LDS.
+// Lanes then act as cells, strided by 64: a cell runs its sub-rays one after the other, each over
+// the present bodies in ascending index with broadcast LDS reads, and keeps the first strict
+// minimum, which is the rule's tie order (least j, then least k).  The cell loop's trip count is
+// wave-uniform, so every ballot and every LDS-synchronised step runs with all 64 lanes active; an
+// LDS index is the lane, a bounded loop index (k < V <= 64) or the winner such a loop left.
+// `seen` comes from per-wave LDS flags, the counts from ballots.
+
+// one Philox draw of a cell's stream: counter (cell, step word, channel, salt word)
+__device__ __forceinline__ hm_u32x4 lidar_draw(int cell, int step, uint32_t ch, uint32_t salt_word,
+                                               uint64_t seed) {
+  return hm_philox4x32_10((uint32_t)cell, (uint32_t)step, ch, salt_word,
+                          (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32));
+}
+
+// one axis of the slab test: false for an empty interval, else its ends
+__device__ __forceinline__ bool lidar_axis(float o, float d, float H, float* lo, float* hi) {
+  if (d == 0.0f) {
+    *lo = -__builtin_inff();
+    *hi = __builtin_inff();
+    return hm_absf(o) <= H;
+  }
+  const float t1 = (-H - o) / d, t2 = (H - o) / d;
+  *lo = hm_minf(t1, t2);
+  *hi = hm_maxf(t1, t2);
+  return true;
+}
+
+__global__ void __launch_bounds__(256) hwy_lidar_kernel(LidarParams P) {
+  __shared__ float4 lds_body[ENVS_PER_BLOCK][WAVE];  // (ou, ow, cos h, sin h)
+  __shared__ float2 lds_vel[ENVS_PER_BLOCK][WAVE];   // (vx, vy)
+  __shared__ int lds_seen[ENVS_PER_BLOCK][WAVE];
+  __shared__ float lds_tail[ENVS_PER_BLOCK][HWY_MAX_FEATURES];
+  const hwy_config& C = P.cfg;
+  const hwy_lidar_args& A = P.a;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int w = threadIdx.x / WAVE;
+  const int e = blockIdx.x * ENVS_PER_BLOCK + w;
+  if (e >= C.num_envs) return;  // whole wave
+  const int V = C.vehicles_count + 1;
+  const int F = C.n_features;
+  const size_t fstride = (size_t)C.num_envs * WAVE;
+  const uint32_t idx = (uint32_t)e * WAVE + lane;  // < 2^32: hwy_create bounds num_envs
+  const uint32_t* st = P.state;
+  const float x = hm_bits2f((st + HWY_F_X * fstride)[idx]);
+  const float y = hm_bits2f((st + HWY_F_Y * fstride)[idx]);
+  const float h = hm_bits2f((st + HWY_F_HEADING * fstride)[idx]);
+  const float spd = hm_bits2f((st + HWY_F_SPEED * fstride)[idx]);
+  const uint32_t fl = (st + HWY_F_FLAGS * fstride)[idx];
+  const uint32_t ew = (st + HWY_F_ENV * fstride)[idx];
+  const bool present = ((fl & HWY_FLAG_PRESENT) != 0u) && lane < V;  // load_veh's rule
+  const int step = rdli((int)ew, HWY_E_STEP);
+  const uint64_t seed = (uint64_t)(uint32_t)rdli((int)ew, HWY_E_SEED_LO) |
+                        ((uint64_t)(uint32_t)rdli((int)ew, HWY_E_SEED_HI) << 32);
+  float cos_h, sin_h;
+  hm_sincosf(h, &sin_h, &cos_h);
+  const float ex = rdlf(x, 0), ey = rdlf(y, 0), eh = rdlf(h, 0), espd = rdlf(spd, 0);
+  const float ec = rdlf(cos_h, 0), es = rdlf(sin_h, 0);
+
+  // ---- lanes as vehicles: the ego's centre in this body's frame, its axes, its velocity
+  const float ox = ex - x, oy = ey - y;
+  const float vx = spd * cos_h, vy = spd * sin_h;
+  const float evx = rdlf(vx, 0), evy = rdlf(vy, 0);
+  lds_body[w][lane] = make_float4(ox * cos_h + oy * sin_h, oy * cos_h - ox * sin_h, cos_h, sin_h);
+  lds_vel[w][lane] = make_float2(vx, vy);
+  lds_seen[w][lane] = 0;
+  float tv = 0.0f;  // the ego tail: lane f holds feature f, as in the grid
+  if (A.ego_tail) {
+#pragma unroll
+    for (int f = 0; f < HWY_MAX_FEATURES; ++f)
+      if (f < F) {
+        float val = feature_value(C.feature_ids[f], ex, ey, espd, eh, ec, es);
+        if (C.normalize && C.has_range[f]) {
+          val = hm_lmap(val, C.features_range[f][0], C.features_range[f][1], -1.0f, 1.0f);
+          if (C.clip) val = hm_clipf(val, -1.0f, 1.0f);
+        }
+        tv = lane == f ? val : tv;
+      }
+  }
+  if (lane < HWY_MAX_FEATURES) lds_tail[w][lane] = tv;
+  const uint64_t otherm = ballot(present && lane >= 1);
+  // Only a hit with d <= range_m counts.  A body whose centre is more than (range_m + 4 m) *
+  // 1.0001 from the ego (its half diagonal is 2.7 m) has no point within a metre of that range,
+  // so no ray can count a hit on it and it is left out of the loop: wave-uniformly, and never on
+  // a NaN distance (the comparison is false).  The same cull, with the same margins, as hwy_sense.
+  const uint64_t bodym = otherm & ~ballot(ox * ox + oy * oy > P.cull2);
+  wave_lds_sync();
+
+  // ---- lanes as cells
+  const float off = 0.5f - 0.5f * (float)A.sub;
+  float* row = A.obs ? A.obs + (size_t)e * A.row_stride : nullptr;
+  int nret = 0, ndrop = 0;  // wave-uniform
+  for (int c0 = 0; c0 < A.cells; c0 += WAVE) {
+    const int c = c0 + lane;
+    const bool live = c < A.cells;
+    float best = __builtin_inff(), bdx = 0.0f, bdy = 0.0f;
+    int bk = -1;
+    if (live) {
+      for (int j = 0; j < A.sub; ++j) {
+        float theta = ((float)(c * A.sub + j) + off) * P.dth;
+        if (A.align) theta = theta + eh;
+        float dx, dy;
+        hm_sincosf(theta, &dy, &dx);
+        for (int k = 1; k < V; ++k) {
+          if (!((bodym >> k) & 1ull)) continue;  // wave-uniform: absent, or out of reach
+          const float4 b = lds_body[w][k];
+          const float du = dx * b.z + dy * b.w;
+          const float dw = dy * b.z - dx * b.w;
+          float lo_u, hi_u, lo_w, hi_w;
+          const bool ok_u = lidar_axis(b.x, du, 0.5f * VEH_LENGTH, &lo_u, &hi_u);
+          const bool ok_w = lidar_axis(b.y, dw, 0.5f * VEH_WIDTH, &lo_w, &hi_w);
+          const float t_in = hm_maxf(lo_u, lo_w), t_out = hm_minf(hi_u, hi_w);
+          const float d = t_in > 0.0f ? t_in : 0.0f;
+          const bool counted = ok_u && ok_w && t_in <= t_out && t_out >= 0.0f && d <= A.range_m;
+          if (counted && d < best) {  // strict: the first of equal distances stays
+            best = d;
+            bk = k;
+            bdx = dx;
+            bdy = dy;
+          }
+        }
+      }
+    }
+    bool dropped = false;
+    if (A.p_drop > 0.0f)  // u < 0 never holds
+      dropped = hm_u01(lidar_draw(c, step, 0u, P.salt_word, seed).v[0]) < A.p_drop;
+    const bool ret = live && bk >= 0 && !dropped;
+    float dist = A.range_m, vel = 0.0f;
+    if (ret) {
+      const float2 vk = lds_vel[w][bk];  // bk: 1..V-1
+      dist = best;
+      vel = ((vk.x - evx) * bdx) + ((vk.y - evy) * bdy);
+    }
+    if (A.sigma_r != 0.0f) {  // a sigma of exactly 0 skips the addition
+      const hm_u32x4 r = lidar_draw(c, step, 1u, P.salt_word, seed);
+      const float u0 = hm_u01(r.v[0]), u1 = hm_u01(r.v[1]), u2 = hm_u01(r.v[2]), u3 = hm_u01(r.v[3]);
+      const float z = (((u0 + u1) + (u2 + u3)) - 2.0f) * 1.7320508f;
+      if (ret) dist = hm_clipf(dist + A.sigma_r * z, 0.0f, A.range_m);
+    }
+    if (A.normalize) {
+      dist = dist / A.range_m;
+      vel = vel / A.speed_scale;
+    }
+    if (live) {
+      if (row) {
+        row[2 * c] = dist;
+        row[2 * c + 1] = vel;
+      }
+      if (A.hit_vehicle) A.hit_vehicle[(size_t)e * A.cells + c] = ret ? bk : -1;
+    }
+    if (ret) lds_seen[w][bk] = 1;
+    nret += __popcll(ballot(ret));
+    ndrop += __popcll(ballot(live && dropped));
+  }
+  wave_lds_sync();
+
+  // ---- the ego tail and the padding; seen; counts
+  if (row) {
+    const int base = 2 * A.cells;
+    for (int k = base + lane; k < A.row_stride; k += WAVE) {
+      const int f = k - base;
+      const float val = lds_tail[w][f < HWY_MAX_FEATURES ? f : 0];
+      row[k] = (A.ego_tail && f < F) ? val : 0.0f;
+    }
+  }
+  const bool sv = lds_seen[w][lane] != 0;
+  if (A.seen) A.seen[idx] = sv ? 1.0f : 0.0f;
+  if (A.counts) {
+    const uint64_t seenm = ballot(sv);  // all 64 lanes: not inside the select below
+    int cv = __popcll(otherm);
+    cv = lane == 1 ? __popcll(seenm) : cv;
+    cv = lane == 2 ? nret : cv;
+    cv = lane == 3 ? ndrop : cv;
+    if (lane < 4) A.counts[(size_t)e * 4 + lane] = cv;
+  }
+}
+
+extern "C" int hwy_launch_lidar(const LidarParams* p, hipStream_t s) {
+  const int blocks = (p->cfg.num_envs + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  hipLaunchKernelGGL(hwy_lidar_kernel, dim3(blocks), dim3(ENVS_PER_BLOCK * WAVE), 0, s, *p);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 #else  // the main unit, to the end of the file
 template <int W>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
@@ -2574,4 +2760,4 @@ extern "C" int hwy_debug_sections(unsigned long long* out, int reset) {
 }
 #endif
 #endif  // HWY_CUT_TU / HWY_INFO_TU / HWY_FINAL_TU / HWY_OBSERVE_TU / HWY_TRAFFIC_TU / HWY_SENSE_TU /
-        // HWY_LOOKAHEAD_TU / HWY_GRID_TU
+        // HWY_LOOKAHEAD_TU / HWY_GRID_TU / HWY_LIDAR_TU

@@ -15,7 +15,8 @@ documents what they do (training/routine.py, ppo/rollout.py):
     ``safety_stats``, ``truncation`` "bootstrap": how the rollout runs and what it books;
   * ``sensor``, ``shield``, ``grid`` (hwy.SensorModel's / hwy.Shield's / hwy.GridSpec's dict, or
     True for the default grid): what the policy acts on, or through, while it trains; under a grid
-    ``state_dim`` is the spec's stride;
+    ``state_dim`` is the spec's stride; ``lidar`` (hwy.LidarSpec's dict, or True for the default)
+    likewise, with the ray-cast range observation;
   * ``attribution``, ``eval_orders``, ``eval_sensors``, ``eval_shields``: evaluations at the
     final weights that go into the metrics JSON and leave the training bit for bit what it was;
   * ``target_kl``, ``lr_anneal_updates``: PPOAgent's KL target and lr schedule.
@@ -142,8 +143,8 @@ class ExperimentRunner:
                     if device.type == "cuda":
                         overrides.setdefault("device", device)
                     # the options of exp.extra that are given (ppo/options.py), each passed on
-                    # as it is -- the routine normalises them -- but for the grid, whose spec
-                    # sets the policy's input width here
+                    # as it is -- the routine normalises them -- but for the grid and the lidar,
+                    # whose spec sets the policy's input width here
                     run_kw = {}
                     for opt in options.extra_given(exp.extra, options.LAUNCH_ORDER):
                         if opt.on_agent:  # _create_agent's
@@ -157,6 +158,10 @@ class ExperimentRunner:
                     grid = None
                     if "grid" in run_kw:
                         grid = run_kw["grid"] = options.BY_NAME["grid"].normalise(run_kw["grid"])
+                    lidar = None
+                    if "lidar" in run_kw:
+                        lidar = run_kw["lidar"] = options.BY_NAME["lidar"].normalise(
+                            run_kw["lidar"])
                     if group is not None:
                         e = int(overrides.get("num_envs", 1))
                         if e <= 1:
@@ -174,6 +179,11 @@ class ExperimentRunner:
                             raise ValueError("extra['grid'] needs the vectorised loop "
                                              "(extra['num_envs'] > 1)")
                         state_dim = grid.stride(int(env.unwrapped.hwy_config.n_features))
+                    if lidar is not None and grid is None:  # likewise (both: the routine refuses)
+                        if not hasattr(env.unwrapped, "lidar_into"):
+                            raise ValueError("extra['lidar'] needs the vectorised loop "
+                                             "(extra['num_envs'] > 1)")
+                        state_dim = lidar.stride(int(env.unwrapped.hwy_config.n_features))
                     action_dim = env.action_space.shape[0]
                     logger.info(f"[{exp.name}] state_dim={state_dim}, action_dim={action_dim}")
                     # every rank seeds the global RNGs with exp.seed (the RankPE table and the

@@ -17,6 +17,7 @@ from ._abi import (  # noqa: F401
     PE_ROPE,
     GridSpec,
     HwyConfig,
+    LidarSpec,
     SensorModel,
     Shield,
     config_from_dict,

@@ -444,6 +444,169 @@ class GridSpec:
         return a
 
 
+class LidarArgs(ctypes.Structure):
+    """hwy_lidar_args (include/hwy.h): one hwy_lidar launch's rays, sensor errors and outputs."""
+    _fields_ = [
+        ("cells", ctypes.c_int32),
+        ("sub", ctypes.c_int32),
+        ("range_m", ctypes.c_float),
+        ("align", ctypes.c_int32),
+        ("normalize", ctypes.c_int32),
+        ("speed_scale", ctypes.c_float),
+        ("p_drop", ctypes.c_float),
+        ("sigma_r", ctypes.c_float),
+        ("salt", ctypes.c_int32),
+        ("ego_tail", ctypes.c_int32),
+        ("row_stride", ctypes.c_int32),
+        ("obs", ctypes.c_void_p),
+        ("hit_vehicle", ctypes.c_void_p),
+        ("seen", ctypes.c_void_p),
+        ("counts", ctypes.c_void_p),
+    ]
+
+
+LIDAR_OUTPUTS = ("obs", "hit_vehicle", "seen", "counts")
+HWY_LIDAR_SALT = 0x4C494441
+LIDAR_MAX_CELLS = 1024
+LIDAR_MAX_SUB = 16
+LIDAR_MAX_RAYS = 4096
+LIDAR_MAX_STRIDE = 4096
+(LCOUNT_BODIES, LCOUNT_SEEN, LCOUNT_RETURNS, LCOUNT_DROPPED) = range(4)
+
+
+class LidarSpec:
+    """The ray-cast range observation of hwy_lidar (include/hwy.h), an immutable, hashable value.
+
+    ``cells`` directions around the ego, cell i centred on i * 2 pi / cells, each the nearest
+    return of its ``sub`` sub-rays within ``range_m`` metres as (distance, relative radial speed);
+    ``align``: cell 0 points along the ego's heading instead of the road's x; ``normalize``:
+    distance / ``range_m`` and speed / ``speed_scale`` (None: ``range_m``, as upstream divides
+    both columns by the range); ``p_drop``, ``sigma_r``, ``salt``: per-cell dropout probability,
+    range noise in metres and the salt of their draws; ``ego_tail``: append the ego's own
+    Kinematics row; ``pad_to``: the row stride is the width rounded up to a multiple of it.  The
+    defaults are upstream's LidarObservation: 16 cells, 60 m, normalised.  Everything
+    hwy_lidar_check refuses is a ValueError here."""
+
+    __slots__ = ("cells", "sub", "range_m", "align", "normalize", "speed_scale", "p_drop",
+                 "sigma_r", "salt", "ego_tail", "pad_to")
+
+    def __init__(self, cells: int = 16, sub: int = 1, range_m: float = 60.0, align: bool = False,
+                 normalize: bool = True, speed_scale: Optional[float] = None, p_drop: float = 0.0,
+                 sigma_r: float = 0.0, salt: int = 0, ego_tail: bool = True, pad_to: int = 4):
+        if speed_scale is None:
+            speed_scale = range_m
+        try:
+            n, s, slt, pad = int(cells), int(sub), int(salt), int(pad_to)
+            rng, scale, drop, sig = (float(v) for v in (range_m, speed_scale, p_drop, sigma_r))
+        except (TypeError, ValueError):
+            raise ValueError(f"bad lidar fields: cells={cells!r} sub={sub!r} range_m={range_m!r} "
+                             f"speed_scale={speed_scale!r} p_drop={p_drop!r} sigma_r={sigma_r!r} "
+                             f"salt={salt!r} pad_to={pad_to!r}") from None
+        if n != cells or not 1 <= n <= LIDAR_MAX_CELLS:
+            raise ValueError(f"cells must be an integer in 1..{LIDAR_MAX_CELLS}, got {cells!r}")
+        if s != sub or not 1 <= s <= LIDAR_MAX_SUB:
+            raise ValueError(f"sub must be an integer in 1..{LIDAR_MAX_SUB}, got {sub!r}")
+        if n * s > LIDAR_MAX_RAYS:
+            raise ValueError(f"cells * sub must be <= {LIDAR_MAX_RAYS}, got {n} x {s}")
+        if not (math.isfinite(rng) and rng > 0.0):
+            raise ValueError(f"range_m must be finite and > 0, got {range_m!r}")
+        if not (math.isfinite(scale) and scale > 0.0):
+            raise ValueError(f"speed_scale must be finite and > 0, got {speed_scale!r}")
+        if not 0.0 <= drop <= 1.0:
+            raise ValueError(f"p_drop must lie in [0, 1], got {p_drop!r}")
+        if not (math.isfinite(sig) and sig >= 0.0):
+            raise ValueError(f"sigma_r must be finite and >= 0, got {sigma_r!r}")
+        if slt != salt or not 0 <= slt <= 65535:
+            raise ValueError(f"salt must be an integer in 0..65535, got {salt!r}")
+        if pad != pad_to or pad < 1:
+            raise ValueError(f"pad_to must be an integer >= 1, got {pad_to!r}")
+        for name, v in (("cells", n), ("sub", s), ("range_m", rng), ("align", bool(align)),
+                        ("normalize", bool(normalize)), ("speed_scale", scale), ("p_drop", drop),
+                        ("sigma_r", sig), ("salt", slt), ("ego_tail", bool(ego_tail)),
+                        ("pad_to", pad)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("LidarSpec is immutable")
+
+    def _key(self):
+        return tuple(getattr(self, n) for n in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, LidarSpec) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "LidarSpec(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+
+    @property
+    def shape(self):
+        """(cells, 2): per cell the distance and the relative radial speed."""
+        return (self.cells, 2)
+
+    def width(self, n_features: int) -> int:
+        """Floats of a row that carry something: the cells' pairs and, with ``ego_tail``, the F
+        values of the ego's Kinematics row."""
+        return 2 * self.cells + (int(n_features) if self.ego_tail else 0)
+
+    def stride(self, n_features: int) -> int:
+        """Floats per env: ``width`` rounded up to a multiple of ``pad_to``."""
+        w = self.width(n_features)
+        s = -(-w // self.pad_to) * self.pad_to
+        if s > LIDAR_MAX_STRIDE:
+            raise ValueError(f"a lidar row of {s} floats is above hwy_lidar's {LIDAR_MAX_STRIDE}")
+        return s
+
+    def to_dict(self) -> Dict[str, Any]:
+        """JSON-ready (the metrics file)."""
+        return {n: getattr(self, n) for n in self.__slots__}
+
+    @classmethod
+    def from_dict(cls, d) -> "LidarSpec":
+        """A LidarSpec from ``to_dict``'s form (missing keys: the defaults), ``d`` itself when it
+        already is one, the default for True; unknown keys are a ValueError."""
+        if isinstance(d, cls):
+            return d
+        if d is True:
+            return cls()
+        if not isinstance(d, dict):
+            raise ValueError(f"a lidar is a LidarSpec, True or a dict of its fields, got {d!r}")
+        unknown = set(d) - set(cls.__slots__)
+        if unknown:
+            raise ValueError(f"unknown lidar keys {sorted(unknown)}; known: {list(cls.__slots__)}")
+        return cls(**d)
+
+    @classmethod
+    def from_observation_config(cls, obs: Dict[str, Any], *, ego_tail: bool = True,
+                                pad_to: int = 4, **more) -> "LidarSpec":
+        """A LidarSpec from the keys of upstream's LidarObservation config: ``cells``,
+        ``maximum_range`` and ``normalize``, each defaulting as upstream's does; any other key but
+        ``type`` is refused.  ``more``: this project's own fields (``sub``, ``align``, ...)."""
+        if not isinstance(obs, dict):
+            raise ValueError(f"an observation config is a dict, got {obs!r}")
+        known = ("type", "cells", "maximum_range", "normalize")
+        unknown = set(obs) - set(known)
+        if unknown:
+            raise ValueError(f"unknown LidarObservation keys {sorted(unknown)}; known: "
+                             f"{list(known)}")
+        if obs.get("type", "LidarObservation") != "LidarObservation":
+            raise ValueError(f"not a LidarObservation config: type {obs.get('type')!r}")
+        return cls(cells=obs.get("cells", 16), range_m=obs.get("maximum_range", 60),
+                   normalize=obs.get("normalize", True), ego_tail=ego_tail, pad_to=pad_to, **more)
+
+    def fill(self, a: LidarArgs, n_features: int) -> LidarArgs:
+        """Write the spec's fields into hwy_lidar_args ``a`` for a handle of ``n_features``."""
+        a.cells, a.sub = self.cells, self.sub
+        a.range_m, a.speed_scale = self.range_m, self.speed_scale
+        a.align, a.normalize = int(self.align), int(self.normalize)
+        a.p_drop, a.sigma_r, a.salt = self.p_drop, self.sigma_r, self.salt
+        a.ego_tail = int(self.ego_tail)
+        a.row_stride = self.stride(n_features)
+        return a
+
+
 class LookaheadArgs(ctypes.Structure):
     """hwy_lookahead_args (include/hwy.h): one hwy_lookahead call's candidates and outputs."""
     _fields_ = [

@@ -13,8 +13,8 @@ import os
 import subprocess
 from typing import Optional
 
-from ._abi import (HWY_ABI_VERSION, GridArgs, HwyConfig, HwyStepInfo, LookaheadArgs, ObserveArgs,
-                   RenderArgs, SenseArgs, TrafficArgs)
+from ._abi import (HWY_ABI_VERSION, GridArgs, HwyConfig, HwyStepInfo, LidarArgs, LookaheadArgs,
+                   ObserveArgs, RenderArgs, SenseArgs, TrafficArgs)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhwy.so")
@@ -97,6 +97,9 @@ def _signatures() -> dict:
         "hwy_grid_args_size": [],
         "hwy_grid_check": [P(GridArgs)],
         "hwy_grid": [vp, P(GridArgs), vp],
+        "hwy_lidar_args_size": [],
+        "hwy_lidar_check": [P(LidarArgs)],
+        "hwy_lidar": [vp, P(LidarArgs), vp],
         "hwy_export_state": [vp, vp, vp],
         "hwy_import_state": [vp, vp, vp],
         "hwy_obs_pe": [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp],
@@ -130,7 +133,8 @@ def lib():
                                 ("hwy_sense_args_size", SenseArgs, "hwy_sense_args"),
                                 ("hwy_lookahead_args_size", LookaheadArgs,
                                  "hwy_lookahead_args"),
-                                ("hwy_grid_args_size", GridArgs, "hwy_grid_args")):
+                                ("hwy_grid_args_size", GridArgs, "hwy_grid_args"),
+                                ("hwy_lidar_args_size", LidarArgs, "hwy_lidar_args")):
         if getattr(L, size)() != ctypes.sizeof(mirror):
             raise HwyNativeError(f"libhwy.so's {cname} differs from the python mirror; rebuild")
     if L.hwy_abi_version() != HWY_ABI_VERSION:

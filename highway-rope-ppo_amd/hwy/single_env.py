@@ -117,6 +117,11 @@ class HighwayEnv(Env):
         for the default), a float32 vector of spec.stride(F)."""
         return self._vec.grid(spec)[0].cpu().numpy()
 
+    def lidar(self, spec):
+        """The current lidar row (HighwayVecEnv.lidar: a hwy.LidarSpec, its dict, or True for the
+        default), a float32 vector of spec.stride(F)."""
+        return self._vec.lidar(spec)[0].cpu().numpy()
+
     def lookahead(self, actions, gamma: float = 1.0, obs: bool = False):
         """What-if rollouts from the current state (HighwayVecEnv.lookahead): ``actions`` is a
         [K, H, 2] array of K action sequences; returns a dict of numpy arrays, ``steps``,

@@ -211,6 +211,27 @@ def grid_args(num_envs: int, n_features: int, device, spec, *, out=None, cell_ve
     return a
 
 
+def lidar_args(num_envs: int, n_features: int, device, spec, *, out=None, hit_vehicle=None,
+               seen=None, counts=None) -> _abi.LidarArgs:
+    """hwy_lidar_args for ``num_envs`` envs of ``n_features`` Kinematics features on ``device``
+    from a LidarSpec (its dict, or True for the default) and caller-owned tensors, every refusal a
+    ValueError (no device call, no library call)."""
+    g = _abi.LidarSpec.from_dict(spec)
+    a = g.fill(_abi.LidarArgs(), n_features)
+    E = int(num_envs)
+    outs = (("obs", out, torch.float32, E * a.row_stride, f"E x {a.row_stride}", "out"),
+            ("hit_vehicle", hit_vehicle, torch.int32, E * g.cells, f"E x {g.cells}",
+             "hit_vehicle"),
+            ("seen", seen, torch.float32, E * HWY_MAX_VEHICLES, "E x 64", "seen"),
+            ("counts", counts, torch.int32, E * 4, "E x 4", "counts"))
+    for field, t, dtype, n, what, name in outs:
+        if t is not None:
+            setattr(a, field, _dev_tensor(name, t, dtype, n, what, device))
+    if all(t is None for _, t, _, _, _, _ in outs):
+        raise ValueError("lidar_into needs at least one of out, hit_vehicle, seen and counts")
+    return a
+
+
 def lookahead_args(num_envs: int, rows: int, fout: int, device, actions, horizon: int, *,
                    hold: bool = False, lazy: bool = False, gamma: float = 1.0, steps=None,
                    terminated=None, truncated=None, rewards=None, ret=None, ego_final=None,
@@ -744,6 +765,41 @@ class HighwayVecEnv:
         g = _abi.GridSpec.from_dict(spec)
         out = torch.empty(self.num_envs, g.nx, g.ny, dtype=torch.int32, device=self.device)
         self.grid_into(g, cell_vehicle=out)
+        return out
+
+    def lidar_into(self, spec, *, out: Optional[torch.Tensor] = None,
+                   hit_vehicle: Optional[torch.Tensor] = None,
+                   seen: Optional[torch.Tensor] = None,
+                   counts: Optional[torch.Tensor] = None) -> None:
+        """The ray-cast range observation of the envs' current states (``spec``: a LidarSpec, its
+        dict, or True for the default) into caller-owned device tensors (hwy_lidar, include/hwy.h:
+        one launch, no synchronisation, graph-capturable).  ``out`` [E, spec.stride(F)] float32:
+        per env the cells' (distance, relative radial speed) pairs, the ego's own Kinematics row
+        with ``ego_tail``, zero padding; ``hit_vehicle`` [E, cells] int32: the vehicle each cell
+        returns, -1 for none; ``seen`` [E, 64] float32: 1.0 for the vehicles some undropped cell
+        returns (render's ``shade`` layout); ``counts`` [E, 4] int32: other vehicles present,
+        of them seen, cells with a return, cells dropped."""
+        a = lidar_args(self.num_envs, int(self._cfg.n_features), self.device, spec, out=out,
+                       hit_vehicle=hit_vehicle, seen=seen, counts=counts)
+        check(lib().hwy_lidar(self._handle, ctypes.byref(a), stream_ptr()), "hwy_lidar")
+        self._keep_lidar = (out, hit_vehicle, seen, counts)
+
+    def lidar(self, spec, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The current lidar rows [E, spec.stride(F)] (lidar_into's ``out``): the observation a
+        lidar-trained policy acts on."""
+        g = _abi.LidarSpec.from_dict(spec)
+        stride = g.stride(int(self._cfg.n_features))
+        if out is None:
+            out = torch.empty(self.num_envs, stride, dtype=torch.float32, device=self.device)
+        self.lidar_into(g, out=out)
+        return out.view(self.num_envs, stride)
+
+    def lidar_hits(self, spec) -> torch.Tensor:
+        """[E, cells] int32: the vehicle each cell of the current lidar returns, -1 for none
+        (lidar_into's ``hit_vehicle``)."""
+        g = _abi.LidarSpec.from_dict(spec)
+        out = torch.empty(self.num_envs, g.cells, dtype=torch.int32, device=self.device)
+        self.lidar_into(g, hit_vehicle=out)
         return out
 
     def lookahead_into(self, actions: torch.Tensor, horizon: int, *, hold: bool = False,

@@ -146,6 +146,19 @@ OPTIONS = (
               vector=_ONE_ENV_LOOP + "does not take it", metrics="value"),
     RunOption("lr_anneal_updates", None, lambda v: v is not None, lambda v: v, on_agent=True,
               grouped=True, vector=_ONE_ENV_LOOP + "does not take it", metrics="value"),
+    # the lidar comes last in the table and so in every order below: no older refusal moves
+    _spec("lidar", "LidarSpec", absent=(None, False), rollout=True, group="launch",
+          metrics="value",
+          excludes=(
+              ("grid", "grid: the policy acts on one of the two observations"),
+              ("sensor", "sensor: the lidar has its own dropout and noise"),
+              ("shield", "shield: " + _UNTESTED),
+              ("truncation", 'truncation="bootstrap": the terminal observations (final_obs) would '
+                             "be Kinematics rows, not lidar rows"),
+              ("episode_schedule", 'episode_schedule="reference": the first observations after '
+                                   "the cut would be Kinematics rows, not lidar rows")),
+          excludes_late=tuple((n, _KINEMATICS) for n in ("attribution", "eval_orders",
+                                                         "eval_sensors", "eval_shields"))),
 )
 BY_NAME = {o.name: o for o in OPTIONS}
 

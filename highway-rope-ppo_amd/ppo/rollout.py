@@ -54,6 +54,11 @@ observation into the env's own observation buffer, and one hwy_grid launch after
 captured graph, writes ``buf.states[t + 1]``; one more on the reset states the caller left writes
 ``buf.states[0]``.  ``buf.states`` is ``spec.stride(F)`` wide.
 
+``lidar=`` (a hwy.LidarSpec, its dict, or True for the default): likewise with the ray-cast range
+observation: one hwy_lidar launch per env step inside the captured graph writes
+``buf.states[t + 1]``, one on the reset states ``buf.states[0]``, and ``buf.states`` is
+``spec.stride(F)`` wide.
+
 Which of these options exclude each other, and why, is ppo/options.py's table.
 """
 
@@ -95,6 +100,14 @@ def check_grid(grid, truncation: str = "terminal", episode_schedule: str = "lock
                            sensor=sensor, shield=shield)
 
 
+def check_lidar(lidar, truncation: str = "terminal", episode_schedule: str = "lockstep",
+                sensor=None, shield=None, grid=None):
+    """``lidar`` as a hwy.LidarSpec (None: none), refusing what a lidar rollout does not do."""
+    return options.checked("lidar", lidar, truncation=truncation,
+                           episode_schedule=episode_schedule, sensor=sensor, shield=shield,
+                           grid=grid)
+
+
 def rollout_chunks(T: int, episode_schedule: str):
     """The (t0, t1) step ranges a rollout of T steps is issued (and captured) in: the whole
     rollout, or, for a long reference-schedule rollout, chunks of REFERENCE_GRAPH_CHUNK steps."""
@@ -127,7 +140,7 @@ class LockstepRollout:
     def __init__(self, agent, env, buf, use_graph: bool = True,
                  episode_schedule: str = "lockstep", episode_stats: bool = False,
                  truncation: str = "terminal", safety_stats: bool = False, sensor=None,
-                 shield=None, grid=None):
+                 shield=None, grid=None, lidar=None):
         self.agent = agent
         self.env = env.unwrapped if hasattr(env, "unwrapped") else env
         self.buf = buf
@@ -137,6 +150,8 @@ class LockstepRollout:
         self.shield = check_shield(shield, truncation, episode_schedule, sensor)
         # one hwy_grid launch per env step (and one now, on the reset states the caller left)
         self.grid = check_grid(grid, truncation, episode_schedule, sensor, shield)
+        # one hwy_lidar launch per env step (and one now, on the reset states the caller left)
+        self.lidar = check_lidar(lidar, truncation, episode_schedule, sensor, shield, grid)
         if self.grid is not None:
             if not hasattr(self.env, "grid_into"):
                 raise ValueError("grid needs a vector env (HighwayVecEnv)")
@@ -144,6 +159,13 @@ class LockstepRollout:
             if buf.states.shape[-1] != stride:
                 raise ValueError(f"grid needs a RolloutBuffer of state width {stride} "
                                  f"(GridSpec.stride), got {buf.states.shape[-1]}")
+        if self.lidar is not None:
+            if not hasattr(self.env, "lidar_into"):
+                raise ValueError("lidar needs a vector env (HighwayVecEnv)")
+            stride = self.lidar.stride(int(self.env.hwy_config.n_features))
+            if buf.states.shape[-1] != stride:
+                raise ValueError(f"lidar needs a RolloutBuffer of state width {stride} "
+                                 f"(LidarSpec.stride), got {buf.states.shape[-1]}")
         if self.shield is not None:
             if not hasattr(self.env, "shield_into"):
                 raise ValueError("shield needs a vector env (HighwayVecEnv)")
@@ -186,6 +208,8 @@ class LockstepRollout:
             self.env.sense_into(self.sensor, obs=buf.states[0])
         if self.grid is not None:
             self.env.grid_into(self.grid, out=buf.states[0])
+        if self.lidar is not None:
+            self.env.lidar_into(self.lidar, out=buf.states[0])
 
     def _launch_key(self):
         from hwy.ppo_native import act_tiles, flat_params
@@ -211,6 +235,8 @@ class LockstepRollout:
             key += (self.sensor,)
         if self.grid is not None:
             key += (self.grid, env.obs_buf.data_ptr())
+        if self.lidar is not None:
+            key += (self.lidar, env.obs_buf.data_ptr())
         if self.shield is not None:
             key += (self.shield, buf.exec_actions.data_ptr(), buf.chosen.data_ptr())
         return key
@@ -228,8 +254,8 @@ class LockstepRollout:
             if self.shield is not None:
                 executed = buf.exec_actions[t]
                 env.shield_into(self.shield, buf.actions[t], executed, chosen=buf.chosen[t])
-            # under a grid the step's Kinematics rows stay in the env's own buffer
-            next_obs = (env.obs_buf if self.grid is not None
+            # under a grid or a lidar the step's Kinematics rows stay in the env's own buffer
+            next_obs = (env.obs_buf if self.grid is not None or self.lidar is not None
                         else buf.states[t + 1].view(E, *obs_shape))
             io = (executed, next_obs, buf.rewards[t],
                   buf.terminated[t], buf.truncated[t], buf.ep_return[t], buf.ep_length[t])
@@ -248,6 +274,8 @@ class LockstepRollout:
                 env.sense_into(self.sensor, obs=buf.states[t + 1])
             if self.grid is not None:
                 env.grid_into(self.grid, out=buf.states[t + 1])
+            if self.lidar is not None:
+                env.lidar_into(self.lidar, out=buf.states[t + 1])
             if self.safety_stats and not (self.episode_schedule == "reference" and t == buf.T - 1):
                 traffic_after_step(env, buf, t)
         if t1 < buf.T:

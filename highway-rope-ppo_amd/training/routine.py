@@ -67,6 +67,10 @@ at the final weights as ``order_rewards``, ``sensor_rewards`` and ``shield_rewar
 name; a shielded run's updates also carry ``shield_rate`` and the summary its last value, and
 under a grid the policy's input is ``G.stride(F)`` wide.  ``shield_profile`` counts, on unshielded
 episodes, the crashes a shield could still have avoided.
+``lidar`` (a hwy.LidarSpec, its dict, or True for the default) is the grid's sibling: ``evaluate(...,
+lidar=L)`` lets the policy act on the ray-cast range observation of the states
+(HighwayVecEnv.lidar), and a run given ``lidar`` trains on it (one hwy_lidar launch per rollout
+step, input ``L.stride(F)`` wide, its own evaluations on the same lidar, ``lidar`` in the metrics).
 """
 
 from __future__ import annotations
@@ -98,7 +102,7 @@ def _flat_dim(env) -> int:
 
 # ---------------------------------------------------------------------------------- evaluation
 def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order=None,
-             sensor=None, shield=None, tape=None, grid=None):
+             sensor=None, shield=None, tape=None, grid=None, lidar=None):
     """Mean return of deterministic episodes seeded exp_seed + 1000 + k.  ``order`` ("sorted" or
     "shuffled"; vector envs only): the same episodes with the policy acting on the states
     re-observed under that row order (HighwayVecEnv.observe) instead of the step's own rows.
@@ -111,12 +115,21 @@ def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order
     as host arrays (tests); a taped evaluation is always run.
     ``grid`` (a hwy.GridSpec, its dict, or True for the default; not with ``order``, ``sensor`` or
     ``shield``): the policy acts on the occupancy grid of the states (HighwayVecEnv.grid; on the
-    one-env facade HighwayEnv.grid per step)."""
+    one-env facade HighwayEnv.grid per step).
+    ``lidar`` (a hwy.LidarSpec, its dict, or True for the default; not with ``order``, ``sensor``,
+    ``shield`` or ``grid``): the policy acts on the ray-cast range observation of the states
+    (HighwayVecEnv.lidar; on the one-env facade HighwayEnv.lidar per step)."""
     from hwy._abi import observe_order
 
     vector = _is_vector(env)
     grid = options.BY_NAME["grid"].normalise(grid)
-    if grid is not None:
+    lidar = options.BY_NAME["lidar"].normalise(lidar)
+    if lidar is not None:
+        if order is not None or sensor is not None or shield is not None or grid is not None:
+            raise ValueError("evaluate(lidar=...) does not go with order, sensor, shield or grid: "
+                             "a lidar has no row order and its own sensor errors, and the other "
+                             "combinations are not built")
+    elif grid is not None:
         if order is not None or sensor is not None or shield is not None:
             raise ValueError("evaluate(grid=...) does not go with order, sensor or shield: a grid "
                              "has no row order, and the other combinations are not built")
@@ -137,18 +150,23 @@ def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order
             observe_order(order)  # ValueError for anything but None / "sorted" / "shuffled"
     if vector:
         return _evaluate_vector(env, agent, num_episodes, exp_seed, **options.given(
-            order=order, sensor=sensor, shield=shield, grid=grid,
+            order=order, sensor=sensor, shield=shield, grid=grid, lidar=lidar,
             tape=None if shield is None else tape))
+    own = None  # the observation the policy acts on instead of the step's rows
+    if grid is not None:
+        own = lambda: env.unwrapped.grid(grid)  # noqa: E731
+    if lidar is not None:
+        own = lambda: env.unwrapped.lidar(lidar)  # noqa: E731
     totals = []
     for ep in range(num_episodes):
         state, _ = env.reset(seed=exp_seed + 1000 + ep)
-        flat = state.reshape(-1) if grid is None else env.unwrapped.grid(grid)
+        flat = state.reshape(-1) if own is None else own()
         done, ep_reward = False, 0.0
         while not done:
             action, _, _, _ = agent.select_action(flat, deterministic=True)
             nxt, reward, terminated, truncated, _ = env.step(action)
             done = terminated or truncated
-            flat = nxt.reshape(-1) if grid is None else env.unwrapped.grid(grid)
+            flat = nxt.reshape(-1) if own is None else own()
             ep_reward += reward
         totals.append(ep_reward)
     return float(np.mean(totals))
@@ -194,13 +212,13 @@ def _eval_key(agent, num_episodes, exp_seed):
 
 
 def _evaluate_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None, shield=None,
-                     grid=None, tape=None):
+                     grid=None, tape=None, lidar=None):
     """_run_eval_vector behind a memo.  With thousands of lockstep envs many eval points (every
     eval_interval completed episodes) fall between two updates; the evaluation is deterministic,
     so a repeat at unchanged weights reuses the last result instead of re-running the episodes.
     Each variant has a memo of its own on the env and neither reads nor writes another's: the
     plain one is the pair ``_eval_memo``; the others are dicts of such pairs, ``_eval_grid_memo``
-    by spec, ``_eval_shield_memo`` by shield, ``_eval_sensor_memo`` by (sensor, order) and
+    and ``_eval_lidar_memo`` by spec, ``_eval_shield_memo`` by shield, ``_eval_sensor_memo`` by (sensor, order) and
     ``_eval_order_memo`` by order, one entry per value ever evaluated on this env, never dropped
     (a handful for eval_sensors; a caller sweeping many may clear the dict).  A taped run
     bypasses the memo."""
@@ -208,6 +226,8 @@ def _evaluate_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None
     key = _eval_key(agent, num_episodes, exp_seed)
     if grid is not None:
         attr, slot = "_eval_grid_memo", (grid,)
+    elif lidar is not None:
+        attr, slot = "_eval_lidar_memo", (lidar,)
     elif shield is not None:
         attr, slot = "_eval_shield_memo", (shield,)
     elif sensor is not None:
@@ -229,7 +249,7 @@ def _evaluate_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None
     if tape is None and hit is not None and hit[0] == key and key[0] is not None:
         return hit[1]
     r = _run_eval_vector(env, agent, num_episodes, exp_seed, **options.given(
-        order=order, sensor=sensor, shield=shield, tape=tape, grid=grid))
+        order=order, sensor=sensor, shield=shield, tape=tape, grid=grid, lidar=lidar))
     if slot is None:
         base._eval_memo = (key, r)
     else:
@@ -319,7 +339,7 @@ def shield_profile(env, agent, shield, num_episodes=10, exp_seed: int = 0, tape=
 
 
 def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None, shield=None,
-                     tape=None, grid=None):
+                     tape=None, grid=None, lidar=None):
     ev = _cached_env(env, "_eval_envs", num_episodes)
     dev = ev.device
     seen = None  # grid / sensor / order given: the states as observed under it, in its own buffer
@@ -331,6 +351,8 @@ def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None
         nonlocal seen
         if grid is not None:
             obs = seen = ev.grid(grid, out=seen)
+        elif lidar is not None:
+            obs = seen = ev.lidar(lidar, out=seen)
         elif sensor is not None:
             obs = seen = ev.sense(sensor, order=order, out=seen)
         elif order is not None:
@@ -382,11 +404,11 @@ def attribution_shade(vec_env, grad, order=None):
     return vec_env.rows_to_vehicles(rel.to(torch.float32).contiguous(), order=order)
 
 
-VISUALIZE_TINTS = ("ttc", "hidden")
+VISUALIZE_TINTS = ("ttc", "hidden", "lidar")
 
 
 def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, out_dir=None,
-                    attribution=None, tape=None, tint=None, sensor=None, grid=None):
+                    attribution=None, tape=None, tint=None, sensor=None, grid=None, lidar=None):
     """Deterministic episodes of a trained agent, seeded exp_seed + 2000 + ep, on a fresh env of
     ``env``'s config and fused wrapper (reference training/routine.py:32-58, which opens a
     render_mode="human" window; there is no display here).  All ``num_episodes`` run as one
@@ -404,7 +426,10 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
     what that sensor perceives, as in evaluate(sensor=...); "hidden" needs it.  ``grid`` (a
     hwy.GridSpec, its dict, or True for the default): the policy acts on the occupancy grid of the
     states, as in evaluate(grid=...); not with ``sensor`` or ``attribution`` (whose overlay is per
-    Kinematics row).
+    Kinematics row).  ``lidar`` (a hwy.LidarSpec, its dict, or True for the default): the policy
+    acts on the ray-cast range observation of the states, as in evaluate(lidar=...); not with
+    ``sensor``, ``grid`` or ``attribution``; ``tint="lidar"`` with it tints the vehicles some cell
+    of the lidar returns at the frame's state (HighwayVecEnv.lidar_into's ``seen``).
     ``tape``: a list that receives, per grabbed step, (observation, exported state, the episodes
     still recording) as clones (tests)."""
     if attribution is not None and attribution not in ATTRIBUTION_OUTPUTS:
@@ -420,6 +445,11 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
     grid = options.BY_NAME["grid"].normalise(grid)
     if grid is not None and (sensor is not None or attribution is not None):
         raise ValueError("visualize_agent(grid=...) does not go with sensor or attribution")
+    lidar = options.BY_NAME["lidar"].normalise(lidar)
+    if lidar is not None and (sensor is not None or grid is not None or attribution is not None):
+        raise ValueError("visualize_agent(lidar=...) does not go with sensor, grid or attribution")
+    if lidar is None and tint == "lidar":
+        raise ValueError('tint="lidar" needs a lidar')
 
     if logger is None:
         logger = logging.getLogger(__name__)
@@ -436,6 +466,8 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
             obs = ev.sense(sensor)
         if grid is not None:
             obs = ev.grid(grid)
+        if lidar is not None:
+            obs = ev.lidar(lidar)
         alive = torch.ones(n, dtype=torch.bool, device=dev)
         total = torch.zeros(n, dtype=torch.float64, device=dev)
         frames = [[] for _ in range(n)]
@@ -451,6 +483,9 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
                 ev.traffic_into(risk=shade)
             elif tint == "hidden":
                 shade = ev.hidden_vehicles(sensor)
+            elif tint == "lidar":
+                shade = torch.empty(n, 64, dtype=torch.float32, device=dev)
+                ev.lidar_into(lidar, seen=shade)
             host = ev.render(shade=shade).cpu().numpy()
             if tape is not None:
                 tape.append((obs.clone(), ev.export_state(), list(running)))
@@ -467,6 +502,8 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
                 obs = ev.sense(sensor)
             if grid is not None:
                 obs = ev.grid(grid)
+            if lidar is not None:
+                obs = ev.lidar(lidar)
             total += torch.where(alive, r.double(), torch.zeros_like(total))
             if out_dir is not None:
                 grab()  # the frame after this step, for the episodes that took it
@@ -919,9 +956,10 @@ class _EvalTracker:
 
     def __init__(self, env, agent, exp_seed, target_reward, checkpoint_dir, experiment_name,
                  metrics_history, logger, exp_prefix, start_time, sensor=None, shield=None,
-                 grid=None):
+                 grid=None, lidar=None):
         self.env, self.agent, self.exp_seed = env, agent, exp_seed
         self.grid = grid  # the grid the run trains on: its own evaluations act on it too
+        self.lidar = lidar  # likewise the lidar (never both)
         self.sensor = sensor  # the sensor the run trains under: its own evaluations use it too
         self.shield = shield  # likewise the shield (never both)
         self.target_reward = target_reward
@@ -933,7 +971,8 @@ class _EvalTracker:
 
     def _evaluate(self):
         return evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed,
-                        **options.given(sensor=self.sensor, shield=self.shield, grid=self.grid))
+                        **options.given(sensor=self.sensor, shield=self.shield, grid=self.grid,
+                                        lidar=self.lidar))
 
     def initial(self, r=None):
         if r is None:
@@ -979,14 +1018,14 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
                                episode_stats: bool = False, truncation: str = "terminal",
                                attribution: bool = False, eval_orders=None,
                                safety_stats: bool = False, sensor=None, eval_sensors=None,
-                               shield=None, eval_shields=None, grid=None):
+                               shield=None, eval_shields=None, grid=None, lidar=None):
     group = getattr(agent, "_dist", None)
     # every option normalised, and every refusal (ppo/options.py's table, in its ROUTINE_ORDER)
     opts = options.check_run(
         dict(episode_schedule=episode_schedule, episode_stats=episode_stats,
              truncation=truncation, attribution=attribution, eval_orders=eval_orders,
              safety_stats=safety_stats, sensor=sensor, eval_sensors=eval_sensors, shield=shield,
-             eval_shields=eval_shields, grid=grid, **_controls_of(agent)),
+             eval_shields=eval_shields, grid=grid, lidar=lidar, **_controls_of(agent)),
         lambda: _is_vector(env), group is not None)
     if logger is None:
         logger = setup_experiment_logger(experiment_name)
@@ -999,7 +1038,7 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
     os.makedirs(checkpoint_dir, exist_ok=True)
     tracker = _EvalTracker(env, agent, exp_seed, target_reward, checkpoint_dir, experiment_name,
                            metrics_history, logger, exp_prefix, start_time, sensor=opts["sensor"],
-                           shield=opts["shield"], grid=opts["grid"])
+                           shield=opts["shield"], grid=opts["grid"], lidar=opts["lidar"])
     rank, _ = _rank_world(group)
     if rank == 0:
         logger.info(f"{exp_prefix} Performing initial evaluation...")
@@ -1117,8 +1156,11 @@ def _train_single(env, agent, max_episodes, log_interval, eval_interval, steps_p
 def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_per_update,
                   exp_seed, logger, prefix, mh, tracker, start_time, episode_schedule="lockstep",
                   episode_stats=False, truncation="terminal", safety_stats=False, sensor=None,
-                  shield=None, grid=None):
+                  shield=None, grid=None, lidar=None):
     """E lockstep envs, device rollout of T steps, batched PPO update.
+
+    lidar: as grid, with the ray-cast range observation: states ``lidar.stride(F)`` wide, written
+    by one hwy_lidar launch on the reset states and one after every env step.
 
     grid: the policy acts on the occupancy grid of the env states: the rollout buffer's states are
     ``grid.stride(F)`` wide, the rollout writes them with one hwy_grid launch on the reset states
@@ -1160,20 +1202,21 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
     reference = episode_schedule == "reference"
     base = env.unwrapped
     E = base.num_envs
-    sd = _flat_dim(env) if grid is None else grid.stride(int(base.hwy_config.n_features))
+    own = grid if grid is not None else lidar  # the spec of the observation the rollout writes
+    sd = _flat_dim(env) if own is None else own.stride(int(base.hwy_config.n_features))
     T = max(1, math.ceil(steps_per_update / E))
     buf = RolloutBuffer(T, E, sd, 2, base.device, **options.given(
         episode_stats=episode_stats, safety_stats=safety_stats, truncation_bootstrap=bootstrap,
         shield=None if shield is None else True))
     base.set_seed_schedule(exp_seed)
     obs, _ = env.reset()
-    if grid is None:  # under a grid the rollout writes states[0] itself, from the reset states
+    if own is None:  # under a grid or a lidar the rollout writes states[0] itself
         buf.states[0].copy_(obs.reshape(E, sd))
     roll = LockstepRollout(agent, base, buf, use_graph=getattr(agent, "use_graphs", True),
                            **options.given(episode_schedule=episode_schedule,
                                            episode_stats=episode_stats, safety_stats=safety_stats,
                                            truncation=truncation, sensor=sensor, shield=shield,
-                                           grid=grid))
+                                           grid=grid, lidar=lidar))
     episode_rewards, training_episodes = [], []
     total_steps = episode_num = 0
     while episode_num < max_episodes:

@@ -7,6 +7,7 @@
     python visualize.py --model <checkpoint> --tint ttc              # who is about to be hit
     python visualize.py --model <checkpoint> --tint hidden --sensor '{"los": true, "range": 80}'
     python visualize.py --model <checkpoint> --grid true              # a grid-trained checkpoint
+    python visualize.py --model <checkpoint> --lidar true --tint lidar   # a lidar-trained one
 
 For every checkpoint the network's dimensions are read from the saved weights
 (``shared.0.weight`` is [hidden_dim, state_dim], ``actor_mean.2.weight`` [action_dim,
@@ -25,8 +26,10 @@ exclude each other.  ``--sensor JSON`` (hwy.SensorModel's fields) lets the polic
 sensor perceives (hwy_sense), and ``--tint hidden`` with it tints the vehicles the sensor does not
 see.  ``--grid JSON`` (hwy.GridSpec's fields, or ``true`` for the default) lets a checkpoint
 trained on the occupancy grid (hwy_grid) drive the episodes: its input width is checked against
-the spec's stride.  There is no live window and no MP4: neither a display nor an encoder is a
-dependency.
+the spec's stride.  ``--lidar JSON`` (hwy.LidarSpec's fields, or ``true``) does the same for a
+checkpoint trained on the ray-cast range observation (hwy_lidar), and ``--tint lidar`` with it
+tints the vehicles the lidar returns.  There is no live window and no MP4: neither a display nor
+an encoder is a dependency.
 """
 
 from __future__ import annotations
@@ -102,7 +105,7 @@ def load_agent(path: str, device=None):
 
 def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=None,
            attribution: Optional[str] = None, tint: Optional[str] = None,
-           sensor=None, grid=None) -> List[float]:
+           sensor=None, grid=None, lidar=None) -> List[float]:
     """Record ``episodes`` episodes of one checkpoint into out_dir/<checkpoint stem>/; returns
     their rewards.  ``attribution`` ("acceleration", "steering" or "value"): tint every vehicle by
     the policy's input-gradient mass on the row that shows it (visualize_agent).  ``tint``
@@ -110,7 +113,8 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
     (a hwy.SensorModel or its dict): the policy acts on what it perceives, and ``tint`` "hidden"
     tints the vehicles it does not see.  ``grid`` (a hwy.GridSpec, its dict, or True): the policy
     acts on the occupancy grid of the states, as a grid-trained checkpoint expects; not with
-    ``sensor`` or ``attribution``."""
+    ``sensor`` or ``attribution``.  ``lidar`` (a hwy.LidarSpec, its dict, or True): likewise with
+    the ray-cast range observation, and ``tint`` "lidar" tints the vehicles it returns."""
     if tint is not None and attribution is not None:
         raise ValueError("tint and attribution both shade the vehicles: give one of them")
     if tint == "hidden" and sensor is None:
@@ -121,6 +125,14 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
         grid = GridSpec.from_dict(grid)
         if sensor is not None or attribution is not None:
             raise ValueError("grid does not go with sensor or attribution")
+    if tint == "lidar" and lidar is None:
+        raise ValueError('tint "lidar" needs a lidar')
+    if lidar is not None:
+        from hwy._abi import LidarSpec
+
+        lidar = LidarSpec.from_dict(lidar)
+        if sensor is not None or grid is not None or attribution is not None:
+            raise ValueError("lidar does not go with sensor, grid or attribution")
     from config.base_config import HIGHWAY_CONFIG
     from experiments.wrappers import make_env
     from training.routine import visualize_agent
@@ -133,6 +145,8 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
         have = int(env.observation_space.shape[0] * env.observation_space.shape[1])
         if grid is not None:
             have = grid.stride(int(env.unwrapped.hwy_config.n_features))
+        if lidar is not None:
+            have = lidar.stride(int(env.unwrapped.hwy_config.n_features))
         want = infer_dims(agent.actor_critic.state_dict())[0]
         if have != want:
             raise ValueError(f"{os.path.basename(path)}: the checkpoint takes {want} inputs, the "
@@ -140,7 +154,8 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
         dest = os.path.join(out_dir, os.path.splitext(os.path.basename(path))[0])
         rewards = visualize_agent(env, agent, num_episodes=episodes, exp_seed=seed, out_dir=dest,
                                   attribution=attribution,
-                                  **given(tint=tint or None, sensor=sensor, grid=grid))
+                                  **given(tint=tint or None, sensor=sensor, grid=grid,
+                                          lidar=lidar))
     finally:
         env.close()
     for ep, r in enumerate(rewards):
@@ -167,7 +182,7 @@ def main(argv=None) -> int:
                    help="episode ep is seeded seed + 2000 + ep, as visualize_agent")
     p.add_argument("--attribution", choices=("acceleration", "steering", "value"), default=None,
                    help="tint each vehicle by |input gradient| of this output on its row")
-    p.add_argument("--tint", choices=("ttc", "hidden"), default=None,
+    p.add_argument("--tint", choices=("ttc", "hidden", "lidar"), default=None,
                    help="tint each vehicle by its time-to-collision risk, or (hidden, with "
                         "--sensor) the vehicles the sensor does not see (not with --attribution)")
     p.add_argument("--sensor", default=None, metavar="JSON",
@@ -176,6 +191,10 @@ def main(argv=None) -> int:
     p.add_argument("--grid", default=None, metavar="JSON",
                    help="the policy acts on this occupancy grid (a grid-trained checkpoint), e.g. "
                         '\'{"nx": 24, "ny": 5, "align": true}\', or true for the default grid')
+    p.add_argument("--lidar", default=None, metavar="JSON",
+                   help="the policy acts on this lidar (a lidar-trained checkpoint), e.g. "
+                        '\'{"cells": 64, "align": true}\', or true for the default lidar; '
+                        "--tint lidar tints the vehicles it returns")
     args = p.parse_args(argv)
     if args.tint and args.attribution:
         p.error("--tint and --attribution both shade the vehicles: give one of them")
@@ -203,10 +222,24 @@ def main(argv=None) -> int:
             p.error(f"--grid: {e}")
         if sensor is not None or args.attribution:
             p.error("--grid does not go with --sensor or --attribution")
+    lidar = None
+    if args.lidar is not None:
+        import json
+
+        from hwy._abi import LidarSpec
+
+        try:
+            lidar = LidarSpec.from_dict(json.loads(args.lidar))
+        except ValueError as e:
+            p.error(f"--lidar: {e}")
+        if sensor is not None or grid is not None or args.attribution:
+            p.error("--lidar does not go with --sensor, --grid or --attribution")
+    if args.tint == "lidar" and lidar is None:
+        p.error("--tint lidar needs --lidar")
     models = [args.model] if args.model else list(models_from_file(args.models_file))
     for m in models:
         record(m, args.out, episodes=args.episodes, seed=args.seed, attribution=args.attribution,
-               tint=args.tint, **given(sensor=sensor, grid=grid))
+               tint=args.tint, **given(sensor=sensor, grid=grid, lidar=lidar))
     return 0
 
 

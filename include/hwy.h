@@ -51,6 +51,8 @@
  *   hwy_lookahead             <- copy.deepcopy(env) then env.step(a), repeated, for K action sequences
  *   hwy_grid                  <- OccupancyGridObservation.observe() [highway-env 1.10.1] of a
  *                                Kinematics env's road (this project's own rule, not upstream's bits)
+ *   hwy_lidar                 <- LidarObservation.observe() [highway-env 1.10.1] of a Kinematics
+ *                                env's road (this project's own rule, not upstream's trace())
  *
  * Conventions
  *   - Plain pointers and sizes only; device pointers are HIP device pointers (e.g. torch
@@ -770,6 +772,109 @@ int hwy_grid_args_size(void);
  * handle's F enters in hwy_grid); pure, no device call. */
 int hwy_grid_check(const hwy_grid_args* a);
 int hwy_grid(hwy_handle* h, const hwy_grid_args* a, void* stream);
+
+/* ---- A ray-cast range observation of the env states: a ring of lidar returns around the ego.
+ *
+ * hwy_lidar casts, for all E envs and from the state words as they stand, n = cells*sub rays from
+ * the ego's centre against the 5.0 x 2.0 rectangles of the other present vehicles and writes per
+ * cell the nearest return: (distance, relative radial speed).  Like the grid it has no row order;
+ * unlike it, it is narrow (2*cells floats) and occlusion-aware by construction: a car behind
+ * another returns nothing.  highway-env's LidarObservation is the model for the shape: the layout
+ * [cells][2], cell i centred on direction i*2pi/cells, and the config keys cells, maximum_range
+ * and normalize (the Python layer takes them over).  The rule itself is this project's own, stated
+ * here, and is not pinned against upstream's trace(): upstream's "centre distance minus half a
+ * width" shortcut for the sector that holds a vehicle's centre is not reproduced; instead a cell
+ * may pool several sub-rays.  Road borders are no returns.  The lidar observes a Kinematics env;
+ * "type": "LidarObservation" in an env config stays refused.
+ *
+ * All arithmetic is binary32 without contraction, each product rounded before the sum it
+ * enters; a comparison with a NaN is false; min(a, b) is b < a ? b : a and max(a, b) is
+ * b > a ? b : a.  The ego is vehicle 0 at (xe, ye) with heading h_e, V = vehicles_count + 1, F
+ * the handle's n_features.  A vehicle k, 1 <= k < V, is a body iff it carries HWY_FLAG_PRESENT (a
+ * flag word in a lane >= V means nothing, as in the step).  A crashed vehicle is a body.
+ *
+ * Rays.  dth = (float)(6.283185307179586 / (double)n), computed in the library.  Sub-ray j of cell
+ * i, r = i*sub + j:
+ *   theta = ((float)r + (0.5f - 0.5f*(float)sub)) * dth; with align != 0, theta = theta + h_e
+ *   (dy, dx) = hm_sincosf(theta)
+ * so sub = 1 gives upstream's directions and a cell's sub-rays are spread evenly about its centre.
+ *
+ * Ray against body k, the slab test in the body's frame:
+ *   (sk, ck) = hm_sincosf(h_k), ox = xe - x_k, oy = ye - y_k
+ *   ou = ox*ck + oy*sk, ow = oy*ck - ox*sk, du = dx*ck + dy*sk, dw = dy*ck - dx*sk
+ *   per axis a with half extent H (2.5 for u, 1.0 for w):
+ *     d_a == 0: the interval is (-inf, +inf) when |o_a| <= H, else empty
+ *     otherwise t1 = (-H - o_a)/d_a, t2 = (H - o_a)/d_a, the interval is [min(t1,t2), max(t1,t2)]
+ *   t_in = max(lower end of u, lower end of w), t_out = min(upper end of u, upper end of w)
+ *   the ray hits k iff neither interval is empty, t_in <= t_out and t_out >= 0
+ *   its distance is d = t_in > 0 ? t_in : +0.0: an origin inside the rectangle gives 0
+ *   the hit counts iff d <= range_m
+ * The d_a == 0 branch is no corner case: the unaligned ray 0 against a heading-0 body has dw == 0
+ * exactly.  A body whose position or heading is not finite returns nothing: every t of it is then
+ * non-finite and fails one of the tests above.
+ *
+ * Winners.  A ray returns its counted hit of least d, among equal d the least k.  A cell returns
+ * its sub-ray of least d, among equal d the least j.  A returning cell has
+ *   dist = d, vel = ((vkx - vex)*dx) + ((vky - vey)*dy)
+ * with dx, dy of the winning sub-ray and v?x = speed*cos, v?y = speed*sin from hm_sincosf of the
+ * stored headings.  A cell without a return has dist = range_m, vel = +0.0, hit_vehicle = -1.
+ *
+ * Per-cell sensor errors, after pooling, keyed like hwy_sense's draws:
+ *   w(c) = philox4x32_10((cell, step word, c, HWY_LIDAR_SALT + salt), key = the episode's seed)
+ *   c = 0, dropout: the cell is dropped iff hm_u01(w(0)[0]) < p_drop, whether it returned or not;
+ *     a dropped cell is written as a cell without a return
+ *   c = 1, range noise, on cells that return and are not dropped: with hwy_sense's
+ *     z = (((u0 + u1) + (u2 + u3)) - 2) * 1.7320508f of w(1),
+ *     dist = hm_clipf(dist + sigma_r*z, 0, range_m); a sigma_r of exactly 0 skips the addition.
+ *   The range test is on the true distance, before the noise.
+ *
+ *   obs [E][row_stride] f32: per env the cells pairs (dist, vel), with normalize != 0 as
+ *     (dist / range_m, vel / speed_scale); then, with ego_tail != 0, the F values of the handle's
+ *     own Kinematics row 0 before any wrapper (exactly hwy_grid's ego tail); entries from the
+ *     width 2*cells + (ego_tail ? F : 0) up to row_stride are +0.0.
+ *   hit_vehicle [E][cells] i32: the vehicle a cell returns, -1 for none.
+ *   seen [E][64] f32: 1.0 where the vehicle is the return of at least one undropped cell, else
+ *     +0.0 (the ego, absent slots and lanes >= V included): hwy_render's shade layout.
+ *   counts [E][4] i32: bodies (present others); bodies seen; cells with a return; cells dropped.
+ *
+ * No entry of a given output is left unwritten and nothing past E*row_stride floats of obs is
+ * touched.  All outputs are device pointers and nullable, but at least one must be given.
+ * hwy_lidar is asynchronous, allocates nothing, is hipGraph-capturable, reads the state and
+ * writes nothing but the outputs it was given.  On non-finite state words the values are
+ * unspecified, but every loop is bounded and every index in bounds.  It returns HWY_EINVAL before
+ * any device call for a NULL handle or NULL args, no output at all, cells outside 1..1024, sub
+ * outside 1..16, cells*sub above 4096, a range_m or speed_scale that is not finite and > 0, a
+ * p_drop outside [0, 1], a sigma_r that is not finite and >= 0, a salt outside 0..65535 and a
+ * row_stride below the width or above 4096. */
+#define HWY_LIDAR_SALT 0x4C494441u
+#define HWY_LIDAR_MAX_CELLS 1024
+#define HWY_LIDAR_MAX_SUB 16
+#define HWY_LIDAR_MAX_RAYS 4096
+#define HWY_LIDAR_MAX_STRIDE 4096
+typedef struct hwy_lidar_args {
+  int32_t cells;         /* 1..1024 */
+  int32_t sub;           /* sub-rays per cell, 1..16, cells*sub <= 4096 */
+  float range_m;         /* m, finite and > 0 */
+  int32_t align;         /* != 0: cell 0 points along the ego's heading, not the road's x */
+  int32_t normalize;     /* != 0: dist / range_m, vel / speed_scale */
+  float speed_scale;     /* m/s, finite and > 0 */
+  float p_drop;          /* per-cell dropout probability, 0..1 */
+  float sigma_r;         /* m, range noise, finite and >= 0 */
+  int32_t salt;          /* 0..65535 */
+  int32_t ego_tail;      /* != 0: append the ego's own Kinematics row */
+  int32_t row_stride;    /* floats per env in obs: width..4096 */
+  float* obs;            /* device [E][row_stride], nullable */
+  int32_t* hit_vehicle;  /* device [E][cells], nullable */
+  float* seen;           /* device [E][64], nullable */
+  int32_t* counts;       /* device [E][4], nullable */
+} hwy_lidar_args;
+/* sizeof(hwy_lidar_args) as compiled into the library (binding layout check). */
+int hwy_lidar_args_size(void);
+/* HWY_OK, or HWY_EINVAL for arguments hwy_lidar refuses (every check that needs no handle: of
+ * row_stride, that it holds the cells, one more float with ego_tail, and is at most 4096; the
+ * handle's F enters in hwy_lidar); pure, no device call. */
+int hwy_lidar_check(const hwy_lidar_args* a);
+int hwy_lidar(hwy_handle* h, const hwy_lidar_args* a, void* stream);
 
 /* Stand-alone observation wrapper on [E,N,F] f32 -> [E,N,F_out] f32 (foreign envs).
  *   kind = enum hwy_pe_kind, d = appended width (rank/dist) or rotate_dim (rope),
