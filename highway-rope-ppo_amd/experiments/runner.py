@@ -13,10 +13,10 @@ documents what they do (training/routine.py, ppo/rollout.py):
   * ``episode_schedule`` "reference" (with it ``num_envs`` 1 runs the vectorised loop on a one-env
     HighwayVecEnv, which is the reference's own episode stream), ``episode_stats``,
     ``safety_stats``, ``truncation`` "bootstrap": how the rollout runs and what it books;
-  * ``sensor``, ``shield``, ``grid`` (hwy.SensorModel's / hwy.Shield's / hwy.GridSpec's dict, or
-    True for the default grid): what the policy acts on, or through, while it trains; under a grid
-    ``state_dim`` is the spec's stride; ``lidar`` (hwy.LidarSpec's dict, or True for the default)
-    likewise, with the ray-cast range observation;
+  * ``sensor``, ``grid``, ``lidar`` (the views: hwy.SensorModel's / hwy.GridSpec's /
+    hwy.LidarSpec's dict, or True for the default grid or lidar) and ``shield`` (hwy.Shield's
+    dict): what the policy acts on, or through, while it trains; under a grid or a lidar
+    ``state_dim`` is HighwayVecEnv.view_width of the spec;
   * ``attribution``, ``eval_orders``, ``eval_sensors``, ``eval_shields``: evaluations at the
     final weights that go into the metrics JSON and leave the training bit for bit what it was;
   * ``target_kl``, ``lr_anneal_updates``: PPOAgent's KL target and lr schedule.
@@ -143,8 +143,8 @@ class ExperimentRunner:
                     if device.type == "cuda":
                         overrides.setdefault("device", device)
                     # the options of exp.extra that are given (ppo/options.py), each passed on
-                    # as it is -- the routine normalises them -- but for the grid and the lidar,
-                    # whose spec sets the policy's input width here
+                    # as it is -- the routine normalises them -- but for the views, whose spec
+                    # may set the policy's input width here
                     run_kw = {}
                     for opt in options.extra_given(exp.extra, options.LAUNCH_ORDER):
                         if opt.on_agent:  # _create_agent's
@@ -155,13 +155,12 @@ class ExperimentRunner:
                         run_kw[opt.name] = exp.extra[opt.name]
                     if run_kw.get("episode_schedule") == "reference":
                         overrides.setdefault("vector_env", True)
-                    grid = None
-                    if "grid" in run_kw:
-                        grid = run_kw["grid"] = options.BY_NAME["grid"].normalise(run_kw["grid"])
-                    lidar = None
-                    if "lidar" in run_kw:
-                        lidar = run_kw["lidar"] = options.BY_NAME["lidar"].normalise(
-                            run_kw["lidar"])
+                    for name in options.VIEWS:
+                        if name in run_kw:
+                            run_kw[name] = options.BY_NAME[name].normalise(run_kw[name])
+                    # the first view that replaces the rows (two: the routine refuses)
+                    own = next((n for n in options.VIEWS
+                                if n in run_kw and run_kw[n].REPLACES_ROWS), None)
                     if group is not None:
                         e = int(overrides.get("num_envs", 1))
                         if e <= 1:
@@ -174,16 +173,11 @@ class ExperimentRunner:
                     if not isinstance(env.observation_space, spaces.Box):
                         raise TypeError(f"Unsupported observation space: {type(env.observation_space)}")
                     state_dim = int(np.prod(env.observation_space.shape))
-                    if grid is not None:  # the policy's input is the grid row, not the rows
-                        if not hasattr(env.unwrapped, "grid_into"):
-                            raise ValueError("extra['grid'] needs the vectorised loop "
+                    if own is not None:  # the policy's input is the view's row, not the rows
+                        if not hasattr(env.unwrapped, "view_width"):
+                            raise ValueError(f"extra[{own!r}] needs the vectorised loop "
                                              "(extra['num_envs'] > 1)")
-                        state_dim = grid.stride(int(env.unwrapped.hwy_config.n_features))
-                    if lidar is not None and grid is None:  # likewise (both: the routine refuses)
-                        if not hasattr(env.unwrapped, "lidar_into"):
-                            raise ValueError("extra['lidar'] needs the vectorised loop "
-                                             "(extra['num_envs'] > 1)")
-                        state_dim = lidar.stride(int(env.unwrapped.hwy_config.n_features))
+                        state_dim = env.unwrapped.view_width(run_kw[own])
                     action_dim = env.action_space.shape[0]
                     logger.info(f"[{exp.name}] state_dim={state_dim}, action_dim={action_dim}")
                     # every rank seeds the global RNGs with exp.seed (the RankPE table and the

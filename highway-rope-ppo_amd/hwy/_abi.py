@@ -125,6 +125,94 @@ def observe_order(order) -> int:
         raise ValueError(f"order must be None, 'sorted' or 'shuffled', got {order!r}") from None
 
 
+class _Record:
+    """What the option records (SensorModel, GridSpec, LidarSpec, Shield) share: immutable,
+    hashable values over the fields of ``__slots__``, JSON-ready through to_dict / from_dict.
+    ``NOUN`` is what the messages call the record, and its run option's name in ppo/options.py;
+    ``TRUE_IS_DEFAULT``: from_dict(True) is the default record; ``REPLACES_ROWS`` (of a view,
+    HighwayVecEnv.view_into): what it writes stands in place of the step's Kinematics rows, with
+    a width of its own, instead of overwriting them."""
+
+    __slots__ = ()
+    NOUN = ""
+    TRUE_IS_DEFAULT = False
+    REPLACES_ROWS = False
+
+    def _init(self, **fields):
+        for name, v in fields.items():
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"{type(self).__name__} is immutable")
+
+    def _key(self):
+        return tuple(getattr(self, n) for n in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, type(self)) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        fields = ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__)
+        return f"{type(self).__name__}({fields})"
+
+    def _json_fields(self) -> Dict[str, Any]:
+        """The fields whose JSON form is not the value itself (tuples as lists or dicts)."""
+        return {}
+
+    def to_dict(self) -> Dict[str, Any]:
+        """JSON-ready (the metrics file)."""
+        d = {n: getattr(self, n) for n in self.__slots__}
+        d.update(self._json_fields())
+        return d
+
+    @classmethod
+    def from_dict(cls, d):
+        """A record from ``to_dict``'s form (missing keys: the defaults), ``d`` itself when it
+        already is one, the default for True where the class takes it; unknown keys are a
+        ValueError."""
+        if isinstance(d, cls):
+            return d
+        if d is True and cls.TRUE_IS_DEFAULT:
+            return cls()
+        if not isinstance(d, dict):
+            raise ValueError(f"a {cls.NOUN} is a {cls.__name__}"
+                             f"{', True' if cls.TRUE_IS_DEFAULT else ''} or a dict of its fields, "
+                             f"got {d!r}")
+        unknown = set(d) - set(cls.__slots__)
+        if unknown:
+            raise ValueError(f"unknown {cls.NOUN} keys {sorted(unknown)}; known: "
+                             f"{list(cls.__slots__)}")
+        return cls(**d)
+
+
+class _RowSpec(_Record):
+    """A record of an observation that is one padded float32 row per env (GridSpec, LidarSpec):
+    ``payload`` floats, the ego's own Kinematics row with ``ego_tail``, zeros up to a multiple of
+    ``pad_to``, at most ``MAX_STRIDE`` floats (hwy_<NOUN>'s cap)."""
+
+    __slots__ = ()
+    TRUE_IS_DEFAULT = True
+    REPLACES_ROWS = True
+    MAX_STRIDE = 0
+
+    def width(self, n_features: int) -> int:
+        """Floats of a row that carry something: the payload and, with ``ego_tail``, the F values
+        of the ego's Kinematics row."""
+        return self.payload + (int(n_features) if self.ego_tail else 0)
+
+    def stride(self, n_features: int) -> int:
+        """Floats per env: ``width`` rounded up to a multiple of ``pad_to``."""
+        w = self.width(n_features)
+        s = -(-w // self.pad_to) * self.pad_to
+        if s > self.MAX_STRIDE:
+            raise ValueError(f"a {self.NOUN} row of {s} floats is above hwy_{self.NOUN}'s "
+                             f"{self.MAX_STRIDE}")
+        return s
+
+
 class SenseArgs(ctypes.Structure):
     """hwy_sense_args (include/hwy.h): one hwy_sense launch's order, sensor and outputs."""
     _fields_ = [
@@ -146,7 +234,7 @@ SENSE_OUTPUTS = ("obs", "row_vehicle", "visible", "hidden", "counts")
 HWY_SENSE_SALT = 0x53454E53
 
 
-class SensorModel:
+class SensorModel(_Record):
     """The sensor of hwy_sense (include/hwy.h), an immutable, hashable value.
 
     ``los``: line-of-sight occlusion by the other vehicles' bodies; ``range``: sensing range in
@@ -156,6 +244,7 @@ class SensorModel:
     refuses is a ValueError here."""
 
     __slots__ = ("los", "range", "dropout", "noise", "salt")
+    NOUN = "sensor"
 
     def __init__(self, los: bool = False, range: Optional[float] = None, dropout: float = 0.0,
                  noise=(0, 0, 0), salt: int = 0):
@@ -177,27 +266,7 @@ class SensorModel:
             raise ValueError(f"noise must be three finite values >= 0 (x, y, speed), got {noise!r}")
         if slt != salt or not 0 <= slt <= 65535:
             raise ValueError(f"salt must be an integer in 0..65535, got {salt!r}")
-        object.__setattr__(self, "los", bool(los))
-        object.__setattr__(self, "range", rng)
-        object.__setattr__(self, "dropout", drop)
-        object.__setattr__(self, "noise", sig)
-        object.__setattr__(self, "salt", slt)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("SensorModel is immutable")
-
-    def _key(self):
-        return (self.los, self.range, self.dropout, self.noise, self.salt)
-
-    def __eq__(self, other):
-        return isinstance(other, SensorModel) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
-
-    def __repr__(self):
-        return (f"SensorModel(los={self.los}, range={self.range}, dropout={self.dropout}, "
-                f"noise={self.noise}, salt={self.salt})")
+        self._init(los=bool(los), range=rng, dropout=drop, noise=sig, salt=slt)
 
     @property
     def is_null(self) -> bool:
@@ -205,23 +274,8 @@ class SensorModel:
         return (not self.los and self.range is None and self.dropout == 0.0
                 and self.noise == (0.0, 0.0, 0.0))
 
-    def to_dict(self) -> Dict[str, Any]:
-        """JSON-ready (the metrics file): range None = unlimited."""
-        return {"los": self.los, "range": self.range, "dropout": self.dropout,
-                "noise": list(self.noise), "salt": self.salt}
-
-    @classmethod
-    def from_dict(cls, d) -> "SensorModel":
-        """A SensorModel from ``to_dict``'s form (missing keys: the defaults), or ``d`` itself
-        when it already is one; unknown keys are a ValueError."""
-        if isinstance(d, cls):
-            return d
-        if not isinstance(d, dict):
-            raise ValueError(f"a sensor is a SensorModel or a dict of its fields, got {d!r}")
-        unknown = set(d) - set(cls.__slots__)
-        if unknown:
-            raise ValueError(f"unknown sensor keys {sorted(unknown)}; known: {list(cls.__slots__)}")
-        return cls(**d)
+    def _json_fields(self):  # range None = unlimited
+        return {"noise": list(self.noise)}
 
     def fill(self, a: SenseArgs) -> SenseArgs:
         """Write the sensor's fields into hwy_sense_args ``a``."""
@@ -267,7 +321,7 @@ GRID_LAYERS = dict(FEATURES, on_road=GRID_ON_ROAD)
 (GCOUNT_PRESENT, GCOUNT_INSIDE, GCOUNT_LOST, GCOUNT_OUTSIDE) = range(4)
 
 
-class GridSpec:
+class GridSpec(_RowSpec):
     """The occupancy grid of hwy_grid (include/hwy.h), an immutable, hashable value.
 
     ``layers``: names out of FEATURES and "on_road", distinct; ``nx`` x ``ny`` cells of
@@ -281,6 +335,8 @@ class GridSpec:
 
     __slots__ = ("layers", "nx", "ny", "x0", "y0", "step_x", "step_y", "ranges", "clip", "align",
                  "ego_tail", "pad_to")
+    NOUN = "grid"
+    MAX_STRIDE = GRID_MAX_STRIDE
 
     def __init__(self, layers=("presence", "vx", "vy"), nx: int = 24, ny: int = 5,
                  x0: float = -32.5, y0: float = -10.0, step_x: float = 5.0, step_y: float = 4.0,
@@ -322,66 +378,23 @@ class GridSpec:
             raise ValueError(f"a range is given twice: {[k for k, _ in rng]}")
         if pad != pad_to or pad < 1:
             raise ValueError(f"pad_to must be an integer >= 1, got {pad_to!r}")
-        for name, v in (("layers", lay), ("nx", gx), ("ny", gy), ("x0", geo[0]), ("y0", geo[1]),
-                        ("step_x", geo[2]), ("step_y", geo[3]), ("ranges", rng),
-                        ("clip", bool(clip)), ("align", bool(align)),
-                        ("ego_tail", bool(ego_tail)), ("pad_to", pad)):
-            object.__setattr__(self, name, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("GridSpec is immutable")
-
-    def _key(self):
-        return tuple(getattr(self, n) for n in self.__slots__)
-
-    def __eq__(self, other):
-        return isinstance(other, GridSpec) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
-
-    def __repr__(self):
-        return "GridSpec(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+        self._init(layers=lay, nx=gx, ny=gy, x0=geo[0], y0=geo[1], step_x=geo[2], step_y=geo[3],
+                   ranges=rng, clip=bool(clip), align=bool(align), ego_tail=bool(ego_tail),
+                   pad_to=pad)
 
     @property
     def shape(self):
         """(C, W, H) of the layers: layer, cell along x, cell along y."""
         return (len(self.layers), self.nx, self.ny)
 
-    def width(self, n_features: int) -> int:
-        """Floats of a row that carry something: the layers and, with ``ego_tail``, the F values
-        of the ego's Kinematics row."""
-        return len(self.layers) * self.nx * self.ny + (int(n_features) if self.ego_tail else 0)
+    @property
+    def payload(self) -> int:
+        """Floats of the layers."""
+        return len(self.layers) * self.nx * self.ny
 
-    def stride(self, n_features: int) -> int:
-        """Floats per env: ``width`` rounded up to a multiple of ``pad_to``."""
-        w = self.width(n_features)
-        s = -(-w // self.pad_to) * self.pad_to
-        if s > GRID_MAX_STRIDE:
-            raise ValueError(f"a grid row of {s} floats is above hwy_grid's {GRID_MAX_STRIDE}")
-        return s
-
-    def to_dict(self) -> Dict[str, Any]:
-        """JSON-ready (the metrics file)."""
-        d = {n: getattr(self, n) for n in self.__slots__}
-        d["layers"] = list(self.layers)
-        d["ranges"] = {k: [lo, hi] for k, (lo, hi) in self.ranges}
-        return d
-
-    @classmethod
-    def from_dict(cls, d) -> "GridSpec":
-        """A GridSpec from ``to_dict``'s form (missing keys: the defaults), ``d`` itself when it
-        already is one, the default for True; unknown keys are a ValueError."""
-        if isinstance(d, cls):
-            return d
-        if d is True:
-            return cls()
-        if not isinstance(d, dict):
-            raise ValueError(f"a grid is a GridSpec, True or a dict of its fields, got {d!r}")
-        unknown = set(d) - set(cls.__slots__)
-        if unknown:
-            raise ValueError(f"unknown grid keys {sorted(unknown)}; known: {list(cls.__slots__)}")
-        return cls(**d)
+    def _json_fields(self):
+        return {"layers": list(self.layers),
+                "ranges": {k: [lo, hi] for k, (lo, hi) in self.ranges}}
 
     @classmethod
     def from_observation_config(cls, obs: Dict[str, Any], *, ego_tail: bool = True,
@@ -474,7 +487,7 @@ LIDAR_MAX_STRIDE = 4096
 (LCOUNT_BODIES, LCOUNT_SEEN, LCOUNT_RETURNS, LCOUNT_DROPPED) = range(4)
 
 
-class LidarSpec:
+class LidarSpec(_RowSpec):
     """The ray-cast range observation of hwy_lidar (include/hwy.h), an immutable, hashable value.
 
     ``cells`` directions around the ego, cell i centred on i * 2 pi / cells, each the nearest
@@ -489,6 +502,8 @@ class LidarSpec:
 
     __slots__ = ("cells", "sub", "range_m", "align", "normalize", "speed_scale", "p_drop",
                  "sigma_r", "salt", "ego_tail", "pad_to")
+    NOUN = "lidar"
+    MAX_STRIDE = LIDAR_MAX_STRIDE
 
     def __init__(self, cells: int = 16, sub: int = 1, range_m: float = 60.0, align: bool = False,
                  normalize: bool = True, speed_scale: Optional[float] = None, p_drop: float = 0.0,
@@ -520,63 +535,19 @@ class LidarSpec:
             raise ValueError(f"salt must be an integer in 0..65535, got {salt!r}")
         if pad != pad_to or pad < 1:
             raise ValueError(f"pad_to must be an integer >= 1, got {pad_to!r}")
-        for name, v in (("cells", n), ("sub", s), ("range_m", rng), ("align", bool(align)),
-                        ("normalize", bool(normalize)), ("speed_scale", scale), ("p_drop", drop),
-                        ("sigma_r", sig), ("salt", slt), ("ego_tail", bool(ego_tail)),
-                        ("pad_to", pad)):
-            object.__setattr__(self, name, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("LidarSpec is immutable")
-
-    def _key(self):
-        return tuple(getattr(self, n) for n in self.__slots__)
-
-    def __eq__(self, other):
-        return isinstance(other, LidarSpec) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
-
-    def __repr__(self):
-        return "LidarSpec(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+        self._init(cells=n, sub=s, range_m=rng, align=bool(align), normalize=bool(normalize),
+                   speed_scale=scale, p_drop=drop, sigma_r=sig, salt=slt, ego_tail=bool(ego_tail),
+                   pad_to=pad)
 
     @property
     def shape(self):
         """(cells, 2): per cell the distance and the relative radial speed."""
         return (self.cells, 2)
 
-    def width(self, n_features: int) -> int:
-        """Floats of a row that carry something: the cells' pairs and, with ``ego_tail``, the F
-        values of the ego's Kinematics row."""
-        return 2 * self.cells + (int(n_features) if self.ego_tail else 0)
-
-    def stride(self, n_features: int) -> int:
-        """Floats per env: ``width`` rounded up to a multiple of ``pad_to``."""
-        w = self.width(n_features)
-        s = -(-w // self.pad_to) * self.pad_to
-        if s > LIDAR_MAX_STRIDE:
-            raise ValueError(f"a lidar row of {s} floats is above hwy_lidar's {LIDAR_MAX_STRIDE}")
-        return s
-
-    def to_dict(self) -> Dict[str, Any]:
-        """JSON-ready (the metrics file)."""
-        return {n: getattr(self, n) for n in self.__slots__}
-
-    @classmethod
-    def from_dict(cls, d) -> "LidarSpec":
-        """A LidarSpec from ``to_dict``'s form (missing keys: the defaults), ``d`` itself when it
-        already is one, the default for True; unknown keys are a ValueError."""
-        if isinstance(d, cls):
-            return d
-        if d is True:
-            return cls()
-        if not isinstance(d, dict):
-            raise ValueError(f"a lidar is a LidarSpec, True or a dict of its fields, got {d!r}")
-        unknown = set(d) - set(cls.__slots__)
-        if unknown:
-            raise ValueError(f"unknown lidar keys {sorted(unknown)}; known: {list(cls.__slots__)}")
-        return cls(**d)
+    @property
+    def payload(self) -> int:
+        """Floats of the cells' pairs."""
+        return 2 * self.cells
 
     @classmethod
     def from_observation_config(cls, obs: Dict[str, Any], *, ego_tail: bool = True,
@@ -635,7 +606,7 @@ LOOKAHEAD_MAX_H = 64
 LOOKAHEAD_MAX_BRANCHES = 1 << 22
 
 
-class Shield:
+class Shield(_Record):
     """The action shield on top of hwy_lookahead (include/hwy.h), an immutable, hashable value.
 
     The policy's action, held for ``horizon`` policy steps, is candidate 0; the ``fallbacks``
@@ -645,6 +616,7 @@ class Shield:
     terminates (the choice is the same either way)."""
 
     __slots__ = ("horizon", "fallbacks", "lazy")
+    NOUN = "shield"
 
     def __init__(self, horizon: int = 3, fallbacks=((-1.0, 0.0), (0.0, 0.0), (1.0, 0.0)),
                  lazy: bool = True):
@@ -660,47 +632,15 @@ class Shield:
             raise ValueError(f"a shield takes 1..{LOOKAHEAD_MAX_K - 1} fallbacks, got {len(fb)}")
         if not all(math.isfinite(x) for pair in fb for x in pair):
             raise ValueError(f"fallback actions must be finite, got {fallbacks!r}")
-        object.__setattr__(self, "horizon", hz)
-        object.__setattr__(self, "fallbacks", fb)
-        object.__setattr__(self, "lazy", bool(lazy))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Shield is immutable")
-
-    def _key(self):
-        return (self.horizon, self.fallbacks, self.lazy)
-
-    def __eq__(self, other):
-        return isinstance(other, Shield) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
-
-    def __repr__(self):
-        return f"Shield(horizon={self.horizon}, fallbacks={self.fallbacks}, lazy={self.lazy})"
+        self._init(horizon=hz, fallbacks=fb, lazy=bool(lazy))
 
     @property
     def k(self) -> int:
         """Candidates per env: the policy's action and the fallbacks."""
         return 1 + len(self.fallbacks)
 
-    def to_dict(self) -> Dict[str, Any]:
-        """JSON-ready (the metrics file)."""
-        return {"horizon": self.horizon, "fallbacks": [list(p) for p in self.fallbacks],
-                "lazy": self.lazy}
-
-    @classmethod
-    def from_dict(cls, d) -> "Shield":
-        """A Shield from ``to_dict``'s form (missing keys: the defaults), or ``d`` itself when it
-        already is one; unknown keys are a ValueError."""
-        if isinstance(d, cls):
-            return d
-        if not isinstance(d, dict):
-            raise ValueError(f"a shield is a Shield or a dict of its fields, got {d!r}")
-        unknown = set(d) - set(cls.__slots__)
-        if unknown:
-            raise ValueError(f"unknown shield keys {sorted(unknown)}; known: {list(cls.__slots__)}")
-        return cls(**d)
+    def _json_fields(self):
+        return {"fallbacks": [list(p) for p in self.fallbacks]}
 
 
 # the view hwy_render draws by default: upstream's AbstractEnv.default_config screen_width,

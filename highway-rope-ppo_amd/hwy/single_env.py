@@ -14,7 +14,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
-from ._abi import REWARD_KEYS
+from ._abi import REWARD_KEYS, GridSpec, LidarSpec, SensorModel
 from .gym import Env, spaces
 from .vec_env import HighwayVecEnv
 
@@ -107,20 +107,22 @@ class HighwayEnv(Env):
         [64] int32 and ``gap``, ``closing``, ``ttc``, ``thw``, ``risk`` [64] float32."""
         return {k: t[0].cpu().numpy() for k, t in self._vec.traffic(**thresholds).items()}
 
+    def view(self, spec):
+        """What a policy under view ``spec`` (a hwy.SensorModel, GridSpec or LidarSpec) acts on at
+        the current state (HighwayVecEnv.view), a float32 vector of view_width(spec)."""
+        return self._vec.view(spec)[0].cpu().numpy()
+
     def sense(self, sensor):
-        """The current observation through ``sensor`` (HighwayVecEnv.sense: a hwy.SensorModel or
-        its dict), an [N, F_out] float32 numpy array."""
-        return self._vec.sense(sensor)[0].cpu().numpy()
+        """view() through ``sensor`` (a hwy.SensorModel or its dict) as [N, F_out] rows."""
+        return self.view(SensorModel.from_dict(sensor)).reshape(self.observation_space.shape)
 
     def grid(self, spec):
-        """The current occupancy grid row (HighwayVecEnv.grid: a hwy.GridSpec, its dict, or True
-        for the default), a float32 vector of spec.stride(F)."""
-        return self._vec.grid(spec)[0].cpu().numpy()
+        """view() of the occupancy grid ``spec`` (a hwy.GridSpec, its dict, or True)."""
+        return self.view(GridSpec.from_dict(spec))
 
     def lidar(self, spec):
-        """The current lidar row (HighwayVecEnv.lidar: a hwy.LidarSpec, its dict, or True for the
-        default), a float32 vector of spec.stride(F)."""
-        return self._vec.lidar(spec)[0].cpu().numpy()
+        """view() of the lidar ``spec`` (a hwy.LidarSpec, its dict, or True)."""
+        return self.view(LidarSpec.from_dict(spec))
 
     def lookahead(self, actions, gamma: float = 1.0, obs: bool = False):
         """What-if rollouts from the current state (HighwayVecEnv.lookahead): ``actions`` is a

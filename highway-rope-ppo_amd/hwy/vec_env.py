@@ -88,6 +88,18 @@ def _dev_tensor(name: str, t, dtype, n: int, what: str, device) -> int:
     return t.data_ptr()
 
 
+def _set_outputs(a, table, device) -> bool:
+    """Set the pointers of args struct ``a`` from ``table``, rows of (field of ``a``, the name the
+    caller knows it by, tensor or None, dtype, elements, layout): every tensor that is given goes
+    through _dev_tensor.  Returns whether any was given."""
+    given = False
+    for field, name, t, dtype, n, what in table:
+        if t is not None:
+            setattr(a, field, _dev_tensor(name, t, dtype, n, what, device))
+            given = True
+    return given
+
+
 def observe_args(num_envs: int, rows: int, fout: int, device, order=None, *, obs=None,
                  row_vehicle=None, row_values=None, veh_values=None) -> _abi.ObserveArgs:
     """hwy_observe_args for an env of ``num_envs`` x ``rows`` x ``fout`` on ``device`` from
@@ -95,13 +107,11 @@ def observe_args(num_envs: int, rows: int, fout: int, device, order=None, *, obs
     a = _abi.ObserveArgs()
     a.order = _abi.observe_order(order)
     E, N = int(num_envs), int(rows)
-    spec = (("obs", obs, torch.float32, E * N * int(fout), "E x N x F_out"),
-            ("row_vehicle", row_vehicle, torch.int32, E * N, "E x N"),
-            ("row_values", row_values, torch.float32, E * N, "E x N"),
-            ("veh_values", veh_values, torch.float32, E * HWY_MAX_VEHICLES, "E x 64"))
-    for name, t, dtype, n, what in spec:
-        if t is not None:
-            setattr(a, name, _dev_tensor(name, t, dtype, n, what, device))
+    _set_outputs(a, (("obs", "obs", obs, torch.float32, E * N * int(fout), "E x N x F_out"),
+                     ("row_vehicle", "row_vehicle", row_vehicle, torch.int32, E * N, "E x N"),
+                     ("row_values", "row_values", row_values, torch.float32, E * N, "E x N"),
+                     ("veh_values", "veh_values", veh_values, torch.float32,
+                      E * HWY_MAX_VEHICLES, "E x 64")), device)
     if obs is None and row_vehicle is None and veh_values is None:
         raise ValueError("observe_into needs at least one of obs, row_vehicle and veh_values")
     if (row_values is None) != (veh_values is None):
@@ -134,18 +144,11 @@ def traffic_args(num_envs: int, device, *, restart=(), ttc_thresh=None, thw_thre
         raise ValueError(f"unknown traffic outputs {sorted(unknown)}; known: {TRAFFIC_OUTPUTS}")
     a = _abi.TrafficArgs()
     E = int(num_envs)
-
-    for name in TRAFFIC_OUTPUTS:
-        t = outputs.get(name)
-        if t is None:
-            continue
-        if name in _abi.TRAFFIC_VEHICLE_OUTPUTS:
-            dtype = torch.int32 if name in ("front", "rear") else torch.float32
-            n, what = E * HWY_MAX_VEHICLES, "E x 64"
-        else:
-            width = _abi.HWY_TRAFFIC_NEGO if name == "ego" else _abi.HWY_TRAFFIC_NACC
-            dtype, n, what = torch.float32, E * width, f"E x {width}"
-        setattr(a, name, _dev_tensor(name, t, dtype, n, what, device))
+    widths = {"ego": _abi.HWY_TRAFFIC_NEGO, "acc": _abi.HWY_TRAFFIC_NACC,
+              "ep_stats": _abi.HWY_TRAFFIC_NACC}
+    _set_outputs(a, [(n, n, outputs.get(n), torch.int32 if n in ("front", "rear")
+                      else torch.float32, E * widths.get(n, HWY_MAX_VEHICLES),
+                      f"E x {widths.get(n, HWY_MAX_VEHICLES)}") for n in TRAFFIC_OUTPUTS], device)
     if all(outputs.get(n) is None for n in TRAFFIC_OUTPUTS if n != "ep_stats"):
         raise ValueError("traffic_into needs at least one output besides ep_stats")
     masks = [m for m in (restart or ()) if m is not None]
@@ -176,15 +179,12 @@ def sense_args(num_envs: int, rows: int, fout: int, device, sensor, order=None, 
     a = _abi.SensorModel.from_dict(sensor).fill(_abi.SenseArgs())
     a.order = _abi.observe_order(order)
     E, N = int(num_envs), int(rows)
-    spec = (("obs", obs, torch.float32, E * N * int(fout), "E x N x F_out"),
-            ("row_vehicle", row_vehicle, torch.int32, E * N, "E x N"),
-            ("visible", visible, torch.uint8, E * HWY_MAX_VEHICLES, "E x 64"),
-            ("hidden", hidden, torch.float32, E * HWY_MAX_VEHICLES, "E x 64"),
-            ("counts", counts, torch.int32, E * 4, "E x 4"))
-    for name, t, dtype, n, what in spec:
-        if t is not None:
-            setattr(a, name, _dev_tensor(name, t, dtype, n, what, device))
-    if all(t is None for _, t, _, _, _ in spec):
+    if not _set_outputs(a, (
+            ("obs", "obs", obs, torch.float32, E * N * int(fout), "E x N x F_out"),
+            ("row_vehicle", "row_vehicle", row_vehicle, torch.int32, E * N, "E x N"),
+            ("visible", "visible", visible, torch.uint8, E * HWY_MAX_VEHICLES, "E x 64"),
+            ("hidden", "hidden", hidden, torch.float32, E * HWY_MAX_VEHICLES, "E x 64"),
+            ("counts", "counts", counts, torch.int32, E * 4, "E x 4")), device):
         raise ValueError("sense_into needs at least one of obs, row_vehicle, visible, hidden and "
                          "counts")
     return a
@@ -198,15 +198,12 @@ def grid_args(num_envs: int, n_features: int, device, spec, *, out=None, cell_ve
     g = _abi.GridSpec.from_dict(spec)
     a = g.fill(_abi.GridArgs(), n_features)
     E, cells = int(num_envs), g.nx * g.ny
-    outs = (("grid", out, torch.float32, E * a.row_stride, f"E x {a.row_stride}", "out"),
-            ("cell_vehicle", cell_vehicle, torch.int32, E * cells, f"E x {g.nx} x {g.ny}",
-             "cell_vehicle"),
-            ("veh_cell", veh_cell, torch.int32, E * HWY_MAX_VEHICLES, "E x 64", "veh_cell"),
-            ("counts", counts, torch.int32, E * 4, "E x 4", "counts"))
-    for field, t, dtype, n, what, name in outs:
-        if t is not None:
-            setattr(a, field, _dev_tensor(name, t, dtype, n, what, device))
-    if all(t is None for _, t, _, _, _, _ in outs):
+    if not _set_outputs(a, (
+            ("grid", "out", out, torch.float32, E * a.row_stride, f"E x {a.row_stride}"),
+            ("cell_vehicle", "cell_vehicle", cell_vehicle, torch.int32, E * cells,
+             f"E x {g.nx} x {g.ny}"),
+            ("veh_cell", "veh_cell", veh_cell, torch.int32, E * HWY_MAX_VEHICLES, "E x 64"),
+            ("counts", "counts", counts, torch.int32, E * 4, "E x 4")), device):
         raise ValueError("grid_into needs at least one of out, cell_vehicle, veh_cell and counts")
     return a
 
@@ -219,15 +216,12 @@ def lidar_args(num_envs: int, n_features: int, device, spec, *, out=None, hit_ve
     g = _abi.LidarSpec.from_dict(spec)
     a = g.fill(_abi.LidarArgs(), n_features)
     E = int(num_envs)
-    outs = (("obs", out, torch.float32, E * a.row_stride, f"E x {a.row_stride}", "out"),
-            ("hit_vehicle", hit_vehicle, torch.int32, E * g.cells, f"E x {g.cells}",
-             "hit_vehicle"),
-            ("seen", seen, torch.float32, E * HWY_MAX_VEHICLES, "E x 64", "seen"),
-            ("counts", counts, torch.int32, E * 4, "E x 4", "counts"))
-    for field, t, dtype, n, what, name in outs:
-        if t is not None:
-            setattr(a, field, _dev_tensor(name, t, dtype, n, what, device))
-    if all(t is None for _, t, _, _, _, _ in outs):
+    if not _set_outputs(a, (
+            ("obs", "out", out, torch.float32, E * a.row_stride, f"E x {a.row_stride}"),
+            ("hit_vehicle", "hit_vehicle", hit_vehicle, torch.int32, E * g.cells,
+             f"E x {g.cells}"),
+            ("seen", "seen", seen, torch.float32, E * HWY_MAX_VEHICLES, "E x 64"),
+            ("counts", "counts", counts, torch.int32, E * 4, "E x 4")), device):
         raise ValueError("lidar_into needs at least one of out, hit_vehicle, seen and counts")
     return a
 
@@ -267,26 +261,17 @@ def lookahead_args(num_envs: int, rows: int, fout: int, device, actions, horizon
     a = _abi.LookaheadArgs()
     a.k, a.horizon, a.hold, a.lazy, a.gamma = K, H, int(bool(hold)), int(bool(lazy)), g
     a.actions = actions.data_ptr()
-    spec = (("steps", steps, torch.int32, E * K, "E x K"),
-            ("terminated", terminated, torch.uint8, E * K, "E x K"),
-            ("truncated", truncated, torch.uint8, E * K, "E x K"),
-            ("rewards", rewards, torch.float32, E * K * H, "E x K x H"),
-            ("ret", ret, torch.float32, E * K, "E x K"),
-            ("ego_final", ego_final, torch.float32, E * K * 4, "E x K x 4"),
-            ("obs", obs, torch.float32, E * K * N * int(fout), "E x K x N x F_out"),
-            ("chosen", chosen, torch.int32, E, "E"),
-            ("chosen_action", chosen_action, torch.float32, E * 2, "E x 2"))
-    for name, t, dtype, n, what in spec:
-        if t is None:
-            continue
-        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
-                and t.numel() == n and t.device == dev):
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements "
-                             f"({what}) on {dev}, got "
-                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} "
-                             f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
-        setattr(a, name, t.data_ptr())
-    if all(t is None for _, t, _, _, _ in spec):
+    if not _set_outputs(a, (
+            ("steps", "steps", steps, torch.int32, E * K, "E x K"),
+            ("terminated", "terminated", terminated, torch.uint8, E * K, "E x K"),
+            ("truncated", "truncated", truncated, torch.uint8, E * K, "E x K"),
+            ("rewards", "rewards", rewards, torch.float32, E * K * H, "E x K x H"),
+            ("ret", "ret", ret, torch.float32, E * K, "E x K"),
+            ("ego_final", "ego_final", ego_final, torch.float32, E * K * 4, "E x K x 4"),
+            ("obs", "obs", obs, torch.float32, E * K * N * int(fout), "E x K x N x F_out"),
+            ("chosen", "chosen", chosen, torch.int32, E, "E"),
+            ("chosen_action", "chosen_action", chosen_action, torch.float32, E * 2, "E x 2")),
+            dev):
         raise ValueError("lookahead_into needs at least one output: "
                          + ", ".join(_abi.LOOKAHEAD_OUTPUTS))
     if (lazy or chosen is not None) and (steps is None or terminated is None):
@@ -621,6 +606,20 @@ class HighwayVecEnv:
         self._keep_render = (ids, shade, out)
         return out.view(shape)
 
+    def _launch(self, fn: str, a, *keep) -> None:
+        """One launch of entry point ``fn`` (hwy_<what>) with args struct ``a`` on the current
+        stream; ``keep``: what ``a`` points into, kept alive on the env as ``_keep_<what>``."""
+        check(getattr(lib(), fn)(self._handle, ctypes.byref(a), stream_ptr()), fn)
+        setattr(self, "_keep_" + fn[len("hwy_"):], keep)
+
+    def _filled(self, into: Callable, shape: tuple, dtype, out: Optional[torch.Tensor]):
+        """``out`` (None: a new ``dtype`` tensor of ``shape``) after ``into(out)`` wrote it, viewed
+        as ``shape``: the allocating form of an ``*_into``."""
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        into(out)
+        return out.view(shape)
+
     def observe_into(self, order: Optional[str] = None, *, obs: Optional[torch.Tensor] = None,
                      row_vehicle: Optional[torch.Tensor] = None,
                      row_values: Optional[torch.Tensor] = None,
@@ -636,35 +635,27 @@ class HighwayVecEnv:
         a = observe_args(self.num_envs, self.obs_rows, self.obs_features, self.device, order,
                          obs=obs, row_vehicle=row_vehicle, row_values=row_values,
                          veh_values=veh_values)
-        check(lib().hwy_observe(self._handle, ctypes.byref(a), stream_ptr()), "hwy_observe")
-        self._keep_observe = (obs, row_vehicle, row_values, veh_values)
+        self._launch("hwy_observe", a, obs, row_vehicle, row_values, veh_values)
 
     def observe(self, order: Optional[str] = None,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The current observation [E, N, F_out] under ``order`` (observe_into's ``obs``)."""
-        if out is None:
-            out = torch.empty(self.num_envs, self.obs_rows, self.obs_features,
-                              dtype=torch.float32, device=self.device)
-        self.observe_into(order, obs=out)
-        return out.view(self.num_envs, self.obs_rows, self.obs_features)
+        return self._filled(lambda o: self.observe_into(order, obs=o),
+                            (self.num_envs, self.obs_rows, self.obs_features), torch.float32, out)
 
     def row_vehicles(self, order: Optional[str] = None,
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The vehicle index each observation row shows, [E, N] int32 (-1: an empty row)."""
-        if out is None:
-            out = torch.empty(self.num_envs, self.obs_rows, dtype=torch.int32, device=self.device)
-        self.observe_into(order, row_vehicle=out)
-        return out.view(self.num_envs, self.obs_rows)
+        return self._filled(lambda o: self.observe_into(order, row_vehicle=o),
+                            (self.num_envs, self.obs_rows), torch.int32, out)
 
     def rows_to_vehicles(self, row_values: torch.Tensor, order: Optional[str] = None,
                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Per-row values [E, N] scattered to the vehicles the rows show, [E, 64] float32 (0 for
         the others): ready to pass as ``render(shade=...)``."""
-        if out is None:
-            out = torch.empty(self.num_envs, HWY_MAX_VEHICLES, dtype=torch.float32,
-                              device=self.device)
-        self.observe_into(order, row_values=row_values, veh_values=out)
-        return out.view(self.num_envs, HWY_MAX_VEHICLES)
+        return self._filled(
+            lambda o: self.observe_into(order, row_values=row_values, veh_values=o),
+            (self.num_envs, HWY_MAX_VEHICLES), torch.float32, out)
 
     def traffic_into(self, *, restart=(), ttc_thresh: Optional[float] = None,
                      thw_thresh: Optional[float] = None, risk_horizon: Optional[float] = None,
@@ -683,8 +674,7 @@ class HighwayVecEnv:
         a = traffic_args(self.num_envs, self.device, restart=restart, ttc_thresh=ttc_thresh,
                          thw_thresh=thw_thresh, risk_horizon=risk_horizon, near_range=near_range,
                          **outputs)
-        check(lib().hwy_traffic(self._handle, ctypes.byref(a), stream_ptr()), "hwy_traffic")
-        self._keep_traffic = (outputs, restart)
+        self._launch("hwy_traffic", a, outputs, restart)
 
     def traffic(self, **thresholds) -> Dict[str, torch.Tensor]:
         """The per-vehicle arrays and the ego row of the current states, a dict of fresh device
@@ -710,27 +700,20 @@ class HighwayVecEnv:
         a = sense_args(self.num_envs, self.obs_rows, self.obs_features, self.device, sensor,
                        order, obs=obs, row_vehicle=row_vehicle, visible=visible, hidden=hidden,
                        counts=counts)
-        check(lib().hwy_sense(self._handle, ctypes.byref(a), stream_ptr()), "hwy_sense")
-        self._keep_sense = (obs, row_vehicle, visible, hidden, counts)
+        self._launch("hwy_sense", a, obs, row_vehicle, visible, hidden, counts)
 
     def sense(self, sensor, order: Optional[str] = None,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The current observation [E, N, F_out] through ``sensor`` under ``order`` (sense_into's
         ``obs``)."""
-        if out is None:
-            out = torch.empty(self.num_envs, self.obs_rows, self.obs_features,
-                              dtype=torch.float32, device=self.device)
-        self.sense_into(sensor, order, obs=out)
-        return out.view(self.num_envs, self.obs_rows, self.obs_features)
+        return self._filled(lambda o: self.sense_into(sensor, order, obs=o),
+                            (self.num_envs, self.obs_rows, self.obs_features), torch.float32, out)
 
     def hidden_vehicles(self, sensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[E, 64] float32, 1 where a present vehicle is hidden from ``sensor`` (sense_into's
         ``hidden``): ready to pass as ``render(shade=...)``."""
-        if out is None:
-            out = torch.empty(self.num_envs, HWY_MAX_VEHICLES, dtype=torch.float32,
-                              device=self.device)
-        self.sense_into(sensor, hidden=out)
-        return out.view(self.num_envs, HWY_MAX_VEHICLES)
+        return self._filled(lambda o: self.sense_into(sensor, hidden=o),
+                            (self.num_envs, HWY_MAX_VEHICLES), torch.float32, out)
 
     def grid_into(self, spec, *, out: Optional[torch.Tensor] = None,
                   cell_vehicle: Optional[torch.Tensor] = None,
@@ -746,26 +729,19 @@ class HighwayVecEnv:
         outside."""
         a = grid_args(self.num_envs, int(self._cfg.n_features), self.device, spec, out=out,
                       cell_vehicle=cell_vehicle, veh_cell=veh_cell, counts=counts)
-        check(lib().hwy_grid(self._handle, ctypes.byref(a), stream_ptr()), "hwy_grid")
-        self._keep_grid = (out, cell_vehicle, veh_cell, counts)
+        self._launch("hwy_grid", a, out, cell_vehicle, veh_cell, counts)
 
     def grid(self, spec, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The current occupancy grid [E, spec.stride(F)] (grid_into's ``out``): the observation
         a grid-trained policy acts on."""
-        g = _abi.GridSpec.from_dict(spec)
-        stride = g.stride(int(self._cfg.n_features))
-        if out is None:
-            out = torch.empty(self.num_envs, stride, dtype=torch.float32, device=self.device)
-        self.grid_into(g, out=out)
-        return out.view(self.num_envs, stride)
+        return self.view(_abi.GridSpec.from_dict(spec), out)
 
     def grid_cells(self, spec) -> torch.Tensor:
         """[E, nx, ny] int32: the vehicle that won each cell of the current grid, -1 for none
         (grid_into's ``cell_vehicle``)."""
         g = _abi.GridSpec.from_dict(spec)
-        out = torch.empty(self.num_envs, g.nx, g.ny, dtype=torch.int32, device=self.device)
-        self.grid_into(g, cell_vehicle=out)
-        return out
+        return self._filled(lambda o: self.grid_into(g, cell_vehicle=o),
+                            (self.num_envs, g.nx, g.ny), torch.int32, None)
 
     def lidar_into(self, spec, *, out: Optional[torch.Tensor] = None,
                    hit_vehicle: Optional[torch.Tensor] = None,
@@ -781,26 +757,36 @@ class HighwayVecEnv:
         of them seen, cells with a return, cells dropped."""
         a = lidar_args(self.num_envs, int(self._cfg.n_features), self.device, spec, out=out,
                        hit_vehicle=hit_vehicle, seen=seen, counts=counts)
-        check(lib().hwy_lidar(self._handle, ctypes.byref(a), stream_ptr()), "hwy_lidar")
-        self._keep_lidar = (out, hit_vehicle, seen, counts)
+        self._launch("hwy_lidar", a, out, hit_vehicle, seen, counts)
 
     def lidar(self, spec, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The current lidar rows [E, spec.stride(F)] (lidar_into's ``out``): the observation a
         lidar-trained policy acts on."""
-        g = _abi.LidarSpec.from_dict(spec)
-        stride = g.stride(int(self._cfg.n_features))
-        if out is None:
-            out = torch.empty(self.num_envs, stride, dtype=torch.float32, device=self.device)
-        self.lidar_into(g, out=out)
-        return out.view(self.num_envs, stride)
+        return self.view(_abi.LidarSpec.from_dict(spec), out)
 
     def lidar_hits(self, spec) -> torch.Tensor:
         """[E, cells] int32: the vehicle each cell of the current lidar returns, -1 for none
         (lidar_into's ``hit_vehicle``)."""
         g = _abi.LidarSpec.from_dict(spec)
-        out = torch.empty(self.num_envs, g.cells, dtype=torch.int32, device=self.device)
-        self.lidar_into(g, hit_vehicle=out)
-        return out
+        return self._filled(lambda o: self.lidar_into(g, hit_vehicle=o),
+                            (self.num_envs, g.cells), torch.int32, None)
+
+    def view_width(self, spec) -> int:
+        """Floats per env of what a policy under view ``spec`` (a SensorModel, a GridSpec or a
+        LidarSpec) acts on: N * F_out through a sensor, ``spec.stride(F)`` of a grid or a lidar."""
+        return _view_rule(spec)[2](self, spec)
+
+    def view_into(self, spec, out: torch.Tensor) -> None:
+        """The one launch that writes what a policy under view ``spec`` acts on, of the envs'
+        current states, into ``out`` (E x view_width(spec) float32): sense_into's ``obs``,
+        grid_into's ``out`` or lidar_into's ``out``."""
+        into, keyword, _ = _view_rule(spec)
+        getattr(self, into)(spec, **{keyword: out})
+
+    def view(self, spec, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """view_into's rows [E, view_width(spec)], in ``out`` or a new tensor."""
+        return self._filled(lambda o: self.view_into(spec, o),
+                            (self.num_envs, self.view_width(spec)), torch.float32, out)
 
     def lookahead_into(self, actions: torch.Tensor, horizon: int, *, hold: bool = False,
                        lazy: bool = False, gamma: float = 1.0, **outputs) -> None:
@@ -820,8 +806,7 @@ class HighwayVecEnv:
                              f"{list(_abi.LOOKAHEAD_OUTPUTS)}")
         a = lookahead_args(self.num_envs, self.obs_rows, self.obs_features, self.device, actions,
                            horizon, hold=hold, lazy=lazy, gamma=gamma, **outputs)
-        check(lib().hwy_lookahead(self._handle, ctypes.byref(a), stream_ptr()), "hwy_lookahead")
-        self._keep_lookahead = (actions, outputs)
+        self._launch("hwy_lookahead", a, actions, outputs)
 
     def lookahead(self, actions, horizon: Optional[int] = None, gamma: float = 1.0,
                   obs: bool = False) -> Dict[str, torch.Tensor]:
@@ -906,6 +891,27 @@ class HighwayVecEnv:
     @property
     def unwrapped(self):
         return self
+
+
+def _row_stride(env, spec) -> int:
+    return spec.stride(int(env.hwy_config.n_features))
+
+
+# The views: per record class, the ``*_into`` that writes what the policy acts on, the keyword it
+# takes that buffer by, and the floats per env.  A new observation kind adds its line here.
+_VIEWS = {
+    _abi.SensorModel: ("sense_into", "obs", lambda env, spec: env.obs_rows * env.obs_features),
+    _abi.GridSpec: ("grid_into", "out", _row_stride),
+    _abi.LidarSpec: ("lidar_into", "out", _row_stride),
+}
+VIEW_RECORDS = {cls.NOUN: cls for cls in _VIEWS}  # by option name (ppo/options.py's views)
+
+
+def _view_rule(spec) -> tuple:
+    try:
+        return _VIEWS[type(spec)]
+    except KeyError:
+        raise ValueError(f"a view is one of {[c.__name__ for c in _VIEWS]}, got {spec!r}") from None
 
 
 def _info_array(iptrs, n: int):

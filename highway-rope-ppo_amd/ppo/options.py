@@ -33,6 +33,9 @@ class RunOption(NamedTuple):
     group_first: bool = False        # the group refusal precedes the vector one
     grouped: bool = False            # launch_group / launch_batch take it (the cells share it)
     rollout: bool = False            # the vectorised loop and LockstepRollout take it
+    # a view: its record (hwy.SensorModel, GridSpec, LidarSpec) says what the policy acts on
+    # instead of the step's own rows, through HighwayVecEnv.view_into; a run has at most one
+    view: bool = False
     on_agent: bool = False           # a PPOAgent argument: the routine reads it from the agent
     # ((other option, reason), ...): "<name> does not go with <reason>", checked with the value
     excludes: Tuple[tuple, ...] = ()
@@ -121,7 +124,7 @@ OPTIONS = (
     _flag("attribution"),
     RunOption("eval_orders", None, bool, check_eval_orders),
     RunOption("eval_sensors", None, bool, check_eval_sensors),
-    _spec("sensor", "SensorModel", rollout=True, group="launch", metrics="value", excludes=(
+    _spec("sensor", "SensorModel", view=True, rollout=True, group="launch", metrics="value", excludes=(
         ("truncation", 'truncation="bootstrap": the terminal observations (final_obs) would not '
                        "be sensed"),
         ("episode_schedule", 'episode_schedule="reference": the first observations after the cut '
@@ -131,7 +134,8 @@ OPTIONS = (
         ("sensor", "sensor: " + _UNTESTED),
         ("truncation", 'truncation="bootstrap": ' + _UNTESTED),
         ("episode_schedule", 'episode_schedule="reference": ' + _UNTESTED))),
-    _spec("grid", "GridSpec", absent=(None, False), rollout=True, group="launch", metrics="value",
+    _spec("grid", "GridSpec", absent=(None, False), view=True, rollout=True, group="launch",
+          metrics="value",
           excludes=(
               ("truncation", 'truncation="bootstrap": the terminal observations (final_obs) would '
                              "be Kinematics rows, not grids"),
@@ -147,7 +151,7 @@ OPTIONS = (
     RunOption("lr_anneal_updates", None, lambda v: v is not None, lambda v: v, on_agent=True,
               grouped=True, vector=_ONE_ENV_LOOP + "does not take it", metrics="value"),
     # the lidar comes last in the table and so in every order below: no older refusal moves
-    _spec("lidar", "LidarSpec", absent=(None, False), rollout=True, group="launch",
+    _spec("lidar", "LidarSpec", absent=(None, False), view=True, rollout=True, group="launch",
           metrics="value",
           excludes=(
               ("grid", "grid: the policy acts on one of the two observations"),
@@ -161,6 +165,8 @@ OPTIONS = (
                                                          "eval_sensors", "eval_shields"))),
 )
 BY_NAME = {o.name: o for o in OPTIONS}
+VIEWS = tuple(o.name for o in OPTIONS if o.view)
+
 
 def _order(*first) -> tuple:
     return first + tuple(o.name for o in OPTIONS if o.name not in first)
@@ -209,6 +215,13 @@ def given(**kw) -> dict:
     call that does not use it."""
     return {k: v for k, v in kw.items()
             if (BY_NAME[k].given(v) if k in BY_NAME else v is not None and v is not False)}
+
+
+def given_view(values: dict):
+    """(name, spec) of the view that ``values`` (normalised, by option name; a missing one is not
+    given) gives, or None.  The view options exclude each other, so where a caller has not yet
+    refused a pair the first in the table's order is named."""
+    return next(((n, values[n]) for n in VIEWS if BY_NAME[n].given(values.get(n))), None)
 
 
 def _excluded(opt, rules, others: dict) -> None:

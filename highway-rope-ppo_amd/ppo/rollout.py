@@ -36,10 +36,14 @@ third mask, so the state the cut throws away is not measured, the cut episodes' 
 ``traffic_stats[T - 1]`` beside the finished ones' (no env is both), and an env that had just
 restarted is not counted twice.
 
-``sensor=`` (a hwy.SensorModel or its dict): the policy acts on the states as that sensor
-perceives them.  One hwy_sense launch after every env step, inside the captured graph, overwrites
-``buf.states[t + 1]`` with the sensed observation of the state the step left, and one on the
-reset states the caller left overwrites ``buf.states[0]``; the env step itself is unchanged.
+``sensor=`` / ``grid=`` / ``lidar=`` (a hwy.SensorModel, GridSpec or LidarSpec, its dict, or True
+for the default grid or lidar; at most one): the view the policy acts through.  One
+``env.view_into`` launch (hwy_sense, hwy_grid or hwy_lidar) after every env step, inside the
+captured graph, writes ``buf.states[t + 1]`` from the state the step left, and one on the reset
+states the caller left writes ``buf.states[0]``; the env step itself is unchanged.  A sensor
+overwrites the rows the step wrote there; a grid or a lidar replaces them: the step writes its
+Kinematics rows into the env's own observation buffer and ``buf.states`` is ``spec.stride(F)``
+wide.
 
 ``shield=`` (a hwy.Shield or its dict): the shield is part of the environment.  After the policy
 acted, one hwy_lookahead call (``env.shield_into``) inside the captured graph rolls the policy's
@@ -47,17 +51,6 @@ action and the shield's fallbacks out from the env's state and writes the action
 to ``buf.exec_actions[t]`` and the candidate picked to ``buf.chosen[t]``; the env step takes
 ``exec_actions[t]``.  ``buf.actions``, ``pre_tanh``, ``log_probs`` and ``values`` stay the
 policy's own, so PPO's stored data is untouched.
-
-``grid=`` (a hwy.GridSpec, its dict, or True for the default): the policy acts on an occupancy
-grid of the env states instead of the Kinematics rows.  Each env step writes its Kinematics
-observation into the env's own observation buffer, and one hwy_grid launch after it, inside the
-captured graph, writes ``buf.states[t + 1]``; one more on the reset states the caller left writes
-``buf.states[0]``.  ``buf.states`` is ``spec.stride(F)`` wide.
-
-``lidar=`` (a hwy.LidarSpec, its dict, or True for the default): likewise with the ray-cast range
-observation: one hwy_lidar launch per env step inside the captured graph writes
-``buf.states[t + 1]``, one on the reset states ``buf.states[0]``, and ``buf.states`` is
-``spec.stride(F)`` wide.
 
 Which of these options exclude each other, and why, is ppo/options.py's table.
 """
@@ -144,28 +137,26 @@ class LockstepRollout:
         self.agent = agent
         self.env = env.unwrapped if hasattr(env, "unwrapped") else env
         self.buf = buf
-        # one hwy_sense launch per env step (and one now, on the reset states the caller left)
         self.sensor = check_sensor(sensor, truncation, episode_schedule)
         # one hwy_lookahead call per env step, between acting and stepping
         self.shield = check_shield(shield, truncation, episode_schedule, sensor)
-        # one hwy_grid launch per env step (and one now, on the reset states the caller left)
         self.grid = check_grid(grid, truncation, episode_schedule, sensor, shield)
-        # one hwy_lidar launch per env step (and one now, on the reset states the caller left)
         self.lidar = check_lidar(lidar, truncation, episode_schedule, sensor, shield, grid)
-        if self.grid is not None:
-            if not hasattr(self.env, "grid_into"):
-                raise ValueError("grid needs a vector env (HighwayVecEnv)")
-            stride = self.grid.stride(int(self.env.hwy_config.n_features))
-            if buf.states.shape[-1] != stride:
-                raise ValueError(f"grid needs a RolloutBuffer of state width {stride} "
-                                 f"(GridSpec.stride), got {buf.states.shape[-1]}")
-        if self.lidar is not None:
-            if not hasattr(self.env, "lidar_into"):
-                raise ValueError("lidar needs a vector env (HighwayVecEnv)")
-            stride = self.lidar.stride(int(self.env.hwy_config.n_features))
-            if buf.states.shape[-1] != stride:
-                raise ValueError(f"lidar needs a RolloutBuffer of state width {stride} "
-                                 f"(LidarSpec.stride), got {buf.states.shape[-1]}")
+        # the view, whichever of the three is given: one env.view_into launch per env step (and
+        # one now, on the reset states the caller left) writes what the policy acts on
+        given = options.given_view(dict(sensor=self.sensor, grid=self.grid, lidar=self.lidar))
+        self.view = None if given is None else given[1]
+        # it replaces the step's rows, which then stay in the env's own buffer (a grid, a lidar),
+        # or overwrites them where the step wrote them (a sensor)
+        self.view_replaces = self.view is not None and self.view.REPLACES_ROWS
+        if self.view_replaces:
+            name, spec = given
+            if not hasattr(self.env, "view_width"):
+                raise ValueError(f"{name} needs a vector env (HighwayVecEnv)")
+            width = self.env.view_width(spec)
+            if buf.states.shape[-1] != width:
+                raise ValueError(f"{name} needs a RolloutBuffer of state width {width} "
+                                 f"({type(spec).__name__}.stride), got {buf.states.shape[-1]}")
         if self.shield is not None:
             if not hasattr(self.env, "shield_into"):
                 raise ValueError("shield needs a vector env (HighwayVecEnv)")
@@ -204,12 +195,8 @@ class LockstepRollout:
             alloc_cut_buffers(self, buf.E, buf.states.shape[-1], buf.states.device)
         if self.safety_stats:
             traffic_after_reset(self.env, buf)
-        if self.sensor is not None:
-            self.env.sense_into(self.sensor, obs=buf.states[0])
-        if self.grid is not None:
-            self.env.grid_into(self.grid, out=buf.states[0])
-        if self.lidar is not None:
-            self.env.lidar_into(self.lidar, out=buf.states[0])
+        if self.view is not None:
+            self.env.view_into(self.view, buf.states[0])
 
     def _launch_key(self):
         from hwy.ppo_native import act_tiles, flat_params
@@ -231,12 +218,8 @@ class LockstepRollout:
             key += (buf.final_obs.data_ptr(), buf.boot_values.data_ptr())
         if self.safety_stats:
             key += (buf.traffic_stats.data_ptr(), buf.traffic_acc.data_ptr())
-        if self.sensor is not None:
-            key += (self.sensor,)
-        if self.grid is not None:
-            key += (self.grid, env.obs_buf.data_ptr())
-        if self.lidar is not None:
-            key += (self.lidar, env.obs_buf.data_ptr())
+        if self.view is not None:
+            key += (self.view, env.obs_buf.data_ptr()) if self.view_replaces else (self.view,)
         if self.shield is not None:
             key += (self.shield, buf.exec_actions.data_ptr(), buf.chosen.data_ptr())
         return key
@@ -254,8 +237,8 @@ class LockstepRollout:
             if self.shield is not None:
                 executed = buf.exec_actions[t]
                 env.shield_into(self.shield, buf.actions[t], executed, chosen=buf.chosen[t])
-            # under a grid or a lidar the step's Kinematics rows stay in the env's own buffer
-            next_obs = (env.obs_buf if self.grid is not None or self.lidar is not None
+            # under a view that replaces them the step's rows stay in the env's own buffer
+            next_obs = (env.obs_buf if self.view_replaces
                         else buf.states[t + 1].view(E, *obs_shape))
             io = (executed, next_obs, buf.rewards[t],
                   buf.terminated[t], buf.truncated[t], buf.ep_return[t], buf.ep_length[t])
@@ -270,12 +253,8 @@ class LockstepRollout:
             if boot:
                 ag.value_masked(buf.final_obs, buf.truncated[t], buf.terminated[t],
                                 out=buf.boot_values[t])
-            if self.sensor is not None:
-                env.sense_into(self.sensor, obs=buf.states[t + 1])
-            if self.grid is not None:
-                env.grid_into(self.grid, out=buf.states[t + 1])
-            if self.lidar is not None:
-                env.lidar_into(self.lidar, out=buf.states[t + 1])
+            if self.view is not None:
+                env.view_into(self.view, buf.states[t + 1])
             if self.safety_stats and not (self.episode_schedule == "reference" and t == buf.T - 1):
                 traffic_after_step(env, buf, t)
         if t1 < buf.T:

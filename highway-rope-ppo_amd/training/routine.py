@@ -56,21 +56,19 @@ random number, so the training is unchanged, bit for bit.
 the policy's input-gradient mass on the observation row that shows it (``attribution_shade``).
 ``tint="ttc"`` tints them by hwy_traffic's ``risk`` instead (1 - ttc / 4 s below 4 s, else 0),
 ``tint="hidden"`` with ``sensor=`` the vehicles that sensor does not see (hwy_sense's ``hidden``).
-``evaluate(..., order= | sensor= | shield= | grid=)`` runs the evaluation's episodes with the
-policy acting on the same worlds observed under that row order (HighwayVecEnv.observe), as that
+``evaluate(..., order= | sensor= | shield= | grid= | lidar=)`` runs the evaluation's episodes with
+the policy acting on the same worlds observed under that row order (HighwayVecEnv.observe), as that
 sensor perceives them (HighwayVecEnv.sense; it combines with ``order``), with that shield picking
-what the env executes (HighwayVecEnv.shield_into), or on the occupancy grid of the states
-(HighwayVecEnv.grid); ``eval_orders``, ``eval_sensors`` and ``eval_shields`` book such evaluations
-at the final weights as ``order_rewards``, ``sensor_rewards`` and ``shield_rewards``.
-``sensor`` / ``shield`` / ``grid`` train under one: the rollout applies it at every step
-(ppo/rollout.py), the run's own evaluations use the same one and the metrics carry it under its
-name; a shielded run's updates also carry ``shield_rate`` and the summary its last value, and
-under a grid the policy's input is ``G.stride(F)`` wide.  ``shield_profile`` counts, on unshielded
-episodes, the crashes a shield could still have avoided.
-``lidar`` (a hwy.LidarSpec, its dict, or True for the default) is the grid's sibling: ``evaluate(...,
-lidar=L)`` lets the policy act on the ray-cast range observation of the states
-(HighwayVecEnv.lidar), and a run given ``lidar`` trains on it (one hwy_lidar launch per rollout
-step, input ``L.stride(F)`` wide, its own evaluations on the same lidar, ``lidar`` in the metrics).
+what the env executes (HighwayVecEnv.shield_into), or on the occupancy grid or the ray-cast range
+observation of the states (HighwayVecEnv.view); ``eval_orders``, ``eval_sensors`` and
+``eval_shields`` book such evaluations at the final weights as ``order_rewards``,
+``sensor_rewards`` and ``shield_rewards``.
+``sensor`` / ``grid`` / ``lidar`` (the views: at most one) and ``shield`` train under one: the
+rollout applies it at every step (ppo/rollout.py), the run's own evaluations use the same one and
+the metrics carry it under its name; under a grid or a lidar the policy's input is
+``spec.stride(F)`` wide; a shielded run's updates also carry ``shield_rate`` and the summary its
+last value.  ``shield_profile`` counts, on unshielded episodes, the crashes a shield could still
+have avoided.
 """
 
 from __future__ import annotations
@@ -101,6 +99,15 @@ def _flat_dim(env) -> int:
 
 
 # ---------------------------------------------------------------------------------- evaluation
+# evaluate()'s refusal of anything beside a view that replaces the rows, by the view's option
+_EVALUATE_ALONE = {
+    "grid": "evaluate(grid=...) does not go with order, sensor or shield: a grid has no row order, "
+            "and the other combinations are not built",
+    "lidar": "evaluate(lidar=...) does not go with order, sensor, shield or grid: a lidar has no "
+             "row order and its own sensor errors, and the other combinations are not built",
+}
+
+
 def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order=None,
              sensor=None, shield=None, tape=None, grid=None, lidar=None):
     """Mean return of deterministic episodes seeded exp_seed + 1000 + k.  ``order`` ("sorted" or
@@ -113,26 +120,20 @@ def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order
     is the executed episode's.  ``tape`` (with ``shield``): a list that receives, per step, the
     exported state before it, the policy's actions, the executed actions and the shield's choice
     as host arrays (tests); a taped evaluation is always run.
-    ``grid`` (a hwy.GridSpec, its dict, or True for the default; not with ``order``, ``sensor`` or
-    ``shield``): the policy acts on the occupancy grid of the states (HighwayVecEnv.grid; on the
-    one-env facade HighwayEnv.grid per step).
-    ``lidar`` (a hwy.LidarSpec, its dict, or True for the default; not with ``order``, ``sensor``,
-    ``shield`` or ``grid``): the policy acts on the ray-cast range observation of the states
-    (HighwayVecEnv.lidar; on the one-env facade HighwayEnv.lidar per step)."""
+    ``grid`` / ``lidar`` (a hwy.GridSpec / hwy.LidarSpec, its dict, or True for the default; with
+    nothing else of these): the policy acts on the occupancy grid / the ray-cast range observation
+    of the states (HighwayVecEnv.view; on the one-env facade HighwayEnv.view per step)."""
     from hwy._abi import observe_order
 
     vector = _is_vector(env)
-    grid = options.BY_NAME["grid"].normalise(grid)
-    lidar = options.BY_NAME["lidar"].normalise(lidar)
-    if lidar is not None:
-        if order is not None or sensor is not None or shield is not None or grid is not None:
-            raise ValueError("evaluate(lidar=...) does not go with order, sensor, shield or grid: "
-                             "a lidar has no row order and its own sensor errors, and the other "
-                             "combinations are not built")
-    elif grid is not None:
-        if order is not None or sensor is not None or shield is not None:
-            raise ValueError("evaluate(grid=...) does not go with order, sensor or shield: a grid "
-                             "has no row order, and the other combinations are not built")
+    given = dict(order=order, sensor=sensor, shield=shield, grid=grid, lidar=lidar)
+    for n in _EVALUATE_ALONE:
+        given[n] = options.BY_NAME[n].normalise(given[n])
+    # a view that replaces the rows goes alone: the last one given refuses whatever precedes it
+    own = next((n for n in reversed(_EVALUATE_ALONE) if given[n] is not None), None)
+    if own is not None:
+        if any(given[n] is not None for n in list(given)[:list(given).index(own)]):
+            raise ValueError(_EVALUATE_ALONE[own])
     else:
         # the view the policy acts through is named after the first of these that is given
         view = next((n for n, v in (("shield", shield), ("sensor", sensor), ("order", order))
@@ -150,23 +151,19 @@ def evaluate(env, agent, num_episodes=10, render=False, exp_seed: int = 0, order
             observe_order(order)  # ValueError for anything but None / "sorted" / "shuffled"
     if vector:
         return _evaluate_vector(env, agent, num_episodes, exp_seed, **options.given(
-            order=order, sensor=sensor, shield=shield, grid=grid, lidar=lidar,
-            tape=None if shield is None else tape))
-    own = None  # the observation the policy acts on instead of the step's rows
-    if grid is not None:
-        own = lambda: env.unwrapped.grid(grid)  # noqa: E731
-    if lidar is not None:
-        own = lambda: env.unwrapped.lidar(lidar)  # noqa: E731
+            order=order, sensor=sensor, shield=shield, tape=None if shield is None else tape,
+            **{n: given[n] for n in _EVALUATE_ALONE}))
+    spec = given.get(own)  # the view the policy acts on instead of the step's rows
     totals = []
     for ep in range(num_episodes):
         state, _ = env.reset(seed=exp_seed + 1000 + ep)
-        flat = state.reshape(-1) if own is None else own()
+        flat = state.reshape(-1) if spec is None else env.unwrapped.view(spec)
         done, ep_reward = False, 0.0
         while not done:
             action, _, _, _ = agent.select_action(flat, deterministic=True)
             nxt, reward, terminated, truncated, _ = env.step(action)
             done = terminated or truncated
-            flat = nxt.reshape(-1) if own is None else own()
+            flat = nxt.reshape(-1) if spec is None else env.unwrapped.view(spec)
             ep_reward += reward
         totals.append(ep_reward)
     return float(np.mean(totals))
@@ -217,25 +214,23 @@ def _evaluate_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None
     eval_interval completed episodes) fall between two updates; the evaluation is deterministic,
     so a repeat at unchanged weights reuses the last result instead of re-running the episodes.
     Each variant has a memo of its own on the env and neither reads nor writes another's: the
-    plain one is the pair ``_eval_memo``; the others are dicts of such pairs, ``_eval_grid_memo``
-    and ``_eval_lidar_memo`` by spec, ``_eval_shield_memo`` by shield, ``_eval_sensor_memo`` by (sensor, order) and
-    ``_eval_order_memo`` by order, one entry per value ever evaluated on this env, never dropped
-    (a handful for eval_sensors; a caller sweeping many may clear the dict).  A taped run
-    bypasses the memo."""
+    plain one is the pair ``_eval_memo``; the others are dicts of such pairs, ``_eval_<name>_memo``:
+    a view's by spec (``_eval_grid_memo``, ``_eval_lidar_memo``; ``_eval_sensor_memo`` by (sensor,
+    order)), ``_eval_shield_memo`` by shield and ``_eval_order_memo`` by order, one entry per
+    value ever evaluated on this env, never dropped (a handful for eval_sensors; a caller
+    sweeping many may clear the dict).  A taped run bypasses the memo."""
     base = env.unwrapped
     key = _eval_key(agent, num_episodes, exp_seed)
-    if grid is not None:
-        attr, slot = "_eval_grid_memo", (grid,)
-    elif lidar is not None:
-        attr, slot = "_eval_lidar_memo", (lidar,)
-    elif shield is not None:
-        attr, slot = "_eval_shield_memo", (shield,)
-    elif sensor is not None:
-        attr, slot = "_eval_sensor_memo", (sensor, order)
+    view = options.given_view(dict(sensor=sensor, grid=grid, lidar=lidar))
+    if shield is not None:
+        name, slot = "shield", (shield,)
+    elif view is not None:  # the rows a sensor overwrites differ by their order too
+        name, slot = view[0], (view[1],) if view[1].REPLACES_ROWS else (view[1], order)
     elif order is not None:
-        attr, slot = "_eval_order_memo", (order,)
+        name, slot = "order", (order,)
     else:
-        attr, slot = "_eval_memo", None
+        name, slot = None, None
+    attr = "_eval_memo" if name is None else f"_eval_{name}_memo"
     memo = getattr(base, attr, None)
     if slot is None:
         hit = memo
@@ -342,17 +337,16 @@ def _run_eval_vector(env, agent, num_episodes, exp_seed, order=None, sensor=None
                      tape=None, grid=None, lidar=None):
     ev = _cached_env(env, "_eval_envs", num_episodes)
     dev = ev.device
-    seen = None  # grid / sensor / order given: the states as observed under it, in its own buffer
+    seen = None  # a view or an order given: the states as observed under it, in its own buffer
+    view = options.given_view(dict(grid=grid, lidar=lidar))  # one that replaces the rows
     if shield is not None:  # the executed actions and the shield's choice
         executed = torch.zeros(num_episodes, 2, dtype=torch.float32, device=dev)
         chosen = torch.zeros(num_episodes, dtype=torch.int32, device=dev)
 
     def act(obs, alive):
         nonlocal seen
-        if grid is not None:
-            obs = seen = ev.grid(grid, out=seen)
-        elif lidar is not None:
-            obs = seen = ev.lidar(lidar, out=seen)
+        if view is not None:
+            obs = seen = ev.view(view[1], out=seen)
         elif sensor is not None:
             obs = seen = ev.sense(sensor, order=order, out=seen)
         elif order is not None:
@@ -405,6 +399,7 @@ def attribution_shade(vec_env, grad, order=None):
 
 
 VISUALIZE_TINTS = ("ttc", "hidden", "lidar")
+TINT_NEEDS = {"hidden": "sensor", "lidar": "lidar"}  # the view whose launch computes the tint
 
 
 def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, out_dir=None,
@@ -423,13 +418,12 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
     frame's state (HighwayVecEnv.traffic_into's ``risk``), or "hidden" to tint the vehicles
     ``sensor`` does not see at the frame's state (HighwayVecEnv.sense_into's ``hidden``); not
     together with ``attribution``.  ``sensor`` (a hwy.SensorModel or its dict): the policy acts on
-    what that sensor perceives, as in evaluate(sensor=...); "hidden" needs it.  ``grid`` (a
-    hwy.GridSpec, its dict, or True for the default): the policy acts on the occupancy grid of the
-    states, as in evaluate(grid=...); not with ``sensor`` or ``attribution`` (whose overlay is per
-    Kinematics row).  ``lidar`` (a hwy.LidarSpec, its dict, or True for the default): the policy
-    acts on the ray-cast range observation of the states, as in evaluate(lidar=...); not with
-    ``sensor``, ``grid`` or ``attribution``; ``tint="lidar"`` with it tints the vehicles some cell
-    of the lidar returns at the frame's state (HighwayVecEnv.lidar_into's ``seen``).
+    what that sensor perceives, as in evaluate(sensor=...); "hidden" needs it.  ``grid`` /
+    ``lidar`` (a hwy.GridSpec / hwy.LidarSpec, its dict, or True for the default): the policy acts
+    on the occupancy grid / the ray-cast range observation of the states, as in evaluate(grid=...);
+    not with another view or ``attribution`` (whose overlay is per Kinematics row);
+    ``tint="lidar"`` with a lidar tints the vehicles some cell of it returns at the frame's state
+    (HighwayVecEnv.lidar_into's ``seen``).
     ``tape``: a list that receives, per grabbed step, (observation, exported state, the episodes
     still recording) as clones (tests)."""
     if attribution is not None and attribution not in ATTRIBUTION_OUTPUTS:
@@ -439,17 +433,17 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
         raise ValueError(f"tint must be None or one of {VISUALIZE_TINTS}, got {tint!r}")
     if tint is not None and attribution is not None:
         raise ValueError("tint and attribution both shade the vehicles: give one of them")
-    sensor = options.BY_NAME["sensor"].normalise(sensor)
-    if sensor is None and tint == "hidden":
-        raise ValueError('tint="hidden" needs a sensor')
-    grid = options.BY_NAME["grid"].normalise(grid)
-    if grid is not None and (sensor is not None or attribution is not None):
-        raise ValueError("visualize_agent(grid=...) does not go with sensor or attribution")
-    lidar = options.BY_NAME["lidar"].normalise(lidar)
-    if lidar is not None and (sensor is not None or grid is not None or attribution is not None):
-        raise ValueError("visualize_agent(lidar=...) does not go with sensor, grid or attribution")
-    if lidar is None and tint == "lidar":
-        raise ValueError('tint="lidar" needs a lidar')
+    views = dict(sensor=sensor, grid=grid, lidar=lidar)
+    for i, name in enumerate(options.VIEWS):  # each refuses the views before it, and its tint
+        views[name] = options.BY_NAME[name].normalise(views[name])
+        before = options.VIEWS[:i]
+        if views[name] is not None and before and (
+                attribution is not None or any(views[b] is not None for b in before)):
+            raise ValueError(f"visualize_agent({name}=...) does not go with {', '.join(before)} "
+                             "or attribution")
+        if views[name] is None and TINT_NEEDS.get(tint) == name:
+            raise ValueError(f'tint="{tint}" needs a {name}')
+    view = options.given_view(views)
 
     if logger is None:
         logger = logging.getLogger(__name__)
@@ -461,13 +455,15 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
     try:
         dev = ev.device
         seeds = torch.arange(n, device=dev, dtype=torch.int64) + (exp_seed + 2000)
-        obs, _ = ev.reset(seeds=seeds)
-        if sensor is not None:
-            obs = ev.sense(sensor)
-        if grid is not None:
-            obs = ev.grid(grid)
-        if lidar is not None:
-            obs = ev.lidar(lidar)
+        def acted_on(obs):
+            """What the policy acts on at the state whose rows are ``obs``: under a view its rows,
+            in ``obs``'s shape where it overwrites them."""
+            if view is None:
+                return obs
+            rows = ev.view(view[1])
+            return rows if view[1].REPLACES_ROWS else rows.view_as(obs)
+
+        obs = acted_on(ev.reset(seeds=seeds)[0])
         alive = torch.ones(n, dtype=torch.bool, device=dev)
         total = torch.zeros(n, dtype=torch.float64, device=dev)
         frames = [[] for _ in range(n)]
@@ -482,10 +478,10 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
                 shade = torch.empty(n, 64, dtype=torch.float32, device=dev)
                 ev.traffic_into(risk=shade)
             elif tint == "hidden":
-                shade = ev.hidden_vehicles(sensor)
+                shade = ev.hidden_vehicles(views["sensor"])
             elif tint == "lidar":
                 shade = torch.empty(n, 64, dtype=torch.float32, device=dev)
-                ev.lidar_into(lidar, seen=shade)
+                ev.lidar_into(views["lidar"], seen=shade)
             host = ev.render(shade=shade).cpu().numpy()
             if tape is not None:
                 tape.append((obs.clone(), ev.export_state(), list(running)))
@@ -498,12 +494,7 @@ def visualize_agent(env, agent, num_episodes=3, exp_seed: int = 0, logger=None, 
         for _ in range(ev.max_episode_steps + 1):
             a, _, _, _ = agent.select_action(obs.reshape(n, -1), deterministic=True)
             obs, r, te, tr, _ = ev.step(a.contiguous())
-            if sensor is not None:
-                obs = ev.sense(sensor)
-            if grid is not None:
-                obs = ev.grid(grid)
-            if lidar is not None:
-                obs = ev.lidar(lidar)
+            obs = acted_on(obs)
             total += torch.where(alive, r.double(), torch.zeros_like(total))
             if out_dir is not None:
                 grab()  # the frame after this step, for the episodes that took it
@@ -955,13 +946,11 @@ class _EvalTracker:
     """Eval / moving-average / checkpoint bookkeeping of routine.py:172-222."""
 
     def __init__(self, env, agent, exp_seed, target_reward, checkpoint_dir, experiment_name,
-                 metrics_history, logger, exp_prefix, start_time, sensor=None, shield=None,
-                 grid=None, lidar=None):
+                 metrics_history, logger, exp_prefix, start_time, shield=None, view=None):
         self.env, self.agent, self.exp_seed = env, agent, exp_seed
-        self.grid = grid  # the grid the run trains on: its own evaluations act on it too
-        self.lidar = lidar  # likewise the lidar (never both)
-        self.sensor = sensor  # the sensor the run trains under: its own evaluations use it too
-        self.shield = shield  # likewise the shield (never both)
+        # the shield or the view (options.given_view's pair) the run trains under, never both:
+        # its own evaluations use it too
+        self.eval_kw = options.given(shield=shield, **dict([view] if view else []))
         self.target_reward = target_reward
         self.checkpoint_dir, self.name = checkpoint_dir, experiment_name
         self.mh, self.logger, self.prefix, self.t0 = metrics_history, logger, exp_prefix, start_time
@@ -971,8 +960,7 @@ class _EvalTracker:
 
     def _evaluate(self):
         return evaluate(self.env, self.agent, num_episodes=5, exp_seed=self.exp_seed,
-                        **options.given(sensor=self.sensor, shield=self.shield, grid=self.grid,
-                                        lidar=self.lidar))
+                        **self.eval_kw)
 
     def initial(self, r=None):
         if r is None:
@@ -1037,8 +1025,8 @@ def train_with_experiment_name(env, agent, max_episodes=500, target_reward=0.0, 
     checkpoint_dir = os.path.join(artifacts_dir, "checkpoints")
     os.makedirs(checkpoint_dir, exist_ok=True)
     tracker = _EvalTracker(env, agent, exp_seed, target_reward, checkpoint_dir, experiment_name,
-                           metrics_history, logger, exp_prefix, start_time, sensor=opts["sensor"],
-                           shield=opts["shield"], grid=opts["grid"], lidar=opts["lidar"])
+                           metrics_history, logger, exp_prefix, start_time, shield=opts["shield"],
+                           view=options.given_view(opts))
     rank, _ = _rank_world(group)
     if rank == 0:
         logger.info(f"{exp_prefix} Performing initial evaluation...")
@@ -1159,20 +1147,15 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
                   shield=None, grid=None, lidar=None):
     """E lockstep envs, device rollout of T steps, batched PPO update.
 
-    lidar: as grid, with the ray-cast range observation: states ``lidar.stride(F)`` wide, written
-    by one hwy_lidar launch on the reset states and one after every env step.
-
-    grid: the policy acts on the occupancy grid of the env states: the rollout buffer's states are
-    ``grid.stride(F)`` wide, the rollout writes them with one hwy_grid launch on the reset states
-    and one after every env step (ppo/rollout.py).
+    sensor / grid / lidar (at most one, the view): the rollout writes the rows the policy acts on
+    with one env.view_into launch on the reset states and one after every env step
+    (ppo/rollout.py); under a grid or a lidar the rollout buffer's states are ``spec.stride(F)``
+    wide.
 
     shield: after the policy acted, the rollout's shield (one hwy_lookahead call per step,
     ppo/rollout.py) picks the action the env executes; PPO's stored actions, log-probs and values
     stay the policy's.  Every update's metrics carry ``shield_rate``, the share of the rollout's
     steps the shield overrode.
-
-    sensor: the rollout senses the reset states and the state every env step leaves into the
-    rows the policy acts on (one hwy_sense launch each, ppo/rollout.py).
 
     safety_stats: the rollout issues one hwy_traffic launch per env step and every booked
     episode's reduction row goes to mh's SAFETY_KEYS lists (read before the next rollout).
@@ -1202,15 +1185,16 @@ def _train_vector(env, agent, max_episodes, log_interval, eval_interval, steps_p
     reference = episode_schedule == "reference"
     base = env.unwrapped
     E = base.num_envs
-    own = grid if grid is not None else lidar  # the spec of the observation the rollout writes
-    sd = _flat_dim(env) if own is None else own.stride(int(base.hwy_config.n_features))
+    view = options.given_view(dict(sensor=sensor, grid=grid, lidar=lidar))
+    own = view is not None and view[1].REPLACES_ROWS  # the rollout writes states[0] itself
+    sd = base.view_width(view[1]) if own else _flat_dim(env)
     T = max(1, math.ceil(steps_per_update / E))
     buf = RolloutBuffer(T, E, sd, 2, base.device, **options.given(
         episode_stats=episode_stats, safety_stats=safety_stats, truncation_bootstrap=bootstrap,
         shield=None if shield is None else True))
     base.set_seed_schedule(exp_seed)
     obs, _ = env.reset()
-    if own is None:  # under a grid or a lidar the rollout writes states[0] itself
+    if not own:
         buf.states[0].copy_(obs.reshape(E, sd))
     roll = LockstepRollout(agent, base, buf, use_graph=getattr(agent, "use_graphs", True),
                            **options.given(episode_schedule=episode_schedule,

@@ -45,7 +45,8 @@ if _HERE not in sys.path:
     sys.path.insert(0, _HERE)
 
 from experiments.config import Condition  # noqa: E402
-from ppo.options import given  # noqa: E402
+from ppo.options import VIEWS, given  # noqa: E402
+from training.routine import TINT_NEEDS  # noqa: E402
 
 CHECKPOINT_RE = re.compile(r"^ppo_highway_(?:best|solved)_(?P<exp>.+)\.pth$")
 # longest prefix first: every positional-embedding condition's name begins with "shuffled"
@@ -111,28 +112,24 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
     the policy's input-gradient mass on the row that shows it (visualize_agent).  ``tint``
     ("ttc"): tint them by their time-to-collision risk instead; not together with it.  ``sensor``
     (a hwy.SensorModel or its dict): the policy acts on what it perceives, and ``tint`` "hidden"
-    tints the vehicles it does not see.  ``grid`` (a hwy.GridSpec, its dict, or True): the policy
-    acts on the occupancy grid of the states, as a grid-trained checkpoint expects; not with
-    ``sensor`` or ``attribution``.  ``lidar`` (a hwy.LidarSpec, its dict, or True): likewise with
-    the ray-cast range observation, and ``tint`` "lidar" tints the vehicles it returns."""
+    tints the vehicles it does not see.  ``grid`` / ``lidar`` (a hwy.GridSpec / hwy.LidarSpec, its
+    dict, or True): the policy acts on the occupancy grid / the ray-cast range observation of the
+    states, as a checkpoint trained on it expects; not with another view or ``attribution``;
+    ``tint`` "lidar" tints the vehicles the lidar returns."""
     if tint is not None and attribution is not None:
         raise ValueError("tint and attribution both shade the vehicles: give one of them")
-    if tint == "hidden" and sensor is None:
-        raise ValueError('tint "hidden" needs a sensor')
-    if grid is not None:
-        from hwy._abi import GridSpec
+    from hwy.vec_env import VIEW_RECORDS
 
-        grid = GridSpec.from_dict(grid)
-        if sensor is not None or attribution is not None:
-            raise ValueError("grid does not go with sensor or attribution")
-    if tint == "lidar" and lidar is None:
-        raise ValueError('tint "lidar" needs a lidar')
-    if lidar is not None:
-        from hwy._abi import LidarSpec
-
-        lidar = LidarSpec.from_dict(lidar)
-        if sensor is not None or grid is not None or attribution is not None:
-            raise ValueError("lidar does not go with sensor, grid or attribution")
+    views = dict(sensor=sensor, grid=grid, lidar=lidar)
+    for i, name in enumerate(VIEWS):  # each refuses the views before it; a tint needs its view
+        before = VIEWS[:i]
+        if views[name] is None:
+            if TINT_NEEDS.get(tint) == name:
+                raise ValueError(f'tint "{tint}" needs a {name}')
+            continue
+        views[name] = VIEW_RECORDS[name].from_dict(views[name])
+        if before and (attribution is not None or any(views[b] is not None for b in before)):
+            raise ValueError(f"{name} does not go with {', '.join(before)} or attribution")
     from config.base_config import HIGHWAY_CONFIG
     from experiments.wrappers import make_env
     from training.routine import visualize_agent
@@ -143,10 +140,9 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
                    env_overrides={"vector_env": True, "device": agent.device})
     try:
         have = int(env.observation_space.shape[0] * env.observation_space.shape[1])
-        if grid is not None:
-            have = grid.stride(int(env.unwrapped.hwy_config.n_features))
-        if lidar is not None:
-            have = lidar.stride(int(env.unwrapped.hwy_config.n_features))
+        own = next((v for v in views.values() if v is not None and v.REPLACES_ROWS), None)
+        if own is not None:  # the policy's input is the view's row
+            have = env.unwrapped.view_width(own)
         want = infer_dims(agent.actor_critic.state_dict())[0]
         if have != want:
             raise ValueError(f"{os.path.basename(path)}: the checkpoint takes {want} inputs, the "
@@ -154,8 +150,7 @@ def record(path: str, out_dir: str, episodes: int = 1, seed: int = 0, device=Non
         dest = os.path.join(out_dir, os.path.splitext(os.path.basename(path))[0])
         rewards = visualize_agent(env, agent, num_episodes=episodes, exp_seed=seed, out_dir=dest,
                                   attribution=attribution,
-                                  **given(tint=tint or None, sensor=sensor, grid=grid,
-                                          lidar=lidar))
+                                  **given(tint=tint or None, **views))
     finally:
         env.close()
     for ep, r in enumerate(rewards):
@@ -198,48 +193,28 @@ def main(argv=None) -> int:
     args = p.parse_args(argv)
     if args.tint and args.attribution:
         p.error("--tint and --attribution both shade the vehicles: give one of them")
-    sensor = None
-    if args.sensor is not None:
-        import json
+    import json
 
-        from hwy._abi import SensorModel
+    from hwy.vec_env import VIEW_RECORDS
 
+    views = {}
+    for i, name in enumerate(VIEWS):  # each refuses the views before it; a tint needs its view
+        raw, before = getattr(args, name), VIEWS[:i]
+        if raw is None:
+            if TINT_NEEDS.get(args.tint) == name:
+                p.error(f"--tint {args.tint} needs --{name}")
+            continue
         try:
-            sensor = SensorModel.from_dict(json.loads(args.sensor))
+            views[name] = VIEW_RECORDS[name].from_dict(json.loads(raw))
         except ValueError as e:   # json.JSONDecodeError is a ValueError too
-            p.error(f"--sensor: {e}")
-    if args.tint == "hidden" and sensor is None:
-        p.error("--tint hidden needs --sensor")
-    grid = None
-    if args.grid is not None:
-        import json
-
-        from hwy._abi import GridSpec
-
-        try:
-            grid = GridSpec.from_dict(json.loads(args.grid))
-        except ValueError as e:
-            p.error(f"--grid: {e}")
-        if sensor is not None or args.attribution:
-            p.error("--grid does not go with --sensor or --attribution")
-    lidar = None
-    if args.lidar is not None:
-        import json
-
-        from hwy._abi import LidarSpec
-
-        try:
-            lidar = LidarSpec.from_dict(json.loads(args.lidar))
-        except ValueError as e:
-            p.error(f"--lidar: {e}")
-        if sensor is not None or grid is not None or args.attribution:
-            p.error("--lidar does not go with --sensor, --grid or --attribution")
-    if args.tint == "lidar" and lidar is None:
-        p.error("--tint lidar needs --lidar")
+            p.error(f"--{name}: {e}")
+        if before and (args.attribution or any(b in views for b in before)):
+            p.error(f"--{name} does not go with {', '.join('--' + b for b in before)} or "
+                    "--attribution")
     models = [args.model] if args.model else list(models_from_file(args.models_file))
     for m in models:
         record(m, args.out, episodes=args.episodes, seed=args.seed, attribution=args.attribution,
-               tint=args.tint, **given(sensor=sensor, grid=grid, lidar=lidar))
+               tint=args.tint, **views)
     return 0
 
 

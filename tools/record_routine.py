@@ -11,7 +11,9 @@ versions of the Python tree (over the same libhwy.so) can be compared value for 
 option alone and every pair, on a one-env and a vector stub, with and without a process group on
 the agent, with a logger whose first ``info`` raises -- the record is the exception's type and
 text, or "reached the run"; the same option values through ExperimentRunner.check_batch (cells of
-two experiments), LockstepRollout(...) on stubs, evaluate(...) and visualize_agent(...).  The
+two experiments), LockstepRollout(...) on stubs, evaluate(...) and visualize_agent(...).  The stubs
+carry what either side of a comparison may look for (the per-kind ``*_into`` methods and the view
+seam's ``view_into`` / ``view_width``), so the same tool text runs against both trees.  The
 file lists each distinct outcome once, by number (``outcomes``); every other section maps an
 option set to its outcomes' numbers, one per entry of the section's ``axes``.
 
@@ -38,10 +40,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VALUES = {"episode_schedule": "reference", "episode_stats": True, "safety_stats": True,
           "truncation": "bootstrap", "attribution": True, "eval_orders": ["shuffled"],
           "eval_sensors": {"a": {}}, "sensor": {}, "eval_shields": {"a": None}, "shield": {},
-          "grid": True, "target_kl": 0.02, "lr_anneal_updates": 10}
+          "grid": True, "lidar": True, "target_kl": 0.02, "lr_anneal_updates": 10}
 CONTROLS = ("target_kl", "lr_anneal_updates")
 ROLLOUT_OPTIONS = ("episode_schedule", "episode_stats", "safety_stats", "truncation", "sensor",
-                   "shield", "grid")
+                   "shield", "grid", "lidar")
 
 
 class Reached(Exception):
@@ -119,27 +121,34 @@ def refusals():
     bufs = {"plain": lambda: RolloutBuffer(2, 2, 4, 2, cpu),
             "full": lambda: RolloutBuffer(2, 2, 4, 2, cpu, episode_stats=True, safety_stats=True,
                                           truncation_bootstrap=True, shield=True)}
-    envs = {"bare": lambda: Stub(),
-            "vec": lambda: Stub(shield_into=None, grid_into=None, hwy_config=Stub(n_features=4))}
+    # every launch a rollout's constructor may issue is there and not callable, under the names
+    # of the per-kind methods and of the view seam; "vec" also answers the constructor's questions
+    launches = dict(sense_into=None, grid_into=None, lidar_into=None, view_into=None)
+    envs = {"bare": lambda: Stub(sense_into=None, view_into=None),
+            "vec": lambda: Stub(shield_into=None, hwy_config=Stub(n_features=4), **launches,
+                                view_width=lambda spec: spec.stride(4))}
     for names in subsets(ROLLOUT_OPTIONS):
         kw = {n: VALUES[n] for n in names}
         for b, e in itertools.product(bufs, envs):
             rec["rollout"][tag(names, buf=b, env=e)] = outcome(
                 lambda: LockstepRollout(Stub(), envs[e](), bufs[b](), **kw))
 
-    views = {"order": "shuffled", "sensor": {}, "shield": {}, "grid": True}
-    for names in subsets(views, upto=4):
+    views = {"order": "shuffled", "sensor": {}, "shield": {}, "grid": True, "lidar": True}
+    for names in subsets(views, upto=5):
         kw = {n: views[n] for n in names}
         for vector in (False, True):
             rec["evaluate"][tag(names, vector=vector)] = outcome(
                 lambda: evaluate(Stub(is_vector_env=vector), Stub(), **kw))
 
-    for attr, tint, sensor, grid in itertools.product((None, "value"), (None, "ttc", "hidden"),
-                                                      (None, {}), (None, True)):
-        rec["visualize"][f"attribution={attr} tint={tint} sensor={sensor} grid={grid}"] = outcome(
+    for attr, tint, sensor, grid, lidar in itertools.product(
+            (None, "value"), (None, "ttc", "hidden", "lidar"), (None, {}), (None, True),
+            (None, True)):
+        rec["visualize"][f"attribution={attr} tint={tint} sensor={sensor} grid={grid} "
+                         f"lidar={lidar}"] = outcome(
             lambda: visualize_agent(Stub(is_vector_env=True), Stub(), num_episodes=1,
                                     logger=StopLogger(), attribution=attr, tint=tint,
-                                    sensor=sensor, grid=grid), reached="reached the episodes")
+                                    sensor=sensor, grid=grid, lidar=lidar),
+            reached="reached the episodes")
     return rec
 
 
@@ -194,7 +203,7 @@ def runs():
 
     from config.base_config import HIGHWAY_CONFIG
     from experiments.runner import ExperimentRunner
-    from hwy import GridSpec
+    from hwy import GridSpec, LidarSpec
     from hwy.vec_env import HighwayVecEnv
     from ppo.agent import PPOAgent
     from training import routine
@@ -216,6 +225,7 @@ def runs():
         "sensor": {"sensor": sensor},
         "shield": {"shield": {}, "eval_shields": {"none": None, "default": {}}},
         "grid": {"grid": True},
+        "lidar": {"lidar": True},
         "evals": {"attribution": True, "eval_orders": ["sorted", "shuffled"],
                   "eval_sensors": {"perfect": {}, "fog": sensor}},
     }
@@ -248,6 +258,7 @@ def runs():
 
     agent = agent_of(env.obs_rows * env.obs_features)
     grid_agent = agent_of(GridSpec().stride(int(env.hwy_config.n_features)))
+    lidar_agent = agent_of(LidarSpec().stride(int(env.hwy_config.n_features)))
     d = rec["direct"]
     try:
         d["evaluate"] = routine.evaluate(env, agent, n, exp_seed=seed)
@@ -257,6 +268,7 @@ def runs():
                                                       order="shuffled")
         d["evaluate shield"] = routine.evaluate(env, agent, n, exp_seed=seed, shield={})
         d["evaluate grid"] = routine.evaluate(env, grid_agent, n, exp_seed=seed, grid=True)
+        d["evaluate lidar"] = routine.evaluate(env, lidar_agent, n, exp_seed=seed, lidar=True)
         d["safety_profile"] = _plain(routine.safety_profile(env, agent, n, exp_seed=seed))
         d["shield_profile"] = _plain(routine.shield_profile(env, agent, {}, n, exp_seed=seed))
         d["attribution"] = _plain(routine.attribution(env, agent, n, exp_seed=seed))
@@ -264,7 +276,8 @@ def runs():
         for name, ag, kw in (("tint=ttc", agent, {"tint": "ttc"}),
                              ("tint=hidden+sensor", agent, {"tint": "hidden", "sensor": sensor}),
                              ("attribution=value", agent, {"attribution": "value"}),
-                             ("grid", grid_agent, {"grid": True})):
+                             ("grid", grid_agent, {"grid": True}),
+                             ("lidar", lidar_agent, {"lidar": True, "tint": "lidar"})):
             out_dir = os.path.join("viz", name.replace("=", "_").replace("+", "_"))
             rewards = routine.visualize_agent(env, ag, num_episodes=n, exp_seed=seed,
                                               out_dir=out_dir, **kw)
